@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — GBP iterations/second on synthetic BAL graphs (BASELINE.json configs[3] "S1" and configs[4] "S8").
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it builds the graph, runs W warm-up steps, times EXACTLY K
+steps (`ms_per_step` = the time of one of them) and prints the JSON line.  Everything else this script measures or checks —
+the roofline (`--profile-steps`, the live PMC passes of `--pmc`), the further and sustained windows (`--windows`,
+`--sustained-seconds`), the flow trace and the CPU baselines (`--cpu-seconds`), the fr1xyz / fr2robot2 configs through the CLIs
+(`--small-configs`) and `host_transfer` — runs with `--full`, with the defaults below; an option given explicitly holds either way.
+`--dump-outputs DIR` writes what the timed path computed after its last step (gbp_read: every belief and the per-factor state) as
+DIR/<name>.npy in float32 / float64, each array flat (1-D, in gbp_read's order); the inputs are seeded, so two builds can be
+compared output for output.  At N > 1 it is rank 0's gbp_read — its landmark shard, so it depends on the partition.
 
 A "step" is one synchronous GBP iteration (GBP_PROG of the reference, ba/ba.cpp:895-905: prep -> messages ->
 beliefs) over the whole factor graph, inputs resident in HBM, no host read-back inside the timed region.
@@ -95,6 +104,10 @@ ALGO_BYTES_PER_FACTOR = 1112   # algorithmic bytes per factor-itera
 # compulsory streams of this layout per factor-iteration of k_sweep: FAC 224 R + CMSG 112 R + 112 W +
 # LMSG 64 R + 64 W + LMK_IDX 4 R + ROWP 11 W = 591 B; landmark-table gathers (belief 64 B + hoisted mean) come on top
 LAYOUT_BYTES_PER_FACTOR = 591
+DUMP_BYTES_MAX = 64 << 20      # --dump-outputs: at most this much in all (a fixed, seeded sample of a larger output)
+# the options of what a plain run leaves out: their defaults with --full, and without it
+FULL_DEFAULTS = {"cpu_seconds": 15.0, "profile_steps": 20, "pmc": "live", "windows": 5, "sustained_seconds": 2.0, "small_configs": "auto"}
+PLAIN_DEFAULTS = {"cpu_seconds": 0.0, "profile_steps": 0, "pmc": "off", "windows": 0, "sustained_seconds": 0.0, "small_configs": "off"}
 
 
 def parse(argv=None):
@@ -107,10 +120,12 @@ def parse(argv=None):
     ap.add_argument("--obs", type=int, default=10, help="observations per landmark")
     ap.add_argument("--weak-s1", action="store_true", help="N > 1: N x S1 (100000 landmarks per GPU) instead of the config-5 family")
     ap.add_argument("--seed", type=int, default=20200303)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline sample (0 = skip)")
-    ap.add_argument("--profile-steps", type=int, default=20, help="per-stage hipEvent-timed iterations for the roofline")
-    ap.add_argument("--pmc", choices=["live", "file", "off"], default="live",
-                    help="roofline.traffic: live rocprofv3 PMC passes (N = 1), the stamped profiles/traffic_S1.json, or none")
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="budget of the cpu_baseline sample (0 = skip; default 15 with --full, else 0)")
+    ap.add_argument("--profile-steps", type=int, default=None,
+                    help="per-stage hipEvent-timed iterations for the roofline (0 = none; default 20 with --full, else 0)")
+    ap.add_argument("--pmc", choices=["live", "file", "off"], default=None,
+                    help="roofline.traffic: live rocprofv3 PMC passes (N = 1), the stamped profiles/traffic_S1.json, or none "
+                         "(default live with --full, else off)")
     ap.add_argument("--save-traffic", default=None, help="write the live PMC traffic + its build stamp to this JSON file")
     ap.add_argument("--keep-pmc", default=None, help="keep the rocprofv3 PMC output of the live passes in this directory")
     ap.add_argument("--force-sharded", action="store_true",
@@ -127,8 +142,10 @@ def parse(argv=None):
                     help="gbp_params.graph_unroll of the single-GPU ctx: iterations per captured hipGraph.  0 (default): the largest graph of at "
                          "most 20 iterations that divides the longest burst of the timed region — a replay costs 10-20 us of launch work, 1 %% of "
                          "ten 1M-factor iterations (measured, alternating on one box: 8 336 / 8 436 / 8 402 iterations/s with 10 / 20 / 50)")
-    ap.add_argument("--windows", type=int, default=5, help="further timed windows of --steps iterations behind the contract's (spread of the figure)")
-    ap.add_argument("--sustained-seconds", type=float, default=2.0, help="one long window of at least this many seconds (0 = none)")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="further timed windows of --steps iterations behind the contract's (spread of the figure; default 5 with --full, else 0)")
+    ap.add_argument("--sustained-seconds", type=float, default=None,
+                    help="one long window of at least this many seconds (0 = none; default 2 with --full, else 0)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="diagnostic: N > 1 ranks on FEWER than N GPUs (device = local rank mod visible devices; torch group on gloo, the "
                          "library's communicator on its host-staged transport, which bin/ba --ipus N uses when ranks share a GPU) — "
@@ -136,14 +153,24 @@ def parse(argv=None):
     ap.add_argument("--preflight", type=int, default=1,
                     help="N > 1 (and --force-sharded), native communicator: the un-timed self-validation block (GPU identities, peer access, "
                          "librccl path/version, all-gather probe, one-stream vs two-stream schedule measured and chosen); 0 = off")
-    ap.add_argument("--small-configs", choices=["auto", "on", "off"], default="auto",
-                    help="the fr1xyz (./ba) and fr2robot2 (./slam) halves of the metric through the C++ CLIs (auto: with the default N = 1 workload)")
+    ap.add_argument("--small-configs", choices=["auto", "on", "off"], default=None,
+                    help="the fr1xyz (./ba) and fr2robot2 (./slam) halves of the metric through the C++ CLIs (auto: with the default N = 1 "
+                         "workload; default auto with --full, else off)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: roofline + live PMC traffic, further and sustained windows, flow trace, "
+                         "CPU baselines, the CLI configs, host_transfer (the defaults of the options above)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed after its last step (gbp_read) to DIR/<name>.npy, float32 / float64, each "
+                         "array flat (1-D, gbp_read's order); N > 1: rank 0's gbp_read, i.e. its landmark shard (depends on the partition)")
     # internal modes
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)       # the process rocprofv3 profiles
     ap.add_argument("--pmc-child-out", default=None, help=argparse.SUPPRESS)          # where it leaves its n_relin trajectory
     ap.add_argument("--launch-selftest", action="store_true", help=argparse.SUPPRESS)  # CPU test of the self-launcher (gloo)
     ap.add_argument("--selftest-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     a = ap.parse_args(argv)
+    for k, v in (FULL_DEFAULTS if a.full else PLAIN_DEFAULTS).items():
+        if getattr(a, k) is None:
+            setattr(a, k, v)
     if a.cams is None:
         a.cams = 1000
     if a.lmks is None:
@@ -681,6 +708,25 @@ def compare_beliefs(g, o):
     return out
 
 
+def dump_outputs(arrays, directory, max_bytes=DUMP_BYTES_MAX):
+    """--dump-outputs: every array as DIR/<name>.npy — float32 as it is, integer state as float64 (exact) — at most `max_bytes` in
+    all: past that, each array keeps the same fixed, seeded sample of its entries (in order).  Returns {name: entries written}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    out = {k: (np.asarray(v, np.float32) if np.asarray(v).dtype == np.float32 else np.asarray(v, np.float64)).ravel()
+           for k, v in sorted(arrays.items())}
+    total = sum(v.nbytes for v in out.values())
+    frac = min(1.0, (max_bytes - 4096 * len(out)) / total) if total else 1.0       # (4096: room for the .npy headers)
+    written = {}
+    for k, v in out.items():
+        if frac < 1.0:
+            n = max(1, int(v.size * frac))
+            v = v[np.sort(np.random.default_rng(20200303).choice(v.size, n, replace=False))]
+        np.save(os.path.join(directory, k + ".npy"), v)
+        written[k] = int(v.size)
+    return written
+
+
 def setup_host_staged_comm(eng, dist, torch, rank, world, n_cams):
     """--share-gpu: the library's communicator over its host-staged transport (what bin/ba --ipus N uses when ranks share a GPU):
     a MAP_SHARED region — here a file in /dev/shm created and initialised by rank 0, its name carried around by the launcher's
@@ -996,6 +1042,11 @@ def run_rank(a):
     first_timed = it
     dt, rank_dt, weak_timed = window(a.steps)
     ev1 = run_eval()
+    dumped = None
+    if a.dump_outputs:
+        res = run.read()                 # what a caller of the timed path receives after its last step (this rank's shard at N > 1)
+        if rank == 0:
+            dumped = dump_outputs(res, a.dump_outputs)
 
     # ---- roofline of the dominant kernel (k_sweep), measured live with hipEvents on its stream: the next P iterations ----
     graph_used = (getattr(run, "graph", None) is not None) if hasattr(run, "use_graph") else (eng.graph_state() == 1)
@@ -1159,7 +1210,7 @@ def run_rank(a):
 
     # ---- what the boundary's host buffers cost (never part of `value`: the iterations run on state resident in HBM) ----
     transfer = None
-    if rank == 0 and not sharded and world == 1:
+    if rank == 0 and not sharded and world == 1 and a.full:
         import numpy as np
         t0 = time.perf_counter()
         back = eng.read()                                   # READ_PROG: beliefs + damping, damping_count, robust_flag
@@ -1196,6 +1247,8 @@ def run_rank(a):
                        "iteration_graph": graph_used, "exchange": exchange_kind, "comm_error": comm_error,
                        "sharded_graph_error": getattr(run, "graph_error", None), "preflight": pre},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "entries": dumped}
         if spread:
             out["windows"] = spread
         if sustained:

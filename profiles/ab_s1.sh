@@ -7,12 +7,12 @@ OUT=$REPO/gpurun_out/$TAG
 mkdir -p $OUT
 cd $REPO
 exec > $OUT/run.log 2>&1
-python3 bench.py --steps 50 --warmup 10 --pmc off --cpu-seconds 0 --small-configs off > /dev/null 2>&1   # warm the box
+python3 bench.py --full --steps 50 --warmup 10 --pmc off --cpu-seconds 0 --small-configs off > /dev/null 2>&1   # warm the box
 for round in $(seq 1 ${ROUNDS:-4}); do
 for v in ${VARIANTS:-default}; do
   if [ $v = default ]; then L=""; else L=$REPO/profiles/_bin/$v/libgbp_mi355x.so; fi
   echo -n "$v round $round: "
-  GBP_LIB=$L python3 bench.py --steps $STEPS --warmup $WARM --pmc off --cpu-seconds 0 --small-configs off 2> $OUT/err.txt | tail -1 | python3 -c "
+  GBP_LIB=$L python3 bench.py --full --steps $STEPS --warmup $WARM --pmc off --cpu-seconds 0 --small-configs off 2> $OUT/err.txt | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 k={x['kernel'].split('<')[0].split('(')[0]:x for x in d['roofline'].get('kernels',[])} if isinstance(d['roofline'].get('kernels'),list) else {}

@@ -3,7 +3,7 @@
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $REPO
 for rep in 1 2 3; do for v in "$@"; do
-  GBP_LIB=$REPO/profiles/_bin/$v/libgbp_mi355x.so python3 bench.py --steps 200 --warmup 20 --cpu-seconds 0 --small-configs off --pmc off 2> /dev/null | grep '^{' | python3 -c "
+  GBP_LIB=$REPO/profiles/_bin/$v/libgbp_mi355x.so python3 bench.py --full --steps 200 --warmup 20 --cpu-seconds 0 --small-configs off --pmc off 2> /dev/null | grep '^{' | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print('$v', 'value %.1f | windows %.1f / %.1f / %.1f | sustained %.1f | sweep %.2f us | beliefs %.2f us' % (d['value'], d['windows']['min'], d['windows']['median'], d['windows']['max'], d['sustained']['value'], r['avg_launch_us'], r['belief_kernels_avg_us']))"

@@ -11,7 +11,7 @@ for sh in ${SHAPES:-1000x100000}; do
   for r in $(seq 1 ${ROUNDS:-3}); do for v in ${VARIANTS:-default}; do
     if [ $v = default ]; then L=""; else L=$PWD/profiles/_bin/$v/libgbp_mi355x.so; fi
     echo -n "$v $sh: " >> $OUT
-    GBP_LIB=$L python3 bench.py --steps ${STEPS:-200} --warmup 20 --cpu-seconds 0 --pmc off --small-configs off --cams $c --lmks $l 2>/dev/null | tail -1 \
+    GBP_LIB=$L python3 bench.py --full --steps ${STEPS:-200} --warmup 20 --cpu-seconds 0 --pmc off --small-configs off --cams $c --lmks $l 2>/dev/null | tail -1 \
       | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'])" >> $OUT
   done; done
 done

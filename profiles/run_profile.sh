@@ -9,8 +9,8 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $REPO/bench.py --steps 20 --warmup 5 --cpu-seconds 0 --pmc off > $OUT/stats_bench.json 2> $OUT/stats.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $REPO/bench.py --full --steps 20 --warmup 5 --cpu-seconds 0 --pmc off > $OUT/stats_bench.json 2> $OUT/stats.log
 cd $REPO
-python3 bench.py --steps 20 --warmup 5 --keep-pmc $OUT/pmc --save-traffic $OUT/traffic_S1.json > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full --steps 20 --warmup 5 --keep-pmc $OUT/pmc --save-traffic $OUT/traffic_S1.json > $OUT/bench.json 2> $OUT/bench.err
 python3 $REPO/profiles/summarise.py $OUT $REPO/gpurun_out/profile_summary_$TAG.md
 cp $OUT/stats/stats_kernel_stats.csv $REPO/gpurun_out/${TAG}_kernel_stats.csv 2>/dev/null

@@ -5,7 +5,7 @@ OUT=$REPO/gpurun_out/r06_seg
 mkdir -p $OUT
 cd $REPO
 for rep in 1 2; do for mode in 0 1; do
-  GBP_SEG_SKIP=$mode python3 bench.py --steps 200 --warmup 20 --cpu-seconds 0 --small-configs off --cams 8000 --lmks 125000 2> $OUT/seg${mode}_$rep.err | grep '^{' > $OUT/seg${mode}_$rep.json
+  GBP_SEG_SKIP=$mode python3 bench.py --full --steps 200 --warmup 20 --cpu-seconds 0 --small-configs off --cams 8000 --lmks 125000 2> $OUT/seg${mode}_$rep.err | grep '^{' > $OUT/seg${mode}_$rep.json
 done; done
 python3 - <<PY
 import json, glob

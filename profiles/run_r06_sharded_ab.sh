@@ -5,9 +5,9 @@ OUT=$REPO/gpurun_out/r06_sharded_ab
 mkdir -p $OUT
 cd $REPO
 for rep in 1 2 3; do
-  python3 bench.py --gpus 1 --force-sharded --cams 8000 --lmks 125000 --steps 20 --warmup 5 --cpu-seconds 0 --pmc off 2> /dev/null | grep '^{' > $OUT/direct_$rep.json
-  python3 bench.py --gpus 1 --force-sharded --cams 8000 --lmks 125000 --steps 20 --warmup 5 --cpu-seconds 0 --pmc off --sharded-graph 1 2> /dev/null | grep '^{' > $OUT/graph_$rep.json
-  python3 bench.py --gpus 1 --cams 8000 --lmks 125000 --steps 20 --warmup 5 --cpu-seconds 0 --pmc off --small-configs off 2> /dev/null | grep '^{' > $OUT/plain_$rep.json
+  python3 bench.py --full --gpus 1 --force-sharded --cams 8000 --lmks 125000 --steps 20 --warmup 5 --cpu-seconds 0 --pmc off 2> /dev/null | grep '^{' > $OUT/direct_$rep.json
+  python3 bench.py --full --gpus 1 --force-sharded --cams 8000 --lmks 125000 --steps 20 --warmup 5 --cpu-seconds 0 --pmc off --sharded-graph 1 2> /dev/null | grep '^{' > $OUT/graph_$rep.json
+  python3 bench.py --full --gpus 1 --cams 8000 --lmks 125000 --steps 20 --warmup 5 --cpu-seconds 0 --pmc off --small-configs off 2> /dev/null | grep '^{' > $OUT/plain_$rep.json
 done
 python3 - <<PY
 import json, glob

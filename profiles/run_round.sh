@@ -6,12 +6,12 @@ OUT=$REPO/gpurun_out/round_$TAG
 mkdir -p $OUT
 cd $REPO
 bash profiles/run_profile.sh $TAG > $OUT/run_profile.log 2>&1
-python3 bench.py --steps 200 --warmup 20 --cpu-seconds 0 --pmc off > $OUT/bench_s1_200.json 2> /dev/null
-python3 bench.py --steps 200 --warmup 20 --cpu-seconds 0 --pmc off --cams 8000 --lmks 125000 > $OUT/bench_c5shape_plain.json 2> /dev/null
-python3 bench.py --steps 200 --warmup 20 --cpu-seconds 0 --force-sharded --cams 8000 --lmks 125000 > $OUT/bench_c5shape_native.json 2> /dev/null
-python3 bench.py --steps 200 --warmup 20 --cpu-seconds 0 --force-sharded --comm torch --sharded-graph 0 --cams 8000 --lmks 125000 > $OUT/bench_c5shape_torch.json 2> /dev/null
+python3 bench.py --full --steps 200 --warmup 20 --cpu-seconds 0 --pmc off > $OUT/bench_s1_200.json 2> /dev/null
+python3 bench.py --full --steps 200 --warmup 20 --cpu-seconds 0 --pmc off --cams 8000 --lmks 125000 > $OUT/bench_c5shape_plain.json 2> /dev/null
+python3 bench.py --full --steps 200 --warmup 20 --cpu-seconds 0 --force-sharded --cams 8000 --lmks 125000 > $OUT/bench_c5shape_native.json 2> /dev/null
+python3 bench.py --full --steps 200 --warmup 20 --cpu-seconds 0 --force-sharded --comm torch --sharded-graph 0 --cams 8000 --lmks 125000 > $OUT/bench_c5shape_torch.json 2> /dev/null
 # the line an N > 1 run prints, on one rank: PMC passes on the shard shape, exchange timing
-python3 bench.py --gpus 1 --force-sharded --cams 8000 --lmks 125000 --steps 20 --warmup 5 --cpu-seconds 0 > $OUT/bench_c5shape_driverline.json 2> /dev/null
+python3 bench.py --full --gpus 1 --force-sharded --cams 8000 --lmks 125000 --steps 20 --warmup 5 --cpu-seconds 0 > $OUT/bench_c5shape_driverline.json 2> /dev/null
 for seq in fr1xyz fr2robot2 fr1desk; do
   for ev in 1 100; do
     for rep in 1 2; do gbp_poplar_amd/bin/ba --bal_file data/sequences/$seq.txt --eval_every $ev > $OUT/ba_${seq}_every$ev.log 2>&1; done

@@ -51,7 +51,7 @@ def _bench_gpu(*args):
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cams", "60", "--lmks", "4000", "--steps", "12",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--cams", "60", "--lmks", "4000", "--steps", "12",
                         "--warmup", "12", "--profile-steps", "5", "--cpu-seconds", "0", *args],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -101,7 +101,7 @@ def test_bench_line_describes_the_run_it_times():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cams", "200", "--lmks", "20000", "--steps", "20", "--warmup", "5",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--cams", "200", "--lmks", "20000", "--steps", "20", "--warmup", "5",
                         "--profile-steps", "12", "--cpu-seconds", "4", "--sustained-seconds", "1", "--small-configs", "off"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -142,7 +142,7 @@ def test_bench_with_real_ranks_sharing_one_gpu(world, oracle_mod):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cams, lmks = 40, 1500                  # per rank
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--share-gpu", "--cams", str(cams), "--lmks", str(lmks),
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--share-gpu", "--cams", str(cams), "--lmks", str(lmks),
                         "--steps", "8", "--warmup", "4", "--profile-steps", "4", "--cpu-seconds", "0", "--pmc", "off", "--windows", "2",
                         "--sustained-seconds", "0.2"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -183,7 +183,7 @@ def test_bench_sharded_line_is_complete_on_the_config5_shard_shape():
     """the line an N > 1 run prints must carry a MEASURED roofline.frac (PMC passes on rank 0's shard
     shape), the exchange time and the per-rank step times — checked here with one rank on the per-GPU shard of BASELINE
     config 5 (8 000 cameras x 125 000 landmarks x 1.25 M factors), the library's own communicator."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-sharded", "--cams", "8000", "--lmks", "125000", "--steps", "20",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--force-sharded", "--cams", "8000", "--lmks", "125000", "--steps", "20",
                         "--warmup", "5", "--cpu-seconds", "0"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
@@ -222,6 +222,85 @@ def test_bench_native_communicator_failure_is_fatal():
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert out["value"] is None and out["n_gpus"] == 1 and "could not be set up" in out["comm_error"]
     assert len(out["config"]["ranks"]) == 1 and "librccl-missing" in out["config"]["ranks"][0]["comm_error"]
+
+
+def test_plain_run_leaves_the_extras_to_full():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` does only what its headline figure needs; the roofline, the live PMC
+    passes, the further windows, the CPU baselines and the CLI configs keep their old defaults behind --full; an explicit value
+    holds either way."""
+    sys.path.insert(0, ROOT)
+    import bench
+    plain, full = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"]), bench.parse(["--full"])
+    assert (plain.steps, plain.warmup, plain.full, plain.dump_outputs) == (7, 3, False, None)
+    assert (plain.cpu_seconds, plain.profile_steps, plain.pmc, plain.windows, plain.sustained_seconds, plain.small_configs) == \
+        (0.0, 0, "off", 0, 0.0, "off")
+    assert (full.cpu_seconds, full.profile_steps, full.pmc, full.windows, full.sustained_seconds, full.small_configs) == \
+        (15.0, 20, "live", 5, 2.0, "auto")
+    mixed = bench.parse(["--windows", "2", "--full", "--pmc", "off"])
+    assert (mixed.windows, mixed.pmc, mixed.profile_steps) == (2, "off", 20)
+    assert bench.parse(["--profile-steps", "4"]).profile_steps == 4
+
+
+def test_dump_outputs_float_arrays_within_the_cap(tmp_path):
+    """--dump-outputs: float32 stays float32, integer state becomes float64 (exact); past the cap every array keeps the same
+    fixed, seeded sample of its entries, in order."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    arrays = {"x": np.linspace(0, 1, 1000, dtype=np.float32), "n": np.arange(3000, dtype=np.int32), "f": np.arange(5, dtype=np.uint32)}
+    assert bench.dump_outputs(arrays, str(tmp_path / "all")) == {"x": 1000, "n": 3000, "f": 5}
+    x, n = np.load(str(tmp_path / "all" / "x.npy")), np.load(str(tmp_path / "all" / "n.npy"))
+    assert x.dtype == np.float32 and np.array_equal(x, arrays["x"]) and n.dtype == np.float64 and np.array_equal(n, np.arange(3000))
+    cap = 4096 * 3 + 12000
+    w1 = bench.dump_outputs(arrays, str(tmp_path / "s1"), max_bytes=cap)
+    w2 = bench.dump_outputs(arrays, str(tmp_path / "s2"), max_bytes=cap)
+    assert w1 == w2 and w1["n"] < 3000
+    total = sum(os.path.getsize(str(tmp_path / "s1" / f)) for f in os.listdir(str(tmp_path / "s1")))
+    assert total <= cap
+    for k in w1:
+        a, b = np.load(str(tmp_path / "s1" / (k + ".npy"))), np.load(str(tmp_path / "s2" / (k + ".npy")))
+        assert np.array_equal(a, b) and np.all(np.diff(a) > 0)          # the same sample, in order
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_what_it_computed(tmp_path, oracle_mod):
+    """`bench.py --steps 7 --warmup 3 --dump-outputs DIR` without --full: the contract's fields, EXACTLY 7 timed steps, none of the
+    extras; the dumped arrays are the beliefs and per-factor state after iteration 10 of the ./ba flow — the same in two runs, and
+    bit-identical to the oracle's in the device's conventions."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    from gbp_poplar_amd import driver, hostlib
+    outs = []
+    for r in range(2):
+        d = str(tmp_path / ("run%d" % r))
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--cams", "60", "--lmks", "4000", "--steps", "7",
+                            "--warmup", "3", "--dump-outputs", d], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        out = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in out, k
+        assert out["steps"] == 7 and out["warmup"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert out["config"]["timed_region"]["iterations"] == 7 and out["config"]["iterations_run_in_all"] == 10
+        assert not {"roofline", "windows", "sustained", "cpu_baseline", "configs", "host_transfer"} & set(out), sorted(out)
+        outs.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    assert set(outs[0]) == {"cam_beliefs_eta", "cam_beliefs_lambda", "lmk_beliefs_eta", "lmk_beliefs_lambda", "damping", "damping_count",
+                            "robust_flag"}
+    for k in outs[0]:
+        assert outs[0][k].dtype in (np.float32, np.float64) and np.array_equal(outs[0][k], outs[1][k], equal_nan=True), k
+    bal = hostlib.synth_generate(60, 4000, 10, 20200303)
+    opts = driver.Options()
+    K, state, _ = driver.build_inputs(bal, opts, hostlib)
+    oracle_mod.set_trig_mode(1)
+    try:
+        o = oracle_mod.Oracle(bal["cam_id"], bal["lmk_id"], bal["n_cams"], bal["n_lmks"], K)
+        o.set_sum_order(1)
+        driver.run_ba(o, state, opts, n_iters=10, eval_every=10)
+        ref = o.read()
+        o.close()
+    finally:
+        oracle_mod.set_trig_mode(0)
+    for k in outs[0]:
+        assert np.array_equal(outs[0][k], np.asarray(ref[k]).ravel().astype(outs[0][k].dtype), equal_nan=True), k
 
 
 def test_cli_metric_lines_are_parsed():
