@@ -94,8 +94,8 @@ static int enqueue_sharded_iteration(gbp_ctx* c, const SweepArgs& a) {
 
 int iterate_sharded(gbp_ctx* c, int n) {
   const SweepArgs a = sweep_args(c);
-  gbp_ctx::Span sp{};
-  if (int rc = span_begin(c, sp)) return rc;
+  TimedSpan sp(c);
+  if (int rc = sp.begin()) return rc;
   int left = n;
   // Measured (config-5 shard shape, 1-rank communicator): direct launches 0.186 ms per iteration, the captured graph with
   // its cross-stream fork/join nodes 0.191 ms — the path is not host-bound, so the graph is opt-in (graph_unroll > 0).
@@ -132,11 +132,9 @@ int iterate_sharded(gbp_ctx* c, int n) {
   }
   for (; left > 0; --left)
     if (int rc = enqueue_sharded_iteration(c, a)) return rc;
-  if (int rc = span_end(c, sp)) return rc;
+  if (int rc = sp.end()) return rc;
   if (!c->comm->stream_ordered() || c->profile_stages) HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (!c->profile_stages) c->timed_iters += (uint64_t)n;    // with profiling the sweep brackets count the iterations
-  c->beliefs_valid = true;
-  return GBP_OK;
+  return sp.commit(c->profile_stages ? 0 : (uint64_t)n);    // with profiling the sweep brackets count the iterations
 }
 
 }  // namespace api

@@ -60,19 +60,29 @@ int resolve_spans(gbp_ctx* c, bool wait) {
   c->spans.erase(c->spans.begin(), c->spans.begin() + (long)done);
   return GBP_OK;
 }
-int span_begin(gbp_ctx* c, gbp_ctx::Span& sp) {
+int TimedSpan::begin() {
+  gbp_ctx* c = c_;
   if (c->spans.size() >= 64) resolve_spans(c, true);
-  if (!c->span_pool.empty()) { sp = c->span_pool.back(); c->span_pool.pop_back(); }
+  if (!c->span_pool.empty()) { sp_ = c->span_pool.back(); c->span_pool.pop_back(); }
   else {
-    HIPCHK(c, hipEventCreate(&sp.a));
-    if (hipError_t e_ = hipEventCreate(&sp.b); e_ != hipSuccess) { (void)hipEventDestroy(sp.a); return fail(c, GBP_ERR_HIP, "hipEventCreate"); }
+    HIPCHK(c, hipEventCreate(&sp_.a));
+    if (hipError_t e_ = hipEventCreate(&sp_.b); e_ != hipSuccess) { (void)hipEventDestroy(sp_.a); return fail(c, GBP_ERR_HIP, "hipEventCreate"); }
   }
-  HIPCHK(c, hipEventRecord(sp.a, c->stream));
+  open_ = true;
+  HIPCHK(c, hipEventRecord(sp_.a, c->stream));
   return GBP_OK;
 }
-int span_end(gbp_ctx* c, const gbp_ctx::Span& sp) {
-  HIPCHK(c, hipEventRecord(sp.b, c->stream));
-  c->spans.push_back(sp);
+int TimedSpan::end() {
+  if (!open_) return GBP_OK;
+  HIPCHK(c_, hipEventRecord(sp_.b, c_->stream));
+  c_->spans.push_back(sp_);
+  open_ = false;
+  return GBP_OK;
+}
+int TimedSpan::commit(uint64_t n) {
+  if (int rc = end()) return rc;
+  c_->timed_iters += n;
+  c_->beliefs_valid = true;
   return GBP_OK;
 }
 

@@ -1,9 +1,11 @@
 // gbp_api_eval.cpp — the metric on the device and the loops that carry it.
 //   gbp_eval                      eval_reprojection_error (reference ba/util.cpp:74-144) + the counters of ba.cpp:1011-1020
 //   gbp_ba_loop                   the BODY of the reference's iteration loop (ba.cpp:1001-1028, slam.cpp:1048-1103): prior weakening,
-//                                 GBP_PROG, the metric — one launch of the persistent kernel per burst on small graphs, the metric
-//                                 riding in the sweeps (k_sweep<EV> / k_beliefs_ev) elsewhere
+//                                 GBP_PROG, the metric — with the metric through iterate_passes_eval (one launch of the persistent
+//                                 kernel per burst on small graphs, the metric riding in the sweeps (k_sweep<EV> / k_beliefs_ev)
+//                                 elsewhere), without it through gbp_api_launch.cpp's iterate_passes
 //   include/gbp_mi355x_compat.h   gbp_eval_begin / _end, gbp_iterate_eval, gbp_iterate_eval_each: earlier forms of the same loop
+//                                 (gbp_iterate_eval_each = iterate_passes_eval with no weakening)
 #include "gbp_ctx.hpp"
 
 #include <algorithm>
@@ -130,6 +132,26 @@ EvalRide eval_ride(gbp_ctx* c) {
   return e;
 }
 
+// The metric phases of a launch of the persistent kernel: one metric after its last iteration into result area `area`, or (each) one
+// after EVERY iteration into the series slots — the host-mapped [kSeriesMax][n_tiles + 1] records persist_setup allocates.
+static PersistEval persist_eval(gbp_ctx* c, int area, bool each) {
+  PersistEval ev{};
+  ev.on = 1;
+  ev.cam_mu = P<float>(c->cam_mu); ev.lmk_mu = P<float>(c->lmk_mu);
+  ev.num_undamped = c->prm.num_undamped_iters;
+  if (each) {
+    ev.each = 1;
+    ev.stride = c->n_tiles + 1;          // [0] = health copy, then one record per tile wave
+    ev.slots = static_cast<DeviceEval*>(c->series_dev);
+  } else {
+    ev.slots = static_cast<DeviceEval*>(c->eval_host_dev) + 1025 * area;      // [0] = health copy, [1 + tile wave] = partial sums
+  }
+  ev.health = P<unsigned long long>(c->health) + 2 * area;
+  ev.health_next = P<unsigned long long>(c->health) + 2 * (area ^ 1);
+  ev.health_each = P<unsigned long long>(c->health);
+  return ev;
+}
+
 // gbp_iterate(n) followed by gbp_eval_begin() in one call.  On a graph that runs in k_persist the metric rides in the same
 // launch (two more phases after the last belief update: what k_means and k_eval compute, bit for bit) — the reference's
 // default loop prints the metric after EVERY iteration (ba.cpp:1009-1028), which otherwise costs four launches per iteration.
@@ -142,42 +164,29 @@ static int iterate_eval(gbp_ctx* c, int n) {
   if (fused) {
     if (int rc = eval_alloc(c)) return rc;
     const int area = c->eval_parity & 1;
-    DeviceEval* slots = static_cast<DeviceEval*>(c->eval_host_dev) + 1025 * area;
-    PersistEval ev{};
-    ev.on = 1;
-    ev.cam_mu = P<float>(c->cam_mu); ev.lmk_mu = P<float>(c->lmk_mu);
-    ev.num_undamped = c->prm.num_undamped_iters;
-    ev.slots = slots;                    // [0] = health copy, [1 + tile wave] = partial sums
-    ev.health = P<unsigned long long>(c->health) + 2 * area;
-    ev.health_next = P<unsigned long long>(c->health) + 2 * (area ^ 1);
-    ev.health_each = P<unsigned long long>(c->health);
-    gbp_ctx::Span sp{};
-    if (int rc = span_begin(c, sp)) return rc;
+    const PersistEval metric = persist_eval(c, area, false);
+    TimedSpan sp(c);
+    if (int rc = sp.begin()) return rc;
     // A long burst with ONE metric at its end: all but the last iteration in the launch that carries no metric code at all (the
     // instantiation with the metric runs every iteration ~0.5 us slower: 59 us per 100 iterations on fr1xyz against ~10 us for
     // one more launch), the last iteration and the metric in a launch of their own.
     int head = n >= 16 ? n - 1 : 0;
     int lrc = head ? launch_persist_burst(c, sweep_args(c), head, nullptr, 0, 0) : GBP_OK;
     if (lrc == kNotLaunched) head = 0;      // nothing ran: everything on the two-kernel path below
-    if (lrc == GBP_OK) lrc = launch_persist_burst(c, sweep_args(c), n - head, &ev, 1, area);
+    if (lrc == GBP_OK) lrc = launch_persist_burst(c, sweep_args(c), n - head, &metric, 1, area);
     if (lrc == kNotLaunched && head) {      // the head ran, the ctx then left the persistent path: the last iteration and the metric on the two-kernel path
-      if (int rc = span_end(c, sp)) return rc;
-      c->timed_iters += (uint64_t)head;
-      c->beliefs_valid = true;
+      if (int rc = sp.commit((uint64_t)head)) return rc;
       if (int rc = iterate(c, n - head)) return rc;
       return eval_begin(c);
     }
     if (lrc == GBP_OK) {
-      if (int rc = span_end(c, sp)) return rc;
-      c->timed_iters += (uint64_t)n;
-      c->beliefs_valid = true;
+      if (int rc = sp.commit((uint64_t)n)) return rc;
       HIPCHK(c, hipEventRecord(c->eval_ev[area], c->stream));
       c->eval_per_wave[area] = true;
       c->eval_parity ^= 1;
       c->eval_pending += 1;
       return GBP_OK;
     }
-    c->span_pool.push_back(sp);
     if (lrc != kNotLaunched) return lrc;
   }
   if (int rc = iterate(c, n)) return rc;
@@ -215,184 +224,110 @@ static int eval_each_ride(gbp_ctx* c, int n, gbp_eval_out* out) {
   static_assert(sizeof(gbp_eval_out) == 56, "k_eval_fold writes gbp_eval_out records");
   SweepArgs a = sweep_args(c);
   a.ev = eval_ride(c);
-  gbp_ctx::Span sp{};
-  if (int rc = span_begin(c, sp)) return rc;
+  TimedSpan sp(c);
+  if (int rc = sp.begin()) return rc;
   for (int done = 0; done < n;) {         // pieces of at most ev_depth iterations, queued behind each other: no host wait in between
     const int m = std::min(n - done, (int)c->ev_depth);
     HIPCHK(c, hipMemsetAsync(c->ev_ctl.p, 0, 64, c->stream));      // iteration counter and health words of this piece
-    if (int rc = iterate_plain(c, a, m, true)) { c->span_pool.push_back(sp); return rc; }
+    if (int rc = iterate_plain(c, a, m, true)) return rc;
     launch_eval_ride(a.ev, P<uint32_t>(c->row_cam), P<uint32_t>(c->lmk_idx), P<float4>(c->lmsg), P<float4>(c->fac), P<float>(c->dK), c->stream);
     launch_eval_fold(a.ev, (uint32_t)m, static_cast<gbp_eval_out*>(c->ev_host_dev) + done, c->stream);
     HIPCHK(c, hipGetLastError());
     done += m;
   }
-  if (int rc = span_end(c, sp)) return rc;
-  c->timed_iters += (uint64_t)n;
-  c->beliefs_valid = true;
+  if (int rc = sp.commit((uint64_t)n)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   std::memcpy(out, c->ev_host, sizeof(gbp_eval_out) * (size_t)n);
   return GBP_OK;
 }
 
-// n iterations with the metric after EVERY one of them (the reference's default loop, ba.cpp:1009-1028 / slam.cpp), blocking:
-// out[k] = what gbp_iterate(1) + gbp_eval_global() would have returned for the k-th of them.  On a graph that runs in
-// k_persist a burst is ONE launch: the metric of iteration k rides in the sweep phase of iteration k + 1 (both only read the
-// beliefs), its partial sums go to host-mapped memory.  Everywhere else it is the loop it replaces, two metrics in flight.
-static int iterate_eval_each_impl(gbp_ctx* c, int n, gbp_eval_out* out) {
+// m <= kSeriesMax passes from loop index i in ONE launch of the persistent kernel with the metric after every one of them (blocking):
+// the metric of pass k rides in the sweep phase of pass k + 1 (both only read the beliefs), its partial sums go to host-mapped memory,
+// out[k] = what gbp_iterate(1) + gbp_eval_global() would have returned.  kNotLaunched: nothing ran, or the launch timed out and the state
+// (priors and flags too) was restored to the start of the burst — the caller runs the passes on the two-kernel path.
+static int series_burst(gbp_ctx* c, int m, unsigned i, unsigned steps2, gbp_eval_out* out) {
+  const int area = c->eval_parity & 1;   // both health areas are zero between evaluations; this launch leaves them so
+  const PersistEval metric = persist_eval(c, area, true);
+  TimedSpan sp(c);
+  if (int rc = sp.begin()) return rc;
+  if (int rc = launch_persist_burst(c, sweep_args(c), m, &metric, 2, area, i, steps2)) return rc;
+  if (int rc = sp.end()) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const bool failed = *static_cast<volatile unsigned*>(c->pstatus_host) != 0u;
+  if (int rc = persist_check(c, 0)) return rc;
+  if (failed) return kNotLaunched;
+  if (int rc = sp.commit((uint64_t)m)) return rc;
+  for (int k = 0; k < m; ++k)
+    sum_eval(c, static_cast<const DeviceEval*>(c->series_host) + (size_t)k * metric.stride, eval_blocks(c->n_tiles), out + k, true);
+  return GBP_OK;
+}
+
+// The driver of passes WITH the metric after every one of them (gbp_iterate_eval_each: i0 = steps2 = 0; gbp_ba_loop), blocking:
+// passes i0 .. i0 + n - 1 of the reference's loop (ba.cpp:1001-1028), WEAKEN_PRIORS in front of pass i iff weakens_before(i, steps2),
+// GBP_PROG, the metric.  On a graph that runs in the persistent kernel the passes are launches of at most kSeriesMax (persist_burst):
+// k_persist_flow applies WeakenPriorVertex itself in front of its later passes, only a weakening in front of a launch's first pass is
+// a launch of its own.  Everywhere else — and after a recovered time-out — each run of passes up to the next weakening carries the
+// metric in its sweeps (eval_each_ride), or is the loop it replaces, two metrics in flight.
+static int iterate_passes_eval(gbp_ctx* c, int n, unsigned i0, unsigned steps2, gbp_eval_out* out) {
+  for (int done = 0; done < n;) {
+    const unsigned i = i0 + (unsigned)done;
+    if (weakens_before(i, steps2))
+      if (int rc = weaken_priors(c)) return rc;
+    if (int rc = settle(c)) return rc;
+    bool fused = false;
+    if (eval_blocks(c->n_tiles) == (c->n_tiles + 3) / 4)
+      if (int rc = persist_ready(c, &fused)) return rc;
+    if (fused) {
+      const int m = persist_burst(c, n - done, i, steps2, (int)kSeriesMax);
+      const int rc = series_burst(c, m, i, steps2, out + done);
+      if (rc == GBP_OK) { done += m; continue; }
+      if (rc != kNotLaunched) return rc;
+    }
+    const int m = weakening_free_run(n - done, i, steps2);
+    if (!c->comm && c->world == 1 && c->hoist && !c->profile_stages && !stream_is_capturing(c)) {
+      if (int rc = eval_each_ride(c, m, out + done)) return rc;
+    } else {
+      int collected = done;
+      for (int k = done; k < done + m; ++k) {
+        if (int rc = iterate(c, 1)) return rc;
+        if (int rc = eval_begin(c)) return rc;
+        if (c->eval_pending == 2) { if (int rc = eval_end(c, out + collected)) return rc; ++collected; }
+      }
+      while (collected < done + m) { if (int rc = eval_end(c, out + collected)) return rc; ++collected; }
+    }
+    done += m;
+  }
+  return GBP_OK;
+}
+
+static int iterate_eval_each(gbp_ctx* c, int n, gbp_eval_out* out) {
   if (!c || !c->uploaded) return fail(c, GBP_ERR_STATE, "gbp_iterate_eval_each: upload first");
   if (n < 0 || (n > 0 && !out)) return fail(c, GBP_ERR_INVALID, "gbp_iterate_eval_each: n >= 0 and an array of n results");
   if (c->eval_pending) return fail(c, GBP_ERR_STATE, "gbp_iterate_eval_each: finish the evaluations in flight (gbp_eval_end) first");
   if (int rc = settle(c)) return rc;                  // blocking call: nothing of this ctx stays in flight across it
-  const uint32_t nb = eval_blocks(c->n_tiles);
-  bool fused = false;
-  if (nb == (c->n_tiles + 3) / 4)
-    if (int rc = persist_ready(c, &fused)) return rc;
-  int done = 0;
-  if (fused) {
-    const uint32_t stride = c->n_tiles + 1;          // [0] = health copy, then one record per tile wave
-    if (!c->series_host) {
-      HIPCHK(c, hipHostMalloc(&c->series_host, sizeof(DeviceEval) * (size_t)stride * kSeriesMax, hipHostMallocMapped));
-      HIPCHK(c, hipHostGetDevicePointer(&c->series_dev, c->series_host, 0));
-    }
-    const int area = c->eval_parity & 1;   // both health areas are zero between evaluations; this launch leaves them so
-    while (done < n && fused) {
-      const int m = std::min(n - done, (int)kSeriesMax);
-      PersistEval ev{};
-      ev.on = 1; ev.each = 1; ev.stride = stride;
-      ev.cam_mu = P<float>(c->cam_mu); ev.lmk_mu = P<float>(c->lmk_mu);
-      ev.num_undamped = c->prm.num_undamped_iters;
-      ev.slots = static_cast<DeviceEval*>(c->series_dev);
-      ev.health = P<unsigned long long>(c->health) + 2 * area;
-      ev.health_next = P<unsigned long long>(c->health) + 2 * (area ^ 1);
-      ev.health_each = P<unsigned long long>(c->health);
-      gbp_ctx::Span sp{};
-      if (int rc = span_begin(c, sp)) return rc;
-      const int lrc = launch_persist_burst(c, sweep_args(c), m, &ev, 2, area);
-      if (lrc != GBP_OK) {
-        c->span_pool.push_back(sp);
-        if (lrc != kNotLaunched) return lrc;
-        fused = false;
-        break;
-      }
-      if (int rc = span_end(c, sp)) return rc;
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      const bool failed = *static_cast<volatile unsigned*>(c->pstatus_host) != 0u;
-      if (int rc = persist_check(c, 0)) return rc;      // a time-out: state restored to the start of this burst
-      if (failed) { fused = false; break; }             // ... which the plain loop below now runs
-      c->timed_iters += (uint64_t)m;
-      c->beliefs_valid = true;
-      for (int k = 0; k < m; ++k) sum_eval(c, static_cast<const DeviceEval*>(c->series_host) + (size_t)k * stride, nb, out + done + k, true);
-      done += m;
-    }
-  }
-  if (done < n && !c->comm && c->world == 1 && c->hoist && !c->profile_stages && !stream_is_capturing(c))
-    return eval_each_ride(c, n - done, out + done);
-  int collected = done;
-  for (int k = done; k < n; ++k) {
-    if (int rc = iterate(c, 1)) return rc;
-    if (int rc = eval_begin(c)) return rc;
-    if (c->eval_pending == 2) { if (int rc = eval_end(c, out + collected)) return rc; ++collected; }
-  }
-  while (collected < n) { if (int rc = eval_end(c, out + collected)) return rc; ++collected; }
-  return GBP_OK;
+  return iterate_passes_eval(c, n, 0, 0, out);
 }
 
-// n passes of the body of the reference's iteration loop (ba.cpp:1001-1028) from loop index iter0: WEAKEN_PRIORS in front of pass i
-// iff (i + 1) % 2 == 0 and i < 2 * steps, GBP_PROG, the metric.  On a graph that runs in the persistent kernel the passes between two
-// host events are ONE launch however many weakenings lie between them (k_persist_flow applies WeakenPriorVertex itself, in front of
-// the iterations the loop weakens before; only a weakening in front of a launch's FIRST iteration is a launch of its own);
-// everywhere else — and after a recovered time-out — it is the calls it stands for, in the loop's order.
-static int ba_loop_impl(gbp_ctx* c, int n, unsigned iter0, unsigned steps, gbp_eval_out* out) {
+// n passes of the body of the reference's iteration loop (ba.cpp:1001-1028) from loop index iter0.  Without the metric (out == NULL)
+// not blocking, like gbp_iterate: one iterate_passes call per piece of at most kPersistChunk passes, the weakening in front of a piece
+// a launch of its own, every later one riding in a launch of the persistent kernel or in the belief update of the iteration before it.
+// A sharded ctx, per-stage timing and a caller's capture keep gbp_iterate's own paths: one call per run of passes up to the next weakening.
+static int ba_loop(gbp_ctx* c, int n, unsigned iter0, unsigned steps, gbp_eval_out* out) {
   if (!c || !c->uploaded) return fail(c, GBP_ERR_STATE, "gbp_ba_loop: upload first");
   if (n < 0) return fail(c, GBP_ERR_INVALID, "gbp_ba_loop: n >= 0");
   if (steps >= (1u << 30)) return fail(c, GBP_ERR_INVALID, "gbp_ba_loop: steps < 2^30 (the loop's test is iter < 2 * steps)");
-  const auto weak = [&](unsigned i) { return ((i + 1u) % 2u == 0u) && i < 2u * steps; };
-  if (!out) {
-    // without the metric (out == NULL): not blocking, like gbp_iterate.  The weakening in front of the first pass is a launch of its
-    // own; every later one rides in the launch of the persistent kernel, or — two-kernel path, single-GPU ctx — in the belief update
-    // of the iteration before it.  A sharded ctx takes the calls one by one.
-    int done = 0;
-    while (done < n) {
-      const unsigned i0 = iter0 + (unsigned)done;
-      if (weak(i0))
-        if (int rc = weaken_priors(c)) return rc;
-      if (c->comm || c->world != 1 || c->profile_stages || stream_is_capturing(c)) {      // (per-stage timing and a caller's capture keep their own paths)
-        int m = 1;
-        while (done + m < n && !weak(iter0 + (unsigned)(done + m))) ++m;
-        if (int rc = iterate(c, m)) return rc;
-        done += m;
-        continue;
-      }
-      const int m = std::min(n - done, kPersistChunk);
-      bool persist = false;
-      if (m >= 2 && c->persist_flow && c->flow.lmsg)      // (a single iteration is as fast from two launches: gbp_iterate's rule)
-        if (int rc = persist_ready(c, &persist)) return rc;
-      if (!persist)
-        if (int rc = settle(c)) return rc;
-      gbp_ctx::Span sp{};
-      if (int rc = span_begin(c, sp)) return rc;
-      int lrc = kNotLaunched;
-      if (persist) lrc = launch_persist_burst(c, sweep_args(c), m, nullptr, 0, 0, i0, 2u * steps);
-      if (lrc == kNotLaunched) lrc = iterate_weaken_plain(c, sweep_args(c), m, i0, 2u * steps);
-      if (lrc != GBP_OK) { c->span_pool.push_back(sp); return lrc; }
-      if (int rc = span_end(c, sp)) return rc;
-      c->timed_iters += (uint64_t)m;
-      c->beliefs_valid = true;
-      done += m;
-    }
-    return GBP_OK;
+  const unsigned steps2 = 2u * steps;
+  if (out) {
+    if (c->eval_pending) return fail(c, GBP_ERR_STATE, "gbp_ba_loop: finish the evaluations in flight (gbp_eval_end) first");
+    return iterate_passes_eval(c, n, iter0, steps2, out);
   }
-  if (c->eval_pending) return fail(c, GBP_ERR_STATE, "gbp_ba_loop: finish the evaluations in flight (gbp_eval_end) first");
-  int done = 0;
-  while (done < n) {
-    const unsigned i0 = iter0 + (unsigned)done;
-    if (weak(i0))
+  const bool one_call = !c->comm && c->world == 1 && !c->profile_stages && !stream_is_capturing(c);
+  for (int done = 0; done < n;) {
+    const unsigned i = iter0 + (unsigned)done;
+    if (weakens_before(i, steps2))
       if (int rc = weaken_priors(c)) return rc;
-    bool fused = false;
-    const uint32_t nb = eval_blocks(c->n_tiles);
-    if (int rc = settle(c)) return rc;
-    if (nb == (c->n_tiles + 3) / 4 && c->persist_flow && c->flow.lmsg)
-      if (int rc = persist_ready(c, &fused)) return rc;
-    if (fused) {
-      const uint32_t stride = c->n_tiles + 1;
-      if (!c->series_host) {
-        HIPCHK(c, hipHostMalloc(&c->series_host, sizeof(DeviceEval) * (size_t)stride * kSeriesMax, hipHostMallocMapped));
-        HIPCHK(c, hipHostGetDevicePointer(&c->series_dev, c->series_host, 0));
-      }
-      const int area = c->eval_parity & 1;
-      const int m = std::min(n - done, (int)kSeriesMax);
-      PersistEval ev{};
-      ev.on = 1; ev.each = 1; ev.stride = stride;
-      ev.cam_mu = P<float>(c->cam_mu); ev.lmk_mu = P<float>(c->lmk_mu);
-      ev.num_undamped = c->prm.num_undamped_iters;
-      ev.slots = static_cast<DeviceEval*>(c->series_dev);
-      ev.health = P<unsigned long long>(c->health) + 2 * area;
-      ev.health_next = P<unsigned long long>(c->health) + 2 * (area ^ 1);
-      ev.health_each = P<unsigned long long>(c->health);
-      gbp_ctx::Span sp{};
-      if (int rc = span_begin(c, sp)) return rc;
-      const int lrc = launch_persist_burst(c, sweep_args(c), m, &ev, 2, area, i0, 2u * steps);
-      if (lrc == GBP_OK) {
-        if (int rc = span_end(c, sp)) return rc;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        const bool failed = *static_cast<volatile unsigned*>(c->pstatus_host) != 0u;
-        if (int rc = persist_check(c, 0)) return rc;      // a time-out: state (priors and flags too) restored to the start of this burst
-        if (!failed) {
-          c->timed_iters += (uint64_t)m;
-          c->beliefs_valid = true;
-          for (int k = 0; k < m; ++k) sum_eval(c, static_cast<const DeviceEval*>(c->series_host) + (size_t)k * stride, nb, out + done + k, true);
-          done += m;
-          continue;
-        }
-      } else {
-        c->span_pool.push_back(sp);
-        if (lrc != kNotLaunched) return lrc;
-      }
-    }
-    // the calls the loop stands for, up to (not including) its next weakening
-    int m = 1;
-    while (done + m < n && !weak(iter0 + (unsigned)(done + m))) ++m;
-    if (int rc = iterate_eval_each_impl(c, m, out + done)) return rc;
+    const int m = one_call ? std::min(n - done, kPersistChunk) : weakening_free_run(n - done, i, steps2);
+    if (int rc = one_call ? iterate_passes(c, m, i, steps2) : iterate(c, m)) return rc;
     done += m;
   }
   return GBP_OK;
@@ -404,7 +339,7 @@ GBP_EXPORT(gbp_eval, c, (gbp_ctx* c, gbp_eval_out* o), (c, o)) { return eval(c, 
 GBP_EXPORT(gbp_eval_begin, c, (gbp_ctx* c), (c)) { return eval_begin(c); }
 GBP_EXPORT(gbp_eval_end, c, (gbp_ctx* c, gbp_eval_out* o), (c, o)) { return eval_end(c, o); }
 GBP_EXPORT(gbp_iterate_eval, c, (gbp_ctx* c, int n), (c, n)) { return iterate_eval(c, n); }
-GBP_EXPORT(gbp_iterate_eval_each, c, (gbp_ctx* c, int n, gbp_eval_out* out), (c, n, out)) { return iterate_eval_each_impl(c, n, out); }
+GBP_EXPORT(gbp_iterate_eval_each, c, (gbp_ctx* c, int n, gbp_eval_out* out), (c, n, out)) { return iterate_eval_each(c, n, out); }
 GBP_EXPORT(gbp_ba_loop, c, (gbp_ctx* c, int n, unsigned iter0, unsigned steps, gbp_eval_out* out), (c, n, iter0, steps, out)) {
-  return ba_loop_impl(c, n, iter0, steps, out);
+  return ba_loop(c, n, iter0, steps, out);
 }

@@ -1,6 +1,7 @@
 // gbp_api_launch.cpp — what the programs of the list launch (include/gbp_mi355x.h):
 //   gbp_linearise        LINEARISE_PROG   reference ba/ba.cpp:890-893   belief refresh + k_linearise
-//   gbp_iterate          GBP_PROG x n     ba.cpp:895-905                persistent kernel / hipGraph replay / direct launches
+//   gbp_iterate          GBP_PROG x n     ba.cpp:895-905                persistent kernel / hipGraph replay / direct launches: iterate_passes,
+//                                                                       the driver gbp_ba_loop without the metric shares
 //   gbp_weaken_priors    WEAKEN_PRIORS    ba.cpp:863-865                ONE k_beliefs launch (the prior owners scale on their way into the sums)
 //   gbp_prepare          Engine::load     ba.cpp:936-937                hipGraph capture + instantiation, runs nothing
 // and the split-phase form of the iteration (include/gbp_mi355x_multi.h) for callers that run the exchange themselves.
@@ -54,6 +55,11 @@ BeliefArgs belief_args(gbp_ctx* c) {
   return b;
 }
 
+void weaken_args(gbp_ctx* c, BeliefArgs& b) {
+  b.cam_prior_rw = P<float>(c->camp); b.cam_scale = P<float>(c->cscale); b.cam_wflag = P<uint32_t>(c->cwf);
+  b.lmk_prior_rw = P<float4>(c->lmkp); b.lmk_scale = P<float>(c->lscale); b.lmk_wflag = P<uint32_t>(c->lwf);
+}
+
 
 // camera beliefs from stored partials (single GPU: d_local; multi: recv_dev) + landmark beliefs re-summed.
 // roll = true at the end of an iteration (the sweep has consumed the current means), false for
@@ -62,8 +68,7 @@ int refresh_beliefs_from_partials(gbp_ctx* c, bool roll, bool do_lmk, bool weake
   BeliefArgs b = belief_args(c);
   if (weaken) {
     b.weaken = 1;
-    b.cam_prior_rw = P<float>(c->camp); b.cam_scale = P<float>(c->cscale); b.cam_wflag = P<uint32_t>(c->cwf);
-    b.lmk_prior_rw = P<float4>(c->lmkp); b.lmk_scale = P<float>(c->lscale); b.lmk_wflag = P<uint32_t>(c->lwf);
+    weaken_args(c, b);
   }
   if (!exch(c)) {
     b.gathered = P<float>(c->local); b.world = 1;
@@ -87,8 +92,7 @@ void enqueue_iteration(gbp_ctx* c, const SweepArgs& a, bool ev, bool weaken_afte
   b.roll = 1;
   if (weaken_after) {
     b.weaken = 1;
-    b.cam_prior_rw = P<float>(c->camp); b.cam_scale = P<float>(c->cscale); b.cam_wflag = P<uint32_t>(c->cwf);
-    b.lmk_prior_rw = P<float4>(c->lmkp); b.lmk_scale = P<float>(c->lscale); b.lmk_wflag = P<uint32_t>(c->lwf);
+    weaken_args(c, b);
   }
   if (ev) b.ev = a.ev;
   launch_beliefs(b, true, true, c->stream, ev);
@@ -147,24 +151,55 @@ int iterate_plain(gbp_ctx* c, const SweepArgs& a, int n, bool ev) {
 // front of pass i0 (if any) already done by the caller: a weakening in front of a later pass rides in the belief update of the
 // iteration before it (enqueue_iteration: weaken_after), the runs between them replay from the hipGraph.
 int iterate_weaken_plain(gbp_ctx* c, const SweepArgs& a, int n, unsigned i0, unsigned steps2) {
-  const auto weak = [&](unsigned i) { return ((i + 1u) % 2u == 0u) && i < steps2; };
-  int k = 0;
-  while (k < n) {
-    int run = 0;      // iterations whose successor (inside this call) is not weakened
-    while (k + run < n && !(k + run + 1 < n && weak(i0 + (unsigned)(k + run) + 1u))) ++run;
-    if (run)
-      if (int rc = iterate_plain(c, a, run)) return rc;
-    k += run;
-    if (k < n) {      // ... and the one whose belief update takes the weakened priors
+  for (int k = 0; k < n;) {
+    const int run = weakening_free_run(n - k, i0 + (unsigned)k, steps2);
+    const bool weaken_after = k + run < n;      // the run's last iteration takes the weakened priors in its belief update
+    if (int rc = iterate_plain(c, a, run - (weaken_after ? 1 : 0))) return rc;
+    if (weaken_after) {
       enqueue_iteration(c, a, false, true);
       HIPCHK(c, hipGetLastError());
-      ++k;
     }
+    k += run;
   }
   return GBP_OK;
 }
 
-// GBP_PROG x n (ba.cpp:895-905) on one GPU: inside the persistent kernel (small graphs), else hipGraph replay / direct launches.
+// The driver of passes WITHOUT the metric (gbp_iterate: steps2 = 0; gbp_ba_loop without the metric): passes i0 .. i0 + n - 1 of the
+// reference's loop on a single-GPU ctx, the weakening in front of pass i0 (if any) already done by the caller; not blocking.  Small
+// graphs run them inside the persistent kernel, in launches of at most kPersistChunk passes (a launch cannot be pre-empted) that apply
+// the weakenings in front of their later passes themselves; everything else — and the rest of the passes once the ctx has left the
+// persistent path — runs on the two-kernel path (iterate_weaken_plain).
+int iterate_passes(gbp_ctx* c, int n, unsigned i0, unsigned steps2) {
+  bool persist = false;
+  if (n >= 2)                          // a single iteration is as fast from two launches (measured)
+    if (int rc = persist_ready(c, &persist)) return rc;
+  if (!persist)
+    if (int rc = settle(c)) return rc;
+  const SweepArgs a = sweep_args(c);
+  TimedSpan sp(c);
+  if (int rc = sp.begin()) return rc;
+  int done = 0;
+  while (persist && done < n) {
+    const int m = persist_burst(c, n - done, i0 + (unsigned)done, steps2, kPersistChunk);
+    const int rc = launch_persist_burst(c, a, m, nullptr, 0, 0, i0 + (unsigned)done, steps2);
+    if (rc == kNotLaunched) break;
+    if (rc != GBP_OK) return rc;
+    done += m;
+    if (done < n) {
+      if (weakens_before(i0 + (unsigned)done, steps2))
+        if (int rc2 = weaken_priors(c)) return rc2;
+      if (int rc2 = persist_ready(c, &persist)) return rc2;
+    }
+  }
+  if (done < n) {       // (settle: free unless the ctx has just left the persistent path with launches in flight)
+    if (int rc = settle(c)) return rc;
+    if (int rc = iterate_weaken_plain(c, a, n - done, i0 + (unsigned)done, steps2)) return rc;
+  }
+  HIPCHK(c, hipGetLastError());
+  return sp.commit((uint64_t)n);
+}
+
+// GBP_PROG x n (ba.cpp:895-905).
 int iterate(gbp_ctx* c, int n) {
   if (!c || !c->uploaded) return fail(c, GBP_ERR_STATE, "gbp_iterate: upload first");
   if (n <= 0) return GBP_OK;
@@ -174,26 +209,24 @@ int iterate(gbp_ctx* c, int n) {
   }
   if (c->world > 1)
     return fail(c, GBP_ERR_STATE, "sharded ctx without a communicator: gbp_comm_init first, or use gbp_iterate_begin / exchange / gbp_iterate_end");
-  bool persist = false;
-  if (n >= 2)                          // a single iteration is as fast from two launches (measured)
-    if (int rc = persist_ready(c, &persist)) return rc;
-  if (!persist)
-    if (int rc = settle(c)) return rc;
-  const SweepArgs a = sweep_args(c);
   if (c->stream != c->own_stream && stream_is_capturing(c)) {
     // the caller is capturing its own stream (gbp_set_stream) into a graph: plain kernel launches only — no persistent kernel
     // (host-computed barrier targets), no timing events that would become graph nodes, no capture of our own inside theirs
+    if (int rc = settle(c)) return rc;
+    const SweepArgs a = sweep_args(c);
     for (int i = 0; i < n; ++i) enqueue_iteration(c, a);
     HIPCHK(c, hipGetLastError());
     c->beliefs_valid = true;
     return GBP_OK;
   }
-  gbp_ctx::Span sp{};
-  if (int rc = span_begin(c, sp)) return rc;
   if (c->profile_stages) {
     // Per-stage timing: all n iterations are queued back to back with a hipEvent before / between / after the
     // two kernels, and read after ONE synchronisation, so a bracket holds the kernel (plus the ~1 us
     // dependent-launch gap), not the idle-queue start-up latency a per-iteration sync would add.
+    if (int rc = settle(c)) return rc;
+    const SweepArgs a = sweep_args(c);
+    TimedSpan sp(c);
+    if (int rc = sp.begin()) return rc;
     struct Events {   // freed on every exit path
       std::vector<hipEvent_t> v;
       ~Events() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); }
@@ -217,33 +250,10 @@ int iterate(gbp_ctx* c, int n) {
       HIPCHK(c, hipEventElapsedTime(&b_ms, ev[2 * i + 1], ev[2 * i + 2]));
       c->sweep_ms += a_ms; c->belief_ms += b_ms;
     }
-  } else if (persist) {
-    // small graph: the whole burst in one launch (k_persist); very long bursts in pieces, a launch cannot be pre-empted
-    for (int left = n; left > 0;) {
-      const int m = std::min(left, kPersistChunk);
-      int rc = launch_persist_burst(c, a, m, nullptr, 0, 0);
-      if (rc == GBP_OK) {
-        left -= m;
-        if (left > 0) {
-          rc = persist_ready(c, &persist);
-          if (rc == GBP_OK && !persist) rc = kNotLaunched;
-        }
-      }
-      if (rc == kNotLaunched) {        // the ctx left the persistent path: the rest on the two-kernel path
-        rc = settle(c);
-        if (rc == GBP_OK) rc = iterate_plain(c, a, left);
-        left = 0;
-      }
-      if (rc != GBP_OK) { c->span_pool.push_back(sp); return rc; }
-    }
-  } else {
-    if (int rc = iterate_plain(c, a, n)) { c->span_pool.push_back(sp); return rc; }
+    HIPCHK(c, hipGetLastError());
+    return sp.commit((uint64_t)n);
   }
-  HIPCHK(c, hipGetLastError());
-  if (int rc = span_end(c, sp)) return rc;
-  c->timed_iters += (uint64_t)n;
-  c->beliefs_valid = true;
-  return GBP_OK;
+  return iterate_passes(c, n, 0, 0);
 }
 
 // WEAKEN_PRIORS (ba.cpp:863-865): WeakenPriorVertex on every variable, then prog_ub.

@@ -161,7 +161,8 @@ int persist_setup(gbp_ctx* c, const gbp_params* prm, bool sharded) {
           for (int i = 0; i < 9; ++i) { *dst[i] = q; q += n4[i]; }
           c->flow.health_iter = reinterpret_cast<unsigned long long*>(q);
           // the host-mapped slots of gbp_iterate_eval_each / gbp_ba_loop: here, not inside the first timed burst (pinning 5 MB takes
-          // ~0.5 ms, a twentieth of a default `ba fr1xyz` run)
+          // ~0.5 ms, a twentieth of a default `ba fr1xyz` run).  gbp_create fails without them: every ctx that can reach the
+          // persistent path has them (series_burst relies on it)
           if (!c->series_host) {
             CK(hipHostMalloc(&c->series_host, sizeof(DeviceEval) * (size_t)(c->n_tiles + 1) * kSeriesMax, hipHostMallocMapped), "hipHostMalloc");
             if (rc == GBP_OK) CK(hipHostGetDevicePointer(&c->series_dev, c->series_host, 0), "hipHostGetDevicePointer");
@@ -266,8 +267,7 @@ int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, int n, const PersistEva
   A.b.roll = 1;
   if (w_steps2) {      // WEAKEN_PRIORS inside the launch (gbp_ba_loop)
     A.w_first = w_first; A.w_steps2 = w_steps2;
-    A.b.cam_prior_rw = P<float>(c->camp); A.b.cam_scale = P<float>(c->cscale); A.b.cam_wflag = P<uint32_t>(c->cwf);
-    A.b.lmk_prior_rw = P<float4>(c->lmkp); A.b.lmk_scale = P<float>(c->lscale); A.b.lmk_wflag = P<uint32_t>(c->lwf);
+    weaken_args(c, A.b);
   }
   A.n_tiles = c->n_tiles;
   A.n_iters = n;

@@ -4,10 +4,11 @@
 //   gbp_api_ctx.cpp      life cycle + the host-stream programs: gbp_create / gbp_destroy, WRITE, READ, READ_PRIORS, NEW_KEYFRAME,
 //                        gbp_sync, gbp_set_stream, gbp_timing                                   (ba.cpp:659-937, slam.cpp:913-928)
 //   gbp_api_launch.cpp   what a program launches: LINEARISE, GBP_PROG (hipGraph replay / direct launches), WEAKEN_PRIORS, the
-//                        split-phase iteration                                                 (ba.cpp:863-865,890-905)
+//                        split-phase iteration, and iterate_passes — the driver of passes without the metric (gbp_iterate,
+//                        gbp_ba_loop without the metric)                                       (ba.cpp:863-865,890-905)
 //   gbp_api_persist.cpp  the persistent kernel's launches: co-residency probe, snapshot, log of unvalidated launches, recovery
-//   gbp_api_eval.cpp     the metric on the device (util.cpp:74-144) and the loops that carry it: gbp_eval*, gbp_iterate_eval*,
-//                        gbp_ba_loop                                                           (ba.cpp:1001-1053)
+//   gbp_api_eval.cpp     the metric on the device (util.cpp:74-144): gbp_eval*, gbp_iterate_eval, and iterate_passes_eval — the
+//                        driver of passes with the metric after each (gbp_iterate_eval_each, gbp_ba_loop)  (ba.cpp:1001-1053)
 //   gbp_api_comm.cpp     sharded ctx: communicator glue, the sharded iteration, gbp_eval_global  (ba.cpp:414-417,617-649)
 //   gbp_api_debug.cpp    the test hooks of include/gbp_mi355x_debug.h (test-hooks builds only)
 //
@@ -201,8 +202,23 @@ struct D2H {
 };
 // timing brackets of the iterate calls (read later: gbp_timing, or when the ring is full)
 int resolve_spans(gbp_ctx* c, bool wait);
-int span_begin(gbp_ctx* c, gbp_ctx::Span& sp);
-int span_end(gbp_ctx* c, const gbp_ctx::Span& sp);
+// The bracket of one iterate call.  begin() records its start event; end() its end event, handing the pair to c->spans; commit(n)
+// ends it (unless end() already has), counts n timed iterations and marks the beliefs valid.  A span that was never ended (an
+// error return) gives its events back to c->span_pool.
+class TimedSpan {
+ public:
+  explicit TimedSpan(gbp_ctx* c) : c_(c) {}
+  TimedSpan(const TimedSpan&) = delete;
+  TimedSpan& operator=(const TimedSpan&) = delete;
+  ~TimedSpan() { if (open_) c_->span_pool.push_back(sp_); }
+  int begin();
+  int end();
+  int commit(uint64_t n);
+ private:
+  gbp_ctx* c_;
+  gbp_ctx::Span sp_{};
+  bool open_ = false;
+};
 void drain_sweep_events(gbp_ctx* c);
 // a pair of timing events for per-stage profiling: created (or fails with the ctx's error text)
 int event_pair(gbp_ctx* c, hipEvent_t* a, hipEvent_t* b);
@@ -235,7 +251,22 @@ inline size_t tile_off(uint32_t p, int G, int f) {  // float offset of float f o
 // ---- gbp_api_launch.cpp -----------------------------------------------------------------------------------------------------
 SweepArgs sweep_args(gbp_ctx* c);
 BeliefArgs belief_args(gbp_ctx* c);
+void weaken_args(gbp_ctx* c, BeliefArgs& b);                  // the prior arrays WeakenPriorVertex writes (b.weaken is the caller's)
 void drop_graph(gbp_ctx* c);
+// The reference's loop (ba.cpp:1001-1008) runs WEAKEN_PRIORS in front of pass i iff (i + 1) % 2 == 0 and i < 2 * steps (= steps2).
+inline bool weakens_before(unsigned i, unsigned steps2) { return ((i + 1u) % 2u == 0u) && i < steps2; }
+// passes from loop index i up to (not including) the next weakening after it, at most n
+inline int weakening_free_run(int n, unsigned i, unsigned steps2) {
+  int m = 1;
+  while (m < n && !weakens_before(i + (unsigned)m, steps2)) ++m;
+  return m;
+}
+// passes from loop index i that ONE launch of the persistent kernel takes, at most cap of the n left: a weakening inside the launch
+// needs the tagged-record kernel; the barrier kernel (test-hooks build) takes the passes up to the next weakening
+inline int persist_burst(const gbp_ctx* c, int n, unsigned i, unsigned steps2, int cap) {
+  const int m = c->persist_flow && c->flow.lmsg != nullptr ? n : weakening_free_run(n, i, steps2);
+  return m < cap ? m : cap;
+}
 // camera beliefs from stored partials (single GPU: the local sums; sharded: recv_dev) + landmark beliefs re-summed.  roll = true
 // at the end of an iteration, false for prior-only refreshes (WEAKEN_PRIORS, NEW_KEYFRAME, LINEARISE).
 int refresh_beliefs_from_partials(gbp_ctx* c, bool roll, bool do_lmk = true, bool weaken = false);
@@ -243,6 +274,7 @@ void enqueue_iteration(gbp_ctx* c, const SweepArgs& a, bool ev = false, bool wea
 void enqueue_cam_partials(gbp_ctx* c, float* dst, hipStream_t s = nullptr);
 int iterate_plain(gbp_ctx* c, const SweepArgs& a, int n, bool ev = false);                      // hipGraph replays + remainder
 int iterate_weaken_plain(gbp_ctx* c, const SweepArgs& a, int n, unsigned i0, unsigned steps2);  // the same with the loop's weakenings riding
+int iterate_passes(gbp_ctx* c, int n, unsigned i0, unsigned steps2);  // the driver of passes without the metric (single GPU)
 int iterate(gbp_ctx* c, int n);                              // GBP_PROG x n: persistent kernel / hipGraph / sharded
 int weaken_priors(gbp_ctx* c);                               // WEAKEN_PRIORS
 
