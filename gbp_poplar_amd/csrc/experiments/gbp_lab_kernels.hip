@@ -110,20 +110,10 @@ GBP_DEV void lab_sweep_tile(const SweepArgs& a, const uint32_t wslot) {
                               x0c[0] = m0.x; x0c[1] = m0.y; x0c[2] = m0.z; x0c[3] = m0.w; x0c[4] = m1.x; x0c[5] = m1.y;
                               cam_lin_unpack(q, cl);
                               // landmark side: the mean is RECOMPUTED from the belief record the lane holds anyway — inf2mean3x3
-                              // (bafuncs.cpp:11-15) with the operations k_beliefs used for LMK_MU, so the same bits — instead of
+                              // (bafuncs.cpp:11-15) by lmk_mean, as k_beliefs computes LMK_MU, so the same bits — instead of
                               // gathered: a second random gather (a 128-B line fill per factor for 12 useful bytes) made the
                               // lock-step relinearising sweep move 104 MB more than it has to
-                              float B[9], S3[9];
-                              GBP_UNROLL
-                              for (int i = 0; i < 9; ++i) B[i] = lb[4 + i];
-                              inv3x3(B, S3);
-                              GBP_UNROLL
-                              for (int i = 0; i < 3; ++i) {
-                                float a2 = 0.f;
-                                GBP_UNROLL
-                                for (int k = 0; k < 3; ++k) a2 += S3[i * 3 + k] * lb[k];
-                                x0l[i] = a2;
-                              }
+                              lmk_mean(lb, x0l);
                             });
 
   // ---- outputs --------------------------------------------------------------------------------

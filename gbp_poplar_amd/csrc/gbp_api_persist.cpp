@@ -61,7 +61,7 @@ int persist_setup(gbp_ctx* c, const gbp_params* prm, bool sharded) {
   const int mode = pe ? std::atoi(pe) : c->prm.persistent;
   const char* pc = prm ? nullptr : std::getenv("GBP_PERSIST_COOP");
   const int coop_mode = pc ? std::atoi(pc) : c->prm.persist_coop;  // 1 = cooperative launch, else (default) plain launch + probe + recovery
-  const uint32_t nb = persist_blocks(c->n_tiles, c->C, c->L_loc, true);
+  const uint32_t nb = persist_grid(c->n_tiles, c->C, c->L_loc, true).nb;
   // measured (profiles/persist_crossover.py, round 5): with hand-offs through tagged records the persistent kernel is faster than
   // the two-kernel path on every graph it is co-resident for — the shipped sequences (14 - 61 workgroups) 1.36 - 1.55x, synthetic
   // graphs 1.16 - 1.43x up to 250 workgroups (64 000 factors: 12.2 against 16.2 us per iteration; round 4's barrier kernel broke
@@ -309,7 +309,7 @@ int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, int n, const PersistEva
     g_persist_last_ctx[dev & 15] = c;
     g_persist_last_stream[dev & 15] = c->stream;
   }
-  const unsigned nb = persist_blocks(c->n_tiles, c->C, c->L_loc, ev != nullptr && ev->each != 0);      // the grid launch_persist used
+  const unsigned nb = persist_grid(c->n_tiles, c->C, c->L_loc, ev != nullptr && ev->each != 0).nb;      // the grid launch_persist used
   // arrivals of this launch (n <= kPersistChunk; the counter wraps, grid_sync compares wrap-safe): two hand-offs per iteration — with
   // tagged records none, and ONE barrier at the end of a launch that carries the metric
   c->persist_epoch_base += flow ? (ev ? nb : 0u) : nb * (unsigned)(2 * n - 1 + (ev ? 1 : 0));

@@ -193,7 +193,7 @@ struct PersistFlow {
 // separate = 0: v = wib * nblk + bid (roles and tiles share waves).  separate = 1: the roles are dealt to the waves WITHOUT a tile first
 // (whole workgroups behind the n_tiles / 4 that hold tiles, one role per workgroup before a second one): cameras, then n_met metric
 // means, then landmark groups.  Host and device (gbp_debug_persist_roles evaluates it on the host: tests/test_persist_roles.py).
-#if defined(__HIPCC__) || defined(__CUDACC__)
+#ifdef __HIPCC__
 #define GBP_HD __host__ __device__ inline
 #else
 #define GBP_HD inline
@@ -209,7 +209,8 @@ GBP_HD uint32_t persist_role(uint32_t bid, uint32_t wib, uint32_t nblk, uint32_t
   const uint32_t g = r - n_cams - n_met;
   return g < n_lmk_groups ? n_cams + g : ~0u;                           // no role left for this wave
 }
-// grid of a launch: workgroups, whether the roles are separated, how many metric roles (persist_blocks / launch_persist use it)
+// grid of a launch of the persistent kernel for a graph: workgroups, whether the roles are separated, how many metric roles;
+// with_metric: + one wave per camera for the metric roles where the placement allows
 struct PersistGrid { uint32_t nb, separate, n_met; };
 PersistGrid persist_grid(uint32_t n_tiles, uint32_t n_cams, uint32_t n_lmks, bool with_metric);
 
@@ -218,7 +219,7 @@ struct PersistArgs {
   BeliefArgs b;
   PersistEval ev;
   PersistFlow f;           // f.lmsg != NULL: k_persist_flow (tagged records) instead of k_persist (barriers)
-  uint32_t separate;       // k_persist_flow: 1 = cameras (and metric means) are owned by waves WITHOUT a tile (persist_blocks sized the grid for it)
+  uint32_t separate;       // k_persist_flow: 1 = cameras (and metric means) are owned by waves WITHOUT a tile (persist_grid sized the grid for it)
   uint32_t n_met;          // ... and this many metric roles follow the camera roles (0 or C)
   // WEAKEN_PRIORS inside the launch (gbp_ba_loop): iteration `it` of the launch is loop index w_first + it of the reference's loop
   // (ba.cpp:1001-1008); WeakenPriorVertex runs in front of it iff (w_first + it + 1) % 2 == 0 and w_first + it < w_steps2 — for it >= 1
@@ -258,8 +259,6 @@ void launch_beliefs(BeliefArgs b, bool do_cam, bool do_lmk, hipStream_t s, bool 
 void launch_eval_fold(const EvalRide& ev, uint32_t n_slots, void* out, hipStream_t s);
 // the riding metric of the CURRENT beliefs (a piece's last iteration: no sweep follows) into ring slot counter - 1
 void launch_eval_ride(const EvalRide& ev, const uint32_t* row_cam, const uint32_t* lmk_idx, const float4* lmsg, const float4* fac, const float* K9_dev, hipStream_t s);
-// workgroups of a k_persist launch for a graph; with_metric: + one wave per camera for the metric roles where the placement allows
-uint32_t persist_blocks(uint32_t n_tiles, uint32_t n_cams, uint32_t n_lmks, bool with_metric);
 int persist_max_resident_blocks();                                            // how many of them this GPU keeps resident at once
 // cooperative != 0: hipLaunchCooperativeKernel — the runtime refuses a grid that cannot be co-resident on the device and the
 // driver never runs two cooperative grids (of any process) side by side; 0: plain launch (the creation-time probe vouches for

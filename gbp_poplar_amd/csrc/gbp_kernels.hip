@@ -190,9 +190,38 @@ GBP_DEV void row16_sums_store(const float (&oc_eta)[6], const float (&oc_lam)[36
   }
 }
 
+// The arithmetic of a belief owner, shared by every kernel that updates beliefs (k_beliefs, both persistent kernels) and by the
+// sweep that recomputes a landmark mean: one copy of the operations, so every path produces the same bits.
+// inf2mean3x3 (bafuncs.cpp:11-15) on a 16-float landmark record (eta at 0..2, Lambda at 4..12)
+GBP_DEV void lmk_mean(const float (&rec)[16], float (&x0l)[3]) {
+  float B[9], S3[9];
+  GBP_UNROLL
+  for (int i = 0; i < 9; ++i) B[i] = rec[4 + i];
+  inv3x3(B, S3);
+  GBP_UNROLL
+  for (int i = 0; i < 3; ++i) {
+    float acc = 0.f;
+    GBP_UNROLL
+    for (int k = 0; k < 3; ++k) acc += S3[i * 3 + k] * rec[k];
+    x0l[i] = acc;
+  }
+}
+// the dmu^2 pieces of the next sweep (k_sweep<HOIST>): the camera prefix S (belief slot 6) and the three landmark terms (slots 3, 13, 14)
+GBP_DEV float cam_dmu2(const float (&used)[6], const float (&x0c)[6]) {
+  float S = 0.f;
+  GBP_UNROLL
+  for (int i = 0; i < 6; ++i) S += (used[i] - x0c[i]) * (used[i] - x0c[i]);
+  return S;
+}
+GBP_DEV void lmk_dmu2(const float4 used, const float (&x0l)[3], float (&u)[3]) {
+  u[0] = (used.x - x0l[0]) * (used.x - x0l[0]);
+  u[1] = (used.y - x0l[1]) * (used.y - x0l[1]);
+  u[2] = (used.z - x0l[2]) * (used.z - x0l[2]);
+}
+
 // belief means: inf2mean6x6 / inf2mean3x3 (bafuncs.cpp:2-15) on CAMB / LMKB records
 GBP_DEV void belief_means(const float (&cb)[44], const float (&lb)[16], float (&x0c)[6], float (&x0l)[3]) {
-  float Al[21], S6[36], B[9], S3[9];
+  float Al[21], S6[36];
   GBP_UNROLL
   for (int i = 0; i < 6; ++i) {
     GBP_UNROLL
@@ -206,16 +235,7 @@ GBP_DEV void belief_means(const float (&cb)[44], const float (&lb)[16], float (&
     for (int k = 0; k < 6; ++k) acc += S6[i * 6 + k] * cb[k];
     x0c[i] = acc;
   }
-  GBP_UNROLL
-  for (int i = 0; i < 9; ++i) B[i] = lb[4 + i];
-  inv3x3(B, S3);
-  GBP_UNROLL
-  for (int i = 0; i < 3; ++i) {
-    float acc = 0.f;
-    GBP_UNROLL
-    for (int k = 0; k < 3; ++k) acc += S3[i * 3 + k] * lb[k];
-    x0l[i] = acc;
-  }
+  lmk_mean(lb, x0l);
 }
 
 // Shared body of gbp_codelets.cpp:90-168 and :294-373 on the packed FAC record: accumulate
@@ -766,20 +786,10 @@ GBP_DEV void sweep_tile(const SweepArgs& a, const uint32_t wslot) {
                               x0c[0] = m0.x; x0c[1] = m0.y; x0c[2] = m0.z; x0c[3] = m0.w; x0c[4] = m1.x; x0c[5] = m1.y;
                               cam_lin_unpack(q, cl);
                               // landmark side: the mean is RECOMPUTED from the belief record the lane holds anyway — inf2mean3x3
-                              // (bafuncs.cpp:11-15) with the operations k_beliefs used for LMK_MU, so the same bits — instead of
+                              // (bafuncs.cpp:11-15) by lmk_mean, as k_beliefs computes LMK_MU, so the same bits — instead of
                               // gathered: a second random gather (a 128-B line fill per factor for 12 useful bytes) made the
                               // lock-step relinearising sweep move 104 MB more than it has to
-                              float B[9], S3[9];
-                              GBP_UNROLL
-                              for (int i = 0; i < 9; ++i) B[i] = lb[4 + i];
-                              inv3x3(B, S3);
-                              GBP_UNROLL
-                              for (int i = 0; i < 3; ++i) {
-                                float a2 = 0.f;
-                                GBP_UNROLL
-                                for (int k = 0; k < 3; ++k) a2 += S3[i * 3 + k] * lb[k];
-                                x0l[i] = a2;
-                              }
+                              lmk_mean(lb, x0l);
                             });
 
   // ---- outputs --------------------------------------------------------------------------------
@@ -1011,9 +1021,7 @@ GBP_DEV void beliefs_body(const BeliefArgs& b) {
         float4 u0 = mu[2], u1 = mu[3];
         if (b.roll) { u0 = mu[0]; u1 = mu[1]; mu[2] = u0; mu[3] = u1; }
         const float used[6] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y};
-        float S = 0.f;
-        GBP_UNROLL
-        for (int i = 0; i < 6; ++i) S += (used[i] - x0c[i]) * (used[i] - x0c[i]);
+        const float S = cam_dmu2(used, x0c);
         mu[0] = make_float4(x0c[0], x0c[1], x0c[2], x0c[3]);
         mu[1] = make_float4(x0c[4], x0c[5], 0.f, 0.f);
         sh[j][6] = S;
@@ -1149,23 +1157,12 @@ GBP_DEV void beliefs_body(const BeliefArgs& b) {
     }
     float u[3] = {0.f, 0.f, 0.f};
     if (live && q == 0) {
-      float B[9], S3[9], x0l[3];
-      GBP_UNROLL
-      for (int i = 0; i < 9; ++i) B[i] = rec[4 + i];
-      inv3x3(B, S3);
-      GBP_UNROLL
-      for (int i = 0; i < 3; ++i) {
-        float a2 = 0.f;
-        GBP_UNROLL
-        for (int k = 0; k < 3; ++k) a2 += S3[i * 3 + k] * rec[k];
-        x0l[i] = a2;
-      }
+      float x0l[3];
+      lmk_mean(rec, x0l);
       float4* mu = b.lmk_mu + (size_t)l * 2;  // [0] = mean of the current belief, [1] = mean the last sweep used
       const float4 used = used_mu;
       if (b.roll) mu[1] = used;
-      u[0] = (used.x - x0l[0]) * (used.x - x0l[0]);
-      u[1] = (used.y - x0l[1]) * (used.y - x0l[1]);
-      u[2] = (used.z - x0l[2]) * (used.z - x0l[2]);
+      lmk_dmu2(used, x0l, u);
       mu[0] = make_float4(x0l[0], x0l[1], x0l[2], 0.f);
       if (EV) {   // the belief (eta 3, Lambda 9) for the metric below
         GBP_UNROLL
@@ -1346,6 +1343,115 @@ __global__ __launch_bounds__(256) void k_copy_segments(const CopySegs t, const u
   }
 }
 
+// ---- what the two persistent kernels (k_persist, k_persist_flow) share ----
+// placement (profiles/r03_small_graphs.md): the grid is `spread` times larger than the work; filler workgroups leave at once.
+// spread > 0: workgroup b works iff b % spread == 0;  spread < 0 (s = -spread): iff (b / 8) % s == 0 (every XCD keeps working,
+// every s-th dispatch slot inside an XCD).  false: a filler; true: workgroup bid of the nblk working ones
+GBP_DEV bool persist_place(const PersistArgs& A, uint32_t& bid, uint32_t& nblk) {
+  bid = blockIdx.x; nblk = gridDim.x;
+  if ((int)A.spread > 1) {
+    if (blockIdx.x % A.spread) return false;
+    bid = blockIdx.x / A.spread; nblk = gridDim.x / A.spread;
+  } else if ((int)A.spread < -1) {
+    const uint32_t sp = (uint32_t)(-(int)A.spread), slot = blockIdx.x >> 3;
+    if (slot % sp) return false;
+    bid = (slot / sp) * 8 + (blockIdx.x & 7u); nblk = A.n_work_blocks;
+    if (bid >= nblk) return false;
+  }
+  return true;
+}
+// The wave's 64 landmark-message records through its LDS stage, swizzled as in k_sweep.  In: `ld(k)` is the lane's float4 of the
+// k-th coalesced 1 KiB access; lm receives the lane's own record.
+template <class Ld>
+GBP_DEV void lm_tile_in(float4* stage, uint32_t lane, Ld&& ld, float (&lm)[16]) {
+  const uint32_t rec_t = lane >> 2, swz_own = ((lane >> 2) & 3u) ^ (lane & 2u);
+  GBP_UNROLL
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t r = k * 16 + rec_t;
+    stage[r * 4 + ((lane & 3u) ^ (((r >> 2) & 3u) ^ (r & 2u)))] = ld((uint32_t)k);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  GBP_UNROLL
+  for (int q = 0; q < 4; ++q) {
+    const float4 v = stage[lane * 4 + ((uint32_t)q ^ swz_own)];
+    lm[4 * q] = v.x; lm[4 * q + 1] = v.y; lm[4 * q + 2] = v.z; lm[4 * q + 3] = v.w;
+  }
+}
+// Out: `piece(q)` is float4 #q of the lane's record; `st(k, v)` stores the lane's float4 of the k-th coalesced access.
+template <class Piece, class St>
+GBP_DEV void lm_tile_out(float4* stage, uint32_t lane, Piece&& piece, St&& st) {
+  const uint32_t rec_t = lane >> 2, swz_own = ((lane >> 2) & 3u) ^ (lane & 2u);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  GBP_UNROLL
+  for (int q = 0; q < 4; ++q) stage[lane * 4 + ((uint32_t)q ^ swz_own)] = piece((uint32_t)q);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  GBP_UNROLL
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t r = k * 16 + rec_t;
+    st((uint32_t)k, stage[r * 4 + ((lane & 3u) ^ (((r >> 2) & 3u) ^ (r & 2u)))]);
+  }
+}
+// A tile wave's registers for the whole launch: the potential, the camera messages and — `ld_lm(i4)` = float4 #i4 of LMSG — the
+// landmark messages of tile `tile`
+template <class LdLm>
+GBP_DEV void tile_regs_load(const SweepArgs& a, uint32_t tile, uint32_t lane, float4* stage, LdLm&& ld_lm, float (&fac)[56], float (&cm)[28],
+                            float (&lm)[16]) {
+  load_tile<kFacG, false>(a.fac, tile, lane, fac);
+  load_tile<kCmsgG, false>(a.cmsg, tile, lane, cm);
+  lm_tile_in(stage, lane, [&](uint32_t k) { return ld_lm(tile * 256u + k * 64u + lane); }, lm);
+}
+// behind factor_update: the factor's scalar state into the pad slots of its new landmark message ol; both new messages become the
+// registers the next iteration starts from
+GBP_DEV void tile_regs_refresh(float (&ol)[16], const float (&oc_eta)[6], const float (&oc_lam)[36], float damping, int count, uint32_t flags,
+                               float var, float (&lm)[16], float (&cm)[28]) {
+  ol[3] = damping;
+  ol[13] = __int_as_float((int)(((uint32_t)count << 3) | flags));
+  ol[14] = var;
+  GBP_UNROLL
+  for (int i = 0; i < 16; ++i) lm[i] = ol[i];
+  GBP_UNROLL
+  for (int i = 0; i < 6; ++i) cm[i] = oc_eta[i];
+  GBP_UNROLL
+  for (int i = 0; i < 6; ++i) {
+    GBP_UNROLL
+    for (int j = 0; j <= i; ++j) cm[6 + tri(i, j)] = oc_lam[i * 6 + j];
+  }
+  cm[27] = 0.f;
+}
+// what stayed in registers goes back to its arrays
+GBP_DEV void tile_regs_store(const SweepArgs& a, uint32_t tile, uint32_t lane, const float (&cm)[28], const float (&fac)[56], bool fac_dirty) {
+  store_tile<kCmsgG, false>(a.cmsg, tile, lane, cm);
+  if (fac_dirty) store_tile<kFacG, false>(a.fac, tile, lane, fac);
+}
+// the metric record of a tile wave (DeviceEval slot 1 + wave): its residual sums (zero where the factor is not active) through the lane
+// tree of eval_wave_tree, the counts of ITS factors' flags (packed: the state word as the evaluated sweep left it) through ballots
+GBP_DEV void eval_wave_record(DeviceEval* slot, uint32_t lane, int packed, int num_undamped, double s_norm, double s_half) {
+  const uint32_t flags = (uint32_t)packed & 7u;
+  const bool pad = (flags & kFlagPad) != 0;
+  eval_wave_tree(s_norm, s_half);
+  const unsigned long long n_act = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(!pad && (flags & kFlagActive) != 0));
+  const unsigned long long n_rel = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(!pad && (packed >> 3) == -num_undamped));
+  const unsigned long long n_rob = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(!pad && (flags & kFlagRobust) != 0));
+  if (lane == 0) {
+    DeviceEval o;
+    o.sum_norm = s_norm; o.sum_half_sq = s_half; o.n_active = n_act; o.n_relin = n_rel; o.n_robust = n_rob; o.pad = 0;
+    *slot = o;
+  }
+}
+// the health words h[0..1] of a metric into its host slot (slot [0] of the metric), and h back to zero for the next one
+GBP_DEV void health_handoff(DeviceEval* slots, unsigned long long* h) {
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(slots);
+  out[0] = __hip_atomic_load(&h[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  out[1] = __hip_atomic_load(&h[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&h[0], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&h[1], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 #ifdef GBP_BUILD_TEST_HOOKS
 #include "hooks/gbp_persist_barrier.hip"      // k_persist<EV>: the barrier kernel of rounds 3-4 (reference of the tests, A/B runs)
 #endif
@@ -1408,16 +1514,8 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
   const PersistFlow& F = A.f;
   const uint32_t wib = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (__hip_atomic_load(A.sync + 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;      // (see k_persist)
-  uint32_t bid = blockIdx.x, nblk = gridDim.x;
-  if ((int)A.spread > 1) {
-    if (blockIdx.x % A.spread) return;
-    bid = blockIdx.x / A.spread; nblk = gridDim.x / A.spread;
-  } else if ((int)A.spread < -1) {
-    const uint32_t sp = (uint32_t)(-(int)A.spread), slot = blockIdx.x >> 3;
-    if (slot % sp) return;
-    bid = (slot / sp) * 8 + (blockIdx.x & 7u); nblk = A.n_work_blocks;
-    if (bid >= nblk) return;
-  }
+  uint32_t bid, nblk;
+  if (!persist_place(A, bid, nblk)) return;
   const uint32_t w = bid * 4 + wib;
   __shared__ float4 lm_stage[4][64 * 4];
   __shared__ float sh[4][48];
@@ -1435,7 +1533,6 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
   // ---- phase-A role: sweep tile w; the factor's potential and both of its messages stay in registers ----
   const bool has_tile = w < A.n_tiles;
   const uint32_t tile = has_tile ? w : 0u, p = tile * 64 + lane;
-  const uint32_t rec_t = lane >> 2, swz_own = ((lane >> 2) & 3u) ^ (lane & 2u);
   const uint32_t lm_tile4 = tile * 256u;
   float fac[56], cm[28], lm[16];
   uint32_t cam_i = 0, lmk_i = 0;
@@ -1443,21 +1540,7 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
   if (has_tile) {
     cam_i = a.row_cam[p >> 4];
     lmk_i = a.lmk_idx[p];
-    load_tile<kFacG, false>(a.fac, tile, lane, fac);
-    load_tile<kCmsgG, false>(a.cmsg, tile, lane, cm);
-    GBP_UNROLL
-    for (int k = 0; k < 4; ++k) {   // the wave's 64 landmark-message records: coalesced, transposed through LDS (see k_sweep)
-      const uint32_t r = k * 16 + rec_t;
-      stage[r * 4 + ((lane & 3u) ^ (((r >> 2) & 3u) ^ (r & 2u)))] = a.lmsg[lm_tile4 + (uint32_t)k * 64u + lane];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    GBP_UNROLL
-    for (int q = 0; q < 4; ++q) {
-      const float4 v = stage[lane * 4 + ((uint32_t)q ^ swz_own)];
-      lm[4 * q] = v.x; lm[4 * q + 1] = v.y; lm[4 * q + 2] = v.z; lm[4 * q + 3] = v.w;
-    }
+    tile_regs_load(a, tile, lane, stage, [&](uint32_t i4) { return a.lmsg[i4]; }, fac, cm, lm);
   }
   float K[9];
   GBP_UNROLL
@@ -1556,18 +1639,8 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
   auto metric = [&](uint32_t kk, int packed, const float (&R)[9], const float (&t)[3], const float (&lmu)[3]) {
     double s_norm = 0, s_half = 0;
     const uint32_t flags = (uint32_t)packed & 7u;
-    const bool pad = (flags & kFlagPad) != 0, active = !pad && (flags & kFlagActive) != 0;
-    if (active) eval_residual(R, t, lmu, fac[54], fac[55], a.K, s_norm, s_half);
-    DeviceEval* slots = A.ev.slots + (size_t)(A.ev.each ? kk : 0u) * A.ev.stride;
-    eval_wave_tree(s_norm, s_half);      // the lane tree of every metric, then one record per wave
-    const unsigned long long n_act = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(active));
-    const unsigned long long n_rel = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(!pad && (packed >> 3) == -A.ev.num_undamped));
-    const unsigned long long n_rob = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(!pad && (flags & kFlagRobust) != 0));
-    if (lane == 0) {
-      DeviceEval o;
-      o.sum_norm = s_norm; o.sum_half_sq = s_half; o.n_active = n_act; o.n_relin = n_rel; o.n_robust = n_rob; o.pad = 0;
-      slots[1 + w] = o;
-    }
+    if (!(flags & kFlagPad) && (flags & kFlagActive)) eval_residual(R, t, lmu, fac[54], fac[55], a.K, s_norm, s_half);
+    eval_wave_record(A.ev.slots + (size_t)(A.ev.each ? kk : 0u) * A.ev.stride + 1 + w, lane, packed, A.ev.num_undamped, s_norm, s_half);
   };
   // the tile wave's share of metric kk (means of iteration kk: half kk & 1, tag0 + kk + 1): c0 / c1 / l0 were loaded early, re-loaded here
   // only if they had not arrived then
@@ -1671,23 +1744,11 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
                                cam_lin_unpack(clq, cl);
                              });
       fac_dirty = fac_dirty || (active && relin);
-      ol[3] = damping;
-      ol[13] = __int_as_float((int)(((uint32_t)count << 3) | flags));
-      ol[14] = var;
+      tile_regs_refresh(ol, oc_eta, oc_lam, damping, count, flags, var, lm, cm);
       // the tagged landmark messages: eta | Lambda row 0 | row 1 | row 2, through the LDS transpose of k_sweep (coalesced stores)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      stage[lane * 4 + (0u ^ swz_own)] = flow_rec(ol[0], ol[1], ol[2], t_out);
-      GBP_UNROLL
-      for (int q = 1; q < 4; ++q) stage[lane * 4 + ((uint32_t)q ^ swz_own)] = flow_rec(ol[1 + 3 * q], ol[2 + 3 * q], ol[3 + 3 * q], t_out);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      GBP_UNROLL
-      for (int k = 0; k < 4; ++k) {
-        const uint32_t r = k * 16 + rec_t;
-        S_lmsg.st4(h_out * Ep * 4u + lm_tile4 + (uint32_t)k * 64u + lane, stage[r * 4 + ((lane & 3u) ^ (((r >> 2) & 3u) ^ (r & 2u)))]);
-      }
+      lm_tile_out(stage, lane,
+                  [&](uint32_t q) { return q == 0u ? flow_rec(ol[0], ol[1], ol[2], t_out) : flow_rec(ol[1 + 3 * q], ol[2 + 3 * q], ol[3 + 3 * q], t_out); },
+                  [&](uint32_t k, float4 v) { S_lmsg.st4(h_out * Ep * 4u + lm_tile4 + k * 64u + lane, v); });
       {  // camera half of the belief reduction: per-row tree sums (row16_sums_store), the holder's twelve floats as four tagged records
         float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0, g2 = g0;
         row16_sums_store(oc_eta, oc_lam, lane, [&](uint32_t g, float4 x) {
@@ -1703,31 +1764,9 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
           if (q < 3u) S_rowp.st4(rp + 3u, flow_rec(g2.y, g2.z, g2.w, t_out));
         }
       }
-      if (last) {   // the ordinary LMSG tile (with the factor's scalars in its pad slots), as k_sweep leaves it
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        GBP_UNROLL
-        for (int q = 0; q < 4; ++q)
-          stage[lane * 4 + ((uint32_t)q ^ swz_own)] = make_float4(ol[4 * q], ol[4 * q + 1], ol[4 * q + 2], ol[4 * q + 3]);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        GBP_UNROLL
-        for (int k = 0; k < 4; ++k) {
-          const uint32_t r = k * 16 + rec_t;
-          a.lmsg[lm_tile4 + (uint32_t)k * 64u + lane] = stage[r * 4 + ((lane & 3u) ^ (((r >> 2) & 3u) ^ (r & 2u)))];
-        }
-      }
-      GBP_UNROLL
-      for (int i = 0; i < 16; ++i) lm[i] = ol[i];
-      GBP_UNROLL
-      for (int i = 0; i < 6; ++i) cm[i] = oc_eta[i];
-      GBP_UNROLL
-      for (int i = 0; i < 6; ++i) {
-        GBP_UNROLL
-        for (int j = 0; j <= i; ++j) cm[6 + tri(i, j)] = oc_lam[i * 6 + j];
-      }
-      cm[27] = 0.f;
+      if (last)   // the ordinary LMSG tile (with the factor's scalars in its pad slots), as k_sweep leaves it
+        lm_tile_out(stage, lane, [&](uint32_t q) { return make_float4(ol[4 * q], ol[4 * q + 1], ol[4 * q + 2], ol[4 * q + 3]); },
+                    [&](uint32_t k, float4 v) { a.lmsg[lm_tile4 + k * 64u + lane] = v; });
     }
 
     // ================= phase B: the belief update (arithmetic of k_beliefs, roll = 1) =================
@@ -1841,9 +1880,7 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
         for (int i = 0; i < 44; ++i) cb[i] = sh[wib][i];
         cam_mean(cb, x0c);
         const float used[6] = {cam_cur0.x, cam_cur0.y, cam_cur0.z, cam_cur0.w, cam_cur1.x, cam_cur1.y};
-        float S = 0.f;
-        GBP_UNROLL
-        for (int i = 0; i < 6; ++i) S += (used[i] - x0c[i]) * (used[i] - x0c[i]);
+        const float S = cam_dmu2(used, x0c);
         if (last) { b.cam_mu[(size_t)v * 4 + 2] = cam_cur0; b.cam_mu[(size_t)v * 4 + 3] = cam_cur1; }
         cam_cur0 = make_float4(x0c[0], x0c[1], x0c[2], x0c[3]);
         cam_cur1 = make_float4(x0c[4], x0c[5], 0.f, 0.f);
@@ -1978,21 +2015,10 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
       }
       float u[3] = {0.f, 0.f, 0.f};
       if (lmk_live && q4 == 0) {
-        float B[9], S3[9], x0l[3];
-        GBP_UNROLL
-        for (int i = 0; i < 9; ++i) B[i] = rec[4 + i];
-        inv3x3(B, S3);
-        GBP_UNROLL
-        for (int i = 0; i < 3; ++i) {
-          float a2 = 0.f;
-          GBP_UNROLL
-          for (int k = 0; k < 3; ++k) a2 += S3[i * 3 + k] * rec[k];
-          x0l[i] = a2;
-        }
+        float x0l[3];
+        lmk_mean(rec, x0l);
         const float4 used = lmk_cur;
-        u[0] = (used.x - x0l[0]) * (used.x - x0l[0]);
-        u[1] = (used.y - x0l[1]) * (used.y - x0l[1]);
-        u[2] = (used.z - x0l[2]) * (used.z - x0l[2]);
+        lmk_dmu2(used, x0l, u);
         lmk_cur = make_float4(x0l[0], x0l[1], x0l[2], 0.f);
         S_lmu.st4(h_out * nL + l, flow_rec(x0l[0], x0l[1], x0l[2], t_out));
         S_lmkb.st4((h_out * nL + l) * kFlowLmk4 + 4u, flow_rec(u[0], u[1], u[2], t_out));
@@ -2028,11 +2054,7 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
       if (!metric_of((uint32_t)it - 1u, ev_packed, ev_c, ev_l0)) return;
   }
 
-  // ---- what stayed in registers goes back to its arrays ----
-  if (has_tile) {
-    store_tile<kCmsgG, false>(a.cmsg, tile, lane, cm);
-    if (fac_dirty) store_tile<kFacG, false>(a.fac, tile, lane, fac);
-  }
+  if (has_tile) tile_regs_store(a, tile, lane, cm, fac, fac_dirty);
 
   // ---- the metric of the last iteration; then the launch's ONE barrier: behind it every owner has counted and block 0 hands the
   // health words of every metric of the launch to the host's slots (and leaves them zero) ----
@@ -2045,20 +2067,9 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
     grid_sync(A.sync, A.epoch_base + nblk, A.status, A.seq);
     if (bid == 0 && (threadIdx.x == 0 || A.ev.each)) {
       if (A.ev.each) {
-        for (int kk = (int)threadIdx.x; kk < A.n_iters; kk += 256) {
-          unsigned long long* out = reinterpret_cast<unsigned long long*>(A.ev.slots + (size_t)kk * A.ev.stride);
-          unsigned long long* h = F.health_iter + 2 * kk;
-          out[0] = __hip_atomic_load(&h[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          out[1] = __hip_atomic_load(&h[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(&h[0], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(&h[1], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        for (int kk = (int)threadIdx.x; kk < A.n_iters; kk += 256) health_handoff(A.ev.slots + (size_t)kk * A.ev.stride, F.health_iter + 2 * kk);
       } else {
-        unsigned long long* out = reinterpret_cast<unsigned long long*>(A.ev.slots);
-        out[0] = __hip_atomic_load(&A.ev.health[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        out[1] = __hip_atomic_load(&A.ev.health[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&A.ev.health[0], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (both areas zero behind every metric: see k_eval)
-        __hip_atomic_store(&A.ev.health[1], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        health_handoff(A.ev.slots, A.ev.health);      // (both areas zero behind every metric: see k_eval)
         A.ev.health_next[0] = 0ull; A.ev.health_next[1] = 0ull;
       }
     }
@@ -2332,7 +2343,7 @@ int lab_persist_spread(int spread);
 
 bool persist_probe(uint32_t n_tiles, uint32_t n_cams, uint32_t n_lmks, unsigned* sync, unsigned* status_dev, volatile unsigned* status_host,
                    bool cooperative, hipStream_t s) {
-  const uint32_t nb = persist_blocks(n_tiles, n_cams, n_lmks, true);     // the larger of the two grids this graph is launched with
+  const uint32_t nb = persist_grid(n_tiles, n_cams, n_lmks, true).nb;     // the larger of the two grids this graph is launched with
   const int spread = persist_spread(nb);
   if (hipMemsetAsync(sync, 0, kPersistSyncWords * sizeof(unsigned), s) != hipSuccess) return false;
   // 96 KiB of dynamic LDS per workgroup: at most ONE workgroup per CU (160 KiB), like k_persist's ~450 registers per lane
@@ -2354,39 +2365,31 @@ bool persist_probe(uint32_t n_tiles, uint32_t n_cams, uint32_t n_lmks, unsigned*
   return ok;
 }
 
-// role separation of k_persist_flow (PersistArgs.separate): the grid has a tile-less wave for every camera (and metric mean) as long
-// as that still is at most one workgroup per CU (0: it is not — roles and tiles share waves as in k_persist).  Measured
+// Workgroups of a launch.  Role separation of k_persist_flow (PersistArgs.separate): the grid has a tile-less wave for every camera (and
+// metric mean) as long as that still is at most one workgroup per CU (else roles and tiles share waves as in k_persist).  Measured
 // (profiles/r05_persist_flow.md): with the metric after every iteration fr1xyz 13.1 -> 12.3 us per iteration, fr2robot2 12.3 -> 11.4,
 // fr1desk unchanged; plain bursts 0.1 - 0.2 us faster.
-static uint32_t persist_blocks_separate(uint32_t n_tiles, uint32_t n_cams, uint32_t n_lmks, bool with_metric) {
+PersistGrid persist_grid(uint32_t n_tiles, uint32_t n_cams, uint32_t n_lmks, bool with_metric) {
   const uint64_t cx = (uint64_t)n_cams * (with_metric ? 2u : 1u), g = ((uint64_t)n_lmks + 15) / 16;
+  const uint32_t n_met = with_metric ? n_cams : 0u;
   // with the metric after every iteration the landmark owners move off the tile waves too where that fits (their fp64 metric solves,
   // and on graphs with landmarks of > 30 factors their extra rounds of loads, then delay no sweep: fr1desk 13.6 -> 12.5 us per
   // iteration, fr1xyz 12.3 -> 12.2, fr2robot2 11.4 -> 11.5; plain bursts do not gain from it)
-  const uint64_t waves_full = (uint64_t)n_tiles + cx + g;
-  if (with_metric && (waves_full + 3) / 4 <= 256u) return (uint32_t)((waves_full + 3) / 4);
-  const uint64_t waves = n_tiles + cx > cx + g ? n_tiles + cx : cx + g;
-  const uint64_t nb = (waves + 3) / 4;
-  return nb <= 256u ? (uint32_t)nb : 0u;
-}
-PersistGrid persist_grid(uint32_t n_tiles, uint32_t n_cams, uint32_t n_lmks, bool with_metric) {
-  const uint32_t nbs = persist_blocks_separate(n_tiles, n_cams, n_lmks, with_metric);
-  if (nbs) return PersistGrid{nbs, 1u, with_metric ? n_cams : 0u};
-  return PersistGrid{persist_blocks(n_tiles, n_cams, n_lmks, with_metric), 0u, 0u};
-}
-uint32_t persist_blocks(uint32_t n_tiles, uint32_t n_cams, uint32_t n_lmks, bool with_metric) {
-  if (const uint32_t nbs = persist_blocks_separate(n_tiles, n_cams, n_lmks, with_metric)) return nbs;
-  const uint64_t waves_b = (uint64_t)n_cams + ((uint64_t)n_lmks + 15) / 16;
+  const uint64_t nb_full = ((uint64_t)n_tiles + cx + g + 3) / 4;
+  const uint64_t nb_sep = with_metric && nb_full <= 256u ? nb_full : ((n_tiles + cx > cx + g ? n_tiles + cx : cx + g) + 3) / 4;
+  if (nb_sep != 0u && nb_sep <= 256u) return PersistGrid{(uint32_t)nb_sep, 1u, n_met};
+  // roles and tiles share waves
+  const uint64_t waves_b = (uint64_t)n_cams + g;
   const uint64_t waves = waves_b > n_tiles ? waves_b : n_tiles;
   const uint32_t nb = (uint32_t)((waves + 3) / 4);
-  if (!with_metric) return nb;
+  if (!with_metric) return PersistGrid{nb, 0u, 0u};
   // a launch that carries the metric after EVERY iteration gets one more wave per camera for the metric roles: fr1xyz 52 -> 56
   // workgroups, fr2robot2 19 -> 24, fr1desk 61 -> 77 (every 2nd dispatch slot instead of every 4th; without barriers more workgroups cost
   // nothing: 16.3 -> 13.9 us per iteration with the metric, round 5) — as long as the larger grid still is one workgroup per CU.
   // Launches without the metric keep the smaller grid.
   const uint64_t waves_m = waves_b + n_cams > n_tiles ? waves_b + n_cams : n_tiles;
   const uint32_t nb_m = (uint32_t)((waves_m + 3) / 4);
-  return nb_m <= 256u ? nb_m : nb;
+  return PersistGrid{nb_m <= 256u ? nb_m : nb, 0u, 0u};
 }
 int persist_max_resident_blocks() {
   int dev = 0, per_cu = 0;
@@ -2403,7 +2406,8 @@ void launch_copy_segments(const CopySegs& t, const unsigned* guard, hipStream_t 
 }
 hipError_t launch_persist(PersistArgs A, bool cooperative, hipStream_t s) {
   A.n_lmk_groups = (A.b.n_lmks + 15) / 16;
-  const uint32_t nb = persist_blocks(A.n_tiles, A.b.n_cams, A.b.n_lmks, A.ev.on != 0 && A.ev.each != 0);   // (one final metric: not worth 4 more workgroups in every barrier)
+  const PersistGrid pg = persist_grid(A.n_tiles, A.b.n_cams, A.b.n_lmks, A.ev.on != 0 && A.ev.each != 0);   // (one final metric: not worth 4 more workgroups in every barrier)
+  const uint32_t nb = pg.nb;
   // Placement: the grid is 4x the work and only every 4th workgroup works (the fillers leave at once).  Measured
   // (profiles/persist_placement.py, profiles/r03_small_graphs.md): with the working workgroups in consecutive dispatch slots a
   // few of them — always all four waves of a workgroup, on a CU next to another working CU — run their fp64-heavy sections
@@ -2417,11 +2421,8 @@ hipError_t launch_persist(PersistArgs A, bool cooperative, hipStream_t s) {
 #endif
   A.n_work_blocks = nb;
   A.spread = (uint32_t)spread;
-  {
-    const PersistGrid pg = persist_grid(A.n_tiles, A.b.n_cams, A.b.n_lmks, A.ev.on != 0 && A.ev.each != 0);
-    A.separate = pg.separate;
-    A.n_met = pg.n_met;
-  }
+  A.separate = pg.separate;
+  A.n_met = pg.n_met;
   const uint32_t grid = spread > 1 ? nb * (uint32_t)spread : spread < -1 ? ((nb + 7) / 8) * (uint32_t)(-spread) * 8 : nb;
   const bool flow = A.f.lmsg != nullptr;      // hand-offs through tagged records (PersistFlow); without: the barrier kernel of the test-hooks build
   const void* f = A.ev.on ? reinterpret_cast<const void*>(k_persist_flow<true>) : reinterpret_cast<const void*>(k_persist_flow<false>);

@@ -16,19 +16,8 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
   // an earlier launch of this ctx gave up at a barrier: the state is not what this launch expects — touch nothing (the host
   // restores the snapshot and replays; every workgroup reads the same word before anyone could write it in THIS launch)
   if (__hip_atomic_load(A.sync + 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;
-  // placement (profiles/r03_small_graphs.md): the grid is `spread` times larger than the work; filler workgroups leave at once.
-  // spread > 0: workgroup b works iff b % spread == 0;  spread < 0 (s = -spread): iff (b / 8) % s == 0 (every XCD keeps working,
-  // every s-th dispatch slot inside an XCD)
-  uint32_t bid = blockIdx.x, nblk = gridDim.x;
-  if ((int)A.spread > 1) {
-    if (blockIdx.x % A.spread) return;
-    bid = blockIdx.x / A.spread; nblk = gridDim.x / A.spread;
-  } else if ((int)A.spread < -1) {
-    const uint32_t sp = (uint32_t)(-(int)A.spread), slot = blockIdx.x >> 3;
-    if (slot % sp) return;
-    bid = (slot / sp) * 8 + (blockIdx.x & 7u); nblk = A.n_work_blocks;
-    if (bid >= nblk) return;
-  }
+  uint32_t bid, nblk;
+  if (!persist_place(A, bid, nblk)) return;
   const uint32_t w = bid * 4 + wib;                           // wave of the grid
   __shared__ float4 lm_stage[4][64 * 4];
   __shared__ float sh[4][48];
@@ -39,7 +28,6 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
   // ---- phase-A role: sweep tile w.  State that only this lane ever touches lives in registers for the whole launch.
   const bool has_tile = w < A.n_tiles;
   const uint32_t tile = has_tile ? w : 0u, p = tile * 64 + lane;
-  const uint32_t rec_t = lane >> 2, swz_own = ((lane >> 2) & 3u) ^ (lane & 2u);
   const uint32_t lm_tile4 = tile * 256u;                        // first float4 of the wave's 64 landmark-message records
   float fac[56], cm[28], lm[16];
   uint32_t cam_i = 0, lmk_i = 0;
@@ -47,21 +35,7 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
   if (has_tile) {
     cam_i = a.row_cam[p >> 4];
     lmk_i = a.lmk_idx[p];
-    load_tile<kFacG, false>(a.fac, tile, lane, fac);
-    load_tile<kCmsgG, false>(a.cmsg, tile, lane, cm);
-    GBP_UNROLL
-    for (int k = 0; k < 4; ++k) {   // the wave's 64 landmark-message records: coalesced, transposed through LDS (see k_sweep)
-      const uint32_t r = k * 16 + rec_t;
-      stage[r * 4 + ((lane & 3u) ^ (((r >> 2) & 3u) ^ (r & 2u)))] = X_lmsg.ld4(lm_tile4 + (uint32_t)k * 64u + lane);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    GBP_UNROLL
-    for (int q = 0; q < 4; ++q) {
-      const float4 v = stage[lane * 4 + ((uint32_t)q ^ swz_own)];
-      lm[4 * q] = v.x; lm[4 * q + 1] = v.y; lm[4 * q + 2] = v.z; lm[4 * q + 3] = v.w;
-    }
+    tile_regs_load(a, tile, lane, stage, [&](uint32_t i4) { return X_lmsg.ld4(i4); }, fac, cm, lm);
   }
   float K[9];
   GBP_UNROLL
@@ -73,7 +47,7 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
   // numbered ACROSS the workgroups (v = wave-in-workgroup * workgroups + workgroup): the camera waves, whose lane 0 runs long
   // serial fp64 chains when the metric rides along, land one per CU instead of four
   // Third kind of role, used only while the metric rides in the launch: waves [C + G, 2C + G) — where the grid has them
-  // (persist_blocks) — take the METRIC mean of camera v - (C + G): they sum the camera's rows themselves (same loads, same
+  // (persist_grid) — take the METRIC mean of camera v - (C + G): they sum the camera's rows themselves (same loads, same
   // order: same belief) and run the fp64 pivoted solve + the fp64 LDL check that would otherwise sit behind the hoisted mean
   // and CAM_LIN on the camera wave's single working lane (belief phase of a camera wave 6.1 us, of everyone else <= 4.0 us:
   // profiles/r04_small_graphs.md).
@@ -139,44 +113,16 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
   const uint32_t emc_half = b.n_cams * 6u, eml_half = b.n_lmks * 3u;
   auto health_of = [&](uint32_t k) -> unsigned long long* { return A.ev.each ? A.ev.health_each + 2u * (k & 1u) : A.ev.health; };
   auto metric = [&](uint32_t k, int packed, const float (&cmv)[6], const float (&lmu)[3]) {
-    double s_norm = 0, s_half = 0;
-    unsigned long long n_act = 0, n_rel = 0, n_rob = 0;
-    if (has_tile) {
-      const uint32_t flags = (uint32_t)packed & 7u;
-      if (!(flags & kFlagPad)) {
-        if (flags & kFlagRobust) ++n_rob;
-        if ((packed >> 3) == -A.ev.num_undamped) ++n_rel;
-        if (flags & kFlagActive) {
-          eval_factor(cmv, lmu, fac[54], fac[55], a.K, s_norm, s_half);
-          ++n_act;
-        }
-      }
-    }
     DeviceEval* slots = A.ev.slots + (size_t)(A.ev.each ? k : 0u) * A.ev.stride;
-    if (has_tile) {     // the lane tree of eval_wave_tree, then one record per wave
-      for (int off = 32; off > 0; off >>= 1) {
-        s_norm += __shfl_down(s_norm, off);
-        s_half += __shfl_down(s_half, off);
-        n_act += __shfl_down(n_act, off);
-        n_rel += __shfl_down(n_rel, off);
-        n_rob += __shfl_down(n_rob, off);
-      }
-      if (lane == 0) {
-        DeviceEval o;
-        o.sum_norm = s_norm; o.sum_half_sq = s_half; o.n_active = n_act; o.n_relin = n_rel; o.n_robust = n_rob; o.pad = 0;
-        slots[1 + w] = o;
-      }
+    if (has_tile) {
+      double s_norm = 0, s_half = 0;
+      const uint32_t flags = (uint32_t)packed & 7u;
+      if (!(flags & kFlagPad) && (flags & kFlagActive)) eval_factor(cmv, lmu, fac[54], fac[55], a.K, s_norm, s_half);
+      eval_wave_record(slots + 1 + w, lane, packed, A.ev.num_undamped, s_norm, s_half);
     }
-    if (bid == 0 && threadIdx.x == 0) {
-      unsigned long long* h = health_of(k);
-      unsigned long long* out = reinterpret_cast<unsigned long long*>(slots);
-      out[0] = __hip_atomic_load(&h[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      out[1] = __hip_atomic_load(&h[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      // each: this half counts from zero again when its turn comes (two hand-offs from now); one metric: the area goes back to zero like
-      // every other user of the health words leaves it (k_eval in gbp_kernels.hip)
-      __hip_atomic_store(&h[0], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&h[1], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    // each: this half counts from zero again when its turn comes (two hand-offs from now); one metric: the area goes back to zero like
+    // every other user of the health words leaves it (k_eval in gbp_kernels.hip)
+    if (bid == 0 && threadIdx.x == 0) health_handoff(slots, health_of(k));
   };
   auto metric_means = [&](uint32_t k, float (&cmv)[6], float (&lmu)[3]) {
     const uint32_t oc = (k & 1u) * emc_half + cam_i * 6u, ol_ = (k & 1u) * eml_half + lmk_i * 3u;
@@ -221,33 +167,10 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
                                cam_lin_unpack(clq, cl);
                              });
       fac_dirty = fac_dirty || (active && relin);
-      ol[3] = damping;
-      ol[13] = __int_as_float((int)(((uint32_t)count << 3) | flags));
-      ol[14] = var;
+      tile_regs_refresh(ol, oc_eta, oc_lam, damping, count, flags, var, lm, cm);
       // the wave's landmark messages go to memory (phase B gathers them by position); this lane keeps its own copy
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      GBP_UNROLL
-      for (int q = 0; q < 4; ++q)
-        stage[lane * 4 + ((uint32_t)q ^ swz_own)] = make_float4(ol[4 * q], ol[4 * q + 1], ol[4 * q + 2], ol[4 * q + 3]);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      GBP_UNROLL
-      for (int k = 0; k < 4; ++k) {
-        const uint32_t r = k * 16 + rec_t;
-        X_lmsg.st4(lm_tile4 + (uint32_t)k * 64u + lane, stage[r * 4 + ((lane & 3u) ^ (((r >> 2) & 3u) ^ (r & 2u)))]);
-      }
-      GBP_UNROLL
-      for (int i = 0; i < 16; ++i) lm[i] = ol[i];
-      GBP_UNROLL
-      for (int i = 0; i < 6; ++i) cm[i] = oc_eta[i];
-      GBP_UNROLL
-      for (int i = 0; i < 6; ++i) {
-        GBP_UNROLL
-        for (int j = 0; j <= i; ++j) cm[6 + tri(i, j)] = oc_lam[i * 6 + j];
-      }
-      cm[27] = 0.f;
+      lm_tile_out(stage, lane, [&](uint32_t q) { return make_float4(ol[4 * q], ol[4 * q + 1], ol[4 * q + 2], ol[4 * q + 3]); },
+                  [&](uint32_t k, float4 v) { X_lmsg.st4(lm_tile4 + k * 64u + lane, v); });
       {  // camera half of the belief reduction: per-row tree sums, as in k_sweep
         const uint32_t rp4 = (p >> 4) * (uint32_t)kCamRec4;
         row16_sums_store(oc_eta, oc_lam, lane, [&](uint32_t g, float4 v) { X_rowp.st4(rp4 + g, v); });
@@ -326,9 +249,7 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
         const uint32_t mu4 = v * 4u;            // [0,1] = means of the current belief, [2,3] = means the last sweep used
         X_cmu.st4(mu4 + 2u, cam_cur0); X_cmu.st4(mu4 + 3u, cam_cur1);
         const float used[6] = {cam_cur0.x, cam_cur0.y, cam_cur0.z, cam_cur0.w, cam_cur1.x, cam_cur1.y};
-        float S = 0.f;
-        GBP_UNROLL
-        for (int i = 0; i < 6; ++i) S += (used[i] - x0c[i]) * (used[i] - x0c[i]);
+        const float S = cam_dmu2(used, x0c);
         cam_cur0 = make_float4(x0c[0], x0c[1], x0c[2], x0c[3]);
         cam_cur1 = make_float4(x0c[4], x0c[5], 0.f, 0.f);
         X_cmu.st4(mu4, cam_cur0); X_cmu.st4(mu4 + 1u, cam_cur1);
@@ -397,23 +318,12 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
       }
       float u[3] = {0.f, 0.f, 0.f};
       if (lmk_live && q4 == 0) {
-        float B[9], S3[9], x0l[3];
-        GBP_UNROLL
-        for (int i = 0; i < 9; ++i) B[i] = rec[4 + i];
-        inv3x3(B, S3);
-        GBP_UNROLL
-        for (int i = 0; i < 3; ++i) {
-          float a2 = 0.f;
-          GBP_UNROLL
-          for (int k = 0; k < 3; ++k) a2 += S3[i * 3 + k] * rec[k];
-          x0l[i] = a2;
-        }
+        float x0l[3];
+        lmk_mean(rec, x0l);
         const uint32_t mu4 = l * 2u;            // [0] = mean of the current belief, [1] = mean the last sweep used
         const float4 used = lmk_cur;
         X_lmu.st4(mu4 + 1u, used);
-        u[0] = (used.x - x0l[0]) * (used.x - x0l[0]);
-        u[1] = (used.y - x0l[1]) * (used.y - x0l[1]);
-        u[2] = (used.z - x0l[2]) * (used.z - x0l[2]);
+        lmk_dmu2(used, x0l, u);
         lmk_cur = make_float4(x0l[0], x0l[1], x0l[2], 0.f);
         X_lmu.st4(mu4, lmk_cur);
         if (ev_means) {   // metric mean of this landmark (k_means), from the belief record in registers
@@ -463,9 +373,5 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
     metric((uint32_t)A.n_iters - 1u, __float_as_int(lm[13]), cmv, lmu);
   }
 
-  // ---- what stayed in registers goes back to its arrays ----
-  if (has_tile) {
-    store_tile<kCmsgG, false>(a.cmsg, tile, lane, cm);
-    if (fac_dirty) store_tile<kFacG, false>(a.fac, tile, lane, fac);
-  }
+  if (has_tile) tile_regs_store(a, tile, lane, cm, fac, fac_dirty);
 }
