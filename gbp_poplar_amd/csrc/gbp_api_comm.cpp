@@ -15,10 +15,26 @@ using namespace gbp::api;
 namespace gbp {
 namespace api {
 
+// The direct peer-memory transport exchanges through the communicator's own buffer: send_dev / recv_dev are this rank's slot / the
+// whole [world][C][44] of the parity of the NEXT exchange (re-bound after every exchange).  No-op for the other transports.
+void bind_exchange(gbp_ctx* c) {
+  float* x = c->comm ? c->comm->exchange_buffer() : nullptr;
+  if (!x) return;
+  float* recv = x + (size_t)c->comm->next_parity() * c->world * c->C * kCamRec;
+  c->recv_dev = recv;
+  c->send_dev = recv + (size_t)c->rank * c->C * kCamRec;
+}
+
+// p2p: every rank's partials of the LAST exchange, read in place (device table); nullptr for the other transports
+const float* const* last_peers(gbp_ctx* c) {
+  return c->comm && c->comm->exchange_buffer() ? c->comm->peer_table(c->comm->next_parity() ^ 1) : nullptr;
+}
+
 // plain exchange on the ctx's stream (LINEARISE, refreshes): partials in send_dev -> recv_dev of every rank
 int exchange_now(gbp_ctx* c) {
   COMMCHK(c, c->comm->all_gather(static_cast<const float*>(c->send_dev), static_cast<float*>(c->recv_dev),
                                  (size_t)c->C * kCamRec, c->stream, e_));
+  bind_exchange(c);
   return GBP_OK;
 }
 
@@ -79,6 +95,17 @@ static int enqueue_sharded_iteration(gbp_ctx* c, const SweepArgs& a) {
       launch_beliefs(b, true, true, c->stream);
     }
     if (x0) HIPCHK(c, hipEventRecord(x0, c->stream));
+    if (c->comm->exchange_buffer()) {
+      // p2p: stream sync + ONE region barrier, then the combine reads every rank's partials in place — no gather copy
+      if (!launch_beliefs_cam_peers) return fail(c, GBP_ERR_STATE, "no device code for the p2p combine");
+      COMMCHK(c, c->comm->exchange_in_place(c->stream, e_));
+      BeliefArgs b = belief_args(c);
+      b.roll = 1;
+      launch_beliefs_cam_peers(b, last_peers(c), c->stream);
+      bind_exchange(c);
+      HIPCHK(c, hipGetLastError());
+      return GBP_OK;
+    }
     if (int rc = exchange_now(c)) return rc;
     if (x1) HIPCHK(c, hipEventRecord(x1, c->stream));
   }
@@ -155,10 +182,14 @@ static int comm_attach(gbp_ctx* c, gbp::Comm* comm) {
   // (sendbuff == recvbuff + rank * count is the in-place form of ncclAllGather: the collective then moves only what comes from
   // other ranks — with a 1-rank communicator nothing at all, where the out-of-place form was a 5 us copy kernel per iteration,
   // profiles/r06_sharded_timeline.md).  (zero-filled on the ctx's stream, in front of everything that uses it)
-  if (!c->xrecv.p)
-    if (int rc = dev_alloc(c, c->xrecv, (size_t)c->world * c->C * kCamRec * 4)) return rc;
-  c->recv_dev = c->xrecv.p;
-  c->send_dev = static_cast<float*>(c->xrecv.p) + (size_t)c->rank * c->C * kCamRec;
+  if (comm->exchange_buffer()) {     // p2p: the communicator's own buffer, [2 parities][world][C][44]
+    bind_exchange(c);
+  } else {
+    if (!c->xrecv.p)
+      if (int rc = dev_alloc(c, c->xrecv, (size_t)c->world * c->C * kCamRec * 4)) return rc;
+    c->recv_dev = c->xrecv.p;
+    c->send_dev = static_cast<float*>(c->xrecv.p) + (size_t)c->rank * c->C * kCamRec;
+  }
   if (!c->comm_stream && !c->comm_single_stream) {
     // highest priority: the all-gather is issued while the landmark half of k_beliefs fills the GPU; it must not queue
     // behind those blocks (the camera combine of every rank waits for it)
@@ -206,7 +237,7 @@ GBP_EXPORT(gbp_comm_init, c, (gbp_ctx* c, void* region, int transport), (c, regi
   if (!c || !region) return GBP_ERR_INVALID;
   if (c->comm) return fail(c, GBP_ERR_STATE, "gbp_comm_init: the ctx already has a communicator");
   std::string err;
-  gbp::Comm* comm = gbp::comm_create_from_region(region, c->rank, c->world, transport, err);
+  gbp::Comm* comm = gbp::comm_create_from_region(region, c->rank, c->world, transport, c->C, err);
   if (!comm) return fail(c, GBP_ERR_COMM, "gbp_comm_init: " + err);
   return comm_attach(c, comm);
 }
@@ -265,7 +296,13 @@ GBP_EXPORT(gbp_comm_set_schedule, c, (gbp_ctx* c, int two_streams), (c, two_stre
 // *avg_us = mean duration between two events.  The buffers keep their content (the gather of the same partials).
 GBP_EXPORT(gbp_comm_probe, c, (gbp_ctx* c, int reps, double* avg_us), (c, reps, avg_us)) {
   if (!c || !c->comm || !avg_us || reps < 1) return fail(c, GBP_ERR_STATE, "gbp_comm_probe: needs a communicator, reps >= 1");
-  if (!c->comm->stream_ordered()) {      // host-staged: wall clock around blocking exchanges
+  if (c->comm->exchange_buffer()) {
+    // p2p: this rank's slot of the next parity still holds the partials of two exchanges ago — give it the last ones, so that every
+    // exchange of the probe (both parities) moves the same partials and leaves what a refresh reads unchanged
+    const float* mine = c->comm->exchange_buffer() + ((size_t)(c->comm->next_parity() ^ 1) * c->world + c->rank) * c->C * kCamRec;
+    HIPCHK(c, hipMemcpyAsync(c->send_dev, mine, (size_t)c->C * kCamRec * 4, hipMemcpyDeviceToDevice, c->stream));
+  }
+  if (!c->comm->stream_ordered()) {      // host-staged, p2p: wall clock around blocking exchanges
     const auto t0 = std::chrono::steady_clock::now();
     for (int i = 0; i < reps; ++i)
       if (int rc = exchange_now(c)) return rc;

@@ -70,6 +70,16 @@ int refresh_beliefs_from_partials(gbp_ctx* c, bool roll, bool do_lmk, bool weake
     b.weaken = 1;
     weaken_args(c, b);
   }
+  if (const float* const* peers = last_peers(c)) {
+    // direct peer-memory transport: the last exchange's partials are read where they lie (the combine of the sharded iteration
+    // gathers nothing into recv_dev); the landmark half, which needs nothing from other ranks, in a launch of its own
+    b.roll = roll ? 1 : 0;
+    if (!launch_beliefs_cam_peers) return fail(c, GBP_ERR_STATE, "no device code for the p2p combine");
+    launch_beliefs_cam_peers(b, peers, c->stream);
+    if (do_lmk) launch_beliefs(b, false, true, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return GBP_OK;
+  }
   if (!exch(c)) {
     b.gathered = P<float>(c->local); b.world = 1;
   } else {

@@ -1,5 +1,6 @@
 // gbp_comm.cpp — transports of the per-iteration camera-partial all-gather (see gbp_comm.hpp).
 #include "gbp_comm.hpp"
+#include "gbp_kernels.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>   // types and prototypes only: the library is dlopen'ed, nothing links against it
@@ -90,6 +91,8 @@ struct RegionHeader {
   char id[kCommIdBytes];
   char gpu_id[kCommMaxWorld][64];
   double scratch[kCommMaxWorld][16];
+  char ipc[kCommMaxWorld][HIP_IPC_HANDLE_SIZE];     // p2p: every rank's IPC handle of its exchange buffer (fixed size: the region's
+                                                     // size stays linear in world x cams)
 };
 static_assert(std::atomic<uint32_t>::is_always_lock_free, "cross-process barrier needs lock-free atomics");
 
@@ -212,6 +215,121 @@ class StagedComm : public Comm {
   const char* name() const override { return "host-staged"; }
 };
 
+// ---- direct peer-memory transport (p2p) ---------------------------------------------------------------------------------
+// Every rank owns X = [2 parities][world][n] fp32 (its own hipMalloc).  Rank r's partials always go into slot r of the parity of the
+// exchange; peers read only that slot, through an IPC mapping of X; a rank's gather writes only the other slots of its own X.
+// Exchange k: partials into parity k & 1 (stream-ordered), stream synchronised, ONE region barrier, then the readers
+// (k_gather_peers / k_beliefs_cam_peers) on the stream.  A rank reaches barrier k + 1 only after its stream has finished everything
+// it enqueued before it — its reads of exchange k included — so by the time any rank writes parity k & 1 again (exchange k + 2, after
+// barrier k + 1) every peer is done reading it.
+class P2pComm : public Comm {
+ public:
+  RegionPeer peer;
+  size_t n_floats = 0;             // slot: one rank's [C][44]
+  float* X = nullptr;
+  std::vector<void*> mapped;       // [world] IPC mappings of the peers' buffers (nullptr: this rank)
+  float** d_tab = nullptr;         // [2][world] device pointer tables
+  int parity = 0;
+  bool armed = false;              // every rank has set up: teardown meets the others at a barrier
+  ~P2pComm() override {
+    (void)hipDeviceSynchronize();
+    std::string err;
+    if (armed) (void)peer.barrier(err);      // no peer reads X any more
+    for (void* p : mapped)
+      if (p) (void)hipIpcCloseMemHandle(p);
+    if (d_tab) (void)hipFree(d_tab);
+    if (X) (void)hipFree(X);
+  }
+  float* slot(int p, int r) const { return X + ((size_t)p * world + r) * n_floats; }
+  float* exchange_buffer() const override { return X; }
+  const float* const* peer_table(int p) const override { return d_tab + (size_t)(p & 1) * world; }
+  int next_parity() const override { return parity; }
+  int exchange_in_place(hipStream_t s, std::string& err) override {
+    if (hipStreamSynchronize(s) != hipSuccess) { err = "p2p exchange: stream synchronisation failed"; return -1; }
+    if (!peer.barrier(err)) return -1;
+    parity ^= 1;
+    return 0;
+  }
+  int all_gather(const float* send, float* recv, size_t n, hipStream_t s, std::string& err) override {
+    if (n != n_floats || send != slot(parity, rank) || recv != slot(parity, 0)) {
+      err = "all_gather: the p2p transport exchanges through its own buffer (send / recv of the current parity)";
+      return -1;
+    }
+    if (!launch_gather_peers) { err = "all_gather: no device code"; return -1; }
+    const int p = parity;
+    if (exchange_in_place(s, err) != 0) return -1;
+    launch_gather_peers(peer_table(p), recv, (uint32_t)(n / 4), world, rank, s);
+    if (hipGetLastError() != hipSuccess) { err = "all_gather: k_gather_peers did not launch"; return -1; }
+    return 0;
+  }
+  bool stream_ordered() const override { return false; }
+  int all_gather_host(const double* mine, double* all, int n, std::string& err) override {
+    return peer.gather_host(rank, mine, all, n, err) ? 0 : -1;
+  }
+  int barrier(std::string& err) override { return peer.barrier(err) ? 0 : -1; }
+  const char* name() const override { return "p2p"; }
+
+  // collective over the ranks; on failure the caller raises the region's abort flag
+  bool setup(RegionHeader* h, int dev, uint32_t n_cams, std::string& err) {
+    n_floats = (size_t)n_cams * 44;
+    // 1. ranks on different GPUs must reach each other's memory
+    for (int r = 0; r < world; ++r) {
+      if (r == rank || std::strncmp(h->gpu_id[r], h->gpu_id[rank], 64) == 0) continue;
+      int pdev = -1, can = 0;
+      if (hipDeviceGetByPCIBusId(&pdev, h->gpu_id[r]) != hipSuccess || hipDeviceCanAccessPeer(&can, dev, pdev) != hipSuccess || !can) {
+        err = std::string("p2p: the GPU of rank ") + std::to_string(rank) + " (" + h->gpu_id[rank] + ") cannot access the GPU of rank " +
+              std::to_string(r) + " (" + h->gpu_id[r] + ")";
+        return false;
+      }
+    }
+    // 2. the buffer, its handle published in the region
+    const size_t bytes = 2 * (size_t)world * n_floats * sizeof(float);
+    if (hipMalloc(&X, bytes < 16 ? 16 : bytes) != hipSuccess) { X = nullptr; err = "p2p: hipMalloc of the exchange buffer failed"; return false; }
+    hipIpcMemHandle_t mine;
+    if (hipIpcGetMemHandle(&mine, X) != hipSuccess) { err = "p2p: hipIpcGetMemHandle failed"; return false; }
+    std::memcpy(h->ipc[rank], &mine, HIP_IPC_HANDLE_SIZE);
+    if (!peer.barrier(err)) return false;
+    // 3. every peer's buffer mapped (never this rank's own handle)
+    mapped.assign(world, nullptr);
+    for (int r = 0; r < world; ++r) {
+      if (r == rank) continue;
+      hipIpcMemHandle_t theirs;
+      std::memcpy(&theirs, h->ipc[r], HIP_IPC_HANDLE_SIZE);
+      if (hipIpcOpenMemHandle(&mapped[r], theirs, hipIpcMemLazyEnablePeerAccess) != hipSuccess || !mapped[r]) {
+        mapped[r] = nullptr;
+        err = "p2p: hipIpcOpenMemHandle of rank " + std::to_string(r) + "'s exchange buffer failed";
+        return false;
+      }
+    }
+    auto base = [&](int r) { return r == rank ? X : static_cast<float*>(mapped[r]); };
+    // 4. every mapping checked with runtime copies before any kernel reads through it: (magic, rank, C, world) in slot r of parity 0
+    const uint32_t pat[4] = {kMagic, (uint32_t)rank, n_cams, (uint32_t)world};
+    if (hipMemcpy(slot(0, rank), pat, sizeof(pat), hipMemcpyHostToDevice) != hipSuccess) { err = "p2p: pattern copy failed"; return false; }
+    if (!peer.barrier(err)) return false;
+    for (int r = 0; r < world; ++r) {
+      if (r == rank) continue;
+      uint32_t got[4] = {0, 0, 0, 0};
+      const uint32_t want[4] = {kMagic, (uint32_t)r, n_cams, (uint32_t)world};
+      if (hipMemcpy(got, base(r) + (size_t)r * n_floats, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess ||
+          std::memcmp(got, want, sizeof(got)) != 0) {
+        err = "p2p: the mapping of rank " + std::to_string(r) + "'s exchange buffer does not hold its pattern";
+        return false;
+      }
+    }
+    if (!peer.barrier(err)) return false;
+    if (hipMemset(X, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { err = "p2p: zero-fill failed"; return false; }
+    // 5. the pointer tables: for parity p, slot r of parity p in rank r's buffer
+    std::vector<float*> tab(2 * (size_t)world);
+    for (int p = 0; p < 2; ++p)
+      for (int r = 0; r < world; ++r) tab[(size_t)p * world + r] = base(r) + ((size_t)p * world + r) * n_floats;
+    if (hipMalloc(&d_tab, tab.size() * sizeof(float*)) != hipSuccess) { d_tab = nullptr; err = "p2p: hipMalloc failed"; return false; }
+    if (hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(float*), hipMemcpyHostToDevice) != hipSuccess) { err = "p2p: table upload failed"; return false; }
+    if (!peer.barrier(err)) return false;
+    armed = true;
+    return true;
+  }
+};
+
 }  // namespace
 
 int comm_unique_id(void* id128, std::string& err) {
@@ -255,6 +373,7 @@ int comm_region_init(void* region, size_t bytes, uint32_t n_cams, int world) {
   h->bar_count.store(0); h->bar_sense.store(0); h->abort_flag.store(0); h->id_ready.store(0);
   std::memset(h->id, 0, sizeof(h->id));
   std::memset(h->gpu_id, 0, sizeof(h->gpu_id));
+  std::memset(h->ipc, 0, sizeof(h->ipc));
   return 0;
 }
 
@@ -281,7 +400,7 @@ int comm_region_selftest(void* region, int rank, int world, int rounds, std::str
   return 0;
 }
 
-Comm* comm_create_from_region(void* region, int rank, int world, int transport, std::string& err) {
+Comm* comm_create_from_region(void* region, int rank, int world, int transport, uint32_t n_cams, std::string& err) {
   RegionHeader* h = static_cast<RegionHeader*>(region);
   if (!h || h->magic != kMagic || (int)h->world != world || rank < 0 || rank >= world) { err = "bad communication region"; return nullptr; }
   RegionPeer peer;
@@ -297,6 +416,13 @@ Comm* comm_create_from_region(void* region, int rank, int world, int transport, 
     for (int b = a + 1; b < world; ++b)
       if (std::strncmp(h->gpu_id[a], h->gpu_id[b], 64) == 0) shared = true;
   if (transport == 1 && shared) { err = "RCCL needs one GPU per rank, but two ranks share a GPU"; h->abort_flag.store(1); return nullptr; }
+  if (transport == 3) {
+    P2pComm* c = new (std::nothrow) P2pComm();
+    if (!c) { err = "out of memory"; h->abort_flag.store(1); return nullptr; }
+    c->rank = rank; c->world = world; c->peer = peer;
+    if (!c->setup(h, dev, n_cams, err)) { h->abort_flag.store(1); delete c; return nullptr; }
+    return c;
+  }
   const bool use_rccl = transport == 1 || (transport == 0 && !shared);
   if (!use_rccl) {
     StagedComm* c = new (std::nothrow) StagedComm();

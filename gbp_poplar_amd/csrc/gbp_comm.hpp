@@ -5,13 +5,16 @@
 // buffer of camera partial sums; one ALL-GATHER per iteration gives every rank all of them, and each rank adds
 // prior + partials in rank order (k_beliefs) — deterministic, bit-identical camera beliefs on all ranks.
 //
-// Two transports behind one interface:
+// Three transports behind one interface:
 //   * RCCL (xGMI): ncclAllGather on a HIP stream — stream-ordered, capturable into the iteration's hipGraph.  librccl
 //     is dlopen'ed on first use (no link-time dependency: a single-GPU user never loads it, and inside a PyTorch
 //     process the already-loaded librccl is reused instead of a second copy).
 //   * host-staged: ranks that SHARE a GPU (fewer GPUs than ranks: test rigs, `--ipus 2` on a one-GPU box) cannot form
 //     an RCCL communicator ("duplicate GPU"); their partials travel through a MAP_SHARED region (D2H, barrier, H2D).
 //     It moves the same bytes in the same layout, only slower; nothing is computed on the host.
+//   * p2p (direct peer memory, asked for explicitly): every rank owns an exchange buffer [2 parities][world][C][44] in its
+//     own device memory, the ranks map each other's through HIP IPC (the same GPU, or peer-accessible GPUs), and a kernel
+//     reads every peer's slot in place after ONE host barrier per exchange.  Not stream-ordered.
 // The shared region also carries the rendezvous of a forked launcher (RCCL unique id, per-rank GPU identity, barrier).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -40,6 +43,16 @@ class Comm {
   // multi-GPU run wants on record next to its numbers
   virtual std::string library_path() const { return ""; }
   virtual int library_version() const { return 0; }
+  // ---- the direct peer-memory transport only (nullptr / an error for the others) ----
+  // its exchange buffer [2 parities][world][n] fp32 (parity 1 at + world * n); rank r's partials go into slot r
+  virtual float* exchange_buffer() const { return nullptr; }
+  // device table of `world` pointers: slot r of parity p in rank r's buffer (its own for r == rank)
+  virtual const float* const* peer_table(int p) const { (void)p; return nullptr; }
+  // parity of the NEXT exchange: advances once per exchange, whatever made it
+  virtual int next_parity() const { return 0; }
+  // the exchange without a copy: synchronise `s`, one region barrier, advance the parity.  Until this rank's next exchange a
+  // kernel on `s` may read peer_table(parity of this exchange) in place.
+  virtual int exchange_in_place(hipStream_t s, std::string& err) { (void)s; err = "not a peer-memory transport"; return -1; }
   int rank = 0, world = 1;
 };
 
@@ -52,7 +65,8 @@ size_t comm_region_bytes(uint32_t n_cams, int world);
 int comm_region_init(void* region, size_t bytes, uint32_t n_cams, int world);
 void comm_region_abort(void* region);
 int comm_region_selftest(void* region, int rank, int world, int rounds, std::string& err);   // protocol check, no device   // a supervisor saw a rank die: wake every rank waiting in the region with an error
-// transport: 0 = auto (RCCL when every rank sits on its own GPU, host-staged otherwise), 1 = RCCL, 2 = host-staged
-Comm* comm_create_from_region(void* region, int rank, int world, int transport, std::string& err);
+// transport: 0 = auto (RCCL when every rank sits on its own GPU, host-staged otherwise), 1 = RCCL, 2 = host-staged,
+// 3 = p2p (never chosen by auto; n_cams: the ctx's cameras, the size of a rank's slot in the p2p exchange buffer)
+Comm* comm_create_from_region(void* region, int rank, int world, int transport, uint32_t n_cams, std::string& err);
 
 }  // namespace gbp

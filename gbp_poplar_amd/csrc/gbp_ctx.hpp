@@ -302,6 +302,8 @@ int eval(gbp_ctx* c, gbp_eval_out* o);
 // ---- gbp_api_comm.cpp -------------------------------------------------------------------------------------------------------
 int exchange_now(gbp_ctx* c);                               // plain all-gather of the camera partials on the ctx's stream
 int iterate_sharded(gbp_ctx* c, int n);
+void bind_exchange(gbp_ctx* c);                             // p2p: send_dev / recv_dev := the parity of the next exchange
+const float* const* last_peers(gbp_ctx* c);                 // p2p: device table of the last exchange's partials (else nullptr)
 
 }  // namespace api
 }  // namespace gbp

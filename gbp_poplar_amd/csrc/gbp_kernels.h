@@ -255,6 +255,15 @@ struct DeviceEval {  // per-block partials, summed on the host in block order
 void launch_sweep(const SweepArgs& a, uint32_t n_tiles, bool hoist, hipStream_t s, bool ev = false);
 void launch_linearise(const SweepArgs& a, uint32_t n_tiles, hipStream_t s);
 void launch_beliefs(BeliefArgs b, bool do_cam, bool do_lmk, hipStream_t s, bool ev = false);
+// The direct peer-memory transport (gbp_comm.cpp: p2p).  peers: device table of `world` pointers, peers[r] = slot r of one parity in
+// rank r's exchange buffer (an IPC mapping for r != self).  Both kernels begin with a system-scope acquire.
+//   launch_beliefs_cam_peers  the camera combine of launch_beliefs(b, true, false) with partial r read from peers[r] in place of
+//                             b.gathered[r] (b.gathered unused): the same additions in the same order
+//   launch_gather_peers       dst[r][0..n4) = peers[r][0..n4) (float4) for every r != self: an all-gather into this rank's buffer
+// Declared weak: the CPU sanitizer build of the host code links stand-ins of the launchers it may reach, and a p2p communicator needs a
+// device; the callers check for a null launcher.
+[[gnu::weak]] void launch_beliefs_cam_peers(BeliefArgs b, const float* const* peers, hipStream_t s);
+[[gnu::weak]] void launch_gather_peers(const float* const* peers, float* dst, uint32_t n4, int world, int self, hipStream_t s);
 // per-tile records of ring slots [0, n_slots) -> out[slot]: one gbp_eval_out-shaped result per slot (may be mapped host memory)
 void launch_eval_fold(const EvalRide& ev, uint32_t n_slots, void* out, hipStream_t s);
 // the riding metric of the CURRENT beliefs (a piece's last iteration: no sweep follows) into ring slot counter - 1

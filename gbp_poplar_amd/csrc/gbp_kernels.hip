@@ -918,8 +918,10 @@ GBP_DEV void cam_mean(REC&& cb, float (&x0c)[6]) {
 // CAM_ONLY: a launch without landmark blocks (the camera combine behind the exchange of a sharded iteration, prior-only refreshes of the
 // split-phase path): the landmark half is compiled out, so the kernel needs the camera half's registers only — 8 waves per SIMD instead of
 // 7, i.e. the 2 000 workgroups of an 8 000-camera graph resident in ONE generation (256 CUs x 8) instead of one and a bit
-template <bool EV, bool CAM_ONLY = false>
-GBP_DEV void beliefs_body(const BeliefArgs& b) {
+// PEERS (with CAM_ONLY): the combine behind the direct peer-memory exchange — partial r straight from peers[r] (rank r's exchange
+// buffer, slot r) instead of b.gathered[r]; the same additions in the same order, so the same bits
+template <bool EV, bool CAM_ONLY = false, bool PEERS = false>
+GBP_DEV void beliefs_body(const BeliefArgs& b, const float* const* __restrict__ peers = nullptr) {
   __shared__ float sh[4][48];
   __shared__ float lrec[EV ? 64 : 1][13];      // EV: the beliefs of the workgroup's 64 landmarks (eta 3, Lambda 9; 13: bank spread)
   if (EV && blockIdx.x == 0 && threadIdx.x == 0) *b.ev.counter = *b.ev.counter + 1u;     // one more iteration of the burst done (read by the NEXT sweep)
@@ -945,7 +947,19 @@ GBP_DEV void beliefs_body(const BeliefArgs& b) {
         prior *= b.cam_scale[c];
         b.cam_prior_rw[(size_t)c * kCamRec + j] = prior;
       }
-      if (b.gathered) {
+      if (PEERS) {
+        const size_t off = (size_t)c * kCamRec + j;
+        float acc = prior;
+        for (int r0 = 0; r0 < b.world; r0 += 8) {      // as below: eight ranks' loads in flight (clamped, unconditional), rank order
+          float v[8];
+          GBP_UNROLL
+          for (int k = 0; k < 8; ++k) v[k] = peers[r0 + k < b.world ? r0 + k : b.world - 1][off];      // wave-uniform table entry
+          GBP_UNROLL
+          for (int k = 0; k < 8; ++k)
+            if (r0 + k < b.world) acc = acc + v[k];
+        }
+        bel = acc;
+      } else if (b.gathered) {
         const float* g = b.gathered + (size_t)c * kCamRec + j;      // exchange layout: [world][C][44]
         float acc = prior;
         for (int r0 = 0; r0 < b.world; r0 += 8) {      // the partials of eight ranks in flight at once (clamped, unconditional), added in rank order
@@ -1201,6 +1215,23 @@ GBP_DEV void beliefs_body(const BeliefArgs& b) {
 __global__ __launch_bounds__(256) void k_beliefs(const BeliefArgs b) { beliefs_body<false>(b); }      // (held at 8 waves per SIMD: S1 +0.1 %, config-5 shape +0.2 %: noise — profiles/HISTORY.md)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_beliefs_cam(const BeliefArgs b) { beliefs_body<false, true>(b); }
 __global__ __launch_bounds__(256) void k_beliefs_ev(const BeliefArgs b) { beliefs_body<true>(b); }
+// The direct peer-memory exchange.  The peers' partials were written by kernels of OTHER processes, whose completion the
+// host has observed before the region barrier that let this launch be enqueued; the system-scope acquire in front of the first peer
+// access drops whatever stale copy of those lines this agent's caches still hold (the read of two exchanges ago, same parity).
+// No flags, no waits on another process inside a kernel.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_beliefs_cam_peers(const BeliefArgs b,
+                                                                                                     const float* const* __restrict__ peers) {
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+  beliefs_body<false, true, true>(b, peers);
+}
+// dst[r] = peers[r] for every rank r != self, 16 bytes per lane (a camera record is 11 float4); grid.y = rank
+__global__ __launch_bounds__(256) void k_gather_peers(const float* const* __restrict__ peers, float* __restrict__ dst, uint32_t n4,
+                                                      int self) {
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+  const uint32_t r = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  if ((int)r == self || i >= n4) return;
+  reinterpret_cast<float4*>(dst)[(size_t)r * n4 + i] = reinterpret_cast<const float4*>(peers[r])[i];
+}
 
 // =================================================================================================
 // k_persist: n iterations of {k_sweep; k_beliefs} in ONE launch, for graphs whose workgroups are all resident at once.
@@ -2313,6 +2344,17 @@ void launch_beliefs(BeliefArgs b, bool do_cam, bool do_lmk, hipStream_t s, bool 
   if (ev) hipLaunchKernelGGL(k_beliefs_ev, dim3(b.cam_blocks + lmk_blocks), dim3(256), 0, s, b);
   else if (lmk_blocks == 0) hipLaunchKernelGGL(k_beliefs_cam, dim3(b.cam_blocks), dim3(256), 0, s, b);
   else hipLaunchKernelGGL(k_beliefs, dim3(b.cam_blocks + lmk_blocks), dim3(256), 0, s, b);
+}
+void launch_beliefs_cam_peers(BeliefArgs b, const float* const* peers, hipStream_t s) {
+  b.cam_blocks = (b.n_cams + 3) / 4;
+  b.lmk_blocks = 0;
+  b.gathered = nullptr;
+  if (b.cam_blocks == 0) return;
+  hipLaunchKernelGGL(k_beliefs_cam_peers, dim3(b.cam_blocks), dim3(256), 0, s, b, peers);
+}
+void launch_gather_peers(const float* const* peers, float* dst, uint32_t n4, int world, int self, hipStream_t s) {
+  if (n4 == 0 || world < 2) return;
+  hipLaunchKernelGGL(k_gather_peers, dim3((n4 + 255) / 256, (uint32_t)world), dim3(256), 0, s, peers, dst, n4, self);
 }
 void launch_eval_ride(const EvalRide& ev, const uint32_t* row_cam, const uint32_t* lmk_idx, const float4* lmsg, const float4* fac, const float* K9_dev, hipStream_t s) {
   hipLaunchKernelGGL(k_eval_ride, dim3(ev.n_tiles / 4), dim3(256), 0, s, ev, row_cam, lmk_idx, lmsg, fac, K9_dev);

@@ -4,7 +4,8 @@
  * into the program).  Here: one process per GPU, each with a SHARDED ctx (gbp_create with a gbp_shard: a contiguous landmark
  * range and every factor incident to it; cameras replicated), ONE all-gather of the [C x 44] camera partial sums per iteration.
  * Two ways to run the exchange:
- *   - owned by the library (gbp_comm_*): RCCL over xGMI, dlopen'ed, or a host-staged transport for ranks that share a GPU; once a
+ *   - owned by the library (gbp_comm_*): RCCL over xGMI, dlopen'ed, a host-staged transport for ranks that share a GPU, or direct
+ *     peer memory (p2p, asked for explicitly); once a
  *     ctx has a communicator the plain program list of gbp_mi355x.h works on it;
  *   - owned by the caller (split-phase: gbp_iterate_begin / exchange / gbp_iterate_end), e.g. torch.distributed.
  * A single-GPU host needs nothing from this header (INTEGRATION.md binds the core header only).
@@ -46,7 +47,12 @@ GBP_API int gbp_linearise_factors(gbp_ctx* ctx);  /* the factor half of LINEARIS
  * Launchers that fork their ranks (bin/ba --ipus N) share one MAP_SHARED region, created and initialised BEFORE the
  * ranks start; it carries the rendezvous (RCCL unique id, barrier) and, for ranks that share a GPU (fewer GPUs than
  * ranks — RCCL refuses duplicate GPUs), the host-staged transport that moves the same buffers through host memory.
- * transport: 0 = auto (RCCL when every rank has its own GPU, host-staged otherwise), 1 = RCCL, 2 = host-staged.
+ * transport: 0 = auto (RCCL when every rank has its own GPU, host-staged otherwise), 1 = RCCL, 2 = host-staged,
+ * 3 = p2p (never chosen by auto): direct peer memory for ranks on ONE GPU or on peer-accessible GPUs — every rank exchanges through a
+ * buffer in its own device memory that the others map (HIP IPC) and read in place; device-only (no collective library, no trip
+ * through host memory), one host barrier per exchange, not stream-ordered (the iteration is not captured into a hipGraph).  Ranks on
+ * GPUs that cannot access each other make gbp_comm_init fail with GBP_ERR_COMM; while the communicator lives, gbp_set_exchange_buffers
+ * is refused (the exchange buffers are the communicator's).
  * Launchers with their own rendezvous (torchrun, MPI) pass the 128-byte RCCL id around themselves:
  * gbp_comm_unique_id on rank 0, gbp_comm_init_rccl on every rank.  All calls are collective over the ranks.
  * Scheduling: with 4 ranks or more the camera side of the exchange (local partial sums, all-gather) runs on a second,
@@ -66,7 +72,7 @@ GBP_API int gbp_comm_region_selftest(void* region, int rank, int world, int roun
 GBP_API int gbp_comm_init(gbp_ctx* ctx, void* region, int transport);
 GBP_API int gbp_comm_unique_id(void* id128);
 GBP_API int gbp_comm_init_rccl(gbp_ctx* ctx, const void* id128);
-GBP_API const char* gbp_comm_transport(const gbp_ctx* ctx);            /* "rccl", "host-staged" or "none" */
+GBP_API const char* gbp_comm_transport(const gbp_ctx* ctx);            /* "rccl", "host-staged", "p2p" or "none" */
 GBP_API int gbp_comm_barrier(gbp_ctx* ctx);
 /* What a first multi-GPU run puts on record next to its numbers (bench.py's preflight block): gbp_comm_describe writes one
  * JSON object (rank, world, device, PCI bus id, transport, the collective library's resolved path and version, schedule);
