@@ -93,6 +93,7 @@ _DEBUG_SIGS = {
     "gbp_debug_set_factor_potentials": (C.c_int, [C.c_void_p, cabi.c_f32p, cabi.c_f32p]),
     "gbp_debug_math": (C.c_int, [C.c_int, cabi.c_f32p, cabi.c_f32p, C.c_int]),
     "gbp_debug_math_timed": (C.c_int, [C.c_int, cabi.c_f32p, cabi.c_f32p, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    "gbp_debug_vertex": (C.c_int, [C.c_int, cabi.c_f32p, cabi.c_f32p, C.c_int]),
     "gbp_debug_layout_default_options": (None, [C.POINTER(cabi.GbpLayoutOptions)]),
     "gbp_debug_layout_options": (C.c_int, [C.POINTER(cabi.GbpLayoutOptions)]),
     "gbp_debug_force_sweep_policy": (C.c_int, [C.c_int]),

@@ -273,10 +273,11 @@ GBP_EXPORT(gbp_debug_set_factor_potentials, c, (gbp_ctx* c, const float* eta9E, 
 
 // Device math layer on caller-supplied vectors (test hook, see k_debug_math): HIP vs the reference's own
 // matlib.cpp / bafuncs.cpp outputs, no ctx and no restated vertex layer involved.
+// (gbp_debug_vertex runs through the same plumbing: its ops are the launcher's ops kDebugVertexOp0 + 0 .. 2, which gbp_debug_math refuses)
 static int debug_math_run(int op, const float* in, float* out, int n, int reps, double* avg_us) {
   int in_w = 0, out_w = 0;
   if (!in || !out || n <= 0 || reps < 1 || !debug_math_widths(op, &in_w, &out_w))
-    return fail(nullptr, GBP_ERR_INVALID, "gbp_debug_math: bad op / arguments");
+    return fail(nullptr, GBP_ERR_INVALID, "gbp_debug_math / gbp_debug_vertex: bad op / arguments");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
     return fail(nullptr, GBP_ERR_NO_DEVICE, "gbp_debug_math: no HIP device (the product has no CPU fallback)");
@@ -294,7 +295,7 @@ static int debug_math_run(int op, const float* in, float* out, int n, int reps, 
   if ((e = hipMalloc(&d_out, (size_t)n * out_w * 4)) != hipSuccess) return done(GBP_ERR_HIP, "hipMalloc", e);
   if ((e = hipMemcpy(d_in, in, (size_t)n * in_w * 4, hipMemcpyHostToDevice)) != hipSuccess) return done(GBP_ERR_HIP, "hipMemcpy", e);
   launch_debug_math(op, d_in, d_out, n, nullptr);
-  if ((e = hipGetLastError()) != hipSuccess) return done(GBP_ERR_HIP, "k_debug_math", e);
+  if ((e = hipGetLastError()) != hipSuccess) return done(GBP_ERR_HIP, op >= kDebugVertexOp0 ? "k_debug_vertex" : "k_debug_math", e);
   if (avg_us) {   // back-to-back launches between two events
     if ((e = hipEventCreate(&e0)) != hipSuccess || (e = hipEventCreate(&e1)) != hipSuccess) return done(GBP_ERR_HIP, "hipEventCreate", e);
     (void)hipEventRecord(e0, nullptr);
@@ -309,10 +310,17 @@ static int debug_math_run(int op, const float* in, float* out, int n, int reps, 
   return done(GBP_OK, "", hipSuccess);
 }
 
-GBP_EXPORT(gbp_debug_math, nullptr, (int op, const float* in, float* out, int n), (op, in, out, n)) { return debug_math_run(op, in, out, n, 1, nullptr); }
+GBP_EXPORT(gbp_debug_math, nullptr, (int op, const float* in, float* out, int n), (op, in, out, n)) {
+  if (op >= kDebugVertexOp0) return fail(nullptr, GBP_ERR_INVALID, "gbp_debug_math: bad op / arguments");
+  return debug_math_run(op, in, out, n, 1, nullptr);
+}
 GBP_EXPORT(gbp_debug_math_timed, nullptr, (int op, const float* in, float* out, int n, int reps, double* avg_us), (op, in, out, n, reps, avg_us)) {
-  if (!avg_us) return GBP_ERR_INVALID;
+  if (!avg_us || op >= kDebugVertexOp0) return GBP_ERR_INVALID;
   return debug_math_run(op, in, out, n, reps, avg_us);
+}
+GBP_EXPORT(gbp_debug_vertex, nullptr, (int op, const float* in, float* out, int n), (op, in, out, n)) {
+  if (op < 0 || op > 2) return fail(nullptr, GBP_ERR_INVALID, "gbp_debug_vertex: bad op / arguments");
+  return debug_math_run(kDebugVertexOp0 + op, in, out, n, 1, nullptr);
 }
 
 

@@ -298,5 +298,8 @@ bool lab_launch_sweep_ablated(const SweepArgs& a, uint32_t n_tiles, int abl, hip
 bool launch_flow_torture(float4* buf, unsigned long long* out, int blocks, int K, int rounds, unsigned mask, unsigned tag0, int inject, hipStream_t s);
 bool debug_math_widths(int op, int* in_w, int* out_w);   // floats per vector of k_debug_math's op
 void launch_debug_math(int op, const float* in, float* out, int n, hipStream_t s);  // test hook
+// (ops kDebugVertexOp0 + 0 .. 2 of the two functions above: k_debug_vertex, hooks/gbp_debug_vertex.hip — the vertex layer on
+// caller-supplied factors, behind gbp_debug_vertex; the math ops of gbp_debug_math end below that number)
+constexpr int kDebugVertexOp0 = 100;
 
 }  // namespace gbp

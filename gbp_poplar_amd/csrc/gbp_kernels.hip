@@ -2503,6 +2503,7 @@ void launch_eval(const uint32_t* row_cam, const uint32_t* lmk_idx, const float4*
 
 #ifdef GBP_BUILD_TEST_HOOKS
 #include "hooks/gbp_flow_torture.hip"        // k_flow_torture: the detector under the tagged records' untorn-16-byte-store assumption
+#include "hooks/gbp_debug_vertex.hip"        // k_debug_vertex: relin_core / factor_update on caller-supplied factors (tests only)
 #include "hooks/gbp_debug_math.hip"          // k_debug_math: the device math layer on caller-supplied vectors (tests only)
 #endif
 #ifdef GBP_BUILD_EXPERIMENTS

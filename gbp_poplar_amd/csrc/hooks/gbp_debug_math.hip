@@ -121,6 +121,7 @@ __global__ __launch_bounds__(64) void k_debug_math(int op, const float* __restri
 
 
 bool debug_math_widths(int op, int* in_w, int* out_w) {
+  if (op >= kDebugVertexOp0) return debug_vertex_widths(op - kDebugVertexOp0, in_w, out_w);      // the vertex ops (gbp_debug_vertex)
   static const int iw[11] = {9, 36, 3, 18, 72, 72, 54, 42, 12, 36, 10}, ow[11] = {9, 36, 9, 20, 18, 18, 36, 6, 3, 36, 9};
   if (op < 0 || op > 10) return false;
   *in_w = iw[op]; *out_w = ow[op];
@@ -129,6 +130,7 @@ bool debug_math_widths(int op, int* in_w, int* out_w) {
 void launch_debug_math(int op, const float* in, float* out, int n, hipStream_t s) {
   int in_w = 0, out_w = 0;
   if (!debug_math_widths(op, &in_w, &out_w) || n <= 0) return;
+  if (op >= kDebugVertexOp0) { launch_debug_vertex(op - kDebugVertexOp0, in, out, n, s); return; }
 #ifdef GBP_BUILD_EXPERIMENTS
   if (op == 9) { lab_launch_inv6_coop(in, out, n, s); return; }    // 16 lanes per matrix (experiments/gbp_lab_kernels.hip)
 #else

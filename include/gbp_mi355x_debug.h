@@ -38,6 +38,20 @@ GBP_API int gbp_debug_set_factor_potentials(gbp_ctx* ctx, const float* eta9E, co
 GBP_API int gbp_debug_math(int op, const float* in, float* out, int n);
 /* same, then `reps` back-to-back launches timed with hipEvents: average microseconds per launch */
 GBP_API int gbp_debug_math_timed(int op, const float* in, float* out, int n, int reps, double* avg_us);
+/* The device VERTEX layer on caller-supplied factors, one GPU lane per case (no ctx): the lane packs one factor's complete vertex
+ * input, given under the reference's tensor names, into the records the kernels work on and runs the product's own per-factor code:
+ *   op 0 RelineariseFactorVertex on a zeroed potential (relin_core as k_linearise calls it, gbp_codelets.cpp:20-172)
+ *   op 1 PrepMessageVertex + the four message vertices with per-factor means (factor_update<false>, gbp_codelets.cpp:215-710)
+ *   op 2 the same with hoisted means: dmu^2 pieces and the CAM_LIN record precomputed as the belief kernels do (factor_update<true>)
+ * in [n][229]: K 9, measurement 2, meas_variance, kf belief eta 6 + lambda 36, lmk belief eta 3 + lambda 9, factor eta 9 + lambda 81
+ *   ([cc36|cl18|lc18|ll9]), previous cam message eta 6 + lambda 36, previous lmk message eta 3 + lambda 9, oldmu 9, damping,
+ *   damping_count (int bits), active_flag, robust_flag before (uint bits), maxeta_damping, num_undamped_iters (int), dmu_threshold,
+ *   min_linear_iters (int), nstds, relin_mode (int).  The device keeps Lambda_cc / Lambda_ll / the previous camera message as lower
+ *   triangles and Lambda_lc as Lambda_cl^T: the upper triangles and the lc block of the input are not read.
+ * out [n][157]: factor eta 9 + lambda 81, cam message eta 6 + lambda 36, lmk message eta 3 + lambda 9, mu 9 (op 2: the hoisted
+ *   means), dmu, damping, damping_count (int bits), robust_flag (uint bits); op 0 writes potential + robust flag, zeros elsewhere.
+ * n need not be a multiple of the wavefront size (tests/test_gpu_vertices.py). */
+GBP_API int gbp_debug_vertex(int op, const float* in, float* out, int n);
 
 /* ---- the device order without a device ---------------------------------------------------------------------------------
  * gbp_create first builds the DEVICE ORDER of the graph — which factor sits at which device position, where a camera's rows

@@ -12,10 +12,13 @@
  * Pin status (details in DESIGN.md "Oracle"):
  *   - dense-math layer (matlib.cpp, bafuncs.cpp): pinned bit-for-bit against the reference's own
  *     code compiled here (ref_adapter.cpp, built out of tree by `make ref`);
- *   - vertex classes + schedule: gbp_codelets.cpp / ba.cpp need the Poplar SDK (absent) and are
- *     NOT built; pinned against the reference-run known answers recorded in BASELINE.md
- *     (metric trajectory of the reference's vertex code on fr1xyz / fr2robot2, incl. the chaotic
- *     1500-iteration finals) — tests/test_oracle_known_answers.py;
+ *   - vertex classes: arithmetic pinned bit for bit against the compute() bodies of the reference's
+ *     gbp_codelets.cpp, compiled unmodified against a stand-in for Poplar's field wrappers
+ *     (poplar_standin/, ref_vertex_adapter.cpp, `make ref`; orc_vertex_* below are the same
+ *     signatures over the restatement) — tests/test_oracle_vertices.py;
+ *   - graph wiring (ba.cpp) + schedule: NOT built (Poplar SDK absent); held to the reference-run
+ *     known answers recorded in BASELINE.md (metric trajectory of the reference's vertex code on
+ *     fr1xyz / fr2robot2, incl. the chaotic 1500-iteration finals) — tests/test_oracle_known_answers.py;
  *   - popops::reduceWithOutput summation order and Eigen's inverse: unpinned by the reference
  *     (third-party, unspecified) — fixed here as ascending slot order / fp64 partial-pivot solve.
  */
@@ -66,6 +69,36 @@ int orc_new_keyframe_sharded(orc_ctx* o, const gbp_kf_update* upd, const float* 
 int orc_get_factor_potentials(orc_ctx* o, float* eta9E, float* lambda81E);
 int orc_get_messages(orc_ctx* o, float* cam_eta6E, float* cam_lam36E, float* lmk_eta3E, float* lmk_lam9E);
 int orc_get_mu(orc_ctx* o, float* mu9E, float* dmuE);
+
+/* The seven vertex classes on plain pointers, arguments under the reference's field names: the signatures of rv_* in
+ * ref_vertex_adapter.cpp (the reference's own compute() bodies), so that one driver (tests/vertex_cases.py) runs both and
+ * compares them bit for bit.  The hyper-parameters are the file globals of gbp_codelets.cpp:11-16; relin_mode is ours. */
+void orc_vertex_set_hyper(float maxeta_damping, int num_undamped_iters, float dmu_threshold, int min_linear_iters, float nstds);
+void orc_vertex_set_relin_mode(int relin_mode);
+void orc_vertex_relinearise_factor(const float* measurement, float meas_variance, const float* K, const float* kf_belief_eta,
+                                   const float* kf_belief_lambda, const float* lmk_belief_eta, const float* lmk_belief_lambda,
+                                   float* factor_eta, float* factor_lambda_cc, float* factor_lambda_ll, float* factor_lambda_cl,
+                                   float* factor_lambda_lc, uint32_t* robust_flag);
+void orc_vertex_prep_message(float* damping, int32_t* damping_count, uint32_t active_flag, uint32_t* robust_flag, const float* measurement,
+                             const float* K, float meas_variance, const float* kf_belief_eta, const float* kf_belief_lambda,
+                             const float* lmk_belief_eta, const float* lmk_belief_lambda, const float* oldmu, float* mu, float* dmu,
+                             float* factor_eta, float* factor_lambda_cc, float* factor_lambda_ll, float* factor_lambda_cl,
+                             float* factor_lambda_lc);
+void orc_vertex_cam_message_eta(float damping, uint32_t active_flag, const float* f_outedge_eta, const float* f_nonoutedge_eta,
+                                const float* f_noe_noe_lambda, const float* f_oe_noe_lambda, const float* belief_nonoutedge_eta,
+                                const float* belief_nonoutedge_lambda, const float* pmess_nonoutedge_eta,
+                                const float* pmess_nonoutedge_lambda, const float* pmess_outedge_eta, float* mess_outedge_eta);
+void orc_vertex_lmk_message_eta(float damping, uint32_t active_flag, const float* f_outedge_eta, const float* f_nonoutedge_eta,
+                                const float* f_noe_noe_lambda, const float* f_oe_noe_lambda, const float* belief_nonoutedge_eta,
+                                const float* belief_nonoutedge_lambda, const float* pmess_nonoutedge_eta,
+                                const float* pmess_nonoutedge_lambda, const float* pmess_outedge_eta, float* mess_outedge_eta);
+void orc_vertex_cam_message_lambda(uint32_t active_flag, const float* f_oe_oe_lambda, const float* f_noe_noe_lambda,
+                                   const float* f_oe_noe_lambda, const float* f_noe_oe_lambda, const float* belief_nonoutedge_lambda,
+                                   const float* pmess_nonoutedge_lambda, float* mess_outedge_lambda);
+void orc_vertex_lmk_message_lambda(uint32_t active_flag, const float* f_oe_oe_lambda, const float* f_noe_noe_lambda,
+                                   const float* f_oe_noe_lambda, const float* f_noe_oe_lambda, const float* belief_nonoutedge_lambda,
+                                   const float* pmess_nonoutedge_lambda, float* mess_outedge_lambda);
+void orc_vertex_weaken_prior(float scaling, uint32_t* weaken_flag, float* prior_eta, uint32_t n_eta, float* prior_lambda, uint32_t n_lambda);
 
 /* host-side restatements */
 int orc_bal_read_header(const char* path, gbp_bal* hdr);

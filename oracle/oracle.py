@@ -8,6 +8,10 @@ Two builds of the same vertex/schedule restatement (oracle_gbp.c):
   variant "ref"        : $TMPDIR/gbp_oracle_ref/liboracle_ref.so — dense math is the reference's own
                          matlib.cpp / bafuncs.cpp compiled in the build container, OUTSIDE the repository:
                          nothing made from the reference's sources sits in the work tree or travels to the GPU box
+and, beside them (same place, build container only):
+  variant "ref_vertices": libref_vertices.so — the reference's own seven vertex classes (gbp_codelets.cpp compiled unmodified
+                         against oracle/poplar_standin), rv_* interface of ref_vertex_adapter.cpp; the restatement exports the
+                         same signatures as orc_vertex_* (vertex_api() hands out either set under one set of names)
 """
 import ctypes as C
 import os
@@ -35,6 +39,8 @@ def lib_path(variant="restatement"):
         return os.path.join(ref_dir(), "liboracle_ref.so")
     if variant == "ref_math":
         return os.path.join(ref_dir(), "libref_math.so")
+    if variant == "ref_vertices":
+        return os.path.join(ref_dir(), "libref_vertices.so")
     raise ValueError(variant)
 
 
@@ -51,6 +57,43 @@ def have(variant):
     return os.path.exists(lib_path(variant))
 
 
+# the vertex-level interface: rv_* (reference, ref_vertex_adapter.cpp) and orc_vertex_* (restatement, oracle.h) share these
+# signatures.  Arrays are passed as addresses (c_void_p), so a driver can step through [n][width] arrays without a ctypes
+# pointer object per call.
+_VP = C.c_void_p
+_VERTEX_SIGS = {
+    "set_hyper": [C.c_float, C.c_int, C.c_float, C.c_int, C.c_float],
+    "relinearise_factor": [_VP, C.c_float] + [_VP] * 11,
+    "prep_message": [_VP, _VP, C.c_uint, _VP, _VP, _VP, C.c_float] + [_VP] * 12,
+    "cam_message_eta": [C.c_float, C.c_uint] + [_VP] * 10,
+    "lmk_message_eta": [C.c_float, C.c_uint] + [_VP] * 10,
+    "cam_message_lambda": [C.c_uint] + [_VP] * 7,
+    "lmk_message_lambda": [C.c_uint] + [_VP] * 7,
+    "weaken_prior": [C.c_float, _VP, _VP, C.c_uint, _VP, C.c_uint],
+}
+
+
+class _VertexApi:
+    pass
+
+
+def vertex_api(variant="restatement"):
+    """The seven vertex classes of `variant` ("restatement": orc_vertex_*, "ref_vertices": rv_*) under common names."""
+    lib = load(variant)
+    prefix = "rv_" if variant == "ref_vertices" else "orc_vertex_"
+    api = _VertexApi()
+    for name, args in _VERTEX_SIGS.items():
+        fn = getattr(lib, prefix + name)
+        fn.argtypes, fn.restype = args, None
+        setattr(api, name, fn)
+    if variant == "ref_vertices":
+        api.set_relin_mode = None          # the reference has no reset mode
+    else:
+        lib.orc_vertex_set_relin_mode.argtypes, lib.orc_vertex_set_relin_mode.restype = [C.c_int], None
+        api.set_relin_mode = lib.orc_vertex_set_relin_mode
+    return api
+
+
 def load(variant="restatement"):
     if variant in _LIBS:
         return _LIBS[variant]
@@ -58,6 +101,10 @@ def load(variant="restatement"):
     if not os.path.exists(path) and variant == "restatement":
         build(ref=False)
     lib = C.CDLL(path)
+    if variant == "ref_vertices":
+        lib.rv_impl_name.restype = C.c_char_p
+        _LIBS[variant] = lib
+        return lib
     if variant != "ref_math":
         lib.orc_create.restype = C.c_void_p
         lib.orc_create.argtypes = [C.POINTER(cabi.GbpProblem), C.POINTER(cabi.GbpParams)]

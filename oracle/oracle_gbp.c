@@ -237,32 +237,33 @@ static void update_beliefs(orc_ctx* o) {
   }
 }
 
+/* ------------------------------------------------------------------------------------------
+ * The seven vertex classes on plain pointers, arguments under the reference's field names: what the
+ * (orc_ctx*, edge) functions below call, and what orc_vertex_* (oracle.h) exports for the
+ * vertex-level comparison with the reference's own compute() bodies (ref_vertex_adapter.cpp).
+ * ------------------------------------------------------------------------------------------ */
+
 /* linearisation point = belief means: inf2mean6x6 / inf2mean3x3, bafuncs.cpp:2-15 */
-static void belief_means(const orc_ctx* o, uint32_t e, float* x0c, float* x0l) {
-  uint32_t c = o->cam_id[e], l = o->lmk_id[e];
+static void means_p(const float* kf_eta, const float* kf_lambda, const float* lmk_eta, const float* lmk_lambda, float* x0c, float* x0l) {
   int i;
   for (i = 0; i < 6; ++i) x0c[i] = 0.f;
   for (i = 0; i < 3; ++i) x0l[i] = 0.f;
-  om_inf2mean6x6(o->cbe + (size_t)c * 6, o->cbl + (size_t)c * 36, x0c);
-  om_inf2mean3x3(o->lbe + (size_t)l * 3, o->lbl + (size_t)l * 9, x0l);
+  om_inf2mean6x6(kf_eta, kf_lambda, x0c);
+  om_inf2mean3x3(lmk_eta, lmk_lambda, x0l);
 }
 
 /* Shared body of gbp_codelets.cpp:90-168 and :294-373: accumulate J^T J and J^T(Jx0+z-h(x0))
  * onto the factor potential, Huber-rescale, Lambda_lc = Lambda_cl^T. */
-static void relin_core(orc_ctx* o, uint32_t e, const float* x0c, const float* x0l) {
-  float* eta = o->fac_eta + (size_t)e * 9;
-  float* cc = o->fac_lam + (size_t)e * 81;
-  float *cl = cc + 36, *lc = cc + 54, *ll = cc + 72;
-  const float* z = o->meas + (size_t)e * 2;
-  float var = o->var[e];
+static void relin_core_p(float nstds, const float* z, float var, const float* K, const float* x0c, const float* x0l,
+                         float* eta, float* cc, float* ll, float* cl, float* lc, uint32_t* robust) {
   float Jkf[12] = {0}, Jl[6] = {0}, hx[2] = {0}, buf[2] = {0}, x0[9], J[18] = {0};
-  float err, mvar, nstds = o->prm.nstds;
+  float err, mvar;
   int i, j;
-  om_jac(x0c, x0l, o->K, Jkf, Jl);
+  om_jac(x0c, x0l, K, Jkf, Jl);
   om_matmul(Jkf, 2, 6, Jkf, 2, 6, cc, 6, 1, 0);
   om_matmul(Jl, 2, 3, Jl, 2, 3, ll, 3, 1, 0);
   om_matmul(Jkf, 2, 6, Jl, 2, 3, cl, 3, 1, 0);
-  om_hfunc(x0c, x0l, o->K, hx);
+  om_hfunc(x0c, x0l, K, hx);
   for (i = 0; i < 6; ++i) x0[i] = x0c[i];
   for (i = 0; i < 3; ++i) x0[i + 6] = x0l[i];
   for (i = 0; i < 2; ++i) {
@@ -278,10 +279,10 @@ static void relin_core(orc_ctx* o, uint32_t e, const float* x0c, const float* x0
   err = sqrtf((hx[0] - z[0]) * (hx[0] - z[0]) + (hx[1] - z[1]) * (hx[1] - z[1]));
   mvar = var;
   if (err > nstds * sqrtf(var)) {
-    o->robust[e] = 1;
+    *robust = 1;
     mvar = var * err * err / (2 * (nstds * sqrtf(var) * err - 0.5 * nstds * nstds * var));
   } else {
-    o->robust[e] = 0;
+    *robust = 0;
   }
   for (i = 0; i < 36; ++i) cc[i] /= mvar;
   for (i = 0; i < 9; ++i) ll[i] /= mvar;
@@ -292,128 +293,167 @@ static void relin_core(orc_ctx* o, uint32_t e, const float* x0c, const float* x0
 }
 
 /* RelineariseFactorVertex, gbp_codelets.cpp:38-171 (no active_flag test: runs on every factor) */
-static void relinearise_zero(orc_ctx* o, uint32_t e) {
+static void relinearise_p(float nstds, const float* z, float var, const float* K, const float* kf_eta, const float* kf_lambda,
+                          const float* lmk_eta, const float* lmk_lambda, float* eta, float* cc, float* ll, float* cl, float* lc,
+                          uint32_t* robust) {
   float x0c[6], x0l[3];
-  memset(o->fac_eta + (size_t)e * 9, 0, 9 * 4);
-  memset(o->fac_lam + (size_t)e * 81, 0, 81 * 4);
-  belief_means(o, e, x0c, x0l);
-  relin_core(o, e, x0c, x0l);
+  memset(eta, 0, 9 * 4);
+  memset(cc, 0, 36 * 4); memset(ll, 0, 9 * 4); memset(cl, 0, 18 * 4); memset(lc, 0, 18 * 4);
+  means_p(kf_eta, kf_lambda, lmk_eta, lmk_lambda, x0c, x0l);
+  relin_core_p(nstds, z, var, K, x0c, x0l, eta, cc, ll, cl, lc, robust);
 }
 
 /* PrepMessageVertex, gbp_codelets.cpp:241-378 */
-static void prep_factor(orc_ctx* o, uint32_t e) {
+static void prep_p(const gbp_params* prm, float* damping, int32_t* count, uint32_t active, uint32_t* robust, const float* z,
+                   const float* K, float var, const float* kf_eta, const float* kf_lambda, const float* lmk_eta,
+                   const float* lmk_lambda, const float* oldmu, float* mu, float* dmu, float* eta, float* cc, float* ll, float* cl,
+                   float* lc) {
   float x0c[6], x0l[3], d;
   int i;
-  if (o->active[e] != 1) return;
-  if (0 == o->count[e]) o->damping[e] = o->prm.maxeta_damping;
-  o->count[e] += 1;
-  belief_means(o, e, x0c, x0l);
+  if (active != 1) return;
+  if (0 == *count) *damping = prm->maxeta_damping;
+  *count += 1;
+  means_p(kf_eta, kf_lambda, lmk_eta, lmk_lambda, x0c, x0l);
   d = 0.0;
   for (i = 0; i < 6; ++i) {
-    d += (o->oldmu[(size_t)e * 9 + i] - x0c[i]) * (o->oldmu[(size_t)e * 9 + i] - x0c[i]);
-    o->mu[(size_t)e * 9 + i] = x0c[i];
+    d += (oldmu[i] - x0c[i]) * (oldmu[i] - x0c[i]);
+    mu[i] = x0c[i];
   }
   for (i = 0; i < 3; ++i) {
-    d += (o->oldmu[(size_t)e * 9 + i + 6] - x0l[i]) * (o->oldmu[(size_t)e * 9 + i + 6] - x0l[i]);
-    o->mu[(size_t)e * 9 + i + 6] = x0l[i];
+    d += (oldmu[i + 6] - x0l[i]) * (oldmu[i + 6] - x0l[i]);
+    mu[i + 6] = x0l[i];
   }
   d = sqrtf(d);
-  o->dmu[e] = d;
-  if ((d < o->prm.dmu_threshold) && (o->count[e] > o->prm.min_linear_iters - o->prm.num_undamped_iters)) {
-    o->damping[e] = 0.0;
-    o->count[e] = -o->prm.num_undamped_iters;
-    if (o->prm.relin_mode == 1) { /* opt-in: zero first (quirk C-1 "fixed") */
-      memset(o->fac_eta + (size_t)e * 9, 0, 9 * 4);
-      memset(o->fac_lam + (size_t)e * 81, 0, 81 * 4);
+  *dmu = d;
+  if ((d < prm->dmu_threshold) && (*count > prm->min_linear_iters - prm->num_undamped_iters)) {
+    *damping = 0.0;
+    *count = -prm->num_undamped_iters;
+    if (prm->relin_mode == 1) { /* opt-in: zero first (quirk C-1 "fixed") */
+      memset(eta, 0, 9 * 4);
+      memset(cc, 0, 36 * 4); memset(ll, 0, 9 * 4); memset(cl, 0, 18 * 4); memset(lc, 0, 18 * 4);
     }
-    relin_core(o, e, x0c, x0l); /* accumulates onto the old potential: matMul is += */
+    relin_core_p(prm->nstds, z, var, K, x0c, x0l, eta, cc, ll, cl, lc, robust); /* accumulates onto the old potential: matMul is += */
   }
 }
 
-/* ComputeCamMessageEtaVertex, gbp_codelets.cpp:411-471 */
-static void msg_cam_eta(orc_ctx* o, uint32_t e) {
-  uint32_t l = o->lmk_id[e];
-  const float* Ef = o->fac_eta + (size_t)e * 9;
-  const float* Lf = o->fac_lam + (size_t)e * 81;
-  float* out = o->mce + (size_t)e * 6;
+/* ComputeCamMessageEtaVertex, gbp_codelets.cpp:411-471 (oe = camera 6, noe = landmark 3) */
+static void msg_cam_eta_p(float d, uint32_t active, const float* f_oe_eta, const float* f_noe_eta, const float* f_noe_noe,
+                          const float* f_oe_noe, const float* bel_noe_eta, const float* bel_noe_lam, const float* pm_noe_eta,
+                          const float* pm_noe_lam, const float* pm_oe_eta, float* out) {
   int i;
-  if (o->active[e] == 1) {
+  if (active == 1) {
     float b1[9], b2[9] = {0}, b3[18] = {0}, b4[3], b5[6] = {0}, b6[6];
-    float d = o->damping[e];
-    for (i = 0; i < 9; ++i) b1[i] = Lf[72 + i] + o->lbl[(size_t)l * 9 + i];
-    for (i = 0; i < 9; ++i) b1[i] = b1[i] - o->pll[(size_t)e * 9 + i];
+    for (i = 0; i < 9; ++i) b1[i] = f_noe_noe[i] + bel_noe_lam[i];
+    for (i = 0; i < 9; ++i) b1[i] = b1[i] - pm_noe_lam[i];
     om_inv3x3(b1, b2);
-    om_matmul(Lf + 36, 6, 3, b2, 3, 3, b3, 3, 0, 0);
-    for (i = 0; i < 3; ++i) b4[i] = Ef[6 + i] + o->lbe[(size_t)l * 3 + i];
-    for (i = 0; i < 3; ++i) b4[i] = b4[i] - o->ple[(size_t)e * 3 + i];
+    om_matmul(f_oe_noe, 6, 3, b2, 3, 3, b3, 3, 0, 0);
+    for (i = 0; i < 3; ++i) b4[i] = f_noe_eta[i] + bel_noe_eta[i];
+    for (i = 0; i < 3; ++i) b4[i] = b4[i] - pm_noe_eta[i];
     om_matmul(b3, 6, 3, b4, 3, 1, b5, 1, 0, 0);
-    for (i = 0; i < 6; ++i) b6[i] = Ef[i] - b5[i];
-    for (i = 0; i < 6; ++i) out[i] = b6[i] * (1 - d) + o->pce[(size_t)e * 6 + i] * d;
+    for (i = 0; i < 6; ++i) b6[i] = f_oe_eta[i] - b5[i];
+    for (i = 0; i < 6; ++i) out[i] = b6[i] * (1 - d) + pm_oe_eta[i] * d;
   } else {
     for (i = 0; i < 6; ++i) out[i] = 0.0;
   }
 }
 
-/* ComputeLmkMessageEtaVertex, gbp_codelets.cpp:503-562 */
-static void msg_lmk_eta(orc_ctx* o, uint32_t e) {
-  uint32_t c = o->cam_id[e];
-  const float* Ef = o->fac_eta + (size_t)e * 9;
-  const float* Lf = o->fac_lam + (size_t)e * 81;
-  float* out = o->mle + (size_t)e * 3;
+/* ComputeLmkMessageEtaVertex, gbp_codelets.cpp:503-562 (oe = landmark 3, noe = camera 6) */
+static void msg_lmk_eta_p(float d, uint32_t active, const float* f_oe_eta, const float* f_noe_eta, const float* f_noe_noe,
+                          const float* f_oe_noe, const float* bel_noe_eta, const float* bel_noe_lam, const float* pm_noe_eta,
+                          const float* pm_noe_lam, const float* pm_oe_eta, float* out) {
   int i;
-  if (o->active[e] == 1) {
+  if (active == 1) {
     float b1[36], b2[36] = {0}, b3[18] = {0}, b4[6], b5[3] = {0}, b6[3];
-    float d = o->damping[e];
-    for (i = 0; i < 36; ++i) b1[i] = Lf[i] + o->cbl[(size_t)c * 36 + i];
-    for (i = 0; i < 36; ++i) b1[i] = b1[i] - o->pcl[(size_t)e * 36 + i];
+    for (i = 0; i < 36; ++i) b1[i] = f_noe_noe[i] + bel_noe_lam[i];
+    for (i = 0; i < 36; ++i) b1[i] = b1[i] - pm_noe_lam[i];
     om_inv6x6(b1, b2);
-    om_matmul(Lf + 54, 3, 6, b2, 6, 6, b3, 6, 0, 0);
-    for (i = 0; i < 6; ++i) b4[i] = Ef[i] + o->cbe[(size_t)c * 6 + i];
-    for (i = 0; i < 6; ++i) b4[i] = b4[i] - o->pce[(size_t)e * 6 + i];
+    om_matmul(f_oe_noe, 3, 6, b2, 6, 6, b3, 6, 0, 0);
+    for (i = 0; i < 6; ++i) b4[i] = f_noe_eta[i] + bel_noe_eta[i];
+    for (i = 0; i < 6; ++i) b4[i] = b4[i] - pm_noe_eta[i];
     om_matmul(b3, 3, 6, b4, 6, 1, b5, 1, 0, 0);
-    for (i = 0; i < 3; ++i) b6[i] = Ef[6 + i] - b5[i];
-    for (i = 0; i < 3; ++i) out[i] = b6[i] * (1 - d) + o->ple[(size_t)e * 3 + i] * d;
+    for (i = 0; i < 3; ++i) b6[i] = f_oe_eta[i] - b5[i];
+    for (i = 0; i < 3; ++i) out[i] = b6[i] * (1 - d) + pm_oe_eta[i] * d;
   } else {
     for (i = 0; i < 3; ++i) out[i] = 0.0;
   }
 }
 
 /* ComputeCamMessageLambdaVertex, gbp_codelets.cpp:592-637 */
-static void msg_cam_lambda(orc_ctx* o, uint32_t e) {
-  uint32_t l = o->lmk_id[e];
-  const float* Lf = o->fac_lam + (size_t)e * 81;
-  float* out = o->mcl + (size_t)e * 36;
+static void msg_cam_lambda_p(uint32_t active, const float* f_oe_oe, const float* f_noe_noe, const float* f_oe_noe, const float* f_noe_oe,
+                             const float* bel_noe_lam, const float* pm_noe_lam, float* out) {
   int i;
-  if (o->active[e] == 1) {
+  if (active == 1) {
     float b1[9], b2[9] = {0}, b3[18] = {0}, b4[36] = {0};
-    for (i = 0; i < 9; ++i) b1[i] = Lf[72 + i] + o->lbl[(size_t)l * 9 + i];
-    for (i = 0; i < 9; ++i) b1[i] = b1[i] - o->pll[(size_t)e * 9 + i];
+    for (i = 0; i < 9; ++i) b1[i] = f_noe_noe[i] + bel_noe_lam[i];
+    for (i = 0; i < 9; ++i) b1[i] = b1[i] - pm_noe_lam[i];
     om_inv3x3(b1, b2);
-    om_matmul(Lf + 36, 6, 3, b2, 3, 3, b3, 3, 0, 0);
-    om_matmul(b3, 6, 3, Lf + 54, 3, 6, b4, 6, 0, 0);
-    for (i = 0; i < 36; ++i) out[i] = Lf[i] - b4[i];
+    om_matmul(f_oe_noe, 6, 3, b2, 3, 3, b3, 3, 0, 0);
+    om_matmul(b3, 6, 3, f_noe_oe, 3, 6, b4, 6, 0, 0);
+    for (i = 0; i < 36; ++i) out[i] = f_oe_oe[i] - b4[i];
   } else {
     for (i = 0; i < 36; ++i) out[i] = 0.0;
   }
 }
 
 /* ComputeLmkMessageLambdaVertex, gbp_codelets.cpp:664-709 */
-static void msg_lmk_lambda(orc_ctx* o, uint32_t e) {
-  uint32_t c = o->cam_id[e];
-  const float* Lf = o->fac_lam + (size_t)e * 81;
-  float* out = o->mll + (size_t)e * 9;
+static void msg_lmk_lambda_p(uint32_t active, const float* f_oe_oe, const float* f_noe_noe, const float* f_oe_noe, const float* f_noe_oe,
+                             const float* bel_noe_lam, const float* pm_noe_lam, float* out) {
   int i;
-  if (o->active[e] == 1) {
+  if (active == 1) {
     float b1[36], b2[36] = {0}, b3[18] = {0}, b4[9] = {0};
-    for (i = 0; i < 36; ++i) b1[i] = Lf[i] + o->cbl[(size_t)c * 36 + i];
-    for (i = 0; i < 36; ++i) b1[i] = b1[i] - o->pcl[(size_t)e * 36 + i];
+    for (i = 0; i < 36; ++i) b1[i] = f_noe_noe[i] + bel_noe_lam[i];
+    for (i = 0; i < 36; ++i) b1[i] = b1[i] - pm_noe_lam[i];
     om_inv6x6(b1, b2);
-    om_matmul(Lf + 54, 3, 6, b2, 6, 6, b3, 6, 0, 0);
-    om_matmul(b3, 3, 6, Lf + 36, 6, 3, b4, 3, 0, 0);
-    for (i = 0; i < 9; ++i) out[i] = Lf[72 + i] - b4[i];
+    om_matmul(f_oe_noe, 3, 6, b2, 6, 6, b3, 6, 0, 0);
+    om_matmul(b3, 3, 6, f_noe_oe, 6, 3, b4, 3, 0, 0);
+    for (i = 0; i < 9; ++i) out[i] = f_oe_oe[i] - b4[i];
   } else {
     for (i = 0; i < 9; ++i) out[i] = 0.0;
   }
+}
+
+/* the same on (orc_ctx*, edge): factor_potentials_lambda = [cc36|cl18|lc18|ll9] (ba.cpp:93-96) */
+static void relinearise_zero(orc_ctx* o, uint32_t e) {
+  uint32_t c = o->cam_id[e], l = o->lmk_id[e];
+  float* cc = o->fac_lam + (size_t)e * 81;
+  relinearise_p(o->prm.nstds, o->meas + (size_t)e * 2, o->var[e], o->K, o->cbe + (size_t)c * 6, o->cbl + (size_t)c * 36,
+                o->lbe + (size_t)l * 3, o->lbl + (size_t)l * 9, o->fac_eta + (size_t)e * 9, cc, cc + 72, cc + 36, cc + 54, &o->robust[e]);
+}
+
+static void prep_factor(orc_ctx* o, uint32_t e) {
+  uint32_t c = o->cam_id[e], l = o->lmk_id[e];
+  float* cc = o->fac_lam + (size_t)e * 81;
+  prep_p(&o->prm, &o->damping[e], &o->count[e], o->active[e], &o->robust[e], o->meas + (size_t)e * 2, o->K, o->var[e],
+         o->cbe + (size_t)c * 6, o->cbl + (size_t)c * 36, o->lbe + (size_t)l * 3, o->lbl + (size_t)l * 9, o->oldmu + (size_t)e * 9,
+         o->mu + (size_t)e * 9, &o->dmu[e], o->fac_eta + (size_t)e * 9, cc, cc + 72, cc + 36, cc + 54);
+}
+
+static void msg_cam_eta(orc_ctx* o, uint32_t e) {
+  uint32_t l = o->lmk_id[e];
+  const float* Ef = o->fac_eta + (size_t)e * 9;
+  const float* Lf = o->fac_lam + (size_t)e * 81;
+  msg_cam_eta_p(o->damping[e], o->active[e], Ef, Ef + 6, Lf + 72, Lf + 36, o->lbe + (size_t)l * 3, o->lbl + (size_t)l * 9,
+                o->ple + (size_t)e * 3, o->pll + (size_t)e * 9, o->pce + (size_t)e * 6, o->mce + (size_t)e * 6);
+}
+
+static void msg_lmk_eta(orc_ctx* o, uint32_t e) {
+  uint32_t c = o->cam_id[e];
+  const float* Ef = o->fac_eta + (size_t)e * 9;
+  const float* Lf = o->fac_lam + (size_t)e * 81;
+  msg_lmk_eta_p(o->damping[e], o->active[e], Ef + 6, Ef, Lf, Lf + 54, o->cbe + (size_t)c * 6, o->cbl + (size_t)c * 36,
+                o->pce + (size_t)e * 6, o->pcl + (size_t)e * 36, o->ple + (size_t)e * 3, o->mle + (size_t)e * 3);
+}
+
+static void msg_cam_lambda(orc_ctx* o, uint32_t e) {
+  uint32_t l = o->lmk_id[e];
+  const float* Lf = o->fac_lam + (size_t)e * 81;
+  msg_cam_lambda_p(o->active[e], Lf, Lf + 72, Lf + 36, Lf + 54, o->lbl + (size_t)l * 9, o->pll + (size_t)e * 9, o->mcl + (size_t)e * 36);
+}
+
+static void msg_lmk_lambda(orc_ctx* o, uint32_t e) {
+  uint32_t c = o->cam_id[e];
+  const float* Lf = o->fac_lam + (size_t)e * 81;
+  msg_lmk_lambda_p(o->active[e], Lf + 72, Lf, Lf + 54, Lf + 36, o->cbl + (size_t)c * 36, o->pcl + (size_t)e * 36, o->mll + (size_t)e * 9);
 }
 
 /* LINEARISE_PROG, ba.cpp:890-893: prog_ub then cs_relinearise */
@@ -458,6 +498,61 @@ static void weaken_var(float scaling, uint32_t* flag, float* eta, int ne, float*
     for (i = 0; i < ne; ++i) eta[i] *= scaling;
     for (i = 0; i < nl; ++i) lam[i] *= scaling;
   }
+}
+
+/* ---- the vertex classes under the signatures of ref_vertex_adapter.cpp's rv_* (oracle.h) ---- */
+static gbp_params vtx_prm = {0.4f, 8, 3e-3f, 10, 2.5f, 0};
+
+void orc_vertex_set_hyper(float maxeta_damping, int num_undamped_iters, float dmu_threshold, int min_linear_iters, float nstds) {
+  vtx_prm.maxeta_damping = maxeta_damping; vtx_prm.num_undamped_iters = num_undamped_iters;
+  vtx_prm.dmu_threshold = dmu_threshold; vtx_prm.min_linear_iters = min_linear_iters; vtx_prm.nstds = nstds;
+}
+void orc_vertex_set_relin_mode(int relin_mode) { vtx_prm.relin_mode = relin_mode; }
+
+void orc_vertex_relinearise_factor(const float* measurement, float meas_variance, const float* K, const float* kf_belief_eta,
+                                   const float* kf_belief_lambda, const float* lmk_belief_eta, const float* lmk_belief_lambda,
+                                   float* factor_eta, float* factor_lambda_cc, float* factor_lambda_ll, float* factor_lambda_cl,
+                                   float* factor_lambda_lc, uint32_t* robust_flag) {
+  relinearise_p(vtx_prm.nstds, measurement, meas_variance, K, kf_belief_eta, kf_belief_lambda, lmk_belief_eta, lmk_belief_lambda,
+                factor_eta, factor_lambda_cc, factor_lambda_ll, factor_lambda_cl, factor_lambda_lc, robust_flag);
+}
+void orc_vertex_prep_message(float* damping, int32_t* damping_count, uint32_t active_flag, uint32_t* robust_flag, const float* measurement,
+                             const float* K, float meas_variance, const float* kf_belief_eta, const float* kf_belief_lambda,
+                             const float* lmk_belief_eta, const float* lmk_belief_lambda, const float* oldmu, float* mu, float* dmu,
+                             float* factor_eta, float* factor_lambda_cc, float* factor_lambda_ll, float* factor_lambda_cl,
+                             float* factor_lambda_lc) {
+  prep_p(&vtx_prm, damping, damping_count, active_flag, robust_flag, measurement, K, meas_variance, kf_belief_eta, kf_belief_lambda,
+         lmk_belief_eta, lmk_belief_lambda, oldmu, mu, dmu, factor_eta, factor_lambda_cc, factor_lambda_ll, factor_lambda_cl,
+         factor_lambda_lc);
+}
+void orc_vertex_cam_message_eta(float damping, uint32_t active_flag, const float* f_outedge_eta, const float* f_nonoutedge_eta,
+                                const float* f_noe_noe_lambda, const float* f_oe_noe_lambda, const float* belief_nonoutedge_eta,
+                                const float* belief_nonoutedge_lambda, const float* pmess_nonoutedge_eta,
+                                const float* pmess_nonoutedge_lambda, const float* pmess_outedge_eta, float* mess_outedge_eta) {
+  msg_cam_eta_p(damping, active_flag, f_outedge_eta, f_nonoutedge_eta, f_noe_noe_lambda, f_oe_noe_lambda, belief_nonoutedge_eta,
+                belief_nonoutedge_lambda, pmess_nonoutedge_eta, pmess_nonoutedge_lambda, pmess_outedge_eta, mess_outedge_eta);
+}
+void orc_vertex_lmk_message_eta(float damping, uint32_t active_flag, const float* f_outedge_eta, const float* f_nonoutedge_eta,
+                                const float* f_noe_noe_lambda, const float* f_oe_noe_lambda, const float* belief_nonoutedge_eta,
+                                const float* belief_nonoutedge_lambda, const float* pmess_nonoutedge_eta,
+                                const float* pmess_nonoutedge_lambda, const float* pmess_outedge_eta, float* mess_outedge_eta) {
+  msg_lmk_eta_p(damping, active_flag, f_outedge_eta, f_nonoutedge_eta, f_noe_noe_lambda, f_oe_noe_lambda, belief_nonoutedge_eta,
+                belief_nonoutedge_lambda, pmess_nonoutedge_eta, pmess_nonoutedge_lambda, pmess_outedge_eta, mess_outedge_eta);
+}
+void orc_vertex_cam_message_lambda(uint32_t active_flag, const float* f_oe_oe_lambda, const float* f_noe_noe_lambda,
+                                   const float* f_oe_noe_lambda, const float* f_noe_oe_lambda, const float* belief_nonoutedge_lambda,
+                                   const float* pmess_nonoutedge_lambda, float* mess_outedge_lambda) {
+  msg_cam_lambda_p(active_flag, f_oe_oe_lambda, f_noe_noe_lambda, f_oe_noe_lambda, f_noe_oe_lambda, belief_nonoutedge_lambda,
+                   pmess_nonoutedge_lambda, mess_outedge_lambda);
+}
+void orc_vertex_lmk_message_lambda(uint32_t active_flag, const float* f_oe_oe_lambda, const float* f_noe_noe_lambda,
+                                   const float* f_oe_noe_lambda, const float* f_noe_oe_lambda, const float* belief_nonoutedge_lambda,
+                                   const float* pmess_nonoutedge_lambda, float* mess_outedge_lambda) {
+  msg_lmk_lambda_p(active_flag, f_oe_oe_lambda, f_noe_noe_lambda, f_oe_noe_lambda, f_noe_oe_lambda, belief_nonoutedge_lambda,
+                   pmess_nonoutedge_lambda, mess_outedge_lambda);
+}
+void orc_vertex_weaken_prior(float scaling, uint32_t* weaken_flag, float* prior_eta, uint32_t n_eta, float* prior_lambda, uint32_t n_lambda) {
+  weaken_var(scaling, weaken_flag, prior_eta, (int)n_eta, prior_lambda, (int)n_lambda);
 }
 
 /* WEAKEN_PRIORS, ba.cpp:863-865 */

@@ -4,8 +4,8 @@
 // compiled from the sources where they lie (no copy is made into this repository; the objects go to
 // $TMPDIR/gbp_oracle_ref, OUTSIDE the repository, so they never travel with a snapshot of it).  matlib.cpp and bafuncs.cpp are self-contained
 // header-style C++ (they need only <cmath>), so this is g++ on the reference's own files —
-// no stand-in headers.  gbp_codelets.cpp (the Poplar vertex classes) is NOT built: it needs
-// <poplar/Vertex.hpp>, which the image lacks, so it is restated in oracle_gbp.c instead.
+// no stand-in headers.  gbp_codelets.cpp (the Poplar vertex classes) needs <poplar/Vertex.hpp>: it is built by
+// ref_vertex_adapter.cpp against the stand-in of poplar_standin/, and restated in oracle_gbp.c.
 #include <cmath>
 #include "/root/reference/ba/matlib.cpp"
 #include "/root/reference/ba/bafuncs.cpp"

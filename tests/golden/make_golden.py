@@ -8,6 +8,8 @@ Sources of truth:
     comes from it (literal std::sin/std::cos, ascending slot-order sums).
   * `dev_` entries: the same restatement in the device's arithmetic conventions (correctly rounded trig,
     row-of-16 tree order for camera sums) — what the HIP kernels must reproduce bit for bit.
+  * vertex_cases.npz: `ref_` comes from the REFERENCE's own vertex classes (gbp_codelets.cpp compiled against
+    oracle/poplar_standin, libref_vertices.so), `dev_` from the restatement's vertices in trig mode 1.
 The fixtures are data only (inputs + expected outputs); no reference source text is stored.
 """
 import os
@@ -156,6 +158,51 @@ def vertex_vectors(name, n_sample=64):
     return out
 
 
+def vertex_cases():
+    """A sub-sample of every group of tests/vertex_cases.py: the inputs, the outputs of the REFERENCE's vertex classes (`ref_`,
+    libm trig; absent for relin_mode 1, which the reference does not have: has_ref) and of the restatement's in the device's
+    trig convention (`dev_`), for op 0 (RelineariseFactorVertex) and op 1 (PrepMessageVertex + the four message vertices); the
+    WeakenPriorVertex cases with the reference's outputs; and what the reference did on the FULL generated set (cases per group,
+    branches taken)."""
+    from tests import vertex_cases as vc
+    ref, mine = orc.vertex_api("ref_vertices"), orc.vertex_api("restatement")
+    X, g = vc.all_cases()
+    idx = vc.golden_subset(g)
+    x, grp = np.ascontiguousarray(X[idx]), g[idx]
+    has_ref = vc.field(x, "relin_mode")[:, 0] == 0
+    out = {"x": x, "group": grp, "index": idx, "has_ref": has_ref}
+    for op in (0, 1):
+        r = np.zeros((len(x), vc.W_OUT), np.float32)
+        r[has_ref] = vc.run_cpu(ref, x[has_ref], op)
+        orc.set_trig_mode(1)
+        try:
+            d = vc.run_cpu(mine, x, op)
+        finally:
+            orc.set_trig_mode(0)
+        out["ref_op%d" % op], out["dev_op%d" % op] = r, d
+    W = vc.weaken_cases()
+    out.update({"weaken_in_" + k: v for k, v in W.items()})
+    out.update({"weaken_ref_" + k: v for k, v in vc.run_weaken(ref, W).items()})
+    out["full_counts"] = vertex_branch_counts(ref, X, g)
+    return out
+
+
+def vertex_branch_counts(ref, X, g):
+    """[group][cases, relinearised, robust after op 1, robust after op 0, active] of the reference's vertices on the full set
+    (relin_mode 1 cases, which the reference cannot run, count as cases only)."""
+    from tests import vertex_cases as vc
+    has_ref = vc.field(X, "relin_mode")[:, 0] == 0
+    Xr, gr = X[has_ref], g[has_ref]
+    y0, y1 = vc.run_cpu(ref, Xr, 0), vc.run_cpu(ref, Xr, 1)
+    rel = vc.relinearised(Xr, y1)
+    rows = []
+    for gi in range(len(vc.GROUPS)):
+        m = gr == gi
+        rows.append([int((g == gi).sum()), int(rel[m].sum()), int(vc.field(y1, "robust", True)[m].sum()),
+                     int(vc.field(y0, "robust", True)[m].sum()), int((vc.field(Xr, "active")[m] == 1).sum())])
+    return np.array(rows, np.int64)
+
+
 def trajectories():
     """printed metric trajectory (iteration, mean reproj, cost, RMSE, n_relins, n_robust, n_active) of
     `./ba` on fr1xyz / fr2robot2 (1500 sweeps) and `./slam` on fr2robot2 (700 sweeps per keyframe), from the
@@ -192,6 +239,11 @@ def main():
         return
     if sys.argv[1:] == ["math"]:
         np.savez_compressed(os.path.join(HERE, "math_vectors.npz"), **math_vectors(ref))
+        return
+    if sys.argv[1:] == ["vertex_cases"]:
+        if not orc.have("ref_vertices"):
+            raise SystemExit("the reference-vertex build is missing: run `make -C oracle ref` in the build container first")
+        np.savez_compressed(os.path.join(HERE, "vertex_cases.npz"), **vertex_cases())
         return
     if sys.argv[1:] == ["traj"]:
         np.savez_compressed(os.path.join(HERE, "trajectories.npz"), **trajectories())
@@ -237,6 +289,7 @@ def main():
     np.savez_compressed(os.path.join(HERE, "sequence_snapshots.npz"), **snaps)
     np.savez_compressed(os.path.join(HERE, "vertex_vectors.npz"), **vertex_vectors("fr2robot2"))
     np.savez_compressed(os.path.join(HERE, "trajectories.npz"), **trajectories())
+    np.savez_compressed(os.path.join(HERE, "vertex_cases.npz"), **vertex_cases())
     print("golden fixtures written:", [f for f in os.listdir(HERE) if f.endswith(".npz")])
 
 

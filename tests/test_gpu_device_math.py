@@ -188,3 +188,67 @@ def test_shared_reciprocal_division_is_the_ieee_division():
             ref = x / m[:, None]
             same = (out.view(np.uint32) == ref.view(np.uint32)) | (np.isnan(out) & np.isnan(ref))
             assert same.all(), (x[~same][:4], np.broadcast_to(m[:, None], x.shape)[~same][:4], out[~same][:4], ref[~same][:4])
+
+
+def _restated(oracle_mod, fn, ins, out_w, n_out=1):
+    """`fn` of the restatement's math layer (trig mode 1: the device's convention) on every row of the inputs"""
+    import ctypes as C
+    fp = C.POINTER(C.c_float)
+    lib = oracle_mod.load("restatement")
+    ins = [np.ascontiguousarray(a, np.float32) for a in ins]
+    outs = [np.zeros((ins[0].shape[0], w), np.float32) for w in (out_w if n_out > 1 else [out_w])]
+    oracle_mod.set_trig_mode(1)
+    try:
+        for i in range(ins[0].shape[0]):
+            getattr(lib, fn)(*[a[i].ctypes.data_as(fp) for a in ins], *[o[i].ctypes.data_as(fp) for o in outs])
+    finally:
+        oracle_mod.set_trig_mode(0)
+    return outs if n_out > 1 else outs[0]
+
+
+def test_wide_range_inputs_match_the_restatement_bit_for_bit(oracle_mod):
+    """ops 0, 1, 3, 7, 8 on the inputs the vertex cases of tests/vertex_cases.py put in front of them — Schur blocks that are
+    indefinite or have a negative / tiny pivot, beliefs whose scale spans 1e-6 .. 1e8, |w| from 2e-6 to 6 rad, depths from 1e-3 to
+    1e3 and behind the camera, non-square K — against the restatement (trig mode 1), bit for bit.  Every expected value is finite
+    (asserted), so no structural-zero shortcut of the device is excused."""
+    from tests import vertex_cases as vc
+    w = vc.wide_math_inputs()
+    assert w["inv3"].shape[0] >= 800 and w["lin"].shape[0] >= 400
+    exp = _restated(oracle_mod, "om_inv3x3", [w["inv3"]], 9)
+    assert np.isfinite(exp).all() and np.array_equal(_run(0, w["inv3"], 9), exp)
+    exp = _restated(oracle_mod, "om_inv6x6", [w["inv6"]], 36)
+    assert np.isfinite(exp).all() and np.array_equal(_run(1, w["inv6"], 36), exp)
+    lin = w["lin"]
+    hx = _restated(oracle_mod, "om_hfunc", [lin[:, :6], lin[:, 6:9], lin[:, 9:]], 2)
+    jk, jl = _restated(oracle_mod, "om_jac", [lin[:, :6], lin[:, 6:9], lin[:, 9:]], (12, 6), n_out=2)
+    exp = np.concatenate([hx, jk, jl], axis=1)
+    assert np.isfinite(exp).all()
+    out = _run(3, lin, 20)
+    bad = np.nonzero((out != exp).any(axis=1))[0]
+    assert bad.size == 0, (bad[:5], lin[bad[:3]], out[bad[:3]], exp[bad[:3]])
+    exp = _restated(oracle_mod, "om_inf2mean6x6", [w["mean6"][:, :6], w["mean6"][:, 6:]], 6)
+    assert np.isfinite(exp).all() and np.array_equal(_run(7, w["mean6"], 6), exp)
+    exp = _restated(oracle_mod, "om_inf2mean3x3", [w["mean3"][:, :3], w["mean3"][:, 3:]], 3)
+    assert np.isfinite(exp).all() and np.array_equal(_run(8, w["mean3"], 3), exp)
+
+
+def test_accumulating_matmul_modes_on_many_vectors(oracle_mod):
+    """ops 4, 5, 6 on 2 000 operand sets whose magnitudes span 1e-6 .. 1e6 per matrix (n not a multiple of 64), P non-zero,
+    against the restatement's matMul, bit for bit."""
+    rng = np.random.default_rng(77)
+    n = 2003
+    sc = lambda: (10.0 ** rng.uniform(-6, 6, (n, 1))).astype(np.float32)
+    A, B = rng.standard_normal((n, 18)).astype(np.float32) * sc(), rng.standard_normal((n, 36)).astype(np.float32) * sc()
+    P18, P36 = rng.standard_normal((n, 18)).astype(np.float32) * sc(), rng.standard_normal((n, 36)).astype(np.float32) * sc()
+    lib = oracle_mod.load("restatement")
+    from gbp_poplar_amd import _cabi as cabi
+    P = lambda a: cabi.ptr(a, cabi.c_f32p)
+    nn, tn, nt = P18.copy(), P18.copy(), P36.copy()
+    for i in range(n):
+        lib.om_matmul(P(B[i]), 6, 6, P(A[i]), 6, 3, P(nn[i]), 3, 0, 0)      # P(6x3) += B A
+        lib.om_matmul(P(A[i]), 6, 3, P(B[i]), 6, 6, P(tn[i]), 6, 1, 0)      # P(3x6) += A^T B
+        lib.om_matmul(P(A[i]), 6, 3, P(A[i]), 6, 3, P(nt[i]), 6, 0, 1)      # P(6x6) += A A^T
+    assert np.isfinite(nn).all() and np.isfinite(tn).all() and np.isfinite(nt).all()
+    assert np.array_equal(_run(4, np.concatenate([A, B, P18], axis=1), 18), nn)
+    assert np.array_equal(_run(5, np.concatenate([A, B, P18], axis=1), 18), tn)
+    assert np.array_equal(_run(6, np.concatenate([A, P36], axis=1), 36), nt)
