@@ -126,3 +126,48 @@ def make_problem(cam_id, lmk_id, n_cams, n_lmks, K9, keep):
     for i in range(9):
         p.K[i] = float(K9[i])
     return p
+
+
+# ---- device-resident arrays: torch tensors on the engine's GPU in place of numpy arrays (include/gbp_mi355x.h, "Device-resident arrays") ----
+_TORCH_DT = {c_f32p: ("torch.float32",), c_i32p: ("torch.int32",), c_u32p: ("torch.uint32", "torch.int32")}   # (flags: torch kernels for uint32 are few, int32 bits are accepted)
+
+
+def is_tensor(a):
+    """a torch tensor (torch is not imported for callers that pass none)"""
+    return type(a).__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr")
+
+
+def is_device_tensor(a):
+    return is_tensor(a) and a.device.type != "cpu"
+
+
+def any_device_tensor(arrays):
+    return any(is_device_tensor(a) for a in arrays.values())
+
+
+def fill_struct_device(struct, tensors, sizes, device, keep):
+    """Set every pointer field of `struct` from dict `tensors`, whose values are torch tensors on `device` (a torch.device;
+    missing / None -> NULL).  Nothing is copied or converted: a tensor of another dtype, a non-contiguous one, one of the wrong
+    size, one on another device and a host array beside device tensors raise.  sizes: field name -> element count."""
+    fields = dict((n, t) for n, t in struct._fields_ if t in _DT)
+    for name in tensors:
+        if name not in fields and tensors[name] is not None:
+            raise TypeError("%s has no member %r" % (type(struct).__name__, name))
+    for name, ctype in fields.items():
+        a = tensors.get(name)
+        if a is None:
+            setattr(struct, name, ctype())
+            continue
+        if not is_device_tensor(a):
+            raise TypeError("%s: a host array beside device tensors — one call takes host arrays or device tensors, not both" % name)
+        if a.device != device:
+            raise TypeError("%s is on %s, the engine's arrays live on %s" % (name, a.device, device))
+        if str(a.dtype) not in _TORCH_DT[ctype]:
+            raise TypeError("%s: dtype %s, expected %s (no silent conversion of device tensors)" % (name, a.dtype, _TORCH_DT[ctype][0]))
+        if not a.is_contiguous():
+            raise TypeError("%s is not contiguous (no silent copy of device tensors)" % name)
+        if name in sizes and a.numel() != sizes[name]:
+            raise TypeError("%s has %d elements, expected %d" % (name, a.numel(), sizes[name]))
+        keep.append(a)
+        setattr(struct, name, C.cast(C.c_void_p(a.data_ptr()), ctype))
+    return struct

@@ -33,7 +33,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden
 DEVICE_SRCS = ["gbp_kernels.hip"]                        # HIP: host + gfx950 device pass
 # the C-ABI (gbp_ctx.hpp names what each holds), the device order, the exchange transports, the host helpers: plain C++
 HOST_SRCS = ["gbp_api_ctx.cpp", "gbp_api_launch.cpp", "gbp_api_persist.cpp", "gbp_api_eval.cpp", "gbp_api_comm.cpp", "gbp_api_debug.cpp",
-             "gbp_layout.cpp", "gbp_comm.cpp", "gbp_host.cpp"]
+             "gbp_api_devio.cpp", "gbp_layout.cpp", "gbp_comm.cpp", "gbp_host.cpp"]
 LIB_SRCS = DEVICE_SRCS + HOST_SRCS
 CLI_SRCS = {"ba": "ba_main.cpp", "slam": "slam_main.cpp", "bal_convert": "bal_convert_main.cpp"}
 

@@ -168,6 +168,28 @@ int D2H::end() {
   return GBP_OK;
 }
 
+int struct_kind(gbp_ctx* c, const char* fn, const void* const* members, const char* const* names, int n, bool* device) {
+  *device = false;
+  int first = -1;
+  PtrKind k0 = kPtrHost;
+  for (int i = 0; i < n; ++i) {
+    if (!members[i]) continue;
+    const PtrKind k = ptr_kind(c, members[i]);
+    if (k == kPtrOtherDevice) return fail(c, GBP_ERR_INVALID, std::string(fn) + ": " + names[i] + " is memory of another GPU than the ctx's");
+    if (k == kPtrManaged) return fail(c, GBP_ERR_INVALID, std::string(fn) + ": " + names[i] + " is managed memory (pass host memory or memory of the ctx's GPU)");
+    if (first < 0) { first = i; k0 = k; }
+    else if (k != k0)
+      return fail(c, GBP_ERR_INVALID, std::string(fn) + ": " + names[i] + " is " + (k == kPtrDevice ? "device" : "host") + " memory, " + names[first] + " is " +
+                                          (k0 == kPtrDevice ? "device" : "host") + " memory: one struct holds host pointers or device pointers, not both");
+  }
+  if (k0 != kPtrDevice) return GBP_OK;
+  if (c->L_loc != c->L || c->world != 1)
+    return fail(c, GBP_ERR_INVALID, std::string(fn) + ": " + names[first] + " is device memory: device pointers are not supported on a landmark-sharded ctx");
+  if (!devio_upload) return fail(c, GBP_ERR_INVALID, std::string(fn) + ": " + names[first] + " is device memory: built without device I/O");
+  *device = true;
+  return GBP_OK;
+}
+
 int event_pair(gbp_ctx* c, hipEvent_t* a, hipEvent_t* b) {
   HIPCHK(c, hipEventCreate(a));
   if (hipError_t e_ = hipEventCreate(b); e_ != hipSuccess) {
@@ -339,6 +361,7 @@ GBP_EXPORT(gbp_create, nullptr, (const gbp_problem* pr, const gbp_params* prm, c
   CK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking), "hipStreamCreate");
   if (rc != GBP_OK) return rc;
   c->stream = c->own_stream;
+  if (hipGetDevice(&c->device) != hipSuccess) { (void)hipGetLastError(); c->device = 0; }
   step("hipStreamCreate");
   // ---- device allocations (zero-filled on the ctx's stream) ----
   auto A = [&](DevBuf& b, size_t bytes) { if (rc == GBP_OK) rc = dev_alloc(c, b, bytes); };
@@ -458,6 +481,15 @@ GBP_EXPORT(gbp_upload, c, (gbp_ctx* c, const gbp_state_in* in), (c, in)) {
   if (!in->cam_priors_eta || !in->cam_priors_lambda || !in->lmk_priors_eta || !in->lmk_priors_lambda ||
       !in->measurements || !in->meas_variances || !in->active_flag)
     return fail(c, GBP_ERR_INVALID, "gbp_upload: priors, measurements, meas_variances and active_flag are required");
+  {
+    const void* const m[] = {in->damping, in->damping_count, in->mu, in->oldmu, in->active_flag, in->cam_scaling, in->lmk_scaling, in->cam_weaken_flag,
+                             in->lmk_weaken_flag, in->cam_priors_eta, in->cam_priors_lambda, in->lmk_priors_eta, in->lmk_priors_lambda, in->measurements, in->meas_variances};
+    static const char* const nm[] = {"damping", "damping_count", "mu", "oldmu", "active_flag", "cam_scaling", "lmk_scaling", "cam_weaken_flag",
+                                     "lmk_weaken_flag", "cam_priors_eta", "cam_priors_lambda", "lmk_priors_eta", "lmk_priors_lambda", "measurements", "meas_variances"};
+    bool dev = false;
+    if (int rc = struct_kind(c, "gbp_upload", m, nm, 15, &dev)) return rc;
+    if (dev) return devio_upload(c, in);
+  }
   if (in->mu && in->oldmu && in->mu != in->oldmu && std::memcmp(in->mu, in->oldmu, (size_t)c->E * 9 * 4) != 0)
     return fail(c, GBP_ERR_INVALID, "gbp_upload: mu != oldmu is not supported (the reference uploads zeros for both, ba.cpp:582-583)");
   if (c->hoist) {
@@ -488,6 +520,7 @@ GBP_EXPORT(gbp_upload, c, (gbp_ctx* c, const gbp_state_in* in), (c, in)) {
   std::vector<St> st(Ep);
   std::vector<float> var(Ep), mu(c->hoist ? 0 : Ep * kMuG * 4, 0.f);
   c->active_host.assign(Ep, 0);
+  c->active_host_stale = false;
   const float* om = in->oldmu ? in->oldmu : in->mu;
   const unsigned T = gbp::host::host_threads(Ep, 1u << 17);      // (a gather by device position: every position is written by one thread)
   gbp::host::on_threads(T, [&](unsigned t) {
@@ -580,6 +613,13 @@ GBP_EXPORT(gbp_upload, c, (gbp_ctx* c, const gbp_state_in* in), (c, in)) {
 // READ_PROG (ba.cpp:908-916)
 GBP_EXPORT(gbp_read, c, (gbp_ctx* c, gbp_state_out* o), (c, o)) {
   if (!c || !o) return GBP_ERR_INVALID;
+  {
+    const void* const m[] = {o->cam_beliefs_eta, o->cam_beliefs_lambda, o->lmk_beliefs_eta, o->lmk_beliefs_lambda, o->damping, o->damping_count, o->robust_flag};
+    static const char* const nm[] = {"cam_beliefs_eta", "cam_beliefs_lambda", "lmk_beliefs_eta", "lmk_beliefs_lambda", "damping", "damping_count", "robust_flag"};
+    bool dev = false;
+    if (int rc = struct_kind(c, "gbp_read", m, nm, 7, &dev)) return rc;
+    if (dev) return devio_read(c, o);
+  }
   if (int rc = gbp_sync(c)) return rc;
   const bool want_cam = o->cam_beliefs_eta || o->cam_beliefs_lambda, want_lmk = (o->lmk_beliefs_eta || o->lmk_beliefs_lambda) && c->L_loc;
   const bool want_state = o->damping || o->damping_count || o->robust_flag;
@@ -627,6 +667,13 @@ GBP_EXPORT(gbp_read, c, (gbp_ctx* c, gbp_state_out* o), (c, o)) {
 // READ_PRIORS (slam.cpp:913-917)
 GBP_EXPORT(gbp_read_priors, c, (gbp_ctx* c, gbp_priors_out* o), (c, o)) {
   if (!c || !o) return GBP_ERR_INVALID;
+  {
+    const void* const m[] = {o->cam_priors_eta, o->cam_priors_lambda, o->lmk_priors_eta, o->lmk_priors_lambda};
+    static const char* const nm[] = {"cam_priors_eta", "cam_priors_lambda", "lmk_priors_eta", "lmk_priors_lambda"};
+    bool dev = false;
+    if (int rc = struct_kind(c, "gbp_read_priors", m, nm, 4, &dev)) return rc;
+    if (dev) return devio_read_priors(c, o);
+  }
   if (int rc = gbp_sync(c)) return rc;
   std::vector<float> rec((size_t)c->C * kCamRec), rec_l((size_t)c->L_loc * 16);
   D2H down;
@@ -651,7 +698,16 @@ GBP_EXPORT(gbp_read_priors, c, (gbp_ctx* c, gbp_priors_out* o), (c, o)) {
 // NEW_KEYFRAME (slam.cpp:919-928): re-upload damping_count, priors, flags; then prog_ub.
 GBP_EXPORT(gbp_new_keyframe, c, (gbp_ctx* c, const gbp_kf_update* u), (c, u)) {
   if (!c || !u || !c->uploaded) return fail(c, GBP_ERR_STATE, "gbp_new_keyframe: upload first");
+  {
+    const void* const m[] = {u->damping_count, u->cam_priors_eta, u->cam_priors_lambda, u->lmk_priors_eta, u->lmk_priors_lambda, u->active_flag, u->cam_weaken_flag, u->lmk_weaken_flag};
+    static const char* const nm[] = {"damping_count", "cam_priors_eta", "cam_priors_lambda", "lmk_priors_eta", "lmk_priors_lambda", "active_flag", "cam_weaken_flag", "lmk_weaken_flag"};
+    bool dev = false;
+    if (int rc = struct_kind(c, "gbp_new_keyframe", m, nm, 8, &dev)) return rc;
+    if (dev) return devio_new_keyframe(c, u);
+  }
   if (int rc = gbp_sync(c)) return rc;
+  if (c->active_host_stale && u->active_flag && devio_refresh_active_shadow)      // device-pointer calls came before: the shadow of the flags is on the device
+    if (int rc = devio_refresh_active_shadow(c)) return rc;
   if (u->damping_count || u->active_flag) {
     // edit the per-factor scalars in place on the device: 8 bytes per factor go over PCIe, not the 64-byte records
     std::vector<int32_t> cnt(c->Ep, 0);

@@ -10,6 +10,7 @@
 //   gbp_api_eval.cpp     the metric on the device (util.cpp:74-144): gbp_eval*, gbp_iterate_eval, and iterate_passes_eval — the
 //                        driver of passes with the metric after each (gbp_iterate_eval_each, gbp_ba_loop)  (ba.cpp:1001-1053)
 //   gbp_api_comm.cpp     sharded ctx: communicator glue, the sharded iteration, gbp_eval_global  (ba.cpp:414-417,617-649)
+//   gbp_api_devio.cpp    WRITE, READ, READ_PRIORS, NEW_KEYFRAME for callers whose arrays live on the ctx's GPU (device pointers)
 //   gbp_api_debug.cpp    the test hooks of include/gbp_mi355x_debug.h (test-hooks builds only)
 //
 // Replaces the Poplar graph / compute-set wiring of the reference (ba/ba.cpp:45-371, 659-937): where the reference maps vertices
@@ -67,6 +68,10 @@ struct gbp_ctx {
   DevBuf idx_arena;                    // the index arrays of the device order (row_cam, lmk_idx, lmk_fpos, lmk_ix, the row / landmark pointers, row_slot, K, tile_perm: views into it)
   DevBuf st_a, st_b;                   // [Ep] scratch of the per-factor state get / set kernels
   std::vector<uint8_t> active_host;    // [Ep] host shadow of the active flags (hoist guard of gbp_new_keyframe)
+  // device-resident caller arrays (gbp_api_devio.cpp)
+  int device = 0;                      // the GPU this ctx lives on (current device of gbp_create)
+  DevBuf d_pos_edge;                   // [Ep] lay.pos_edge on the device; allocated by the first call that passes device pointers
+  bool active_host_stale = false;      // a device-pointer call changed the active flags: the shadow is read back before its next use
   bool use_tile_perm = false;
   DevBuf seg_live;                     // [n_tiles] which 64-byte segments of a tile hold a factor (view into idx_arena; SweepArgs.seg_live)
   bool use_seg_live = false;
@@ -298,6 +303,29 @@ int eval_enqueue(gbp_ctx* c, int area);                     // k_means + k_eval 
 int eval_begin(gbp_ctx* c);
 int eval_end(gbp_ctx* c, gbp_eval_out* o);
 int eval(gbp_ctx* c, gbp_eval_out* o);
+
+// ---- gbp_api_devio.cpp ------------------------------------------------------------------------------------------------------
+// What kind of memory a caller's pointer is (hipPointerGetAttributes): host = pageable or pinned / registered host memory (today's
+// path); device = memory of the ctx's GPU.  Leaves no error behind in the runtime (an unregistered pointer is reported as one).
+enum PtrKind { kPtrHost = 0, kPtrDevice = 1, kPtrOtherDevice = 2, kPtrManaged = 3 };
+inline PtrKind ptr_kind(const gbp_ctx* c, const void* p) {
+  hipPointerAttribute_t at;
+  std::memset(&at, 0, sizeof(at));
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return kPtrHost; }
+  if (at.type == hipMemoryTypeManaged || at.isManaged) return kPtrManaged;
+  if (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeArray) return at.device == c->device ? kPtrDevice : kPtrOtherDevice;
+  return kPtrHost;
+}
+// One struct of a call: every non-NULL member must be of the kind of the first.  *device = the struct holds device pointers.
+// GBP_ERR_INVALID (text names the member): a mix, another GPU's memory, managed memory, a landmark-sharded ctx.
+int struct_kind(gbp_ctx* c, const char* fn, const void* const* members, const char* const* names, int n, bool* device);
+// The device-pointer forms of the four programs.  Weak: the CPU sanitizer build of the host code is linked without gbp_api_devio.cpp
+// and the kernels; the callers (gbp_api_ctx.cpp) check for a null function.
+[[gnu::weak]] int devio_upload(gbp_ctx* c, const gbp_state_in* in);
+[[gnu::weak]] int devio_read(gbp_ctx* c, gbp_state_out* out);
+[[gnu::weak]] int devio_read_priors(gbp_ctx* c, gbp_priors_out* out);
+[[gnu::weak]] int devio_new_keyframe(gbp_ctx* c, const gbp_kf_update* upd);
+[[gnu::weak]] int devio_refresh_active_shadow(gbp_ctx* c);   // c->active_host from the device (after a device-pointer call changed the flags)
 
 // ---- gbp_api_comm.cpp -------------------------------------------------------------------------------------------------------
 int exchange_now(gbp_ctx* c);                               // plain all-gather of the camera partials on the ctx's stream

@@ -283,6 +283,29 @@ void launch_state_set(float4* lmsg, const int* new_count, const uint32_t* ctl, u
 // host-mapped — into the records of the device order: the whole LMSG record of position p (zero messages + state) and the measurement
 // slots of its FAC tile (the rest of FAC is zeroed by the caller)
 void launch_upload_scatter(float4* lmsg, float4* fac, const float4* st, const float* var, uint32_t n, hipStream_t s);
+// ---- device-resident caller arrays (gbp_api_devio.cpp; the kernels: "device-resident caller arrays" in gbp_kernels.hip) ----
+// gbp_upload from device pointers: the caller's file-order arrays (NULL = zeros, as in gbp_state_in) -> the records k_upload_scatter writes
+struct UploadDev {
+  const uint32_t* pos_edge;        // [n] file index of the factor at device position p, ~0u = pad
+  const float* damping; const int* damping_count; const uint32_t* active_flag;
+  const float* measurements; const float* meas_variances;
+  const float* om;                 // [9E] oldmu (or mu), read only when mu != NULL
+  float4* lmsg; float4* fac;
+  float4* mu;                      // the literal mu tensor (per_factor_mu) or NULL
+  uint32_t n;                      // device positions (Ep)
+};
+constexpr int kMaxRecSegs = 8;
+struct RecSegs {                   // see k_rec_copy
+  int n;
+  void* caller[kMaxRecSegs];       // the caller's row-major array (read when copying to the records, written otherwise)
+  void* rec[kMaxRecSegs];          // the device records
+  uint32_t total[kMaxRecSegs];     // 4-byte words of the caller's array
+  uint32_t w[kMaxRecSegs], stride[kMaxRecSegs], off[kMaxRecSegs];   // words per record in the caller's array / in the device records, offset inside a device record
+};
+void launch_upload_dev(const UploadDev& a, hipStream_t s);
+void launch_read_state_dev(const uint32_t* pos_edge, const float4* lmsg, float* damping, int* damping_count, uint32_t* robust_flag, uint32_t n, hipStream_t s);
+void launch_keyframe_state_dev(const uint32_t* pos_edge, float4* lmsg, const int* new_count, const uint32_t* active_flag, uint32_t n, hipStream_t s);
+void launch_rec_copy(const RecSegs& t, bool to_rec, hipStream_t s);
 void launch_means(const float4* camb, const float4* lmkb, float* cam_mu, float* lmk_mu, uint32_t n_cams,
                   uint32_t n_lmks, unsigned long long* health2 /* [0] non-finite means, [1] non-PD beliefs: zero on entry */,
                   unsigned long long* health2_next /* zeroed by this launch for the next evaluation */,

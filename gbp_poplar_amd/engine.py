@@ -32,6 +32,7 @@ class GbpEngine:
         if rc != 0:
             raise GbpError("gbp_create: %s (status %d)" % (self.lib.gbp_last_error(None).decode(), rc))
         self.h = h
+        self._device = self._current_device(only_if_initialised=True)      # the GPU the ctx lives on: the current device of gbp_create
 
     def close(self):
         if getattr(self, "h", None):
@@ -52,10 +53,60 @@ class GbpEngine:
         """Text of the last error — or of the last recovered incident (a call that returned 0 can leave a `warning: ...` here)."""
         return self.lib.gbp_last_error(self.h).decode()
 
+    # ---- device-resident arrays ----
+    # upload / new_keyframe take a dict of torch tensors on the engine's GPU in place of numpy arrays, read / read_priors fill such
+    # tensors (out=...) or allocate them (device=True): the library reads and writes them in place, nothing passes through the host
+    # and none of these calls waits for the GPU.  The work is ordered on the ctx's stream.  After set_stream(torch.cuda.current_stream()
+    # .cuda_stream) that is torch's stream and tensor code before and behind a call is ordered with it as with any torch op; without
+    # set_stream the ctx runs on a stream of its own: finish what produces the inputs first (torch.cuda.current_stream().synchronize())
+    # and call sync() before touching what a read returned.
+    def _sizes(self):
+        C_, L, E = self.C, self.L, self.E
+        return {"damping": E, "damping_count": E, "mu": 9 * E, "oldmu": 9 * E, "active_flag": E, "robust_flag": E, "cam_scaling": C_, "lmk_scaling": L,
+                "cam_weaken_flag": C_, "lmk_weaken_flag": L, "measurements": 2 * E, "meas_variances": E,
+                "cam_priors_eta": 6 * C_, "cam_priors_lambda": 36 * C_, "lmk_priors_eta": 3 * L, "lmk_priors_lambda": 9 * L,
+                "cam_beliefs_eta": 6 * C_, "cam_beliefs_lambda": 36 * C_, "lmk_beliefs_eta": 3 * L, "lmk_beliefs_lambda": 9 * L}
+
+    @staticmethod
+    def _current_device(only_if_initialised=False):
+        import sys
+        torch = sys.modules.get("torch")
+        if only_if_initialised and (torch is None or not torch.cuda.is_initialized()):
+            return None      # (torch has not touched the GPU yet: asked again at the first device-tensor call, nothing is initialised for host-array users)
+        import torch
+        return torch.cuda.current_device()
+
+    def device(self):
+        """torch.device of the GPU the ctx was created on (the current device at construction; where torch had not initialised the GPU
+        by then: the current device at the first call that needs to know, so do not switch devices in between)"""
+        import torch
+        if self._device is None:
+            self._device = self._current_device()
+        return torch.device("cuda", self._device)
+
+    def _device_struct(self, struct, tensors, keep):
+        dev = next((a.device for a in tensors.values() if cabi.is_device_tensor(a)), None)
+        if dev is None:
+            raise TypeError("expected torch tensors on the engine's GPU")
+        if dev.type == "cuda":
+            dev = self.device()      # (every tensor must be on the ctx's GPU; the C-ABI checks the same from the pointers)
+        return cabi.fill_struct_device(struct, tensors, self._sizes(), dev, keep)
+
+    def _device_out(self, fields, device):
+        import torch
+        dev = self.device() if device is True else torch.device(device)
+        sz = self._sizes()
+        dt = {cabi.c_f32p: torch.float32, cabi.c_i32p: torch.int32, cabi.c_u32p: torch.int32}
+        return {n: torch.empty(sz[n], dtype=dt[t], device=dev) for n, t in fields}
+
     # ---- program list ----
     def upload(self, state):
+        """state: dict of numpy arrays — or of torch tensors on the engine's GPU (read in place, not blocking)."""
         keep = []
-        s = cabi.fill_struct(cabi.GbpStateIn(), state, keep)
+        if cabi.any_device_tensor(state):
+            s = self._device_struct(cabi.GbpStateIn(), state, keep)
+        else:
+            s = cabi.fill_struct(cabi.GbpStateIn(), state, keep)
         self._chk(self.lib.gbp_upload(self.h, C.byref(s)), "gbp_upload")
 
     def linearise(self):
@@ -71,7 +122,16 @@ class GbpEngine:
     def weaken_priors(self):
         self._chk(self.lib.gbp_weaken_priors(self.h), "gbp_weaken_priors")
 
-    def read(self):
+    def read(self, out=None, device=False):
+        """Host arrays by default.  out = dict of torch tensors on the engine's GPU: those are filled (members left out are skipped);
+        device=True: the same into tensors freshly allocated on the engine's GPU (flags as int32).  Neither waits for the GPU."""
+        if out is not None or device:
+            if out is None:
+                out = self._device_out(cabi.GbpStateOut._fields_, device)
+            keep = []
+            s = self._device_struct(cabi.GbpStateOut(), out, keep)
+            self._chk(self.lib.gbp_read(self.h, C.byref(s)), "gbp_read")
+            return out
         out = {"cam_beliefs_eta": np.zeros(6 * self.C, np.float32),
                "cam_beliefs_lambda": np.zeros(36 * self.C, np.float32),
                "lmk_beliefs_eta": np.zeros(3 * self.L, np.float32),
@@ -84,7 +144,15 @@ class GbpEngine:
         self._chk(self.lib.gbp_read(self.h, C.byref(s)), "gbp_read")
         return out
 
-    def read_priors(self):
+    def read_priors(self, out=None, device=False):
+        """as read(): host arrays by default, device tensors with out=... / device=True"""
+        if out is not None or device:
+            if out is None:
+                out = self._device_out(cabi.GbpPriorsOut._fields_, device)
+            keep = []
+            s = self._device_struct(cabi.GbpPriorsOut(), out, keep)
+            self._chk(self.lib.gbp_read_priors(self.h, C.byref(s)), "gbp_read_priors")
+            return out
         out = {"cam_priors_eta": np.zeros(6 * self.C, np.float32),
                "cam_priors_lambda": np.zeros(36 * self.C, np.float32),
                "lmk_priors_eta": np.zeros(3 * self.L, np.float32),
@@ -95,8 +163,12 @@ class GbpEngine:
         return out
 
     def new_keyframe(self, upd):
+        """upd: dict of numpy arrays — or of torch tensors on the engine's GPU (read in place, not blocking)."""
         keep = []
-        s = cabi.fill_struct(cabi.GbpKfUpdate(), upd, keep)
+        if cabi.any_device_tensor(upd):
+            s = self._device_struct(cabi.GbpKfUpdate(), upd, keep)
+        else:
+            s = cabi.fill_struct(cabi.GbpKfUpdate(), upd, keep)
         self._chk(self.lib.gbp_new_keyframe(self.h, C.byref(s)), "gbp_new_keyframe")
 
     def eval(self):

@@ -12,11 +12,35 @@
  *
  * Conventions: plain C, no exceptions across the ABI, every function returns 0 on success and a
  * negative gbp_status otherwise (text via gbp_last_error).  All pointers are HOST memory owned by
- * the caller unless the name ends in `_dev`.  A ctx is not thread-safe; calls are blocking unless
+ * the caller unless the name ends in `_dev` — or, in the four calls that move state, DEVICE memory
+ * ("Device-resident arrays" below).  A ctx is not thread-safe; calls are blocking unless
  * stated.  All floating point is IEEE fp32, integers are 32-bit, layouts are the reference's
  * row-major AoS host layouts (ba/ba.cpp:690-713,778-790).  All device work of a ctx is ordered on ITS stream (its own, or the one handed
  * over with gbp_set_stream), copies to and from the host included: nothing goes through the NULL stream, so work a caller queues on other
  * streams is the caller's to synchronise with.
+ *
+ * Device-resident arrays.  gbp_upload, gbp_read, gbp_read_priors and gbp_new_keyframe also take structs whose members point into
+ * memory of the ctx's GPU (hipMalloc, a torch tensor): same functions, same structs, same row-major layouts, same results bit for bit —
+ * kernels read and write the caller's arrays in place, nothing passes through the host.
+ *   Host or device is decided per call and per struct, not per member: the first non-NULL member is classified with
+ *     hipPointerGetAttributes (after the argument and state checks of the call); an error from it or an unregistered pointer means
+ *     host, the path every caller has had so far.  Pinned and host-registered memory (hipHostMalloc, hipHostRegister) is HOST memory
+ *     here although the device can reach it.  GBP_ERR_INVALID, with the member's name in gbp_last_error and the ctx untouched: a
+ *     struct that mixes host and device members; memory of another GPU; managed memory (hipMallocManaged: where it lives is not the
+ *     library's to guess); device pointers on a landmark-sharded ctx (gbp_mi355x_multi.h: not supported); a build without the device
+ *     path.  NULL members mean what they mean in host structs: "all zeros" on upload, "skipped" on read, "unchanged" in a keyframe.
+ *   Ordering — the point of it: the device-pointer forms do not block.  Their kernels are queued on the ctx's stream (gbp_set_stream
+ *     is honoured, nothing goes to the NULL stream, the device is never synchronised).  gbp_upload and gbp_new_keyframe return at
+ *     once; the caller's arrays may be reused by work queued BEHIND the call on that stream, or after gbp_sync.  gbp_read and
+ *     gbp_read_priors return at once; the outputs are valid for work queued behind them on that stream, or after gbp_sync.  A caller
+ *     on another stream orders against the ctx's stream itself (an event, or gbp_sync).  Two exceptions that wait: the first
+ *     device-pointer call of a ctx copies one index array to the GPU, and a call that finds launches of the persistent kernel
+ *     (gbp_params.persistent) not yet validated waits for those, as every entry point that queues other work does.
+ *   Pre-conditions the host path checks by looking at the values cannot be checked without a read-back and are the CALLER'S DUTY
+ *     with device arrays: gbp_upload — mu and oldmu hold the same values (oldmu is the one uploaded when both are given), and on a ctx
+ *     with per_factor_mu = 0 they are all zero (the members are not read there); gbp_new_keyframe — no factor is activated with
+ *     damping_count + 1 > min_linear_iters - num_undamped_iters on a ctx with per_factor_mu = 0.
+ *   Alignment: 4 bytes suffice (a view into a larger buffer); arrays whose base is 16-byte aligned are moved with 16-byte accesses.
  */
 #ifndef GBP_MI355X_H
 #define GBP_MI355X_H
