@@ -171,3 +171,36 @@ def fill_struct_device(struct, tensors, sizes, device, keep):
         keep.append(a)
         setattr(struct, name, C.cast(C.c_void_p(a.data_ptr()), ctype))
     return struct
+
+
+# ---- the metric in device memory: gbp_eval / gbp_iterate_eval_each / gbp_ba_loop with `out` on the engine's GPU ----
+EVAL_FIELDS = tuple(n for n, _ in GbpEvalOut._fields_)      # seven 8-byte members: a record is a row of seven int64
+EVAL_F64 = ("sum_norm", "sum_half_sq")
+
+
+def check_eval_buffer(buf, shape, device):
+    """`buf` can receive gbp_eval_out records on `device` (a torch.device): a contiguous torch.int64 tensor of `shape` — (7,) or (n, 7) —
+    on that device.  TypeError otherwise (nothing is copied or converted)."""
+    if not is_tensor(buf):
+        raise TypeError("out: expected a torch.int64 tensor on the engine's GPU, got %s" % type(buf).__name__)
+    if not is_device_tensor(buf):
+        raise TypeError("out is on the CPU: the device form writes records on the engine's GPU (leave out= away for host results)")
+    if buf.device != device:
+        raise TypeError("out is on %s, the engine lives on %s" % (buf.device, device))
+    if str(buf.dtype) != "torch.int64":
+        raise TypeError("out: dtype %s, expected torch.int64 (a record is seven 8-byte words)" % buf.dtype)
+    if tuple(buf.shape) != tuple(shape):
+        raise TypeError("out has shape %s, expected %s" % (tuple(buf.shape), tuple(shape)))
+    if not buf.is_contiguous():
+        raise TypeError("out is not contiguous (no silent copy of device tensors)")
+    return buf
+
+
+def eval_buffer_views(buf):
+    """int64 tensor [7] or [n, 7] of gbp_eval_out records (any device) -> dict with the keys of GbpEngine.eval(): every value a 1-D
+    tensor of length n (1 for [7]) that VIEWS column k of `buf`, sum_norm and sum_half_sq as float64.  Nothing is copied."""
+    import torch
+    if str(buf.dtype) != "torch.int64" or buf.dim() not in (1, 2) or buf.shape[-1] != len(EVAL_FIELDS):
+        raise TypeError("expected a torch.int64 tensor of shape [7] or [n, 7], got %s %s" % (buf.dtype, tuple(buf.shape)))
+    rows = buf.unsqueeze(0) if buf.dim() == 1 else buf
+    return {name: (rows[:, k].view(torch.float64) if name in EVAL_F64 else rows[:, k]) for k, name in enumerate(EVAL_FIELDS)}

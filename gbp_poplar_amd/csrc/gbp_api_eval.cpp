@@ -6,6 +6,9 @@
 //                                 elsewhere), without it through gbp_api_launch.cpp's iterate_passes
 //   include/gbp_mi355x_compat.h   gbp_eval_begin / _end, gbp_iterate_eval, gbp_iterate_eval_each: earlier forms of the same loop
 //                                 (gbp_iterate_eval_each = iterate_passes_eval with no weakening)
+// gbp_eval, gbp_ba_loop and gbp_iterate_eval_each with an `out` in memory of the ctx's GPU (include/gbp_mi355x.h, "Device-resident arrays"):
+// the same launches with their partial sums in device memory, folded on the device (k_eval_fold_part, k_eval_fold) into the caller's
+// records; nothing waits — `dev` below.
 #include "gbp_ctx.hpp"
 
 #include <algorithm>
@@ -33,8 +36,8 @@ static int eval_alloc(gbp_ctx* c) {
 }
 
 // k_means + k_eval of the current beliefs into result area `area`, its event recorded behind them
-int eval_enqueue(gbp_ctx* c, int area) {
-  DeviceEval* slots = static_cast<DeviceEval*>(c->eval_host_dev) + 1025 * area;
+int eval_enqueue(gbp_ctx* c, int area, DeviceEval* dev_slots) {
+  DeviceEval* slots = dev_slots ? dev_slots : static_cast<DeviceEval*>(c->eval_host_dev) + 1025 * area;
   unsigned long long* h_cur = P<unsigned long long>(c->health) + 2 * area;
   unsigned long long* h_next = P<unsigned long long>(c->health) + 2 * (area ^ 1);
   launch_means(P<float4>(c->camb), P<float4>(c->lmkb), P<float>(c->cam_mu), P<float>(c->lmk_mu), c->C, c->L_loc,
@@ -42,8 +45,44 @@ int eval_enqueue(gbp_ctx* c, int area) {
   launch_eval(P<uint32_t>(c->row_cam), P<uint32_t>(c->lmk_idx), P<float4>(c->lmsg), P<float4>(c->fac), P<float>(c->cam_mu), P<float>(c->lmk_mu),
               P<float>(c->dK), c->prm.num_undamped_iters, slots + 1, h_cur, reinterpret_cast<unsigned long long*>(slots), c->n_tiles, c->stream);
   HIPCHK(c, hipGetLastError());
+  if (dev_slots) return GBP_OK;
   HIPCHK(c, hipEventRecord(c->eval_ev[area], c->stream));
   c->eval_per_wave[area] = false;
+  return GBP_OK;
+}
+
+// Is `out` of fn memory of the ctx's GPU?  Called after the argument and state checks of the call.  Host memory (unregistered, pinned,
+// host-registered): *device = false, today's path.  GBP_ERR_INVALID naming `out`: another GPU's memory, managed memory, a landmark-sharded
+// ctx (struct_kind), a device address that is not 8-byte aligned; GBP_ERR_STATE: the caller is capturing the ctx's stream.
+static int out_kind(gbp_ctx* c, const char* fn, const void* out, bool* device) {
+  const void* const members[1] = {out};
+  const char* const names[1] = {"out"};
+  if (int rc = struct_kind(c, fn, members, names, 1, device)) return rc;
+  if (!*device) return GBP_OK;
+  *device = false;
+  if (!launch_eval_fold_part) return fail(c, GBP_ERR_INVALID, std::string(fn) + ": out is device memory: built without the device metric");
+  if (reinterpret_cast<uintptr_t>(out) % 8 != 0)
+    return fail(c, GBP_ERR_INVALID, std::string(fn) + ": out is device memory that is not 8-byte aligned (a record holds doubles and 64-bit counters)");
+  if (stream_is_capturing(c))
+    return fail(c, GBP_ERR_STATE, std::string(fn) + ": out is device memory and the ctx's stream is being captured: not supported");
+  *device = true;
+  return GBP_OK;
+}
+
+// the device twin of one result area of k_eval (first use allocates)
+static int eval_scratch(gbp_ctx* c) {
+  if (c->eval_scratch.p) return GBP_OK;
+  return dev_alloc(c, c->eval_scratch, sizeof(DeviceEval) * 1025);
+}
+
+// One metric of the current beliefs into the caller's device record: k_means + k_eval as eval_begin queues them (the same health area,
+// the parity advanced as one eval_begin / eval_end pair advances it), their partial sums in device memory, the fold behind them.
+static int eval_to_device(gbp_ctx* c, gbp_eval_out* out) {
+  const int area = c->eval_parity & 1;
+  if (int rc = eval_enqueue(c, area, P<DeviceEval>(c->eval_scratch))) return rc;
+  c->eval_parity ^= 1;
+  launch_eval_fold_part(P<DeviceEval>(c->eval_scratch), 0, eval_blocks(c->n_tiles), c->n_tiles, false, 1, out, c->stream);
+  HIPCHK(c, hipGetLastError());
   return GBP_OK;
 }
 
@@ -112,6 +151,13 @@ int eval_end(gbp_ctx* c, gbp_eval_out* o) {
 int eval(gbp_ctx* c, gbp_eval_out* o) {
   if (!c || !o || !c->uploaded) return fail(c, GBP_ERR_STATE, "gbp_eval: upload first");
   if (c->eval_pending) return fail(c, GBP_ERR_STATE, "gbp_eval: finish the evaluations in flight (gbp_eval_end) first");
+  bool dev = false;
+  if (int rc = out_kind(c, "gbp_eval", o, &dev)) return rc;
+  if (dev) {      // not blocking (settle: k_means and k_eval are other device work than the launches it validates)
+    if (int rc = settle(c)) return rc;
+    if (int rc = eval_scratch(c)) return rc;
+    return eval_to_device(c, o);
+  }
   if (int rc = eval_begin(c)) return rc;
   return eval_end(c, o);
 }
@@ -211,10 +257,11 @@ static int ev_alloc(gbp_ctx* c) {
   c->ev_depth = depth;
   return GBP_OK;
 }
-static int eval_each_ride(gbp_ctx* c, int n, gbp_eval_out* out) {
+// dev: `out` is the caller's device memory — k_eval_fold writes there, nothing waits.  timed = false: the replay of a burst that gbp_timing has counted.
+static int eval_each_ride(gbp_ctx* c, int n, gbp_eval_out* out, bool dev = false, bool timed = true) {
   if (int rc = settle(c)) return rc;
   if (int rc = ev_alloc(c)) return rc;
-  if ((size_t)n > c->ev_host_cap) {       // one 56-byte result per iteration of the burst, host-mapped
+  if (!dev && (size_t)n > c->ev_host_cap) {       // one 56-byte result per iteration of the burst, host-mapped
     if (c->ev_host) { (void)hipHostFree(c->ev_host); c->ev_host = nullptr; c->ev_host_cap = 0; }
     const size_t cap = std::max<size_t>(1024, (size_t)n);
     HIPCHK(c, hipHostMalloc(&c->ev_host, sizeof(gbp_eval_out) * cap, hipHostMallocMapped));
@@ -225,17 +272,21 @@ static int eval_each_ride(gbp_ctx* c, int n, gbp_eval_out* out) {
   SweepArgs a = sweep_args(c);
   a.ev = eval_ride(c);
   TimedSpan sp(c);
-  if (int rc = sp.begin()) return rc;
+  if (timed)
+    if (int rc = sp.begin()) return rc;
+  gbp_eval_out* const results = dev ? out : static_cast<gbp_eval_out*>(c->ev_host_dev);
   for (int done = 0; done < n;) {         // pieces of at most ev_depth iterations, queued behind each other: no host wait in between
     const int m = std::min(n - done, (int)c->ev_depth);
     HIPCHK(c, hipMemsetAsync(c->ev_ctl.p, 0, 64, c->stream));      // iteration counter and health words of this piece
     if (int rc = iterate_plain(c, a, m, true)) return rc;
     launch_eval_ride(a.ev, P<uint32_t>(c->row_cam), P<uint32_t>(c->lmk_idx), P<float4>(c->lmsg), P<float4>(c->fac), P<float>(c->dK), c->stream);
-    launch_eval_fold(a.ev, (uint32_t)m, static_cast<gbp_eval_out*>(c->ev_host_dev) + done, c->stream);
+    launch_eval_fold(a.ev, (uint32_t)m, results + done, c->stream);
     HIPCHK(c, hipGetLastError());
     done += m;
   }
-  if (int rc = sp.commit((uint64_t)n)) return rc;
+  if (timed)
+    if (int rc = sp.commit((uint64_t)n)) return rc;
+  if (dev) return GBP_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   std::memcpy(out, c->ev_host, sizeof(gbp_eval_out) * (size_t)n);
   return GBP_OK;
@@ -262,30 +313,67 @@ static int series_burst(gbp_ctx* c, int m, unsigned i, unsigned steps2, gbp_eval
   return GBP_OK;
 }
 
+// The same launch for a caller whose records live on the GPU, not blocking: the per-pass records go to a device-memory twin of the series
+// slots, one workgroup of k_eval_fold_part per pass folds them into out[k] behind the launch (and in front of the next launch, which
+// reuses the twin), and the launch stays in the log of unvalidated launches with what a replay needs — whoever validates it later
+// (settle / persist_check) and finds that it timed out restores the snapshot and replays it on the riding path into the same records
+// (persist_recover -> replay_series_dev).  The only host-mapped word involved is the status word of the kernel.
+static int series_burst_dev(gbp_ctx* c, int m, unsigned i, unsigned steps2, gbp_eval_out* out) {
+  if (!c->series_twin.p)
+    if (int rc = dev_alloc(c, c->series_twin, sizeof(DeviceEval) * (size_t)(c->n_tiles + 1) * kSeriesMax)) return rc;
+  const int area = c->eval_parity & 1;
+  PersistEval metric = persist_eval(c, area, true);
+  metric.slots = P<DeviceEval>(c->series_twin);
+  TimedSpan sp(c);
+  if (int rc = sp.begin()) return rc;
+  if (int rc = launch_persist_burst(c, sweep_args(c), m, &metric, 3, area, i, steps2, out)) return rc;
+  launch_eval_fold_part(metric.slots, metric.stride, eval_blocks(c->n_tiles), c->n_tiles, true, (uint32_t)m, out, c->stream);
+  HIPCHK(c, hipGetLastError());
+  return sp.commit((uint64_t)m);
+}
+
+// per_factor_mu = 1, per-stage timing, a ctx with a communicator: the loop the riding path replaces, with device records — per pass
+// gbp_iterate(1), k_means + k_eval into the device scratch, its fold (stream order keeps the scratch until its fold has read it)
+static int eval_each_plain_dev(gbp_ctx* c, int m, gbp_eval_out* out) {
+  if (int rc = eval_scratch(c)) return rc;
+  for (int k = 0; k < m; ++k) {
+    if (int rc = iterate(c, 1)) return rc;
+    if (int rc = eval_to_device(c, out + k)) return rc;
+  }
+  return GBP_OK;
+}
+
 // The driver of passes WITH the metric after every one of them (gbp_iterate_eval_each: i0 = steps2 = 0; gbp_ba_loop), blocking:
 // passes i0 .. i0 + n - 1 of the reference's loop (ba.cpp:1001-1028), WEAKEN_PRIORS in front of pass i iff weakens_before(i, steps2),
 // GBP_PROG, the metric.  On a graph that runs in the persistent kernel the passes are launches of at most kSeriesMax (persist_burst):
 // k_persist_flow applies WeakenPriorVertex itself in front of its later passes, only a weakening in front of a launch's first pass is
 // a launch of its own.  Everywhere else — and after a recovered time-out — each run of passes up to the next weakening carries the
 // metric in its sweeps (eval_each_ride), or is the loop it replaces, two metrics in flight.
-static int iterate_passes_eval(gbp_ctx* c, int n, unsigned i0, unsigned steps2, gbp_eval_out* out) {
+// dev: out[] is memory of the ctx's GPU and nothing here blocks — launches of the persistent kernel queue behind the unvalidated ones
+// as gbp_iterate's do (persist_ready), the other paths wait for those first (settle) as every other kind of device work does.
+static int iterate_passes_eval(gbp_ctx* c, int n, unsigned i0, unsigned steps2, gbp_eval_out* out, bool dev = false) {
   for (int done = 0; done < n;) {
     const unsigned i = i0 + (unsigned)done;
     if (weakens_before(i, steps2))
       if (int rc = weaken_priors(c)) return rc;
-    if (int rc = settle(c)) return rc;
+    if (!dev)
+      if (int rc = settle(c)) return rc;
     bool fused = false;
     if (eval_blocks(c->n_tiles) == (c->n_tiles + 3) / 4)
       if (int rc = persist_ready(c, &fused)) return rc;
     if (fused) {
       const int m = persist_burst(c, n - done, i, steps2, (int)kSeriesMax);
-      const int rc = series_burst(c, m, i, steps2, out + done);
+      const int rc = dev ? series_burst_dev(c, m, i, steps2, out + done) : series_burst(c, m, i, steps2, out + done);
       if (rc == GBP_OK) { done += m; continue; }
       if (rc != kNotLaunched) return rc;
     }
+    if (dev)
+      if (int rc = settle(c)) return rc;
     const int m = weakening_free_run(n - done, i, steps2);
     if (!c->comm && c->world == 1 && c->hoist && !c->profile_stages && !stream_is_capturing(c)) {
-      if (int rc = eval_each_ride(c, m, out + done)) return rc;
+      if (int rc = eval_each_ride(c, m, out + done, dev)) return rc;
+    } else if (dev) {
+      if (int rc = eval_each_plain_dev(c, m, out + done)) return rc;
     } else {
       int collected = done;
       for (int k = done; k < done + m; ++k) {
@@ -304,6 +392,10 @@ static int iterate_eval_each(gbp_ctx* c, int n, gbp_eval_out* out) {
   if (!c || !c->uploaded) return fail(c, GBP_ERR_STATE, "gbp_iterate_eval_each: upload first");
   if (n < 0 || (n > 0 && !out)) return fail(c, GBP_ERR_INVALID, "gbp_iterate_eval_each: n >= 0 and an array of n results");
   if (c->eval_pending) return fail(c, GBP_ERR_STATE, "gbp_iterate_eval_each: finish the evaluations in flight (gbp_eval_end) first");
+  bool dev = false;
+  if (out)
+    if (int rc = out_kind(c, "gbp_iterate_eval_each", out, &dev)) return rc;
+  if (dev) return iterate_passes_eval(c, n, 0, 0, out, true);
   if (int rc = settle(c)) return rc;                  // blocking call: nothing of this ctx stays in flight across it
   return iterate_passes_eval(c, n, 0, 0, out);
 }
@@ -319,7 +411,9 @@ static int ba_loop(gbp_ctx* c, int n, unsigned iter0, unsigned steps, gbp_eval_o
   const unsigned steps2 = 2u * steps;
   if (out) {
     if (c->eval_pending) return fail(c, GBP_ERR_STATE, "gbp_ba_loop: finish the evaluations in flight (gbp_eval_end) first");
-    return iterate_passes_eval(c, n, iter0, steps2, out);
+    bool dev = false;
+    if (int rc = out_kind(c, "gbp_ba_loop", out, &dev)) return rc;
+    return iterate_passes_eval(c, n, iter0, steps2, out, dev);
   }
   const bool one_call = !c->comm && c->world == 1 && !c->profile_stages && !stream_is_capturing(c);
   for (int done = 0; done < n;) {
@@ -334,6 +428,22 @@ static int ba_loop(gbp_ctx* c, int n, unsigned iter0, unsigned steps, gbp_eval_o
 }
 
 }  // namespace
+
+// persist_recover: launch b (mode 3) is undone, the state is the one it started from — the weakening in front of its first pass
+// included, which was a launch of its own.  Its passes on the riding path into the records it was given: what iterate_passes_eval
+// queues for a ctx that is not on the persistent path (a ctx that was runs hoisted, on one GPU, without a communicator).
+int gbp::api::replay_series_dev(gbp_ctx* c, const gbp_ctx::Burst& b) {
+  gbp_eval_out* out = static_cast<gbp_eval_out*>(b.out);
+  for (int done = 0; done < b.n;) {
+    const unsigned i = b.w_first + (unsigned)done;
+    if (done > 0 && weakens_before(i, b.w_steps2))
+      if (int rc = weaken_priors(c)) return rc;
+    const int m = weakening_free_run(b.n - done, i, b.w_steps2);
+    if (int rc = eval_each_ride(c, m, out + done, true, false)) return rc;
+    done += m;
+  }
+  return GBP_OK;
+}
 
 GBP_EXPORT(gbp_eval, c, (gbp_ctx* c, gbp_eval_out* o), (c, o)) { return eval(c, o); }
 GBP_EXPORT(gbp_eval_begin, c, (gbp_ctx* c), (c)) { return eval_begin(c); }

@@ -212,6 +212,11 @@ static int persist_recover(gbp_ctx* c) {
   long iters = 0;
   for (const gbp_ctx::Burst& b : redo) {
     if (b.mode == 2) continue;                        // gbp_iterate_eval_each is blocking: it replays its own burst
+    if (b.mode == 3) {                                // ... with device records it is not: passes, weakenings and metrics replayed here
+      if (int rc = replay_series_dev(c, b)) return rc;
+      iters += b.n;
+      continue;
+    }
     if (b.w_steps2) { if (int rc = iterate_weaken_plain(c, a, b.n, b.w_first, b.w_steps2)) return rc; }
     else if (int rc = iterate_plain(c, a, b.n)) return rc;
     iters += b.n;
@@ -260,7 +265,7 @@ int persist_ready(gbp_ctx* c, bool* yes) {
 // n iterations inside ONE k_persist launch (+ the metric phases when `ev` is given).  The barrier counter keeps counting
 // across the launches of a ctx (no memset per launch): the host tracks how many arrivals it has seen.
 int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, int n, const PersistEval* ev, int mode, int area,
-                         uint32_t w_first, uint32_t w_steps2) {
+                         uint32_t w_first, uint32_t w_steps2, void* out_dev) {
   PersistArgs A{};
   A.s = a;
   A.b = belief_args(c);
@@ -314,7 +319,7 @@ int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, int n, const PersistEva
   // tagged records none, and ONE barrier at the end of a launch that carries the metric
   c->persist_epoch_base += flow ? (ev ? nb : 0u) : nb * (unsigned)(2 * n - 1 + (ev ? 1 : 0));
   c->persist_seq += 1;
-  c->persist_log.push_back(gbp_ctx::Burst{c->persist_seq, n, mode, area, w_first, w_steps2});
+  c->persist_log.push_back(gbp_ctx::Burst{c->persist_seq, n, mode, area, w_first, w_steps2, out_dev});
   c->persist_launches += 1;
   return GBP_OK;
 }

@@ -114,6 +114,10 @@ struct gbp_ctx {
   void* eval_host_dev = nullptr;
   void* series_host = nullptr;         // gbp_iterate_eval_each: [kSeriesMax metrics][1 + workgroups] slots, same kind of memory
   void* series_dev = nullptr;
+  // the metric into gbp_eval_out records on the GPU (gbp_eval / gbp_ba_loop / gbp_iterate_eval_each with a device `out`): the same
+  // records in DEVICE memory, folded by k_eval_fold_part; allocated by the first call that needs them
+  DevBuf eval_scratch;                 // [1025] one result area of k_eval
+  DevBuf series_twin;                  // [kSeriesMax][n_tiles + 1] the series slots of the persistent kernel
   int eval_parity = 0, eval_pending = 0;
   bool eval_per_wave[2] = {false, false};   // result area written by k_persist (one record per tile wave) or by k_eval (one per workgroup)
   hipEvent_t eval_ev[2] = {nullptr, nullptr};
@@ -126,9 +130,10 @@ struct gbp_ctx {
   // two-kernel path: every launch is preceded by a snapshot of the arrays it mutates (one copy kernel, skipped once the abort
   // word is set), later launches of the ctx return at once, and the host — at the next point where it synchronises anyway —
   // restores the snapshot and replays the logged launches from the first failed one on.
-  // mode 0 = gbp_iterate, 1 = gbp_iterate_eval (metric in eval area `area`), 2 = eval_each / gbp_ba_loop with metrics (blocking);
+  // mode 0 = gbp_iterate, 1 = gbp_iterate_eval (metric in eval area `area`), 2 = eval_each / gbp_ba_loop with metrics (blocking),
+  // 3 = the same with the results going to the caller's device records `out` (not blocking: the recovery replays passes and metrics);
   // w_steps2 != 0: the launch weakens priors itself (gbp_ba_loop: loop index of its first iteration, twice the --steps)
-  struct Burst { unsigned seq; int n; int mode; int area; unsigned w_first = 0, w_steps2 = 0; };
+  struct Burst { unsigned seq; int n; int mode; int area; unsigned w_first = 0, w_steps2 = 0; void* out = nullptr; };
   DevBuf pflow;                        // tagged shadows of k_persist_flow (PersistFlow), one allocation
   gbp::PersistFlow flow{};                  // the tagged shadows of k_persist_flow
   uint32_t flow_total4 = 0;            // test-hooks builds: float4 of the shadows (the redundant copies of gbp_debug_persist_verify follow them)
@@ -296,10 +301,14 @@ int persist_check(gbp_ctx* c, unsigned upto);               // the stream has be
 bool stream_is_capturing(gbp_ctx* c);
 int persist_ready(gbp_ctx* c, bool* yes);                   // may the next burst run inside the persistent kernel?
 int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, int n, const PersistEval* ev, int mode, int area,
-                         uint32_t w_first = 0, uint32_t w_steps2 = 0);
+                         uint32_t w_first = 0, uint32_t w_steps2 = 0, void* out_dev = nullptr);
 
 // ---- gbp_api_eval.cpp -------------------------------------------------------------------------------------------------------
-int eval_enqueue(gbp_ctx* c, int area);                     // k_means + k_eval of the current beliefs into result area `area`
+// k_means + k_eval of the current beliefs with the health words of area `area`, into that result area (host-mapped, its event recorded
+// behind them) or into dev_slots (device memory, [1025]: no event)
+int eval_enqueue(gbp_ctx* c, int area, DeviceEval* dev_slots = nullptr);
+// recovery of a timed-out launch of mode 3 (persist_recover): its passes on the two-kernel path, the metric riding, into the same device records
+int replay_series_dev(gbp_ctx* c, const gbp_ctx::Burst& b);
 int eval_begin(gbp_ctx* c);
 int eval_end(gbp_ctx* c, gbp_eval_out* o);
 int eval(gbp_ctx* c, gbp_eval_out* o);

@@ -266,6 +266,11 @@ void launch_beliefs(BeliefArgs b, bool do_cam, bool do_lmk, hipStream_t s, bool 
 [[gnu::weak]] void launch_gather_peers(const float* const* peers, float* dst, uint32_t n4, int world, int self, hipStream_t s);
 // per-tile records of ring slots [0, n_slots) -> out[slot]: one gbp_eval_out-shaped result per slot (may be mapped host memory)
 void launch_eval_fold(const EvalRide& ev, uint32_t n_slots, void* out, hipStream_t s);
+// sum_eval (gbp_api_eval.cpp) on the device, for gbp_eval_out records that live on the GPU: metric r of n_records = the DeviceEval records
+// parts + r * stride ([0] = health words, then nb <= 1 024 block sums — or, per_wave, one record per tile wave of n_tiles <= 4 096) -> out[r].
+// Weak: the CPU sanitizer build of the host code links stand-ins of the launchers it may reach; the callers check for a null launcher.
+[[gnu::weak]] void launch_eval_fold_part(const DeviceEval* parts, uint32_t stride, uint32_t nb, uint32_t n_tiles, bool per_wave, uint32_t n_records,
+                                         void* out, hipStream_t s);
 // the riding metric of the CURRENT beliefs (a piece's last iteration: no sweep follows) into ring slot counter - 1
 void launch_eval_ride(const EvalRide& ev, const uint32_t* row_cam, const uint32_t* lmk_idx, const float4* lmsg, const float4* fac, const float* K9_dev, hipStream_t s);
 int persist_max_resident_blocks();                                            // how many of them this GPU keeps resident at once

@@ -2358,6 +2358,21 @@ struct EvalSum {       // == gbp_eval_out (include/gbp_mi355x.h)
   double sum_norm, sum_half_sq;
   unsigned long long n_active, n_relin, n_robust, n_nonfinite, n_nonpd;
 };
+// The last step of every device-side fold: the n_sums <= 1 024 block sums one workgroup staged in LDS (entries >= n_sums hold zeros)
+// added serially from 0 by ONE lane, as the host adds k_eval's block sums (sum_eval in gbp_api_eval.cpp); o's health words are the caller's.
+GBP_DEV void eval_fold_chain(const double (&sh_d)[2][1024], const unsigned (&sh_u)[3][1024], uint32_t n_sums, EvalSum& o) {
+  o.sum_norm = 0; o.sum_half_sq = 0; o.n_active = 0; o.n_relin = 0; o.n_robust = 0;
+  for (uint32_t k0 = 0; k0 < n_sums; k0 += 16) {      // sixteen LDS reads in flight, added in order
+    double a[16], h[16];
+    GBP_UNROLL
+    for (int u = 0; u < 16; ++u) { a[u] = sh_d[0][k0 + u]; h[u] = sh_d[1][k0 + u]; }
+    GBP_UNROLL
+    for (int u = 0; u < 16; ++u)
+      if (k0 + (uint32_t)u < n_sums) { o.sum_norm += a[u]; o.sum_half_sq += h[u]; }
+    GBP_UNROLL
+    for (int u = 0; u < 16; ++u) { o.n_active += sh_u[0][k0 + u]; o.n_relin += sh_u[1][k0 + u]; o.n_robust += sh_u[2][k0 + u]; }
+  }
+}
 __global__ __launch_bounds__(1024) void k_eval_fold(const EvalRide ev, EvalSum* out, uint32_t n_sums) {
   __shared__ double sh_d[2][1024];
   __shared__ unsigned sh_u[3][1024];
@@ -2389,19 +2404,53 @@ __global__ __launch_bounds__(1024) void k_eval_fold(const EvalRide ev, EvalSum* 
   __syncthreads();
   if (j == 0) {
     EvalSum o;
-    o.sum_norm = 0; o.sum_half_sq = 0; o.n_active = 0; o.n_relin = 0; o.n_robust = 0;
-    for (uint32_t k0 = 0; k0 < n_sums; k0 += 16) {      // sixteen LDS reads in flight, added in order (entries >= n_sums hold zeros)
-      double a[16], h[16];
-      GBP_UNROLL
-      for (int u = 0; u < 16; ++u) { a[u] = sh_d[0][k0 + u]; h[u] = sh_d[1][k0 + u]; }
-      GBP_UNROLL
-      for (int u = 0; u < 16; ++u)
-        if (k0 + (uint32_t)u < n_sums) { o.sum_norm += a[u]; o.sum_half_sq += h[u]; }
-      GBP_UNROLL
-      for (int u = 0; u < 16; ++u) { o.n_active += sh_u[0][k0 + u]; o.n_relin += sh_u[1][k0 + u]; o.n_robust += sh_u[2][k0 + u]; }
-    }
+    eval_fold_chain(sh_d, sh_u, n_sums, o);
     o.n_nonfinite = ev.slot_health[2 * (size_t)slot]; o.n_nonpd = ev.slot_health[2 * (size_t)slot + 1];
     out[slot] = o;
+  }
+}
+
+// sum_eval of gbp_api_eval.cpp on the device, for a caller whose gbp_eval_out records live on the GPU: the DeviceEval records of ONE
+// metric (part[0] = its two health words, then its partial sums) reduced to one result, workgroup r taking metric r (part + r *
+// stride -> out[r]).  per_wave = 0: part[1 .. nb] are the block sums S_j of k_eval; per_wave = 1: part[1 + t] is the record of tile
+// wave t of the persistent kernel and thread b forms B_b = ((w_4b + w_4b+1) + w_4b+2) + w_4b+3 (nb = n_tiles / 4 <= 1 024: no block
+// stride on a graph that runs there).  Thread 0 then adds them serially from 0: the additions of "THE ORDER OF THE METRIC'S SUMS".
+__global__ __launch_bounds__(1024) void k_eval_fold_part(const DeviceEval* __restrict__ parts, uint32_t stride, uint32_t nb, uint32_t n_tiles,
+                                                         int per_wave, EvalSum* out) {
+  __shared__ double sh_d[2][1024];
+  __shared__ unsigned sh_u[3][1024];
+  const uint32_t j = threadIdx.x;
+  const DeviceEval* part = parts + (size_t)blockIdx.x * stride;
+  double s_norm = 0, s_half = 0;
+  unsigned n_act = 0, n_rel = 0, n_rob = 0;      // (one record counts at most the positions of its tiles: 32 bits hold them, the totals are 64-bit)
+  if (j < nb) {
+    if (per_wave) {
+      DeviceEval w[4];
+      GBP_UNROLL
+      for (uint32_t k = 0; k < 4; ++k) {
+        const uint32_t t = 4 * j + k;
+        w[k] = part[1 + (t < n_tiles ? t : 4 * j)];      // (clamped, unconditional: four loads in flight)
+        if (t >= n_tiles) { w[k].sum_norm = 0; w[k].sum_half_sq = 0; w[k].n_active = 0; w[k].n_relin = 0; w[k].n_robust = 0; }
+      }
+      s_norm = ((w[0].sum_norm + w[1].sum_norm) + w[2].sum_norm) + w[3].sum_norm;
+      s_half = ((w[0].sum_half_sq + w[1].sum_half_sq) + w[2].sum_half_sq) + w[3].sum_half_sq;
+      n_act = (unsigned)(w[0].n_active + w[1].n_active + w[2].n_active + w[3].n_active);
+      n_rel = (unsigned)(w[0].n_relin + w[1].n_relin + w[2].n_relin + w[3].n_relin);
+      n_rob = (unsigned)(w[0].n_robust + w[1].n_robust + w[2].n_robust + w[3].n_robust);
+    } else {
+      const DeviceEval w = part[1 + j];
+      s_norm = w.sum_norm; s_half = w.sum_half_sq;
+      n_act = (unsigned)w.n_active; n_rel = (unsigned)w.n_relin; n_rob = (unsigned)w.n_robust;
+    }
+  }
+  sh_d[0][j] = s_norm; sh_d[1][j] = s_half; sh_u[0][j] = n_act; sh_u[1][j] = n_rel; sh_u[2][j] = n_rob;
+  __syncthreads();
+  if (j == 0) {
+    EvalSum o;
+    eval_fold_chain(sh_d, sh_u, nb, o);
+    const unsigned long long* h = reinterpret_cast<const unsigned long long*>(part);
+    o.n_nonfinite = h[0]; o.n_nonpd = h[1];
+    out[blockIdx.x] = o;
   }
 }
 
@@ -2469,6 +2518,10 @@ void launch_eval_ride(const EvalRide& ev, const uint32_t* row_cam, const uint32_
 void launch_eval_fold(const EvalRide& ev, uint32_t n_slots, void* out, hipStream_t s) {
   if (n_slots == 0) return;
   hipLaunchKernelGGL(k_eval_fold, dim3(n_slots), dim3(1024), 0, s, ev, static_cast<EvalSum*>(out), eval_blocks(ev.n_tiles));
+}
+void launch_eval_fold_part(const DeviceEval* parts, uint32_t stride, uint32_t nb, uint32_t n_tiles, bool per_wave, uint32_t n_records, void* out, hipStream_t s) {
+  if (n_records == 0) return;
+  hipLaunchKernelGGL(k_eval_fold_part, dim3(n_records), dim3(1024), 0, s, parts, stride, nb, n_tiles, per_wave ? 1 : 0, static_cast<EvalSum*>(out));
 }
 // The placement of k_persist without its work: the same grid, the same filler rule, three barriers.  gbp_create runs it
 // once: if the working workgroups of this graph are NOT all resident at once on this device (another partition mode, another

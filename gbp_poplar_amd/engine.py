@@ -171,7 +171,27 @@ class GbpEngine:
             s = cabi.fill_struct(cabi.GbpKfUpdate(), upd, keep)
         self._chk(self.lib.gbp_new_keyframe(self.h, C.byref(s)), "gbp_new_keyframe")
 
-    def eval(self):
+    # The metric in device memory.  eval / iterate_eval_each / ba_loop with device=True (or out= a contiguous torch.int64 tensor on the
+    # engine's GPU, [7] for eval, [n, 7] for the loops) make the library write its gbp_eval_out records there: the call does not wait, the
+    # records are valid for work queued behind it on the ctx's stream (set_stream) or after sync(), and the tensor must stay allocated
+    # until the next sync() or blocking call of the engine.  Returned: a dict with the keys of eval(), every value a 1-D tensor that views
+    # one column of that buffer (sum_norm, sum_half_sq as float64); pass out= and keep it where the records are wanted whole.
+    def _eval_buffer(self, out, shape):
+        import torch
+        if out is None:
+            return torch.empty(shape, dtype=torch.int64, device=self.device())
+        return cabi.check_eval_buffer(out, shape, self.device())
+
+    @staticmethod
+    def _eval_ptr(buf):
+        return C.cast(C.c_void_p(buf.data_ptr()), C.POINTER(cabi.GbpEvalOut))
+
+    def eval(self, device=False, out=None):
+        """Host numbers by default; device=True / out=...: the record on the engine's GPU, not blocking (see above)."""
+        if device or out is not None:
+            buf = self._eval_buffer(out, (7,))
+            self._chk(self.lib.gbp_eval(self.h, self._eval_ptr(buf)), "gbp_eval")
+            return cabi.eval_buffer_views(buf)
         o = cabi.GbpEvalOut()
         self._chk(self.lib.gbp_eval(self.h, C.byref(o)), "gbp_eval")
         return {k: getattr(o, k) for k, _ in o._fields_}
@@ -183,18 +203,29 @@ class GbpEngine:
         """iterate(n) + eval_begin() in one call (fused into one launch on graphs that run in the persistent kernel)."""
         self._chk(self.lib.gbp_iterate_eval(self.h, int(n)), "gbp_iterate_eval")
 
-    def iterate_eval_each(self, n):
+    def iterate_eval_each(self, n, device=False, out=None):
         """n iterations with the metric after every one (blocking); one launch per burst on graphs that run in the
-        persistent kernel.  Returns a list of n dicts like eval()."""
+        persistent kernel.  Returns a list of n dicts like eval().  device=True / out=...: the n records on the engine's GPU, not
+        blocking; returns one dict of length-n tensors."""
         n = int(n)
+        if device or out is not None:
+            buf = self._eval_buffer(out, (n, 7))
+            self._chk(self.lib.gbp_iterate_eval_each(self.h, n, self._eval_ptr(buf) if n else None), "gbp_iterate_eval_each")
+            return cabi.eval_buffer_views(buf)
         arr = (cabi.GbpEvalOut * max(n, 1))()
         self._chk(self.lib.gbp_iterate_eval_each(self.h, n, arr), "gbp_iterate_eval_each")
         return [{k: getattr(arr[i], k) for k, _ in arr[i]._fields_} for i in range(n)]
 
-    def ba_loop(self, n, iter0, steps, metrics=True):
+    def ba_loop(self, n, iter0, steps, metrics=True, device=False, out=None):
         """n passes of the body of the reference's loop from loop index iter0 (prior weakening where the loop weakens, the iteration,
-        the metric): gbp_ba_loop.  Returns a list of n dicts like eval()."""
+        the metric): gbp_ba_loop.  Returns a list of n dicts like eval().  device=True / out=...: the n records on the engine's GPU,
+        not blocking; returns one dict of length-n tensors."""
         n = int(n)
+        if metrics and (device or out is not None):
+            buf = self._eval_buffer(out, (n, 7))
+            if n:
+                self._chk(self.lib.gbp_ba_loop(self.h, n, int(iter0), int(steps), self._eval_ptr(buf)), "gbp_ba_loop")
+            return cabi.eval_buffer_views(buf)
         if not metrics:      # the passes without the metric: not blocking, returns nothing
             self._chk(self.lib.gbp_ba_loop(self.h, n, int(iter0), int(steps), None), "gbp_ba_loop")
             return None

@@ -12,8 +12,8 @@
  *
  * Conventions: plain C, no exceptions across the ABI, every function returns 0 on success and a
  * negative gbp_status otherwise (text via gbp_last_error).  All pointers are HOST memory owned by
- * the caller unless the name ends in `_dev` — or, in the four calls that move state, DEVICE memory
- * ("Device-resident arrays" below).  A ctx is not thread-safe; calls are blocking unless
+ * the caller unless the name ends in `_dev` — or, in the four calls that move state and the three that return the metric, DEVICE
+ * memory ("Device-resident arrays" below).  A ctx is not thread-safe; calls are blocking unless
  * stated.  All floating point is IEEE fp32, integers are 32-bit, layouts are the reference's
  * row-major AoS host layouts (ba/ba.cpp:690-713,778-790).  All device work of a ctx is ordered on ITS stream (its own, or the one handed
  * over with gbp_set_stream), copies to and from the host included: nothing goes through the NULL stream, so work a caller queues on other
@@ -41,6 +41,22 @@
  *     with per_factor_mu = 0 they are all zero (the members are not read there); gbp_new_keyframe — no factor is activated with
  *     damping_count + 1 > min_linear_iters - num_undamped_iters on a ctx with per_factor_mu = 0.
  *   Alignment: 4 bytes suffice (a view into a larger buffer); arrays whose base is 16-byte aligned are moved with 16-byte accesses.
+ *   The metric.  gbp_eval, gbp_ba_loop and gbp_iterate_eval_each (gbp_mi355x_compat.h) take an `out` in memory of the ctx's GPU the same
+ *     way: `out` is classified like a struct with the one member `out`, after the argument and state checks of the call; host memory
+ *     (unregistered, pinned, host-registered) takes the blocking path every caller has had.  GBP_ERR_INVALID with `out` named in
+ *     gbp_last_error and the ctx untouched: memory of another GPU, managed memory, a landmark-sharded ctx, a device address that is
+ *     not 8-byte aligned (a record holds doubles and 64-bit counters).  GBP_ERR_STATE: the caller is capturing the ctx's stream, or an
+ *     evaluation is in flight (gbp_eval_begin), as in the host forms.  out[i] then holds the same seven fields, bit for bit, as the
+ *     host form of the same call on the same state — the partial sums are folded on the device in the order the host adds them — and
+ *     the ctx is left in the same state.  The device forms do not block: everything is queued on the ctx's stream, `out` is valid
+ *     for work queued behind the call on that stream, or after gbp_sync; gbp_timing counts the passes as in the host forms.  What
+ *     waits: first-use allocations, and unvalidated launches of the persistent kernel in front of other device work (gbp_eval always,
+ *     a weakening in front of a call's first pass, a ctx that does not run in that kernel) — consecutive gbp_ba_loop /
+ *     gbp_iterate_eval_each bursts on a graph that runs in the persistent kernel queue behind each other as gbp_iterate bursts do.
+ *     LIFETIME: `out` must stay allocated until the next gbp_sync, or the next blocking call of the ctx, has returned: a launch of
+ *     the persistent kernel that is later found to have timed out is undone and replayed on the two-kernel path INTO THE SAME
+ *     RECORDS (identical results; until then they hold no valid data, as after any call that has not completed).
+ *     gbp_eval_begin / gbp_eval_end / gbp_iterate_eval and gbp_eval_global take host memory only.
  */
 #ifndef GBP_MI355X_H
 #define GBP_MI355X_H
@@ -258,7 +274,10 @@ GBP_API int gbp_weaken_priors(gbp_ctx* ctx);                           /* WEAKEN
 GBP_API int gbp_read(gbp_ctx* ctx, gbp_state_out* out);                /* READ_PROG       ba.cpp:908-916  */
 GBP_API int gbp_read_priors(gbp_ctx* ctx, gbp_priors_out* out);        /* READ_PRIORS     slam.cpp:913-917 */
 GBP_API int gbp_new_keyframe(gbp_ctx* ctx, const gbp_kf_update* upd);  /* NEW_KEYFRAME    slam.cpp:919-928 */
-GBP_API int gbp_eval(gbp_ctx* ctx, gbp_eval_out* out);                 /* util.cpp:74-144 on device (local shard) */
+GBP_API int gbp_eval(gbp_ctx* ctx, gbp_eval_out* out);                 /* util.cpp:74-144 on device (local shard); blocking —
+                                                                  or `out` in memory of the ctx's GPU (8-byte aligned): not blocking,
+                                                                  the record is valid behind the call on the ctx's stream ("Device-
+                                                                  resident arrays": The metric) */
 /* n passes of the BODY of the reference's iteration loop (ba.cpp:1001-1028, slam.cpp:1048-1103), blocking, from loop index iter0:
  *   if ((i + 1) % 2 == 0 && i < 2 * steps) WEAKEN_PRIORS;  GBP_PROG;  out[i - iter0] = the metric      for i = iter0 .. iter0 + n - 1
  * (steps = the reference's --steps; steps = 0: n iterations with the metric after every one).  Exactly the calls it stands for
@@ -267,7 +286,12 @@ GBP_API int gbp_eval(gbp_ctx* ctx, gbp_eval_out* out);                 /* util.c
  * WeakenPriorVertex itself in front of the iterations the loop weakens before) — the ten short launches of a run's, or a SLAM
  * keyframe's, weakening phase become one.  No evaluation may be in flight.
  * out == NULL: the passes WITHOUT the metric, not blocking (like gbp_iterate): a weakening then rides in the launch of the persistent
- * kernel or, on the two-kernel path, in the belief update of the iteration in front of it (one launch instead of two). */
+ * kernel or, on the two-kernel path, in the belief update of the iteration in front of it (one launch instead of two).
+ * out in memory of the ctx's GPU (8-byte aligned; "Device-resident arrays": The metric): the same passes and the same n_passes records,
+ * not blocking — on a graph that runs in the persistent kernel still one launch per burst of at most 512 passes, its per-pass records
+ * folded on the device behind it; elsewhere the metric rides in the sweeps and is folded per piece of at most 256 passes.  The records
+ * are valid for work queued behind the call on the ctx's stream, or after gbp_sync, and must stay allocated until the next gbp_sync
+ * or blocking call of the ctx has returned. */
 GBP_API int gbp_ba_loop(gbp_ctx* ctx, int n_passes, unsigned iter0, unsigned steps, gbp_eval_out* out /* [n_passes] */);
 GBP_API int gbp_sync(gbp_ctx* ctx);                                    /* wait for queued device work     */
 GBP_API int gbp_timing(gbp_ctx* ctx, gbp_timing_out* out, int reset);  /* ba.cpp:980,1056-1058            */

@@ -27,7 +27,10 @@ GBP_API int gbp_iterate_eval(gbp_ctx* ctx, int n_iters);
 /* n iterations with the metric after EVERY one (what the loops of ba.cpp:1001-1028 and slam.cpp print), blocking: out[k] is
  * what gbp_iterate(ctx, 1) followed by gbp_eval would have returned for the k-th of them.  A burst between two host events
  * (prior weakening, a new keyframe) is ONE launch on a graph that runs in the persistent kernel — the metric of iteration k
- * is computed inside the sweep phase of iteration k + 1 — and the plain loop elsewhere.  No evaluation may be in flight. */
+ * is computed inside the sweep phase of iteration k + 1 — and the plain loop elsewhere.  No evaluation may be in flight.
+ * out in memory of the ctx's GPU: as gbp_ba_loop(ctx, n, 0, 0, out) with such an `out` — the same records, not blocking, valid behind
+ * the call on the ctx's stream; they must stay allocated until the next gbp_sync or blocking call of the ctx has returned
+ * (gbp_mi355x.h, "Device-resident arrays": The metric). */
 GBP_API int gbp_iterate_eval_each(gbp_ctx* ctx, int n_iters, gbp_eval_out* out /* [n_iters] */);
 
 #ifdef __cplusplus
