@@ -25,12 +25,12 @@ GBP_DEV void lab_sweep_tile(const SweepArgs& a, const uint32_t wslot) {
   const uint32_t cam_i = a.row_cam[p >> 4];
   const uint32_t lmk_i = __builtin_nontemporal_load(a.lmk_idx + p);
 
-  float fac[56], cm[28], mu[12], lm[16], cb[44], lb[16];
+  float fac[56], cmr[16], mu[12], lm[16], cb[44], lb[16];
   load_tile<kFacG>(a.fac, tile, lane, fac);
   // The camera messages: non-temporal like the potentials, or — SweepArgs.cmsg_cached, graphs with few cameras — with the
   // default policy like the landmark messages below (both are rewritten in place by this tile).  The potentials, which an
   // ordinary sweep only reads, keep the hint on every graph: with default-policy loads they cost 3 %.
-  load_tile<kCmsgG>(a.cmsg, tile, lane, cm);
+  load_tile<kCmsgG>(a.cmsg, tile, lane, cmr);
   if (!true) load_tile<kMuG>(a.mu, tile, lane, mu);
   // Landmark messages live as 64-byte records in DEVICE (camera-major) order: the wave's 64 records are one
   // contiguous 4 KiB block, moved with four coalesced 1 KiB accesses and transposed through a wave-private
@@ -89,18 +89,21 @@ GBP_DEV void lab_sweep_tile(const SweepArgs& a, const uint32_t wslot) {
   GBP_UNROLL
   for (int i = 0; i < 9; ++i) K[i] = a.K[i];
 
-  float oc_eta[6], oc_lam[36], ol[16];
+  float oc_eta[6], oc_lam[36], bi[9], ol[16], cm[28];
   bool relin;
+  if (!(LAB & 4)) cmsg_expand(fac, cmr, a.cmsg_lit, tile, lane, cm);
   if (LAB & 4) {         // no arithmetic: every load kept alive, every store fed
     relin = false;
     GBP_UNROLL
     for (int i = 0; i < 16; ++i) ol[i] = lm[i] + lb[i];
     GBP_UNROLL
-    for (int i = 0; i < 6; ++i) oc_eta[i] = cm[i] + fac[i];
+    for (int i = 0; i < 6; ++i) oc_eta[i] = cmr[i] + fac[i];
     GBP_UNROLL
-    for (int i = 0; i < 36; ++i) oc_lam[i] = fac[9 + i] + cb[8 + i] + cm[6 + (i % 21)];
+    for (int i = 0; i < 36; ++i) oc_lam[i] = fac[9 + i] + cb[8 + i] + cmr[6 + (i % 10)];
+    GBP_UNROLL
+    for (int i = 0; i < 9; ++i) bi[i] = cmr[6 + i] + fac[45 + i];
   } else
-  factor_update<true>(fac, cm, mu, lm, cb, lb, K, a.hp, damping, count, flags, var, active, oc_eta, oc_lam, ol, relin,
+  factor_update<true>(fac, cm, mu, lm, cb, lb, K, a.hp, damping, count, flags, var, active, oc_eta, oc_lam, bi, ol, relin,
                             [&](float (&x0c)[6], float (&x0l)[3], CamLin& cl) {   // rare path: loaded only by relinearising lanes
                               // camera side: the hoisted mean and its CAM_LIN record — per-camera tables (C x 144 B) that live in L2
                               const float4 m0 = a.cam_mu[(size_t)cam_i * 4], m1 = a.cam_mu[(size_t)cam_i * 4 + 1];
@@ -137,15 +140,8 @@ GBP_DEV void lab_sweep_tile(const SweepArgs& a, const uint32_t wslot) {
   }
   }
   {
-    float cmo[28];
-    GBP_UNROLL
-    for (int i = 0; i < 6; ++i) cmo[i] = oc_eta[i];
-    GBP_UNROLL
-    for (int i = 0; i < 6; ++i) {
-      GBP_UNROLL
-      for (int j = 0; j <= i; ++j) cmo[6 + tri(i, j)] = oc_lam[i * 6 + j];
-    }
-    cmo[27] = 0.f;
+    float cmo[16];
+    cmsg_pack(oc_eta, bi, active, cmo);
     store_tile<kCmsgG>(a.cmsg, tile, lane, cmo);
   }
   // camera half of the belief reduction: per-row (16 factors of one camera) tree sums
@@ -281,11 +277,21 @@ __global__ __launch_bounds__(256) void k_sweep_coop16(const SweepArgs a) {
     float4 v;
     int dst = -1;
     if (i < 14) { v = a.fac[((size_t)tile * kFacG + i) * 64 + lt]; dst = kF + 4 * i; }
-    else if (i < 21) { v = a.cmsg[((size_t)tile * kCmsgG + (i - 14)) * 64 + lt]; dst = kCm + 4 * (i - 14); }
+    else if (i < 21) { }                 // (the camera message: expanded below)
     else if (i < 25) { v = a.lmsg[(size_t)p * 4 + (i - 21)]; dst = kLm + 4 * (i - 21); }
     else if (i < 36) { v = a.camb[(size_t)cam_i * kCamRec4 + (i - 25)]; dst = kCb + 4 * (i - 25); }
     else if (i < 40) { v = a.lmkb[(size_t)lmk_i * kLmkRec4 + (i - 36)]; dst = kLb + 4 * (i - 36); }
     if (dst >= 0) { w[dst] = v.x; w[dst + 1] = v.y; w[dst + 2] = v.z; w[dst + 3] = v.w; }
+  }
+  sync();
+  if (t == 0) {      // the camera message the factor starts from: cmsg_expand on one lane, as the product kernel runs it
+    float fr[56], rec[16], cmx[28];
+    GBP_UNROLL
+    for (int i = 0; i < 56; ++i) fr[i] = w[kF + i];
+    load_tile<kCmsgG, false>(a.cmsg, tile, lt, rec);
+    cmsg_expand(fr, rec, a.cmsg_lit, tile, lt, cmx);
+    GBP_UNROLL
+    for (int i = 0; i < 28; ++i) w[kCm + i] = cmx[i];
   }
   sync();
   const float* fac = w + kF; const float* cm = w + kCm; const float* lm = w + kLm; const float* cb = w + kCb; const float* lb = w + kLb;
@@ -435,22 +441,15 @@ __global__ __launch_bounds__(256) void k_sweep_coop16(const SweepArgs a) {
     out[14] = var;
   }
   sync();
-  // ---- stores: landmark-message record (64 B), camera message (7 groups of the tile layout), potential if relinearised ----
+  // ---- stores: landmark-message record (64 B), camera message (the CMSG record: eta, Bi, format word), potential if relinearised ----
   if (t < 4) a.lmsg[(size_t)p * 4 + t] = make_float4(out[4 * t], out[4 * t + 1], out[4 * t + 2], out[4 * t + 3]);
-  if (t < 7) {
+  if (t < 4) {
     float c4[4];
     GBP_UNROLL
     for (int q = 0; q < 4; ++q) {
-      const int e = 4 * (int)t + q;            // cmo[e]: eta 0..5, lower triangle 6..26, pad
+      const int e = 4 * (int)t + q;            // record slot e: eta 0..5, Bi 6..14, format word (an inactive factor: the zero record)
       float v = 0.f;
-      if (e < 6) v = out[16 + e];
-      else if (e < 27) {
-        const int m = e - 6;
-        int i = 0;
-        while ((i + 1) * (i + 2) / 2 <= m) ++i;
-        const int j = m - i * (i + 1) / 2;
-        v = out[22 + i * 6 + j];
-      }
+      if (active) v = e < 6 ? out[16 + e] : (e < 15 ? w[kBi + (e - 6)] : kCmsgDerived);
       c4[q] = v;
     }
     a.cmsg[((size_t)tile * kCmsgG + t) * 64 + lt] = make_float4(c4[0], c4[1], c4[2], c4[3]);

@@ -577,7 +577,8 @@ GBP_EXPORT(gbp_upload, c, (gbp_ctx* c, const gbp_state_in* in), (c, in)) {
   lap("staging + k_upload_scatter queued");
   if (!c->hoist)
     if (int rc = up.put(c->mu.p, mu.data(), mu.size() * 4)) return rc;
-  HIPCHK(c, hipMemsetAsync(c->cmsg.p, 0, c->cmsg.bytes, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->cmsg.p, 0, c->cmsg.bytes, c->stream));      // every record kCmsgZero
+  c->cmsg_zero = true;
   HIPCHK(c, hipMemsetAsync(c->rowp.p, 0, c->rowp.bytes, c->stream));
   HIPCHK(c, hipMemsetAsync(c->local.p, 0, c->local.bytes, c->stream));
   HIPCHK(c, hipMemsetAsync(c->camb.p, 0, c->camb.bytes, c->stream));

@@ -41,14 +41,24 @@ GBP_EXPORT(gbp_debug_get, c, (gbp_ctx* c, int what, float* a, float* b), (c, wha
       for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) lam[72 + i * 3 + j] = F(48 + tri(i, j));
     }
   } else if (what == 1) {
-    std::vector<float> f((size_t)c->Ep * kCmsgG * 4);
-    HIPCHK(c, hipMemcpy(f.data(), c->cmsg.p, f.size() * 4, hipMemcpyDeviceToHost));
+    // the CMSG records keep eta and the 3x3 inverse the message's Lambda derives from (gbp_kernels.h): expanded on the device, by the
+    // code the sweeps expand them with, into 28 floats per position (eta 6, lower triangle 21, 0)
+    if (!launch_cmsg_expand) return fail(c, GBP_ERR_STATE, "gbp_debug_get: no device code for the camera messages");
+    std::vector<float> f((size_t)c->Ep * 28);
+    float* tmp = nullptr;
+    HIPCHK(c, hipMalloc(&tmp, f.size() * 4));
+    launch_cmsg_expand(sweep_args(c, /*sweeps=*/false), c->n_tiles, tmp, c->stream);
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
+    if (err == hipSuccess) err = hipMemcpy(f.data(), tmp, f.size() * 4, hipMemcpyDeviceToHost);
+    (void)hipFree(tmp);
+    HIPCHK(c, err);
     for (size_t p = 0; p < c->Ep; ++p) {
       const uint32_t e = c->lay.pos_edge[p];
       if (e == ~0u) continue;
-      for (int i = 0; i < 6; ++i) a[(size_t)e * 6 + i] = f[tile_off((uint32_t)p, kCmsgG, i)];
+      for (int i = 0; i < 6; ++i) a[(size_t)e * 6 + i] = f[p * 28 + i];
       for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j)
-        b[(size_t)e * 36 + i * 6 + j] = (i >= j) ? f[tile_off((uint32_t)p, kCmsgG, 6 + tri(i, j))] : 0.f;
+        b[(size_t)e * 36 + i * 6 + j] = (i >= j) ? f[p * 28 + 6 + tri(i, j)] : 0.f;
     }
   } else if (what == 2) {
     std::vector<float> f((size_t)c->Ep * 16);
@@ -253,6 +263,9 @@ GBP_EXPORT(gbp_debug_tile_order_local, nullptr, (const uint8_t* tile_class, uint
 // symmetric blocks and Lambda_cl are taken; Lambda_lc is implied).  Test hook only.
 GBP_EXPORT(gbp_debug_set_factor_potentials, c, (gbp_ctx* c, const float* eta9E, const float* lam81E), (c, eta9E, lam81E)) {
   if (!c || !eta9E || !lam81E) return GBP_ERR_INVALID;
+  // (a kCmsgDerived record derives its message from the potential, gbp_kernels.h: the potentials may be replaced only while every
+  // record is the zero message — behind the upload or the LINEARISE that follows it, where the tests call this)
+  if (!c->cmsg_zero) return fail(c, GBP_ERR_STATE, "gbp_debug_set_factor_potentials: camera messages are live (call it before the first sweep)");
   if (int rc = gbp_sync(c)) return rc;
   auto tri = [](int i, int j) { return i * (i + 1) / 2 + j; };
   std::vector<float> f((size_t)c->Ep * kFacG * 4);

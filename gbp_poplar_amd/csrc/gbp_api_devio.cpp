@@ -54,6 +54,7 @@ int devio_upload(gbp_ctx* c, const gbp_state_in* in) {
   c->active_host_stale = true;
   for (DevBuf* b : {&c->fac, &c->cmsg, &c->rowp, &c->local, &c->camb, &c->lmkb, &c->hmu_c, &c->hmu_l, &c->clin, &c->camp, &c->lmkp, &c->cscale, &c->cwf, &c->lscale, &c->lwf})
     HIPCHK(c, hipMemsetAsync(b->p, 0, b->bytes, c->stream));
+  c->cmsg_zero = true;      // (the fill of CMSG: every record kCmsgZero)
   UploadDev a{};
   a.pos_edge = P<uint32_t>(c->d_pos_edge);
   a.damping = in->damping; a.damping_count = in->damping_count; a.active_flag = in->active_flag;

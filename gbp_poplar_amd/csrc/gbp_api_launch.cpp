@@ -15,9 +15,13 @@ using namespace gbp::api;
 namespace gbp {
 namespace api {
 
-SweepArgs sweep_args(gbp_ctx* c) {
+// (every path that runs sweeps — direct launches, graph captures, the persistent kernel — takes its arguments from here, so from here
+// on the camera messages count as live: what gbp_linearise_factors looks at)
+SweepArgs sweep_args(gbp_ctx* c, bool sweeps) {
+  if (sweeps) c->cmsg_zero = false;
   SweepArgs a;
   a.row_cam = P<uint32_t>(c->row_cam); a.lmk_idx = P<uint32_t>(c->lmk_idx); a.fac = P<float4>(c->fac); a.cmsg = P<float4>(c->cmsg);
+  a.cmsg_lit = P<float4>(c->cmsg_lit);
   a.mu = P<float4>(c->mu); a.lmsg = P<float4>(c->lmsg); a.camb = P<float4>(c->camb); a.lmkb = P<float4>(c->lmkb);
   a.rowp = P<float4>(c->rowp);
   a.cam_mu = P<float4>(c->hmu_c); a.lmk_mu = P<float4>(c->hmu_l); a.cam_lin = P<float4>(c->clin);
@@ -300,7 +304,14 @@ GBP_EXPORT(gbp_refresh_end, c, (gbp_ctx* c), (c)) {
 GBP_EXPORT(gbp_linearise_factors, c, (gbp_ctx* c), (c)) {
   if (!c || !c->uploaded) return fail(c, GBP_ERR_STATE, "upload first");
   if (int rc = settle(c)) return rc;
-  launch_linearise(sweep_args(c), c->n_tiles, c->stream);
+  if (!c->cmsg_zero && !c->cmsg_lit.p) {
+    // LINEARISE under live messages: k_linearise rewrites the potentials the kCmsgDerived records derive their Lambda from, so it
+    // first makes those records literal (gbp_kernels.h: CMSG) — in a side array that only such a call pays for.  A captured graph
+    // holds the sweep's arguments without it: dropped, the next burst captures again.
+    if (int rc = dev_alloc(c, c->cmsg_lit, (size_t)c->Ep * kCmsgLitG * 16)) return rc;
+    drop_graph(c);
+  }
+  launch_linearise(sweep_args(c, /*sweeps=*/false), c->n_tiles, c->stream);
   HIPCHK(c, hipGetLastError());
   return GBP_OK;
 }

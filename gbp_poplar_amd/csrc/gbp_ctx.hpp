@@ -65,6 +65,8 @@ struct gbp_ctx {
   void* stage_dev = nullptr;
   size_t stage_cap = 0;
   size_t stage_hint = 0;               // what gbp_upload will stage: the buffer is pinned once, at that size (gbp_create)
+  DevBuf cmsg_lit;                     // CMSG_LIT (gbp_kernels.h): allocated by the first gbp_linearise that finds camera messages live
+  bool cmsg_zero = true;               // no sweep has been set up since the zero fill of the last upload: every CMSG record is kCmsgZero
   DevBuf idx_arena;                    // the index arrays of the device order (row_cam, lmk_idx, lmk_fpos, lmk_ix, the row / landmark pointers, row_slot, K, tile_perm: views into it)
   DevBuf st_a, st_b;                   // [Ep] scratch of the per-factor state get / set kernels
   std::vector<uint8_t> active_host;    // [Ep] host shadow of the active flags (hoist guard of gbp_new_keyframe)
@@ -259,7 +261,7 @@ inline size_t tile_off(uint32_t p, int G, int f) {  // float offset of float f o
 }
 
 // ---- gbp_api_launch.cpp -----------------------------------------------------------------------------------------------------
-SweepArgs sweep_args(gbp_ctx* c);
+SweepArgs sweep_args(gbp_ctx* c, bool sweeps = true);      // sweeps = false: for a launch that runs no sweep (k_linearise, the hooks)
 BeliefArgs belief_args(gbp_ctx* c);
 void weaken_args(gbp_ctx* c, BeliefArgs& b);                  // the prior arrays WeakenPriorVertex writes (b.weaken is the caller's)
 void drop_graph(gbp_ctx* c);

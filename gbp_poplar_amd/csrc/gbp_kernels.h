@@ -20,10 +20,20 @@ constexpr int kRow = 16;
 //   [0..8] eta (c0..5,l0..2)  [9..29] Lambda_cc lower  [30..47] Lambda_cl 6x3  [48..53] Lambda_ll lower
 //   [54,55] measurement z
 constexpr int kFacG = 14;
-// CMSG: factor->camera message as the sweep re-reads it, 28 floats / 7 groups:
-//   [0..5] eta  [6..26] Lambda lower triangle (only the lower triangle is ever read back:
-//   inv6x6 reads A(i,j), i>=j, matlib.cpp:195-201; the full 6x6 goes into the row partial sums)
-constexpr int kCmsgG = 7;
+// CMSG: the factor->camera message as the factor carries it from sweep to sweep, 16 floats / 4 groups.  Nobody but the factor reads
+// it (the camera belief is built from ROWP), and only its eta depends on older history (it is damped): the Lambda part of an active
+// factor's message is Lambda_cc - (Lambda_cl Bi) Lambda_lc (gbp_codelets.cpp:592-637), a function of the potential the factor holds
+// anyway and of the 3x3 inverse Bi it was computed from; the same fp32 operations on the same operands give the same bits, so the
+// record keeps Bi and the sweep re-derives the 21 lower-triangle entries it needs (cam_msg_lambda in gbp_kernels.hip):
+//   [0..5] eta  [6..14] Bi (row-major)  [15] format word
+// Format (a float, so that the zero fill of gbp_upload IS format 0):
+//   kCmsgZero     the message is zero: what the fill leaves and what an inactive or pad factor writes
+//   kCmsgDerived  Lambda = f(FAC, Bi): what every active factor writes in a sweep
+//   kCmsgLiteral  Lambda's lower triangle lies in the side array CMSG_LIT (6 groups, the same tile addressing): left by k_linearise,
+//                 which rewrites FAC under live messages; the factor's next store returns the record to kCmsgDerived
+constexpr int kCmsgG = 4;
+constexpr int kCmsgLitG = 6;
+constexpr float kCmsgZero = 0.f, kCmsgDerived = 1.f, kCmsgLiteral = 2.f;
 // MU: [0..8] mu (== oldmu between sweeps, ba.cpp:898)  [9] dmu
 constexpr int kMuG = 3;
 // Per-factor scalar state rides in the pad slots of the landmark-message record (below); flags:
@@ -87,6 +97,7 @@ struct SweepArgs {
   const uint32_t* lmk_idx;   // [Ep]    landmark (local index) of each factor
   float4* fac;
   float4* cmsg;
+  float4* cmsg_lit;          // CMSG_LIT or NULL (allocated by the first gbp_linearise that finds messages live): read by kCmsgLiteral records only
   float4* mu;
   float4* lmsg;
   const float4* camb;
@@ -254,6 +265,9 @@ struct DeviceEval {  // per-block partials, summed on the host in block order
 
 void launch_sweep(const SweepArgs& a, uint32_t n_tiles, bool hoist, hipStream_t s, bool ev = false);
 void launch_linearise(const SweepArgs& a, uint32_t n_tiles, hipStream_t s);
+// the camera messages as the reference stores them, out[p] = 28 floats (eta 6, Lambda lower triangle 21, 0) of device position p (test hooks;
+// weak, as the launchers below: the CPU sanitizer build of the host code has no device code behind it, the caller checks for a null launcher)
+[[gnu::weak]] void launch_cmsg_expand(const SweepArgs& a, uint32_t n_tiles, float* out, hipStream_t s);
 void launch_beliefs(BeliefArgs b, bool do_cam, bool do_lmk, hipStream_t s, bool ev = false);
 // The direct peer-memory transport (gbp_comm.cpp: p2p).  peers: device table of `world` pointers, peers[r] = slot r of one parity in
 // rank r's exchange buffer (an IPC mapping for r != self).  Both kernels begin with a system-scope acquire.

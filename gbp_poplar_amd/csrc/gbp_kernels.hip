@@ -313,15 +313,73 @@ GBP_DEV bool relin_core(float (&fac)[56], const float (&x0c)[6], const float (&x
   return robust;
 }
 
+// The Lambda half of ComputeCamMessage{Eta,Lambda}Vertex (gbp_codelets.cpp:411-471, 592-637) from the potential and the 3x3 inverse Bi:
+// G2 = Lambda_cl Bi, then put(i, j, Lambda_cc(i,j) - sum_k G2(i,k) Lambda_lc(k,j)) — all 36 entries, or (LOWER) the 21 with i >= j.
+// THE one copy of these loops: factor_update produces a factor's new message with it, cmsg_expand re-derives the message a CMSG
+// record stands for.  Every entry is its own chain (t = 0.f, k = 0, 1, 2), so the same fac and Bi give the same bits wherever it runs.
+template <bool LOWER, class Put>
+GBP_DEV void cam_msg_lambda(const float (&fac)[56], const float (&Bi)[9], float (&G2)[18], Put&& put) {
+  GBP_UNROLL
+  for (int i = 0; i < 6; ++i) {
+    GBP_UNROLL
+    for (int j = 0; j < 3; ++j) {
+      float acc = 0.f;
+      GBP_UNROLL
+      for (int k = 0; k < 3; ++k) acc += fac[30 + i * 3 + k] * Bi[k * 3 + j];
+      G2[i * 3 + j] = acc;
+    }
+  }
+  GBP_UNROLL
+  for (int i = 0; i < 6; ++i) {
+    GBP_UNROLL
+    for (int j = 0; j < (LOWER ? i + 1 : 6); ++j) {
+      float t = 0.f;
+      GBP_UNROLL
+      for (int k = 0; k < 3; ++k) t += G2[i * 3 + k] * fac[30 + j * 3 + k];  // Lambda_lc(k,j) = Lambda_cl(j,k)
+      put(i, j, fac[9 + trisym(i, j)] - t);
+    }
+  }
+}
+// The camera message a factor starts a sweep from — the 28 floats factor_update reads: eta 6, Lambda lower triangle 21, a spare slot —
+// out of its CMSG record (gbp_kernels.h) and its potential AS LOADED: the potential that produced the message, so this runs before
+// factor_update may relinearise it.  Every lane derives (no branch; a select keeps the zero message of a kCmsgZero record, whose
+// potential may hold anything); only kCmsgLiteral lanes — behind a gbp_linearise under live messages, until their next store —
+// take the divergent branch to the side array.
+GBP_DEV void cmsg_expand(const float (&fac)[56], const float (&rec)[16], const float4* lit, uint32_t tile, uint32_t lane, float (&cm)[28]) {
+  GBP_UNROLL
+  for (int i = 0; i < 6; ++i) cm[i] = rec[i];
+  float Bi[9], G2[18];
+  GBP_UNROLL
+  for (int i = 0; i < 9; ++i) Bi[i] = rec[6 + i];
+  const bool derived = rec[15] == kCmsgDerived;
+  cam_msg_lambda<true>(fac, Bi, G2, [&](int i, int j, float v) { cm[6 + tri(i, j)] = derived ? v : 0.f; });
+  cm[27] = 0.f;
+  if (rec[15] == kCmsgLiteral) {
+    float l[kCmsgLitG * 4];
+    load_tile<kCmsgLitG, false>(lit, tile, lane, l);
+    GBP_UNROLL
+    for (int i = 0; i < 21; ++i) cm[6 + i] = l[i];
+  }
+}
+// ... and the record an active factor leaves behind (an inactive or pad factor: the zero record)
+GBP_DEV void cmsg_pack(const float (&oc_eta)[6], const float (&bi)[9], bool active, float (&rec)[16]) {
+  GBP_UNROLL
+  for (int i = 0; i < 6; ++i) rec[i] = active ? oc_eta[i] : 0.f;
+  GBP_UNROLL
+  for (int i = 0; i < 9; ++i) rec[6 + i] = active ? bi[i] : 0.f;
+  rec[15] = active ? kCmsgDerived : kCmsgZero;
+}
+
 // One factor's share of a sweep on register state: PrepMessageVertex + the four Compute*Message*Vertex classes
 // (gbp_codelets.cpp:215-710).  Shared by k_sweep (state streamed from HBM every launch) and k_persist (state kept in
 // registers across iterations).  `means(x0c, x0l, cl)` supplies the hoisted linearisation point and the camera-only Jacobian
-// terms of that point when a lane relinearises.
+// terms of that point when a lane relinearises.  cm: the previous camera message (cmsg_expand); bi: the 3x3 inverse the new one was
+// computed from (written for an active factor only) — with oc_eta what cmsg_pack keeps of it.
 template <bool HOIST, class Means>
 GBP_DEV void factor_update(float (&fac)[56], const float (&cm)[28], float (&mu)[12], const float (&lm)[16], const float (&cb)[44],
                            const float (&lb)[16], const float (&K)[9], const Hyper& hp, float& damping, int& count, uint32_t& flags,
-                           const float var, const bool active, float (&oc_eta)[6], float (&oc_lam)[36], float (&ol)[16], bool& relin,
-                           Means&& means) {
+                           const float var, const bool active, float (&oc_eta)[6], float (&oc_lam)[36], float (&bi)[9], float (&ol)[16],
+                           bool& relin, Means&& means) {
   relin = false;
   // (zero messages of an inactive factor are written in the ELSE branch at the bottom: 58 v_mov the wavefronts of a graph
   // with every factor active never execute, instead of an initialisation in front of the branch that all of them do)
@@ -425,7 +483,7 @@ GBP_DEV void factor_update(float (&fac)[56], const float (&cm)[28], float (&mu)[
     }
     // ---- Compute{Cam}Message{Eta,Lambda}Vertex, gbp_codelets.cpp:411-471, 592-637 ----
     {
-      float Bp[9], Bi[9], G2[18], el[3];
+      float Bp[9], G2[18], el[3];
       GBP_UNROLL
       for (int i = 0; i < 3; ++i) {
         GBP_UNROLL
@@ -435,17 +493,8 @@ GBP_DEV void factor_update(float (&fac)[56], const float (&cm)[28], float (&mu)[
           Bp[i * 3 + j] = t;
         }
       }
-      inv3x3(Bp, Bi);
-      GBP_UNROLL
-      for (int i = 0; i < 6; ++i) {
-        GBP_UNROLL
-        for (int j = 0; j < 3; ++j) {
-          float acc = 0.f;
-          GBP_UNROLL
-          for (int k = 0; k < 3; ++k) acc += fac[30 + i * 3 + k] * Bi[k * 3 + j];
-          G2[i * 3 + j] = acc;
-        }
-      }
+      inv3x3(Bp, bi);
+      cam_msg_lambda<false>(fac, bi, G2, [&](int i, int j, float v) { oc_lam[i * 6 + j] = v; });
       GBP_UNROLL
       for (int k = 0; k < 3; ++k) {
         float t = fac[6 + k] + lb[k];
@@ -459,16 +508,6 @@ GBP_DEV void factor_update(float (&fac)[56], const float (&cm)[28], float (&mu)[
         for (int k = 0; k < 3; ++k) s += G2[i * 3 + k] * el[k];
         const float h = fac[i] - s;
         oc_eta[i] = h * omd + cm[i] * damping;
-      }
-      GBP_UNROLL
-      for (int i = 0; i < 6; ++i) {
-        GBP_UNROLL
-        for (int j = 0; j < 6; ++j) {
-          float t = 0.f;
-          GBP_UNROLL
-          for (int k = 0; k < 3; ++k) t += G2[i * 3 + k] * fac[30 + j * 3 + k];  // Lambda_lc(k,j) = Lambda_cl(j,k)
-          oc_lam[i * 6 + j] = fac[9 + trisym(i, j)] - t;
-        }
       }
     }
   } else {
@@ -688,14 +727,14 @@ GBP_DEV void sweep_tile(const SweepArgs& a, const uint32_t wslot) {
   // SEG: bit s of the tile's mask = the 64-byte segment of lanes 4s .. 4s + 3 holds at least one factor (one scalar load)
   const uint32_t segm = SEG ? a.seg_live[tile] : 0xffffu;
   const bool live8 = !SEG || ((segm >> (lane >> 2)) & 1u) != 0u;
-  float fac[56], cm[28], mu[12], lm[16], cb[44], lb[16];
+  float fac[56], cmr[16], mu[12], lm[16], cb[44], lb[16];
   if (SEG) load_tile_seg<kFacG>(a.fac, tile, lane, live8, fac);
   else load_tile<kFacG>(a.fac, tile, lane, fac);
   // The camera messages: non-temporal like the potentials, or — SweepArgs.cmsg_cached, graphs with few cameras — with the
   // default policy like the landmark messages below (both are rewritten in place by this tile).  The potentials, which an
   // ordinary sweep only reads, keep the hint on every graph: with default-policy loads they cost 3 %.
-  if (SEG) load_tile_seg<kCmsgG, !(POL & kPolCmsgLoadCached)>(a.cmsg, tile, lane, live8, cm);
-  else load_tile<kCmsgG, !(POL & kPolCmsgLoadCached)>(a.cmsg, tile, lane, cm);
+  if (SEG) load_tile_seg<kCmsgG, !(POL & kPolCmsgLoadCached)>(a.cmsg, tile, lane, live8, cmr);
+  else load_tile<kCmsgG, !(POL & kPolCmsgLoadCached)>(a.cmsg, tile, lane, cmr);
   if (!HOIST) load_tile<kMuG>(a.mu, tile, lane, mu);
   // Landmark messages live as 64-byte records in DEVICE (camera-major) order: the wave's 64 records are one
   // contiguous 4 KiB block, moved with four coalesced 1 KiB accesses and transposed through a wave-private
@@ -774,9 +813,13 @@ GBP_DEV void sweep_tile(const SweepArgs& a, const uint32_t wslot) {
     park[lane] = evq0; park[64 + lane] = evq1; park[128 + lane] = evq2; park[192 + lane] = evq3;
   }
 
-  float oc_eta[6], oc_lam[36], ol[16];
+  // the message the record stands for, from the potential as loaded (it needs the two tile streams only: it runs under the gathers)
+  float cm[28];
+  cmsg_expand(fac, cmr, a.cmsg_lit, tile, lane, cm);
+
+  float oc_eta[6], oc_lam[36], bi[9], ol[16];
   bool relin;
-  factor_update<HOIST>(fac, cm, mu, lm, cb, lb, K, a.hp, damping, count, flags, var, active, oc_eta, oc_lam, ol, relin,
+  factor_update<HOIST>(fac, cm, mu, lm, cb, lb, K, a.hp, damping, count, flags, var, active, oc_eta, oc_lam, bi, ol, relin,
                             [&](float (&x0c)[6], float (&x0l)[3], CamLin& cl) {   // rare path: loaded only by relinearising lanes
                               // camera side: the hoisted mean and its CAM_LIN record — per-camera tables (C x 144 B) that live in L2
                               const float4 m0 = a.cam_mu[(size_t)cam_i * 4], m1 = a.cam_mu[(size_t)cam_i * 4 + 1];
@@ -821,15 +864,8 @@ GBP_DEV void sweep_tile(const SweepArgs& a, const uint32_t wslot) {
     }
   }
   {
-    float cmo[28];
-    GBP_UNROLL
-    for (int i = 0; i < 6; ++i) cmo[i] = oc_eta[i];
-    GBP_UNROLL
-    for (int i = 0; i < 6; ++i) {
-      GBP_UNROLL
-      for (int j = 0; j <= i; ++j) cmo[6 + tri(i, j)] = oc_lam[i * 6 + j];
-    }
-    cmo[27] = 0.f;
+    float cmo[16];
+    cmsg_pack(oc_eta, bi, active, cmo);
     if (SEG) store_tile_seg<kCmsgG>(a.cmsg, tile, lane, live8, cmo);
     else store_tile<kCmsgG>(a.cmsg, tile, lane, cmo);
   }
@@ -870,6 +906,22 @@ __global__ __launch_bounds__(256) void k_linearise(const SweepArgs a) {
   load_tile<kFacG>(a.fac, tile, lane, fac);
   load_rec<kCamRec4>(a.camb + (size_t)cam_i * kCamRec4, cb);
   load_rec<kLmkRec4>(a.lmkb + (size_t)lmk_i * kLmkRec4, lb);
+  // The potential is about to change under the factor's camera message, which a kCmsgDerived record derives from it: such a record
+  // is first made literal — its Lambda, from the potential it still holds here, into CMSG_LIT.  (a.cmsg_lit == NULL: no sweep has run
+  // since the upload's zero fill — the shipped flows, LINEARISE right behind WRITE — so no record is derived)
+  if (a.cmsg_lit) {
+    float4* last = a.cmsg + ((size_t)tile * kCmsgG + (kCmsgG - 1)) * 64 + lane;      // Bi[6..8], format word
+    const float4 w3 = *last;
+    if (w3.w == kCmsgDerived) {
+      float rec[16], cm[28], l[kCmsgLitG * 4];
+      load_tile<kCmsgG, false>(a.cmsg, tile, lane, rec);
+      cmsg_expand(fac, rec, nullptr, tile, lane, cm);
+      GBP_UNROLL
+      for (int i = 0; i < kCmsgLitG * 4; ++i) l[i] = i < 21 ? cm[6 + i] : 0.f;
+      store_tile<kCmsgLitG, false>(a.cmsg_lit, tile, lane, l);
+      *last = make_float4(w3.x, w3.y, w3.z, kCmsgLiteral);
+    }
+  }
   GBP_UNROLL
   for (int i = 0; i < 9; ++i) K[i] = a.K[i];
   GBP_UNROLL
@@ -1428,12 +1480,15 @@ GBP_DEV void lm_tile_out(float4* stage, uint32_t lane, Piece&& piece, St&& st) {
   }
 }
 // A tile wave's registers for the whole launch: the potential, the camera messages and — `ld_lm(i4)` = float4 #i4 of LMSG — the
-// landmark messages of tile `tile`
+// landmark messages of tile `tile`.  The camera message stays LITERAL in registers across the iterations: cmsg_expand of the CMSG
+// record once, then each iteration's output; its record is written by the launch's last iteration (tile_cmsg_store)
 template <class LdLm>
 GBP_DEV void tile_regs_load(const SweepArgs& a, uint32_t tile, uint32_t lane, float4* stage, LdLm&& ld_lm, float (&fac)[56], float (&cm)[28],
                             float (&lm)[16]) {
   load_tile<kFacG, false>(a.fac, tile, lane, fac);
-  load_tile<kCmsgG, false>(a.cmsg, tile, lane, cm);
+  float rec[16];
+  load_tile<kCmsgG, false>(a.cmsg, tile, lane, rec);
+  cmsg_expand(fac, rec, a.cmsg_lit, tile, lane, cm);
   lm_tile_in(stage, lane, [&](uint32_t k) { return ld_lm(tile * 256u + k * 64u + lane); }, lm);
 }
 // behind factor_update: the factor's scalar state into the pad slots of its new landmark message ol; both new messages become the
@@ -1454,9 +1509,15 @@ GBP_DEV void tile_regs_refresh(float (&ol)[16], const float (&oc_eta)[6], const 
   }
   cm[27] = 0.f;
 }
+// behind the factor_update of the launch's LAST iteration, where the 3x3 inverse of the new camera message is at hand: the CMSG record
+// the launch leaves (nobody reads the records of the iterations before it: their messages live in cm)
+GBP_DEV void tile_cmsg_store(const SweepArgs& a, uint32_t tile, uint32_t lane, const float (&oc_eta)[6], const float (&bi)[9], bool active) {
+  float rec[16];
+  cmsg_pack(oc_eta, bi, active, rec);
+  store_tile<kCmsgG, false>(a.cmsg, tile, lane, rec);
+}
 // what stayed in registers goes back to its arrays
-GBP_DEV void tile_regs_store(const SweepArgs& a, uint32_t tile, uint32_t lane, const float (&cm)[28], const float (&fac)[56], bool fac_dirty) {
-  store_tile<kCmsgG, false>(a.cmsg, tile, lane, cm);
+GBP_DEV void tile_regs_store(const SweepArgs& a, uint32_t tile, uint32_t lane, const float (&fac)[56], bool fac_dirty) {
   if (fac_dirty) store_tile<kFacG, false>(a.fac, tile, lane, fac);
 }
 // the metric record of a tile wave (DeviceEval slot 1 + wave): its residual sums (zero where the factor is not active) through the lane
@@ -1760,9 +1821,9 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
       uint32_t flags = (uint32_t)packed & 7u;
       const float var = lm[14];
       const bool active = (flags & kFlagActive) != 0;
-      float oc_eta[6], oc_lam[36], ol[16];
+      float oc_eta[6], oc_lam[36], bi[9], ol[16];
       bool relin;
-      factor_update<true>(fac, cm, mu, lm, cb, lb, K, a.hp, damping, count, flags, var, active, oc_eta, oc_lam, ol, relin,
+      factor_update<true>(fac, cm, mu, lm, cb, lb, K, a.hp, damping, count, flags, var, active, oc_eta, oc_lam, bi, ol, relin,
                              [&](float (&x0c)[6], float (&x0l)[3], CamLin& cl) {
                                x0c[0] = m4[0].x; x0c[1] = m4[0].y; x0c[2] = m4[0].z; x0c[3] = m4[1].x; x0c[4] = m4[1].y; x0c[5] = m4[1].z;
                                x0l[0] = u4.x; x0l[1] = u4.y; x0l[2] = u4.z;
@@ -1776,6 +1837,7 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
                              });
       fac_dirty = fac_dirty || (active && relin);
       tile_regs_refresh(ol, oc_eta, oc_lam, damping, count, flags, var, lm, cm);
+      if (last) tile_cmsg_store(a, tile, lane, oc_eta, bi, active);
       // the tagged landmark messages: eta | Lambda row 0 | row 1 | row 2, through the LDS transpose of k_sweep (coalesced stores)
       lm_tile_out(stage, lane,
                   [&](uint32_t q) { return q == 0u ? flow_rec(ol[0], ol[1], ol[2], t_out) : flow_rec(ol[1 + 3 * q], ol[2 + 3 * q], ol[3 + 3 * q], t_out); },
@@ -2085,7 +2147,7 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
       if (!metric_of((uint32_t)it - 1u, ev_packed, ev_c, ev_l0)) return;
   }
 
-  if (has_tile) tile_regs_store(a, tile, lane, cm, fac, fac_dirty);
+  if (has_tile) tile_regs_store(a, tile, lane, fac, fac_dirty);
 
   // ---- the metric of the last iteration; then the launch's ONE barrier: behind it every owner has counted and block 0 hands the
   // health words of every metric of the launch to the host's slots (and leaves them zero) ----

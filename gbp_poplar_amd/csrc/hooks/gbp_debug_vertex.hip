@@ -3,7 +3,7 @@
 // reference's tensor names and layouts.  Included by gbp_kernels.hip inside namespace gbp when the library is built with
 // -DGBP_BUILD_TEST_HOOKS (libgbp_mi355x_test.so); the product library does not contain it.
 //
-// A case is one factor's complete vertex input; the lane packs it into the FAC[56] / CMSG[28] / LMSG[16] / CAMB[44] / LMKB[16] records
+// A case is one factor's complete vertex input; the lane packs it into the FAC[56] / literal camera message [28] / LMSG[16] / CAMB[44] / LMKB[16] records
 // as the upload and the belief kernels lay them out, runs one op and unpacks every output:
 //   op 0  RelineariseFactorVertex (gbp_codelets.cpp:20-172) as k_linearise does it: potential zeroed, belief_means, cam_lin, relin_core
 //   op 1  PrepMessageVertex + the four Compute*Message*Vertex classes (gbp_codelets.cpp:215-710): factor_update<false> (per-factor means)
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(64) void k_debug_vertex(const float* __restrict__ i
   const bool active = __float_as_uint(x[iActive]) == 1u;
   uint32_t flags = (active ? kFlagActive : 0u) | (__float_as_uint(x[iRobust]) != 0u ? kFlagRobust : 0u);
 
-  float oc_eta[6], oc_lam[36], ol[16], mu_out[9];
+  float oc_eta[6], oc_lam[36], bi[9], ol[16], mu_out[9];
   GBP_UNROLL
   for (int i = 0; i < 6; ++i) oc_eta[i] = 0.f;
   GBP_UNROLL
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(64) void k_debug_vertex(const float* __restrict__ i
     damping = 0.f; count = 0;
   } else if (OP == 1) {
     bool relin;
-    factor_update<false>(fac, cm, mu, lm, cb, lb, K, hp, damping, count, flags, var, active, oc_eta, oc_lam, ol, relin,
+    factor_update<false>(fac, cm, mu, lm, cb, lb, K, hp, damping, count, flags, var, active, oc_eta, oc_lam, bi, ol, relin,
                          [&](float (&)[6], float (&)[3], CamLin&) {});
     GBP_UNROLL
     for (int i = 0; i < 9; ++i) mu_out[i] = mu[i];
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(64) void k_debug_vertex(const float* __restrict__ i
     cb[6] = S;
     lb[3] = u[0]; lb[13] = u[1]; lb[14] = u[2];
     bool relin;
-    factor_update<true>(fac, cm, mu, lm, cb, lb, K, hp, damping, count, flags, var, active, oc_eta, oc_lam, ol, relin,
+    factor_update<true>(fac, cm, mu, lm, cb, lb, K, hp, damping, count, flags, var, active, oc_eta, oc_lam, bi, ol, relin,
                         [&](float (&x0c)[6], float (&x0l)[3], CamLin& cl) {      // as sweep_tile hands them to a relinearising lane
                           x0c[0] = m0.x; x0c[1] = m0.y; x0c[2] = m0.z; x0c[3] = m0.w; x0c[4] = m1.x; x0c[5] = m1.y;
                           cam_lin_unpack(q, cl);
@@ -184,6 +184,21 @@ __global__ __launch_bounds__(64) void k_debug_vertex(const float* __restrict__ i
   y[oDamp] = damping;
   y[oCount] = __int_as_float(count);
   y[oRobust] = __uint_as_float((flags & kFlagRobust) != 0u ? 1u : 0u);
+}
+
+// gbp_debug_get(what = 1): the camera messages as the reference stores them, from the CMSG records — cmsg_expand, as every sweep
+// runs it; out[p] = eta 6, Lambda lower triangle 21, 0
+__global__ __launch_bounds__(256) void k_cmsg_expand(const SweepArgs a, float* __restrict__ out) {
+  const uint32_t p = blockIdx.x * 256 + threadIdx.x, tile = p >> 6, lane = p & 63;
+  float fac[56], rec[16], cm[28];
+  load_tile<kFacG, false>(a.fac, tile, lane, fac);
+  load_tile<kCmsgG, false>(a.cmsg, tile, lane, rec);
+  cmsg_expand(fac, rec, a.cmsg_lit, tile, lane, cm);
+  GBP_UNROLL
+  for (int i = 0; i < 28; ++i) out[(size_t)p * 28 + i] = cm[i];
+}
+void launch_cmsg_expand(const SweepArgs& a, uint32_t n_tiles, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_cmsg_expand, dim3(n_tiles / 4), dim3(256), 0, s, a, out);
 }
 
 // reached through debug_math_widths / launch_debug_math (hooks/gbp_debug_math.hip) as ops kDebugVertexOp0 + op

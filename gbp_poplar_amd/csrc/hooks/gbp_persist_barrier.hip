@@ -158,9 +158,9 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
       uint32_t flags = (uint32_t)packed & 7u;
       const float var = lm[14];
       const bool active = (flags & kFlagActive) != 0;
-      float oc_eta[6], oc_lam[36], ol[16];
+      float oc_eta[6], oc_lam[36], bi[9], ol[16];
       bool relin;
-      factor_update<true>(fac, cm, mu, lm, cb, lb, K, a.hp, damping, count, flags, var, active, oc_eta, oc_lam, ol, relin,
+      factor_update<true>(fac, cm, mu, lm, cb, lb, K, a.hp, damping, count, flags, var, active, oc_eta, oc_lam, bi, ol, relin,
                              [&](float (&x0c)[6], float (&x0l)[3], CamLin& cl) {
                                x0c[0] = m0.x; x0c[1] = m0.y; x0c[2] = m0.z; x0c[3] = m0.w; x0c[4] = m1.x; x0c[5] = m1.y;
                                x0l[0] = l0.x; x0l[1] = l0.y; x0l[2] = l0.z;
@@ -168,6 +168,7 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
                              });
       fac_dirty = fac_dirty || (active && relin);
       tile_regs_refresh(ol, oc_eta, oc_lam, damping, count, flags, var, lm, cm);
+      if (it + 1 == A.n_iters) tile_cmsg_store(a, tile, lane, oc_eta, bi, active);
       // the wave's landmark messages go to memory (phase B gathers them by position); this lane keeps its own copy
       lm_tile_out(stage, lane, [&](uint32_t q) { return make_float4(ol[4 * q], ol[4 * q + 1], ol[4 * q + 2], ol[4 * q + 3]); },
                   [&](uint32_t k, float4 v) { X_lmsg.st4(lm_tile4 + k * 64u + lane, v); });
@@ -373,5 +374,5 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
     metric((uint32_t)A.n_iters - 1u, __float_as_int(lm[13]), cmv, lmu);
   }
 
-  if (has_tile) tile_regs_store(a, tile, lane, cm, fac, fac_dirty);
+  if (has_tile) tile_regs_store(a, tile, lane, fac, fac_dirty);
 }
