@@ -96,7 +96,7 @@ struct Options {
   bool verbose = false;
   unsigned long long seed = 0;
   int eval_every = 1;
-  int transport = 0;            // --transport: 0 auto, 1 RCCL, 2 host-staged (ranks sharing a GPU), 3 p2p (direct peer memory)
+  int transport = 0;            // --transport: 0 auto, 1 RCCL, 2 host-staged (ranks sharing a GPU), 3 p2p (direct peer memory), 4 p2p-slices (the same, cameras reduced in slices)
   std::string out_file;         // --out_file: write the refined problem (belief means) in the input's format
   bool force_sharded = false;   // --force_sharded: run the multi-rank code path (fork, shard ctx, communicator) with one rank
 };
@@ -123,7 +123,7 @@ inline void usage(bool slam) {
                "  --v arg (=0)                   Verbose: print beliefs\n"
                "  --seed arg (=0)                seed of the initialisation noise (0 = from the clock)\n"
                "  --eval_every arg (=1)          read back + evaluate every K iterations\n"
-               "  --transport arg (=auto)        exchange between ranks: auto | rccl | host | p2p (host, p2p: ranks may share a GPU)\n"
+               "  --transport arg (=auto)        exchange between ranks: auto | rccl | host | p2p | p2p-slices (host, p2p, p2p-slices: ranks may share a GPU)\n"
                "  --out_file arg                 write the refined cameras / landmarks (belief means) in the input's format\n";
 }
 
@@ -167,7 +167,7 @@ inline int parse(int argc, char** argv, bool slam, Options& o) {
       else if (k == "eval_every") o.eval_every = std::max(1, std::stoi(v));
       else if (k == "force_sharded") o.force_sharded = B(v);
       else if (k == "out_file") o.out_file = v;
-      else if (k == "transport") o.transport = v == "rccl" ? 1 : v == "host" ? 2 : v == "p2p" ? 3 : v == "auto" ? 0 : std::stoi(v);
+      else if (k == "transport") o.transport = v == "rccl" ? 1 : v == "host" ? 2 : v == "p2p" ? 3 : v == "p2p-slices" ? 4 : v == "auto" ? 0 : std::stoi(v);
       else { std::cerr << "unrecognised option '--" << k << "'\n"; return 2; }
     }
   } catch (const std::exception&) {

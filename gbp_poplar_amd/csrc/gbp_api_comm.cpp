@@ -25,8 +25,15 @@ void bind_exchange(gbp_ctx* c) {
   c->send_dev = recv + (size_t)c->rank * c->C * kCamRec;
 }
 
-// p2p: every rank's partials of the LAST exchange, read in place (device table); nullptr for the other transports
+const float* last_own_slot(gbp_ctx* c) {
+  if (!c->comm || !c->comm->sliced() || c->world != 1) return nullptr;
+  return c->comm->exchange_buffer() + (size_t)(c->comm->next_parity() ^ 1) * c->C * kCamRec;
+}
+
+// p2p: every rank's partials of the LAST exchange, read in place (device table); nullptr for the other transports — and for a 1-rank
+// p2p-slices communicator, which launches no peer kernel: its refreshes read last_own_slot() with the plain combine
 const float* const* last_peers(gbp_ctx* c) {
+  if (last_own_slot(c)) return nullptr;
   return c->comm && c->comm->exchange_buffer() ? c->comm->peer_table(c->comm->next_parity() ^ 1) : nullptr;
 }
 
@@ -95,6 +102,39 @@ static int enqueue_sharded_iteration(gbp_ctx* c, const SweepArgs& a) {
       launch_beliefs(b, true, true, c->stream);
     }
     if (x0) HIPCHK(c, hipEventRecord(x0, c->stream));
+    if (c->comm->sliced() && c->world > 1) {
+      // p2p-slices: barrier A behind the partials, the reduce of this rank's slice of the cameras (sums in rank order out of every
+      // peer's partials, the camera chain, once per camera), barrier B behind it, then the gather of the other slices' finished
+      // records — every rank ends with the tables the full combine leaves
+      if (!launch_beliefs_cam_slice || !launch_gather_slices) return fail(c, GBP_ERR_STATE, "no device code for the sliced exchange");
+      const int p = c->comm->next_parity();
+      COMMCHK(c, c->comm->exchange_in_place(c->stream, e_));
+      BeliefArgs b = belief_args(c);
+      b.roll = 1;
+      CamSlice sl;
+      slice_bounds(c->C, c->world, c->rank, &sl.lo, &sl.hi);
+      sl.res = c->comm->result_buffer(p);
+      launch_beliefs_cam_slice(b, c->comm->peer_table(p), sl, c->stream);
+      bind_exchange(c);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      COMMCHK(c, c->comm->barrier(e_));
+      launch_gather_slices(c->comm->result_table(p), b, c->rank, c->stream);
+      HIPCHK(c, hipGetLastError());
+      return GBP_OK;
+    }
+    if (c->comm->sliced()) {
+      // ... with ONE rank: nothing to share — the plain combine over this rank's own slot, no peer kernel
+      const float* mine = static_cast<const float*>(c->send_dev);
+      COMMCHK(c, c->comm->exchange_in_place(c->stream, e_));
+      BeliefArgs b = belief_args(c);
+      b.gathered = mine;
+      b.roll = 1;
+      launch_beliefs(b, true, false, c->stream);
+      bind_exchange(c);
+      HIPCHK(c, hipGetLastError());
+      return GBP_OK;
+    }
     if (c->comm->exchange_buffer()) {
       // p2p: stream sync + ONE region barrier, then the combine reads every rank's partials in place — no gather copy
       if (!launch_beliefs_cam_peers) return fail(c, GBP_ERR_STATE, "no device code for the p2p combine");

@@ -84,7 +84,9 @@ int refresh_beliefs_from_partials(gbp_ctx* c, bool roll, bool do_lmk, bool weake
     HIPCHK(c, hipGetLastError());
     return GBP_OK;
   }
-  if (!exch(c)) {
+  if (const float* own = last_own_slot(c)) {
+    b.gathered = own;      // (recv_dev is the parity of the NEXT exchange)
+  } else if (!exch(c)) {
     b.gathered = P<float>(c->local); b.world = 1;
   } else {
     if (!c->recv_dev) return fail(c, GBP_ERR_STATE, "exchange buffers not set");

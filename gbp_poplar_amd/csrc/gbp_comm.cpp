@@ -231,10 +231,17 @@ class P2pComm : public Comm {
   float** d_tab = nullptr;         // [2][world] device pointer tables
   int parity = 0;
   bool armed = false;              // every rank has set up: teardown meets the others at a barrier
-  ~P2pComm() override {
+  bool quiet = false;              // quiesce() has run
+  // first step of every teardown, once: this rank's work done, then (armed) every rank's — no peer reads this rank's buffers any more
+  void quiesce() {
+    if (quiet) return;
+    quiet = true;
     (void)hipDeviceSynchronize();
     std::string err;
-    if (armed) (void)peer.barrier(err);      // no peer reads X any more
+    if (armed) (void)peer.barrier(err);
+  }
+  ~P2pComm() override {
+    quiesce();
     for (void* p : mapped)
       if (p) (void)hipIpcCloseMemHandle(p);
     if (d_tab) (void)hipFree(d_tab);
@@ -324,6 +331,82 @@ class P2pComm : public Comm {
       for (int r = 0; r < world; ++r) tab[(size_t)p * world + r] = base(r) + ((size_t)p * world + r) * n_floats;
     if (hipMalloc(&d_tab, tab.size() * sizeof(float*)) != hipSuccess) { d_tab = nullptr; err = "p2p: hipMalloc failed"; return false; }
     if (hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(float*), hipMemcpyHostToDevice) != hipSuccess) { err = "p2p: table upload failed"; return false; }
+    if (!peer.barrier(err)) return false;
+    armed = true;
+    return true;
+  }
+};
+
+// ---- sliced peer-memory transport (p2p-slices) ---------------------------------------------------------------------------------------
+// P2pComm (its exchange buffer X, its tables, its all_gather for everything outside the iteration) plus a second IPC-mapped buffer per
+// rank, the RESULT buffer R = [2 parities][widest slice][kCamRes4] float4, written only by its owner.  The cameras are cut into `world`
+// slices (slice_bounds, gbp_kernels.h), rank s owns slice s.  Exchange k of the iteration, parity p = k & 1:
+//   partials into X[p][rank]; stream sync; barrier A (exchange_in_place)
+//   reduce: the owner sums its slice out of every peer's X[p] and writes the finished records into its own R[p]; stream sync; barrier B
+//   gather: every rank copies the other slices out of their owners' R[p]
+// A rank reaches the next barrier, whichever it is, only after its stream has finished everything enqueued before it.  So X[p] is written
+// again (exchange k + 2, behind a barrier of exchange k + 1) only after every rank's reduce k has ended, and R[p] is written again (reduce
+// k + 2, behind barrier A of k + 2) only after every rank's gather k has ended.
+class P2pSlicesComm : public P2pComm {
+ public:
+  size_t res4 = 0;                 // float4 of one parity of R
+  float4* R = nullptr;
+  std::vector<void*> rmapped;      // [world] IPC mappings of the peers' result buffers (nullptr: this rank)
+  float4** d_rtab = nullptr;       // [2][world] device pointer tables: R of rank r, parity p
+  ~P2pSlicesComm() override {
+    quiesce();                     // no peer reads R (or X) any more
+    for (void* p : rmapped)
+      if (p) (void)hipIpcCloseMemHandle(p);
+    if (d_rtab) (void)hipFree(d_rtab);
+    if (R) (void)hipFree(R);
+  }
+  bool sliced() const override { return true; }
+  float4* result_buffer(int p) const override { return R + (size_t)(p & 1) * res4; }
+  const float4* const* result_table(int p) const override { return d_rtab + (size_t)(p & 1) * world; }
+  const char* name() const override { return "p2p-slices"; }
+
+  // collective, behind P2pComm::setup: the same steps for R — handle published in the region's (now idle) handle slots, every peer's
+  // mapping opened and checked with runtime copies before any kernel reads through it
+  bool setup_results(RegionHeader* h, uint32_t n_cams, std::string& err) {
+    armed = false;                 // (a failure below is met by the region's abort flag, not by a teardown barrier)
+    res4 = ((size_t)n_cams + (size_t)world - 1) / (size_t)world * kCamRes4;
+    const size_t bytes = 2 * res4 * sizeof(float4);
+    if (hipMalloc(&R, bytes < 16 ? 16 : bytes) != hipSuccess) { R = nullptr; err = "p2p-slices: hipMalloc of the result buffer failed"; return false; }
+    hipIpcMemHandle_t mine;
+    if (hipIpcGetMemHandle(&mine, R) != hipSuccess) { err = "p2p-slices: hipIpcGetMemHandle failed"; return false; }
+    std::memcpy(h->ipc[rank], &mine, HIP_IPC_HANDLE_SIZE);      // every rank has opened the handles of X: setup() ended with barriers behind that
+    if (!peer.barrier(err)) return false;
+    rmapped.assign(world, nullptr);
+    for (int r = 0; r < world; ++r) {
+      if (r == rank) continue;
+      hipIpcMemHandle_t theirs;
+      std::memcpy(&theirs, h->ipc[r], HIP_IPC_HANDLE_SIZE);
+      if (hipIpcOpenMemHandle(&rmapped[r], theirs, hipIpcMemLazyEnablePeerAccess) != hipSuccess || !rmapped[r]) {
+        rmapped[r] = nullptr;
+        err = "p2p-slices: hipIpcOpenMemHandle of rank " + std::to_string(r) + "'s result buffer failed";
+        return false;
+      }
+    }
+    auto base = [&](int r) { return r == rank ? R : static_cast<float4*>(rmapped[r]); };
+    const uint32_t pat[4] = {~kMagic, (uint32_t)rank, n_cams, (uint32_t)world};      // (~magic: not the pattern of X)
+    if (hipMemcpy(R, pat, sizeof(pat), hipMemcpyHostToDevice) != hipSuccess) { err = "p2p-slices: pattern copy failed"; return false; }
+    if (!peer.barrier(err)) return false;
+    for (int r = 0; r < world; ++r) {
+      if (r == rank) continue;
+      uint32_t got[4] = {0, 0, 0, 0};
+      const uint32_t want[4] = {~kMagic, (uint32_t)r, n_cams, (uint32_t)world};
+      if (hipMemcpy(got, base(r), sizeof(got), hipMemcpyDeviceToHost) != hipSuccess || std::memcmp(got, want, sizeof(got)) != 0) {
+        err = "p2p-slices: the mapping of rank " + std::to_string(r) + "'s result buffer does not hold its pattern";
+        return false;
+      }
+    }
+    if (!peer.barrier(err)) return false;
+    if (hipMemset(R, 0, bytes < 16 ? 16 : bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { err = "p2p-slices: zero-fill failed"; return false; }
+    std::vector<float4*> tab(2 * (size_t)world);
+    for (int p = 0; p < 2; ++p)
+      for (int r = 0; r < world; ++r) tab[(size_t)p * world + r] = base(r) + (size_t)p * res4;
+    if (hipMalloc(&d_rtab, tab.size() * sizeof(float4*)) != hipSuccess) { d_rtab = nullptr; err = "p2p-slices: hipMalloc failed"; return false; }
+    if (hipMemcpy(d_rtab, tab.data(), tab.size() * sizeof(float4*), hipMemcpyHostToDevice) != hipSuccess) { err = "p2p-slices: table upload failed"; return false; }
     if (!peer.barrier(err)) return false;
     armed = true;
     return true;
@@ -421,6 +504,13 @@ Comm* comm_create_from_region(void* region, int rank, int world, int transport, 
     if (!c) { err = "out of memory"; h->abort_flag.store(1); return nullptr; }
     c->rank = rank; c->world = world; c->peer = peer;
     if (!c->setup(h, dev, n_cams, err)) { h->abort_flag.store(1); delete c; return nullptr; }
+    return c;
+  }
+  if (transport == 4) {
+    P2pSlicesComm* c = new (std::nothrow) P2pSlicesComm();
+    if (!c) { err = "out of memory"; h->abort_flag.store(1); return nullptr; }
+    c->rank = rank; c->world = world; c->peer = peer;
+    if (!c->setup(h, dev, n_cams, err) || !c->setup_results(h, n_cams, err)) { h->abort_flag.store(1); delete c; return nullptr; }
     return c;
   }
   const bool use_rccl = transport == 1 || (transport == 0 && !shared);

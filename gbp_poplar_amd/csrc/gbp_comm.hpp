@@ -5,7 +5,7 @@
 // buffer of camera partial sums; one ALL-GATHER per iteration gives every rank all of them, and each rank adds
 // prior + partials in rank order (k_beliefs) — deterministic, bit-identical camera beliefs on all ranks.
 //
-// Three transports behind one interface:
+// Four transports behind one interface:
 //   * RCCL (xGMI): ncclAllGather on a HIP stream — stream-ordered, capturable into the iteration's hipGraph.  librccl
 //     is dlopen'ed on first use (no link-time dependency: a single-GPU user never loads it, and inside a PyTorch
 //     process the already-loaded librccl is reused instead of a second copy).
@@ -15,6 +15,10 @@
 //   * p2p (direct peer memory, asked for explicitly): every rank owns an exchange buffer [2 parities][world][C][44] in its
 //     own device memory, the ranks map each other's through HIP IPC (the same GPU, or peer-accessible GPUs), and a kernel
 //     reads every peer's slot in place after ONE host barrier per exchange.  Not stream-ordered.
+//   * p2p-slices (asked for explicitly): p2p's buffers and rules, but in the iteration every camera is summed ONCE, by the rank that owns
+//     its slice of the cameras, out of the peers' partials; the owner runs the camera chain behind the sum and leaves the finished record
+//     in a second IPC-mapped buffer of its own, from where the other ranks gather it — two host barriers per exchange.
+//     Everything outside the iteration (LINEARISE's exchange, NEW_KEYFRAME's and the prior-only refreshes, gbp_comm_probe) is p2p's.
 // The shared region also carries the rendezvous of a forked launcher (RCCL unique id, per-rank GPU identity, barrier).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -53,6 +57,13 @@ class Comm {
   // the exchange without a copy: synchronise `s`, one region barrier, advance the parity.  Until this rank's next exchange a
   // kernel on `s` may read peer_table(parity of this exchange) in place.
   virtual int exchange_in_place(hipStream_t s, std::string& err) { (void)s; err = "not a peer-memory transport"; return -1; }
+  // ---- the sliced peer-memory transport only ----
+  // true: the iteration reduces every camera once, on the rank that owns its slice (slice_bounds, gbp_kernels.h), and gathers the results
+  virtual bool sliced() const { return false; }
+  // this rank's result buffer, parity p: one record of kCamRes4 float4 per camera of its slice (written by its reduce only)
+  virtual float4* result_buffer(int p) const { (void)p; return nullptr; }
+  // device table of `world` pointers: the result buffer of rank r, parity p (its own for r == rank)
+  virtual const float4* const* result_table(int p) const { (void)p; return nullptr; }
   int rank = 0, world = 1;
 };
 
@@ -66,7 +77,7 @@ int comm_region_init(void* region, size_t bytes, uint32_t n_cams, int world);
 void comm_region_abort(void* region);
 int comm_region_selftest(void* region, int rank, int world, int rounds, std::string& err);   // protocol check, no device   // a supervisor saw a rank die: wake every rank waiting in the region with an error
 // transport: 0 = auto (RCCL when every rank sits on its own GPU, host-staged otherwise), 1 = RCCL, 2 = host-staged,
-// 3 = p2p (never chosen by auto; n_cams: the ctx's cameras, the size of a rank's slot in the p2p exchange buffer)
+// 3 = p2p, 4 = p2p-slices (neither ever chosen by auto; n_cams: the ctx's cameras, the size of a rank's slot in the p2p exchange buffer)
 Comm* comm_create_from_region(void* region, int rank, int world, int transport, uint32_t n_cams, std::string& err);
 
 }  // namespace gbp

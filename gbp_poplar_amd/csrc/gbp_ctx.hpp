@@ -342,6 +342,7 @@ int struct_kind(gbp_ctx* c, const char* fn, const void* const* members, const ch
 int exchange_now(gbp_ctx* c);                               // plain all-gather of the camera partials on the ctx's stream
 int iterate_sharded(gbp_ctx* c, int n);
 void bind_exchange(gbp_ctx* c);                             // p2p: send_dev / recv_dev := the parity of the next exchange
+const float* last_own_slot(gbp_ctx* c);                     // 1-rank p2p-slices: this rank's partials of the last exchange (else nullptr)
 const float* const* last_peers(gbp_ctx* c);                 // p2p: device table of the last exchange's partials (else nullptr)
 
 }  // namespace api

@@ -220,6 +220,20 @@ GBP_HD uint32_t persist_role(uint32_t bid, uint32_t wib, uint32_t nblk, uint32_t
   const uint32_t g = r - n_cams - n_met;
   return g < n_lmk_groups ? n_cams + g : ~0u;                           // no role left for this wave
 }
+// The sliced peer-memory transport (gbp_comm.cpp: p2p-slices) cuts the cameras into `world` contiguous slices, slice s owned by rank s:
+// [*lo, *hi) = [floor(C s / world), floor(C (s + 1) / world)) — consecutive, together exactly [0, C), none wider than ceil(C / world),
+// empty ones when C < world.  Host and device (the gather finds every owner's slice with it).
+GBP_HD void slice_bounds(uint32_t n_cams, int world, int s, uint32_t* lo, uint32_t* hi) {
+  *lo = (uint32_t)((uint64_t)n_cams * (uint64_t)s / (uint64_t)world);
+  *hi = (uint32_t)((uint64_t)n_cams * ((uint64_t)s + 1u) / (uint64_t)world);
+}
+// What an owner leaves per camera of its slice for the other ranks, 18 float4: [0..10] the belief record (CAMB), [11, 12] the hoisted
+// mean (cam_mu[c][0, 1]), [13..17] CAM_LIN.  res: record c - lo of the owner's result buffer (one parity).
+constexpr int kCamRes4 = 18;
+struct CamSlice {
+  uint32_t lo, hi;
+  float4* res;
+};
 // grid of a launch of the persistent kernel for a graph: workgroups, whether the roles are separated, how many metric roles;
 // with_metric: + one wave per camera for the metric roles where the placement allows
 struct PersistGrid { uint32_t nb, separate, n_met; };
@@ -278,6 +292,13 @@ void launch_beliefs(BeliefArgs b, bool do_cam, bool do_lmk, hipStream_t s, bool 
 // device; the callers check for a null launcher.
 [[gnu::weak]] void launch_beliefs_cam_peers(BeliefArgs b, const float* const* peers, hipStream_t s);
 [[gnu::weak]] void launch_gather_peers(const float* const* peers, float* dst, uint32_t n4, int world, int self, hipStream_t s);
+// The sliced peer-memory transport (gbp_comm.cpp: p2p-slices), the two kernels of its iteration (weak for the same reason):
+//   launch_beliefs_cam_slice  launch_beliefs_cam_peers over the cameras [sl.lo, sl.hi) only, every finished camera also written as a
+//                             result record into sl.res (nothing is launched for an empty slice)
+//   launch_gather_slices      the records of every slice but `self`'s out of results[s] (device table of `world` pointers: the result
+//                             buffer of rank s, one parity) into b.camb / b.cam_mu / b.cam_lin (b.n_cams, b.world, b.hoist, b.roll)
+[[gnu::weak]] void launch_beliefs_cam_slice(BeliefArgs b, const float* const* peers, const CamSlice& sl, hipStream_t s);
+[[gnu::weak]] void launch_gather_slices(const float4* const* results, const BeliefArgs& b, int self, hipStream_t s);
 // per-tile records of ring slots [0, n_slots) -> out[slot]: one gbp_eval_out-shaped result per slot (may be mapped host memory)
 void launch_eval_fold(const EvalRide& ev, uint32_t n_slots, void* out, hipStream_t s);
 // sum_eval (gbp_api_eval.cpp) on the device, for gbp_eval_out records that live on the GPU: metric r of n_records = the DeviceEval records

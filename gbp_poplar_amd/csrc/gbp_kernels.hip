@@ -972,8 +972,11 @@ GBP_DEV void cam_mean(REC&& cb, float (&x0c)[6]) {
 // 7, i.e. the 2 000 workgroups of an 8 000-camera graph resident in ONE generation (256 CUs x 8) instead of one and a bit
 // PEERS (with CAM_ONLY): the combine behind the direct peer-memory exchange — partial r straight from peers[r] (rank r's exchange
 // buffer, slot r) instead of b.gathered[r]; the same additions in the same order, so the same bits
-template <bool EV, bool CAM_ONLY = false, bool PEERS = false>
-GBP_DEV void beliefs_body(const BeliefArgs& b, const float* const* __restrict__ peers = nullptr) {
+// SLICE (with PEERS): the reduce of the sliced peer-memory exchange — the launch covers the cameras [sl.lo, sl.hi) only (block 0 starts at
+// camera sl.lo) and, next to this rank's own tables, leaves every finished camera as one result record (CamSlice in gbp_kernels.h) for
+// the other ranks to gather
+template <bool EV, bool CAM_ONLY = false, bool PEERS = false, bool SLICE = false>
+GBP_DEV void beliefs_body(const BeliefArgs& b, const float* const* __restrict__ peers = nullptr, const CamSlice sl = CamSlice{}) {
   __shared__ float sh[4][48];
   __shared__ float lrec[EV ? 64 : 1][13];      // EV: the beliefs of the workgroup's 64 landmarks (eta 3, Lambda 9; 13: bank spread)
   if (EV && blockIdx.x == 0 && threadIdx.x == 0) *b.ev.counter = *b.ev.counter + 1u;     // one more iteration of the burst done (read by the NEXT sweep)
@@ -986,8 +989,9 @@ GBP_DEV void beliefs_body(const BeliefArgs& b, const float* const* __restrict__ 
   if (cam_block) {
     const uint32_t w = threadIdx.x >> 6, j = threadIdx.x & 63;
     const uint32_t cblk = cams_last ? blockIdx.x - b.lmk_blocks : blockIdx.x;
-    const uint32_t c = cblk * 4 + w;
-    const bool live = c < b.n_cams && j < (uint32_t)kCamRec;
+    const uint32_t cam0 = SLICE ? sl.lo : 0u, cam1 = SLICE ? sl.hi : b.n_cams;      // the cameras of this launch
+    const uint32_t c = cam0 + cblk * 4 + w;
+    const bool live = c < cam1 && j < (uint32_t)kCamRec;
     float bel = 0.f;
     if (live) {
       // WeakenPriorVertex (gbp_codelets.cpp:176-197) rides in the belief refresh WEAKEN_PRIORS ends with (ba.cpp:863-865): the
@@ -1079,8 +1083,8 @@ GBP_DEV void beliefs_body(const BeliefArgs& b, const float* const* __restrict__ 
     // single stream (lanes 0..3 of wave 0) instead of issuing it from four wavefronts: with thousands of cameras the
     // camera part is bound by exactly these issue slots (8 000 cameras: 11 -> 4 us).
     if (b.hoist && w == 0 && j < 4) {
-      const uint32_t cj = cblk * 4 + j;
-      if (cj < b.n_cams) {
+      const uint32_t cj = cam0 + cblk * 4 + j;
+      if (cj < cam1) {
         float x0c[6];
         cam_mean(sh[j], x0c);                    // operands straight from LDS: the 44-float copy cost 14 VGPRs of occupancy
         float4* mu = b.cam_mu + (size_t)cj * 4;  // [0,1] = means of the current belief, [2,3] = means the last sweep used
@@ -1100,6 +1104,13 @@ GBP_DEV void beliefs_body(const BeliefArgs& b, const float* const* __restrict__ 
         cam_lin_pack(cl, q);
         GBP_UNROLL
         for (int g = 0; g < kCamLin4; ++g) b.cam_lin[(size_t)cj * kCamLin4 + g] = q[g];
+        if (SLICE) {      // the same registers into the camera's result record: float4 11, 12 = the mean, 13 .. 17 = CAM_LIN
+          float4* res = sl.res + (size_t)(cj - cam0) * kCamRes4 + kCamRec4;
+          res[0] = make_float4(x0c[0], x0c[1], x0c[2], x0c[3]);
+          res[1] = make_float4(x0c[4], x0c[5], 0.f, 0.f);
+          GBP_UNROLL
+          for (int g = 0; g < kCamLin4; ++g) res[2 + g] = q[g];
+        }
       }
     }
     if (EV && (w == 1 || w == 2) && j < 4) {
@@ -1110,8 +1121,8 @@ GBP_DEV void beliefs_body(const BeliefArgs& b, const float* const* __restrict__ 
       // 68 to 96 VGPRs = from 7 to 5 waves per SIMD, which costs the landmark part 1.5 us; measured and worse: the occupancy
       // pinned at 7 (the tableau spills: 20.1 us against 18.3), the tableau in LDS (21.4 - 25.1 us: the camera chain then sets the
       // kernel's length) — profiles/r05_default_loop.md.
-      const uint32_t cj = cblk * 4 + j;
-      if (cj < b.n_cams) {
+      const uint32_t cj = cam0 + cblk * 4 + j;
+      if (cj < cam1) {
         if (w == 1) {
           float xm[6], R[9];
           solve_pivot<6>(sh[j] + 8, 6, sh[j], xm);
@@ -1131,6 +1142,7 @@ GBP_DEV void beliefs_body(const BeliefArgs& b, const float* const* __restrict__ 
     }
     __syncthreads();
     if (live) b.camb[(size_t)c * kCamRec + j] = sh[w][j];
+    if (SLICE && live) reinterpret_cast<float*>(sl.res + (size_t)(c - cam0) * kCamRes4)[j] = sh[w][j];      // float4 0 .. 10 = the belief record
     return;
   }
   if (CAM_ONLY) return;
@@ -1283,6 +1295,46 @@ __global__ __launch_bounds__(256) void k_gather_peers(const float* const* __rest
   const uint32_t r = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
   if ((int)r == self || i >= n4) return;
   reinterpret_cast<float4*>(dst)[(size_t)r * n4 + i] = reinterpret_cast<const float4*>(peers[r])[i];
+}
+// The sliced peer-memory exchange (p2p-slices): the camera sums and the chain behind them run ONCE per camera, on the rank
+// that owns the camera's slice (slice_bounds), and only the finished records travel.
+//   k_beliefs_cam_slice   the reduce: k_beliefs_cam_peers over the cameras of this rank's slice — partial r of those cameras straight from
+//                         peers[r], the same additions in rank order, the same means and CAM_LIN — into this rank's tables AND into its
+//                         result buffer (record c - lo of the parity)
+//   k_gather_slices       the gather: the records of every OTHER slice out of their owners' result buffers (results[s], IPC mappings) into
+//                         this rank's CAMB, hoisted means and CAM_LIN: what the reduce left on the owner, so what k_beliefs_cam_peers would
+//                         have computed here.  grid.y = owner rank, 16 bytes per lane.  "Means used by the last sweep" := this rank's own
+//                         current means (roll), which equal the owner's: every rank held the same tables before the exchange.
+// Both begin with the acquire of the peer readers above; neither waits on another process.
+static_assert(kCamLin4 == 5 && kCamRes4 == kCamRec4 + 2 + kCamLin4, "result record: belief 11 + mean 2 + CAM_LIN 5 float4");
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_beliefs_cam_slice(const BeliefArgs b,
+                                                                                                     const float* const* __restrict__ peers,
+                                                                                                     const CamSlice sl) {
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+  beliefs_body<false, true, true, true>(b, peers, sl);
+}
+__global__ __launch_bounds__(256) void k_gather_slices(const float4* const* __restrict__ results, float4* __restrict__ camb,
+                                                       float4* __restrict__ cam_mu, float4* __restrict__ cam_lin, uint32_t n_cams, int world,
+                                                       int self, int hoist, int roll) {
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+  const int s = (int)blockIdx.y;
+  if (s == self) return;
+  uint32_t lo, hi;
+  slice_bounds(n_cams, world, s, &lo, &hi);
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= (hi - lo) * (uint32_t)kCamRes4) return;
+  const uint32_t c = lo + i / (uint32_t)kCamRes4, k = i % (uint32_t)kCamRes4;
+  if (k >= (uint32_t)kCamRec4 && !hoist) return;      // no hoisted tables on this ctx: the owner wrote none
+  const float4 v = results[s][i];
+  if (k < (uint32_t)kCamRec4) {
+    camb[(size_t)c * kCamRec4 + k] = v;
+  } else if (k < (uint32_t)kCamRec4 + 2u) {
+    float4* mu = cam_mu + (size_t)c * 4 + (k - kCamRec4);
+    if (roll) mu[2] = mu[0];
+    mu[0] = v;
+  } else {
+    cam_lin[(size_t)c * kCamLin4 + (k - kCamRec4 - 2u)] = v;
+  }
 }
 
 // =================================================================================================
@@ -2573,6 +2625,19 @@ void launch_beliefs_cam_peers(BeliefArgs b, const float* const* peers, hipStream
 void launch_gather_peers(const float* const* peers, float* dst, uint32_t n4, int world, int self, hipStream_t s) {
   if (n4 == 0 || world < 2) return;
   hipLaunchKernelGGL(k_gather_peers, dim3((n4 + 255) / 256, (uint32_t)world), dim3(256), 0, s, peers, dst, n4, self);
+}
+void launch_beliefs_cam_slice(BeliefArgs b, const float* const* peers, const CamSlice& sl, hipStream_t s) {
+  b.cam_blocks = (sl.hi - sl.lo + 3) / 4;
+  b.lmk_blocks = 0;
+  b.gathered = nullptr;
+  if (sl.hi <= sl.lo) return;      // an empty slice (fewer cameras than ranks)
+  hipLaunchKernelGGL(k_beliefs_cam_slice, dim3(b.cam_blocks), dim3(256), 0, s, b, peers, sl);
+}
+void launch_gather_slices(const float4* const* results, const BeliefArgs& b, int self, hipStream_t s) {
+  if (b.n_cams == 0 || b.world < 2) return;
+  const uint32_t widest = (b.n_cams + (uint32_t)b.world - 1) / (uint32_t)b.world;      // no slice holds more cameras (slice_bounds)
+  hipLaunchKernelGGL(k_gather_slices, dim3((widest * kCamRes4 + 255) / 256, (uint32_t)b.world), dim3(256), 0, s, results,
+                     reinterpret_cast<float4*>(b.camb), b.cam_mu, b.cam_lin, b.n_cams, b.world, self, b.hoist, b.roll);
 }
 void launch_eval_ride(const EvalRide& ev, const uint32_t* row_cam, const uint32_t* lmk_idx, const float4* lmsg, const float4* fac, const float* K9_dev, hipStream_t s) {
   hipLaunchKernelGGL(k_eval_ride, dim3(ev.n_tiles / 4), dim3(256), 0, s, ev, row_cam, lmk_idx, lmsg, fac, K9_dev);

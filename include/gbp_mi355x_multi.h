@@ -53,6 +53,12 @@ GBP_API int gbp_linearise_factors(gbp_ctx* ctx);  /* the factor half of LINEARIS
  * through host memory), one host barrier per exchange, not stream-ordered (the iteration is not captured into a hipGraph).  Ranks on
  * GPUs that cannot access each other make gbp_comm_init fail with GBP_ERR_COMM; while the communicator lives, gbp_set_exchange_buffers
  * is refused (the exchange buffers are the communicator's).
+ * 4 = p2p-slices (never chosen by auto): p2p's buffers and every rule above, but inside the iteration the cameras are cut into `world`
+ * contiguous slices and rank s alone sums slice s — out of every rank's partials, in rank order — and runs the camera chain behind the
+ * sum (means, Jacobian terms); the finished records lie in a second IPC-mapped buffer of the owner's, from where the other ranks
+ * gather them: two host barriers per exchange, a third of p2p's bytes at 8 ranks, the same bits.  Outside the iteration
+ * (gbp_linearise's exchange, gbp_new_keyframe's and the prior-only refreshes, gbp_comm_probe) it uses p2p's full peer gather unchanged;
+ * gbp_comm_set_schedule has no effect on either.
  * Launchers with their own rendezvous (torchrun, MPI) pass the 128-byte RCCL id around themselves:
  * gbp_comm_unique_id on rank 0, gbp_comm_init_rccl on every rank.  All calls are collective over the ranks.
  * Scheduling: with 4 ranks or more the camera side of the exchange (local partial sums, all-gather) runs on a second,
@@ -72,7 +78,7 @@ GBP_API int gbp_comm_region_selftest(void* region, int rank, int world, int roun
 GBP_API int gbp_comm_init(gbp_ctx* ctx, void* region, int transport);
 GBP_API int gbp_comm_unique_id(void* id128);
 GBP_API int gbp_comm_init_rccl(gbp_ctx* ctx, const void* id128);
-GBP_API const char* gbp_comm_transport(const gbp_ctx* ctx);            /* "rccl", "host-staged", "p2p" or "none" */
+GBP_API const char* gbp_comm_transport(const gbp_ctx* ctx);            /* "rccl", "host-staged", "p2p", "p2p-slices" or "none" */
 GBP_API int gbp_comm_barrier(gbp_ctx* ctx);
 /* What a first multi-GPU run puts on record next to its numbers (bench.py's preflight block): gbp_comm_describe writes one
  * JSON object (rank, world, device, PCI bus id, transport, the collective library's resolved path and version, schedule);
