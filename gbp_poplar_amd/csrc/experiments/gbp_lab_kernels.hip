@@ -32,42 +32,18 @@ GBP_DEV void lab_sweep_tile(const SweepArgs& a, const uint32_t wslot) {
   // ordinary sweep only reads, keep the hint on every graph: with default-policy loads they cost 3 %.
   load_tile<kCmsgG>(a.cmsg, tile, lane, cmr);
   if (!true) load_tile<kMuG>(a.mu, tile, lane, mu);
-  // Landmark messages live as 64-byte records in DEVICE (camera-major) order: the wave's 64 records are one
-  // contiguous 4 KiB block, moved with four coalesced 1 KiB accesses and transposed through a wave-private
-  // LDS staging area.  Piece q of record r sits at float4 slot r*4 + (q ^ swz(r)), swz(r) = ((r>>2)&3) ^ (r&2):
-  // a permutation inside each 64-B record, so the tile-order accesses (whole records) and the record-order
-  // accesses (one piece per lane) are both bank-conflict-free for ds_read_b128 (16-lane groups, 64 banks)
-  // and ds_write_b128 (8-lane groups, 32 banks).  k_beliefs gathers the records of a landmark by position
-  // (random 64-B READS are ~2.3x cheaper than random 64-B writes: measured, profiles/HISTORY.md).
-  __shared__ float4 lm_stage[kWpb][64 * 4];
+  // Landmark messages and the state planes as sweep_tile moves them (lmsg_tile_in / lmsg_tile_out)
+  __shared__ float4 lm_stage[kWpb][64 * kLmsgG];
   float4* stage = lm_stage[threadIdx.x >> 6];
-  const uint32_t rec_t = lane >> 2;                                   // record handled in tile order (+16k)
-  const uint32_t swz_own = ((lane >> 2) & 3u) ^ (lane & 2u);          // swizzle of the lane's own record
-  float4* lm_tile = a.lmsg + (size_t)tile * 256;
+  float4* lm_tile = a.lmsg + (size_t)tile * (64 * kLmsgG);
+  GBP_UNROLL
+  for (int i = 0; i < 16; ++i) lm[i] = 0.f;
   if (LAB & (1 | 16)) {  // no landmark-message load: a plausible active record
-    GBP_UNROLL
-    for (int i = 0; i < 16; ++i) lm[i] = 0.f;
     lm[13] = __int_as_float((int)((5u << 3) | kFlagActive));
     lm[14] = 4.f;
   } else {
-  GBP_UNROLL
-  for (int k = 0; k < 4; ++k) {
-    // (DEFAULT policy for this one stream unless the shape says otherwise: the tile is rewritten in place ten microseconds later
-    // and gathered by k_beliefs right after the sweep — measured +1.5 % iterations/s on the 1M-factor graph against the
-    // non-temporal hint, with either store policy; the potentials keep the hint on every graph)
-    const v4f* src = reinterpret_cast<const v4f*>(lm_tile) + k * 64 + lane;
-    const v4f v = *src;
-    const uint32_t r = k * 16 + rec_t;
-    stage[r * 4 + ((lane & 3u) ^ (((r >> 2) & 3u) ^ (r & 2u)))] = make_float4(v.x, v.y, v.z, v.w);
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  GBP_UNROLL
-  for (int q = 0; q < 4; ++q) {
-    const float4 v = stage[lane * 4 + ((uint32_t)q ^ swz_own)];
-    lm[4 * q] = v.x; lm[4 * q + 1] = v.y; lm[4 * q + 2] = v.z; lm[4 * q + 3] = v.w;
-  }
+    lm[3] = a.fst_damp[p]; lm[13] = __int_as_float(a.fst_packed[p]);
+    lmsg_tile_in(stage, lane, [&](uint32_t k) { return lm_tile[k * 64u + lane]; }, lm);
   }
   load_rec<kCamRec4>(a.camb + (size_t)cam_i * kCamRec4, cb);
   if (LAB & 2) {         // no landmark-belief gather: the identity
@@ -76,9 +52,9 @@ GBP_DEV void lab_sweep_tile(const SweepArgs& a, const uint32_t wslot) {
   } else {
     load_rec<kLmkRec4>(a.lmkb + (size_t)lmk_i * kLmkRec4, lb);
   }
-  // per-factor scalar state rides in the pad slots of the landmark-message record (read and rewritten
-  // every sweep anyway): [3] damping, [13] (damping_count << 3) | flags, [14] measurement variance
+  // per-factor scalar state (in the register image's pad slots here): [3] damping, [13] (damping_count << 3) | flags, [14] variance
   float damping = lm[3];
+  const float damping_in = damping;
   const int packed = __float_as_int(lm[13]);
   int count = packed >> 3;
   uint32_t flags = (uint32_t)packed & 7u;
@@ -104,7 +80,8 @@ GBP_DEV void lab_sweep_tile(const SweepArgs& a, const uint32_t wslot) {
     for (int i = 0; i < 9; ++i) bi[i] = cmr[6 + i] + fac[45 + i];
   } else
   factor_update<true>(fac, cm, mu, lm, cb, lb, K, a.hp, damping, count, flags, var, active, oc_eta, oc_lam, bi, ol, relin,
-                            [&](float (&x0c)[6], float (&x0l)[3], CamLin& cl) {   // rare path: loaded only by relinearising lanes
+                            [&](float (&x0c)[6], float (&x0l)[3], CamLin& cl, float& var_r) {   // rare path: loaded only by relinearising lanes
+                              if (!(LAB & (1 | 16))) var_r = a.fst_var[p];
                               // camera side: the hoisted mean and its CAM_LIN record — per-camera tables (C x 144 B) that live in L2
                               const float4 m0 = a.cam_mu[(size_t)cam_i * 4], m1 = a.cam_mu[(size_t)cam_i * 4 + 1];
                               float4 q[kCamLin4];
@@ -120,24 +97,10 @@ GBP_DEV void lab_sweep_tile(const SweepArgs& a, const uint32_t wslot) {
                             });
 
   // ---- outputs --------------------------------------------------------------------------------
-  ol[3] = damping;
-  ol[13] = __int_as_float((int)(((uint32_t)count << 3) | flags));
-  ol[14] = var;
   if (!(LAB & (1 | 32))) {   // (32: no landmark-message store)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  GBP_UNROLL
-  for (int q = 0; q < 4; ++q)
-    stage[lane * 4 + ((uint32_t)q ^ swz_own)] = make_float4(ol[4 * q], ol[4 * q + 1], ol[4 * q + 2], ol[4 * q + 3]);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  GBP_UNROLL
-  for (int k = 0; k < 4; ++k) {
-    const uint32_t r = k * 16 + rec_t;
-    const float4 f = stage[r * 4 + ((lane & 3u) ^ (((r >> 2) & 3u) ^ (r & 2u)))];
-    lm_tile[k * 64 + lane] = f;
-  }
+    lmsg_tile_out(stage, lane, ol, [&](uint32_t k, float4 f) { lm_tile[k * 64u + lane] = f; });
+    a.fst_packed[p] = (int)(((uint32_t)count << 3) | flags);
+    if (__builtin_amdgcn_ballot_w64(__float_as_uint(damping) != __float_as_uint(damping_in)) != 0ull) a.fst_damp[p] = damping;
   }
   {
     float cmo[16];
@@ -278,7 +241,15 @@ __global__ __launch_bounds__(256) void k_sweep_coop16(const SweepArgs a) {
     int dst = -1;
     if (i < 14) { v = a.fac[((size_t)tile * kFacG + i) * 64 + lt]; dst = kF + 4 * i; }
     else if (i < 21) { }                 // (the camera message: expanded below)
-    else if (i < 25) { v = a.lmsg[(size_t)p * 4 + (i - 21)]; dst = kLm + 4 * (i - 21); }
+    else if (i < 24) {                   // the landmark message: dense float j of LMSG -> slot j (eta) / j + 1 (Lambda) of the 16-float image
+      const float4 d = a.lmsg[(size_t)p * kLmsgG + (i - 21)];
+      const float dv[4] = {d.x, d.y, d.z, d.w};
+      GBP_UNROLL
+      for (int c = 0; c < 4; ++c) { const int j = 4 * (i - 21) + c; w[kLm + (j < 3 ? j : j + 1)] = dv[c]; }
+    }
+    else if (i < 25) {                   // ... and the factor's scalars from their planes into its pad slots
+      w[kLm + 3] = a.fst_damp[p]; w[kLm + 13] = __int_as_float(a.fst_packed[p]); w[kLm + 14] = a.fst_var[p]; w[kLm + 15] = 0.f;
+    }
     else if (i < 36) { v = a.camb[(size_t)cam_i * kCamRec4 + (i - 25)]; dst = kCb + 4 * (i - 25); }
     else if (i < 40) { v = a.lmkb[(size_t)lmk_i * kLmkRec4 + (i - 36)]; dst = kLb + 4 * (i - 36); }
     if (dst >= 0) { w[dst] = v.x; w[dst + 1] = v.y; w[dst + 2] = v.z; w[dst + 3] = v.w; }
@@ -441,8 +412,14 @@ __global__ __launch_bounds__(256) void k_sweep_coop16(const SweepArgs a) {
     out[14] = var;
   }
   sync();
-  // ---- stores: landmark-message record (64 B), camera message (the CMSG record: eta, Bi, format word), potential if relinearised ----
-  if (t < 4) a.lmsg[(size_t)p * 4 + t] = make_float4(out[4 * t], out[4 * t + 1], out[4 * t + 2], out[4 * t + 3]);
+  // ---- stores: landmark message (48 B) and the two mutable state planes, camera message (the CMSG record: eta, Bi, format word), potential if relinearised ----
+  if (t < (uint32_t)kLmsgG) {
+    float d[4];
+    GBP_UNROLL
+    for (int c = 0; c < 4; ++c) { const int j = 4 * (int)t + c; d[c] = out[j < 3 ? j : j + 1]; }
+    a.lmsg[(size_t)p * kLmsgG + t] = make_float4(d[0], d[1], d[2], d[3]);
+  }
+  if (t == 3) { a.fst_damp[p] = out[3]; a.fst_packed[p] = __float_as_int(out[13]); }
   if (t < 4) {
     float c4[4];
     GBP_UNROLL

@@ -373,17 +373,14 @@ GBP_EXPORT(gbp_create, nullptr, (const gbp_problem* pr, const gbp_params* prm, c
                     {&c->d_cam_row_ptr, y.cam_row_ptr.data(), (size_t)(C + 1) * 4, 0}, {&c->d_lmk_ptr, y.lmk_ptr.data(), (size_t)(c->L_loc + 1) * 4, 0},
                     {&c->d_row_slot, y.row_slot.data(), y.row_slot.size() * 4, 0}, {&c->dK, c->K, 9 * 4, 0},
                     {&c->tile_perm, y.tile_perm.data(), y.tile_perm.size() * 4, 0}, {&c->seg_live, nullptr, 0, 0}};
-  // Which 64-byte segments (four positions) of a tile hold a factor at all?  A camera is padded to whole rows of 16: the tail of its
+  // Which segments (four positions) of a tile hold a factor at all?  A camera is padded to whole rows of 16: the tail of its
   // last row is empty — on a graph of many small cameras (BASELINE config 5: ~156 factors per camera and rank) the all-pad segments
   // are 3.7 % of all positions, which the sweep then neither streams in nor out (k_sweep<..., SEG>).  Used where it is worth a kernel
   // of its own: at least 1 % of the positions, a graph that runs on the two-kernel path with the default cache policy.
   std::vector<uint32_t> seg_live(y.n_tiles, 0u);
   size_t dead = 0;
   for (size_t t = 0; t < y.n_tiles; ++t) {
-    uint32_t m = 0;
-    for (uint32_t sgi = 0; sgi < 16; ++sgi)
-      for (uint32_t k = 0; k < 4; ++k)
-        if (y.pos_edge[t * 64 + sgi * 4 + k] != kNoEdge) { m |= 1u << sgi; break; }
+    const uint32_t m = tile_seg_mask(&y.pos_edge[t * 64]);
     seg_live[t] = m;
     dead += 16u - (uint32_t)__builtin_popcount(m);
   }
@@ -398,7 +395,7 @@ GBP_EXPORT(gbp_create, nullptr, (const gbp_problem* pr, const gbp_params* prm, c
   for (Piece& pc : pieces) { pc.b->p = rc == GBP_OK ? static_cast<char*>(c->idx_arena.p) + pc.off : nullptr; pc.b->bytes = pc.bytes; }      // views: freed with the arena
   A(c->fac, Ep * kFacG * 16); A(c->cmsg, Ep * kCmsgG * 16);
   A(c->mu, c->hoist ? 0 : Ep * kMuG * 16);   // literal mu/oldmu tensor: only with per_factor_mu
-  A(c->lmsg, Ep * 64);
+  A(c->lmsg, Ep * kLmsgG * 16); A(c->fst_packed, Ep * 4); A(c->fst_damp, Ep * 4); A(c->fst_var, Ep * 4);
   A(c->camb, (size_t)C * kCamRec * 4); A(c->camp, (size_t)C * kCamRec * 4); A(c->local, (size_t)C * kCamRec * 4);
   A(c->lmkb, (size_t)c->L_loc * 64); A(c->lmkp, (size_t)c->L_loc * 64);
   A(c->rowp, (Ep / kRow) * kCamRec * 4);
@@ -512,7 +509,7 @@ GBP_EXPORT(gbp_upload, c, (gbp_ctx* c, const gbp_state_in* in), (c, in)) {
   lap("argument checks, stream sync, persistent-kernel reset");
   const size_t Ep = c->Ep;
   // The per-factor streams in their compact form, in device order: {damping, count << 3 | flags, z0, z1} + the variance = 20 bytes per
-  // position.  k_upload_scatter writes them into the records they belong to (the whole 64-byte LMSG record: zero messages + state; the
+  // position.  k_upload_scatter writes them into the records they belong to (the zero message of LMSG and the three state planes; the
   // measurement slots of the FAC tile, the other 216 bytes per position zeroed on the device) — 288 bytes per position used to be built on
   // the host and cross PCIe: 0.11 s of a `bin/ba` run on a file of 10^6 factors (profiles/r06_configs.md section 2).
   struct St { float damping; int32_t packed; float z0, z1; };
@@ -569,7 +566,11 @@ GBP_EXPORT(gbp_upload, c, (gbp_ctx* c, const gbp_state_in* in), (c, in)) {
       if (e2 != hipSuccess) { (void)hipFree(tmp.p); HIPCHK(c, e2); }
       st_dev = static_cast<const float4*>(tmp.p); var_dev = reinterpret_cast<const float*>(static_cast<char*>(tmp.p) + Ep * 16);
     }
-    launch_upload_scatter(P<float4>(c->lmsg), P<float4>(c->fac), st_dev, var_dev, (uint32_t)Ep, c->stream);
+    if (!launch_upload_scatter_fst) {
+      if (tmp.p) (void)hipFree(tmp.p);
+      return fail(c, GBP_ERR_STATE, "gbp_upload: no device code");
+    }
+    launch_upload_scatter_fst(P<float4>(c->lmsg), factor_state(c), P<float4>(c->fac), st_dev, var_dev, (uint32_t)Ep, c->stream);
     const hipError_t le = hipGetLastError();
     if (tmp.p) { (void)hipStreamSynchronize(c->stream); (void)hipFree(tmp.p); }
     HIPCHK(c, le);
@@ -626,18 +627,12 @@ GBP_EXPORT(gbp_read, c, (gbp_ctx* c, gbp_state_out* o), (c, o)) {
   const bool want_state = o->damping || o->damping_count || o->robust_flag;
   std::vector<float> rec_c(want_cam ? (size_t)c->C * kCamRec : 0), rec_l(want_lmk ? (size_t)c->L_loc * 16 : 0), damp(want_state ? c->Ep : 0);
   std::vector<int32_t> packed(want_state ? c->Ep : 0);
-  if (want_state) {
-    // per-factor scalars ride in the message records: a small kernel extracts them into two compact arrays
-    launch_state_get(P<float4>(c->lmsg), P<float>(c->st_a), P<int>(c->st_b), c->Ep, c->stream);
-    HIPCHK(c, hipGetLastError());
-  }
-  D2H down;
+  D2H down;      // (the per-factor scalars: their planes as they are, FST_DAMP and FST_PACKED)
   if (int rc = down.begin(c, (rec_c.size() + rec_l.size() + damp.size() + packed.size()) * 4, 4)) return rc;
-  if (want_state && down.up.direct) HIPCHK(c, hipStreamSynchronize(c->stream));      // (a large graph: the copies below are blocking hipMemcpy calls, which do not order against the ctx's stream)
   if (int rc = down.get(rec_c.data(), c->camb.p, rec_c.size() * 4)) return rc;
   if (int rc = down.get(rec_l.data(), c->lmkb.p, rec_l.size() * 4)) return rc;
-  if (int rc = down.get(damp.data(), c->st_a.p, damp.size() * 4)) return rc;
-  if (int rc = down.get(packed.data(), c->st_b.p, packed.size() * 4)) return rc;
+  if (int rc = down.get(damp.data(), c->fst_damp.p, damp.size() * 4)) return rc;
+  if (int rc = down.get(packed.data(), c->fst_packed.p, packed.size() * 4)) return rc;
   if (int rc = down.end()) return rc;
   if (want_cam) {
     const std::vector<float>& rec = rec_c;
@@ -735,7 +730,8 @@ GBP_EXPORT(gbp_new_keyframe, c, (gbp_ctx* c, const gbp_kf_update* u), (c, u)) {
     if (int rc = up.put(c->st_b.p, cnt.data(), (size_t)c->Ep * 4)) return rc;
     if (int rc = up.put(c->st_a.p, ctl.data(), (size_t)c->Ep * 4)) return rc;
     if (int rc = up.end()) return rc;
-    launch_state_set(P<float4>(c->lmsg), P<int>(c->st_b), P<uint32_t>(c->st_a), c->Ep, c->stream);
+    if (!launch_fst_set) return fail(c, GBP_ERR_STATE, "gbp_new_keyframe: no device code");
+    launch_fst_set(P<int>(c->fst_packed), P<int>(c->st_b), P<uint32_t>(c->st_a), c->Ep, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (u->active_flag)

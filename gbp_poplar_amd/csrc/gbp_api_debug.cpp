@@ -10,9 +10,10 @@ using namespace gbp;
 using namespace gbp::api;
 
 namespace {
-int download_lmsg(gbp_ctx* c, std::vector<float>& rec) {
-  rec.resize((size_t)c->Ep * 16);
-  HIPCHK(c, hipMemcpy(rec.data(), c->lmsg.p, rec.size() * 4, hipMemcpyDeviceToHost));
+// LMSG as it lies in memory: kLmsgG * 4 = 12 floats per device position (eta 3, Lambda 9)
+int download_lmsg(gbp_ctx* c, std::vector<float>& msg) {
+  msg.resize((size_t)c->Ep * kLmsgG * 4);
+  HIPCHK(c, hipMemcpy(msg.data(), c->lmsg.p, msg.size() * 4, hipMemcpyDeviceToHost));
   return GBP_OK;
 }
 }  // namespace
@@ -61,26 +62,26 @@ GBP_EXPORT(gbp_debug_get, c, (gbp_ctx* c, int what, float* a, float* b), (c, wha
         b[(size_t)e * 36 + i * 6 + j] = (i >= j) ? f[p * 28 + 6 + tri(i, j)] : 0.f;
     }
   } else if (what == 2) {
-    std::vector<float> f((size_t)c->Ep * 16);
-    HIPCHK(c, hipMemcpy(f.data(), c->lmsg.p, f.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<float> f;
+    if (int rc = download_lmsg(c, f)) return rc;
     for (size_t p = 0; p < c->Ep; ++p) {
       const uint32_t e = c->lay.pos_edge[p];
       if (e == ~0u) continue;
-      const float* r = &f[p * 16];
+      const float* r = &f[p * kLmsgG * 4];
       for (int i = 0; i < 3; ++i) a[(size_t)e * 3 + i] = r[i];
-      for (int i = 0; i < 9; ++i) b[(size_t)e * 9 + i] = r[4 + i];
+      for (int i = 0; i < 9; ++i) b[(size_t)e * 9 + i] = r[3 + i];
     }
   } else if (what == 3 && c->hoist) {
     // hoisted mode: mu of a factor = the per-variable means its last sweep used; dmu is not kept per factor
     std::vector<float> mc((size_t)c->C * 16), ml((size_t)c->L_loc * 8);
     HIPCHK(c, hipMemcpy(mc.data(), c->hmu_c.p, mc.size() * 4, hipMemcpyDeviceToHost));
     if (c->L_loc) HIPCHK(c, hipMemcpy(ml.data(), c->hmu_l.p, ml.size() * 4, hipMemcpyDeviceToHost));
-    std::vector<float> rec;
-    if (int rc = download_lmsg(c, rec)) return rc;
+    std::vector<int32_t> packed(c->Ep);
+    HIPCHK(c, hipMemcpy(packed.data(), c->fst_packed.p, packed.size() * 4, hipMemcpyDeviceToHost));
     for (size_t p = 0; p < c->Ep; ++p) {
       const uint32_t e = c->lay.pos_edge[p];
       if (e == ~0u) continue;
-      if (!(get_state(rec, p).flags & kFlagActive)) continue;  // inactive factors never update mu (gbp_codelets.cpp:242)
+      if (!((uint32_t)packed[p] & kFlagActive)) continue;  // inactive factors never update mu (gbp_codelets.cpp:242)
       for (int i = 0; i < 6; ++i) a[(size_t)e * 9 + i] = mc[(size_t)c->lay.pos_cam[p] * 16 + 8 + i];
       for (int i = 0; i < 3; ++i) a[(size_t)e * 9 + 6 + i] = ml[(size_t)c->lay.pos_lmk_loc[p] * 8 + 4 + i];
       b[e] = 0.f;
@@ -133,7 +134,8 @@ GBP_EXPORT(gbp_debug_time_sweep, c, (gbp_ctx* c, int ablation, int reps, double*
 }
 
 // ---- the device order without a device (gbp_layout.cpp): what gbp_create builds, handed out for CPU property tests ----
-struct gbp_layout { Layout y; };
+// (lmsg_maps, lmsg_live: gbp_debug_layout_array 11, 12 — the address maps of a tile's landmark messages evaluated on the host)
+struct gbp_layout { Layout y; std::vector<uint32_t> lmsg_maps, lmsg_live; };
 static LayoutOptions to_options(const gbp_layout_options* o) {
   LayoutOptions r;
   if (o) {
@@ -247,6 +249,26 @@ GBP_EXPORT(gbp_debug_layout_array, nullptr, (const gbp_layout* h, int which, con
   const Layout& y = h->y;
   const std::vector<uint32_t>* a[11] = {&y.pos_edge, &y.pos_cam, &y.pos_lmk_loc, &y.pos_lpos, &y.cam_row_ptr, &y.row_slot, &y.row_cam,
                                         &y.lmk_ptr, &y.lmk_fpos, &y.lmk_ix, &y.tile_perm};
+  // 11, 12: the address maps of a tile's landmark messages (gbp_kernels.h), as the kernels evaluate them, for every float4 index i4 of a
+  // tile's kLmsgG * 64: 11 = [i4]{record, piece, lmsg_tile_i4(record, piece), lmsg_lds_slot(record, piece)};  12 = [tile][i4] 1 where
+  // lmsg_seg_live(the tile's segment mask as gbp_create derives it, i4), else 0
+  if (which == 11 || which == 12) {
+    gbp_layout* m = const_cast<gbp_layout*>(h);
+    const uint32_t n4 = (uint32_t)kLmsgG * 64u;
+    if (m->lmsg_maps.empty()) {
+      for (uint32_t i4 = 0; i4 < n4; ++i4) {
+        const uint32_t r = lmsg_tile_rec(i4), q = lmsg_tile_piece(i4);
+        for (uint32_t v : {r, q, lmsg_tile_i4(r, q), lmsg_lds_slot(r, q)}) m->lmsg_maps.push_back(v);
+      }
+      for (size_t t = 0; t < y.n_tiles; ++t) {
+        const uint32_t mask = tile_seg_mask(&y.pos_edge[t * 64]);
+        for (uint32_t i4 = 0; i4 < n4; ++i4) m->lmsg_live.push_back(lmsg_seg_live(mask, i4) ? 1u : 0u);
+      }
+    }
+    const std::vector<uint32_t>& v = which == 11 ? m->lmsg_maps : m->lmsg_live;
+    *data = v.data(); *n = v.size();
+    return GBP_OK;
+  }
   if (which < 0 || which > 10) return GBP_ERR_INVALID;
   *data = a[which]->data(); *n = a[which]->size();
   return GBP_OK;

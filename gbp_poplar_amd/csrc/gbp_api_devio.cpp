@@ -60,7 +60,7 @@ int devio_upload(gbp_ctx* c, const gbp_state_in* in) {
   a.damping = in->damping; a.damping_count = in->damping_count; a.active_flag = in->active_flag;
   a.measurements = in->measurements; a.meas_variances = in->meas_variances;
   a.om = in->oldmu ? in->oldmu : in->mu;
-  a.lmsg = P<float4>(c->lmsg); a.fac = P<float4>(c->fac);
+  a.lmsg = P<float4>(c->lmsg); a.fs = factor_state(c); a.fac = P<float4>(c->fac);
   a.mu = c->hoist ? nullptr : P<float4>(c->mu);
   a.n = c->Ep;
   launch_upload_dev(a, c->stream);
@@ -89,7 +89,7 @@ int devio_read(gbp_ctx* c, gbp_state_out* o) {
   if (int rc = settle(c)) return rc;
   if (o->damping || o->damping_count || o->robust_flag) {
     if (int rc = need_pos_edge(c)) return rc;
-    launch_read_state_dev(P<uint32_t>(c->d_pos_edge), P<float4>(c->lmsg), o->damping, o->damping_count, o->robust_flag, c->Ep, c->stream);
+    launch_read_state_dev(P<uint32_t>(c->d_pos_edge), factor_state(c), o->damping, o->damping_count, o->robust_flag, c->Ep, c->stream);
     HIPCHK(c, hipGetLastError());
   }
   RecSegs t{};
@@ -123,7 +123,7 @@ int devio_new_keyframe(gbp_ctx* c, const gbp_kf_update* u) {
   if (int rc = settle(c)) return rc;
   if (u->damping_count || u->active_flag) {
     if (int rc = need_pos_edge(c)) return rc;
-    launch_keyframe_state_dev(P<uint32_t>(c->d_pos_edge), P<float4>(c->lmsg), u->damping_count, u->active_flag, c->Ep, c->stream);
+    launch_keyframe_state_dev(P<uint32_t>(c->d_pos_edge), P<int>(c->fst_packed), u->damping_count, u->active_flag, c->Ep, c->stream);
     HIPCHK(c, hipGetLastError());
     if (u->active_flag) c->active_host_stale = true;
   }
@@ -145,15 +145,13 @@ int devio_new_keyframe(gbp_ctx* c, const gbp_kf_update* u) {
   return refresh_beliefs_from_partials(c, false);
 }
 
-// the host shadow of the active flags (hoist guard of the host-pointer gbp_new_keyframe) read back from the message records; blocking
+// the host shadow of the active flags (hoist guard of the host-pointer gbp_new_keyframe) read back from the state plane; blocking
 int devio_refresh_active_shadow(gbp_ctx* c) {
   std::vector<int32_t> packed(c->Ep);
-  launch_state_get(P<float4>(c->lmsg), P<float>(c->st_a), P<int>(c->st_b), c->Ep, c->stream);
-  HIPCHK(c, hipGetLastError());
   D2H down;
   if (int rc = down.begin(c, (size_t)c->Ep * 4, 1)) return rc;
   if (down.up.direct) HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (int rc = down.get(packed.data(), c->st_b.p, (size_t)c->Ep * 4)) return rc;
+  if (int rc = down.get(packed.data(), c->fst_packed.p, (size_t)c->Ep * 4)) return rc;
   if (int rc = down.end()) return rc;
   c->active_host.assign(c->Ep, 0);
   for (size_t p = 0; p < c->Ep; ++p) c->active_host[p] = ((uint32_t)packed[p] & (kFlagActive | kFlagPad)) == kFlagActive;

@@ -42,7 +42,8 @@ int eval_enqueue(gbp_ctx* c, int area, DeviceEval* dev_slots) {
   unsigned long long* h_next = P<unsigned long long>(c->health) + 2 * (area ^ 1);
   launch_means(P<float4>(c->camb), P<float4>(c->lmkb), P<float>(c->cam_mu), P<float>(c->lmk_mu), c->C, c->L_loc,
                h_cur, h_next, /*count_cams=*/c->rank == 0, c->stream);
-  launch_eval(P<uint32_t>(c->row_cam), P<uint32_t>(c->lmk_idx), P<float4>(c->lmsg), P<float4>(c->fac), P<float>(c->cam_mu), P<float>(c->lmk_mu),
+  if (!launch_eval_fst) return fail(c, GBP_ERR_STATE, "gbp_eval: no device code");
+  launch_eval_fst(P<uint32_t>(c->row_cam), P<uint32_t>(c->lmk_idx), P<int>(c->fst_packed), P<float4>(c->fac), P<float>(c->cam_mu), P<float>(c->lmk_mu),
               P<float>(c->dK), c->prm.num_undamped_iters, slots + 1, h_cur, reinterpret_cast<unsigned long long*>(slots), c->n_tiles, c->stream);
   HIPCHK(c, hipGetLastError());
   if (dev_slots) return GBP_OK;
@@ -279,7 +280,8 @@ static int eval_each_ride(gbp_ctx* c, int n, gbp_eval_out* out, bool dev = false
     const int m = std::min(n - done, (int)c->ev_depth);
     HIPCHK(c, hipMemsetAsync(c->ev_ctl.p, 0, 64, c->stream));      // iteration counter and health words of this piece
     if (int rc = iterate_plain(c, a, m, true)) return rc;
-    launch_eval_ride(a.ev, P<uint32_t>(c->row_cam), P<uint32_t>(c->lmk_idx), P<float4>(c->lmsg), P<float4>(c->fac), P<float>(c->dK), c->stream);
+    if (!launch_eval_ride_fst) return fail(c, GBP_ERR_STATE, "gbp_iterate_eval_each: no device code");
+    launch_eval_ride_fst(a.ev, P<uint32_t>(c->row_cam), P<uint32_t>(c->lmk_idx), P<int>(c->fst_packed), P<float4>(c->fac), P<float>(c->dK), c->stream);
     launch_eval_fold(a.ev, (uint32_t)m, results + done, c->stream);
     HIPCHK(c, hipGetLastError());
     done += m;

@@ -22,7 +22,7 @@ SweepArgs sweep_args(gbp_ctx* c, bool sweeps) {
   SweepArgs a;
   a.row_cam = P<uint32_t>(c->row_cam); a.lmk_idx = P<uint32_t>(c->lmk_idx); a.fac = P<float4>(c->fac); a.cmsg = P<float4>(c->cmsg);
   a.cmsg_lit = P<float4>(c->cmsg_lit);
-  a.mu = P<float4>(c->mu); a.lmsg = P<float4>(c->lmsg); a.camb = P<float4>(c->camb); a.lmkb = P<float4>(c->lmkb);
+  a.mu = P<float4>(c->mu); a.lmsg = P<float4>(c->lmsg); a.fst_packed = P<int>(c->fst_packed); a.fst_damp = P<float>(c->fst_damp); a.fst_var = P<float>(c->fst_var); a.camb = P<float4>(c->camb); a.lmkb = P<float4>(c->lmkb);
   a.rowp = P<float4>(c->rowp);
   a.cam_mu = P<float4>(c->hmu_c); a.lmk_mu = P<float4>(c->hmu_l); a.cam_lin = P<float4>(c->clin);
   std::memcpy(a.K, c->K, sizeof(a.K));

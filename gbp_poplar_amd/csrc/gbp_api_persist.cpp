@@ -121,8 +121,9 @@ int persist_setup(gbp_ctx* c, const gbp_params* prm, bool sharded) {
       if (rc == GBP_OK && c->persist_ok) {
         // snapshot arena: one slot for every array a k_persist launch mutates
         // (+ the priors and the weaken flags: a launch of gbp_ba_loop weakens priors itself)
-        DevBuf* segs[] = {&c->lmsg, &c->cmsg, &c->fac, &c->rowp, &c->camb, &c->lmkb, &c->hmu_c, &c->hmu_l, &c->clin, &c->local,
+        DevBuf* segs[] = {&c->lmsg, &c->fst_packed, &c->fst_damp, &c->cmsg, &c->fac, &c->rowp, &c->camb, &c->lmkb, &c->hmu_c, &c->hmu_l, &c->clin, &c->local,
                           &c->camp, &c->lmkp, &c->cwf, &c->lwf};
+        static_assert(sizeof(segs) / sizeof(segs[0]) <= (size_t)kMaxCopySegs, "k_copy_segments takes kMaxCopySegs segments");
         size_t total = 0;
         for (DevBuf* b : segs) total += (b->bytes + 15) / 16 * 16;
         rc = dev_alloc(c, c->psnap, total);

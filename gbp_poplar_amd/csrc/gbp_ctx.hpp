@@ -58,6 +58,7 @@ struct gbp_ctx {
   // device memory
   using DevBuf = gbp::api::DevBuf;
   std::vector<DevBuf*> all;
+  DevBuf fst_packed, fst_damp, fst_var;      // [Ep] the per-factor state planes (gbp_kernels.h)
   DevBuf row_cam, lmk_idx, fac, cmsg, mu, lmsg, camb, camp, lmkb, lmkp, rowp, local, d_cam_row_ptr, d_row_slot, d_lmk_ptr, cwf, lwf,
       cscale, lscale, cam_mu, lmk_mu, dK, evalp, hmu_c, hmu_l, clin, d_lmk_fpos, d_lmk_ix, health, tile_perm;
   // host -> device copies of small graphs go through this pinned, device-mapped buffer and a copy kernel (gbp_api_ctx.cpp: H2D)
@@ -68,14 +69,14 @@ struct gbp_ctx {
   DevBuf cmsg_lit;                     // CMSG_LIT (gbp_kernels.h): allocated by the first gbp_linearise that finds camera messages live
   bool cmsg_zero = true;               // no sweep has been set up since the zero fill of the last upload: every CMSG record is kCmsgZero
   DevBuf idx_arena;                    // the index arrays of the device order (row_cam, lmk_idx, lmk_fpos, lmk_ix, the row / landmark pointers, row_slot, K, tile_perm: views into it)
-  DevBuf st_a, st_b;                   // [Ep] scratch of the per-factor state get / set kernels
+  DevBuf st_a, st_b;                   // [Ep] scratch of the per-factor state set kernel
   std::vector<uint8_t> active_host;    // [Ep] host shadow of the active flags (hoist guard of gbp_new_keyframe)
   // device-resident caller arrays (gbp_api_devio.cpp)
   int device = 0;                      // the GPU this ctx lives on (current device of gbp_create)
   DevBuf d_pos_edge;                   // [Ep] lay.pos_edge on the device; allocated by the first call that passes device pointers
   bool active_host_stale = false;      // a device-pointer call changed the active flags: the shadow is read back before its next use
   bool use_tile_perm = false;
-  DevBuf seg_live;                     // [n_tiles] which 64-byte segments of a tile hold a factor (view into idx_arena; SweepArgs.seg_live)
+  DevBuf seg_live;                     // [n_tiles] which segments (four positions) of a tile hold a factor (view into idx_arena; SweepArgs.seg_live)
   bool use_seg_live = false;
   uint32_t sweep_policy = 0;           // kPol* bits of SweepArgs.policy for this graph's shape (sweep_policy_for)
   bool hoist = true;  // per-variable belief means (k_sweep<true>); false = literal per-factor mu/oldmu tensors
@@ -240,22 +241,8 @@ extern LayoutOptions g_layout_options;
 extern int g_force_sweep_policy;
 extern int g_force_seg_skip;      // -1: by shape; 0 / 1: never / always skip the all-pad segments in the sweep (gbp_debug_force_seg_skip)
 
-// Per-factor scalar state lives in the pad slots of the LMSG records (gbp_kernels.h): {damping, count, flags, variance} per
-// device position, as the host code sees it.
-struct HostState { float damping; int32_t count; uint32_t flags; float var; };
-inline HostState get_state(const std::vector<float>& rec, size_t p) {
-  HostState h;
-  int32_t packed;
-  std::memcpy(&packed, &rec[p * 16 + 13], 4);
-  h.damping = rec[p * 16 + 3]; h.count = packed >> 3; h.flags = (uint32_t)packed & 7u; h.var = rec[p * 16 + 14];
-  return h;
-}
-inline void put_state(std::vector<float>& rec, size_t p, const HostState& h) {
-  const int32_t packed = (int32_t)(((uint32_t)h.count << 3) | (h.flags & 7u));
-  rec[p * 16 + 3] = h.damping;
-  std::memcpy(&rec[p * 16 + 13], &packed, 4);
-  rec[p * 16 + 14] = h.var;
-}
+// Per-factor scalar state lives in three planes indexed by device position (gbp_kernels.h)
+inline FactorState factor_state(gbp_ctx* c) { return FactorState{P<int>(c->fst_packed), P<float>(c->fst_damp), P<float>(c->fst_var)}; }
 inline size_t tile_off(uint32_t p, int G, int f) {  // float offset of float f of position p in a G-group tiled array
   return (((size_t)(p >> 6) * G + (f >> 2)) * 64 + (p & 63)) * 4 + (f & 3);
 }

@@ -36,17 +36,21 @@ constexpr int kCmsgLitG = 6;
 constexpr float kCmsgZero = 0.f, kCmsgDerived = 1.f, kCmsgLiteral = 2.f;
 // MU: [0..8] mu (== oldmu between sweeps, ba.cpp:898)  [9] dmu
 constexpr int kMuG = 3;
-// Per-factor scalar state rides in the pad slots of the landmark-message record (below); flags:
+// Per-factor scalar state lives in three planes indexed by device position (below); flags:
 constexpr uint32_t kFlagActive = 1u, kFlagRobust = 2u, kFlagPad = 4u;
 // Indices: ROW_CAM[p/16] = camera of a row, LMK_IDX[p] = landmark (local index) of a factor.
 //
-// Landmark-side records are AoS of 16 floats (one 64-byte sector each):
-//   LMSG[p] (factor->landmark message of the factor at DEVICE position p; a landmark's records are found
-//   through LMK_FPOS[lmk_ptr[l] .. lmk_ptr[l+1]) in slot order), LMKB[l] / LMKP[l] beliefs / priors:
-//   [0..2] eta  [3] pad  [4..12] Lambda 3x3  [13..15] pad
-//   LMKB pads carry the hoisted dmu^2 pieces; LMSG pads carry the factor's scalar state:
-//   [3] damping  [13] (damping_count << 3) | flags (int bits)  [14] measurement variance
+// LMSG[p]: the factor->landmark message of the factor at DEVICE position p, 12 floats = 3 float4, nothing else (a landmark's
+//   messages are found through LMK_FPOS[lmk_ptr[l] .. lmk_ptr[l+1]) in slot order):  [0..2] eta  [3..11] Lambda 3x3 row-major.
+//   A wave's 64 messages are one contiguous 3 KiB block.  The lmsg_* maps below say where a float4 of that block belongs.
+// The factor's scalar state, one plane each, indexed by device position (a wave's access is 256 contiguous bytes):
+//   FST_PACKED[p] (damping_count << 3) | flags   FST_DAMP[p] damping   FST_VAR[p] measurement variance (written by the upload only)
+// Landmark beliefs / priors LMKB[l] / LMKP[l] are AoS of 16 floats (one 64-byte sector each):
+//   [0..2] eta  [3] pad  [4..12] Lambda 3x3  [13..15] pad        (LMKB pads carry the hoisted dmu^2 pieces)
+// In REGISTERS a factor's message keeps that 16-float shape with its scalars in the pad slots — [3] damping, [13] the packed word,
+// [14] the variance — so the arithmetic reads what it always read; only loads and stores know the memory image.
 constexpr int kLmkRec4 = 4;
+constexpr int kLmsgG = 3;
 // Camera-side records are 44 floats (11 float4):  [0..5] eta  [6,7] pad  [8..43] Lambda 6x6
 //   CAMB[c] beliefs, CAMP[c] priors, ROWP[row] row partial sums, exchange buffers [rank][c]
 constexpr int kCamRec4 = 11;
@@ -99,7 +103,10 @@ struct SweepArgs {
   float4* cmsg;
   float4* cmsg_lit;          // CMSG_LIT or NULL (allocated by the first gbp_linearise that finds messages live): read by kCmsgLiteral records only
   float4* mu;
-  float4* lmsg;
+  float4* lmsg;              // [Ep][3] the landmark messages
+  int* fst_packed;           // [Ep] (damping_count << 3) | flags
+  float* fst_damp;           // [Ep] damping
+  const float* fst_var;      // [Ep] measurement variance: read by relinearising lanes only
   const float4* camb;
   const float4* lmkb;
   float4* rowp;
@@ -112,7 +119,7 @@ struct SweepArgs {
   const uint32_t* tile_perm; // [n_tiles] or NULL: wave slot (4 * block + wave) -> tile.  The XCD-aware execution order (gbp_layout.cpp):
                              // workgroups are dealt round-robin over the 8 XCDs, the table hands every XCD the tiles of one landmark
                              // class so that its private L2 holds that slice of the gathered landmark tables
-  const uint32_t* seg_live;  // [n_tiles] or NULL: bit s = the 64-byte segment (lanes 4s .. 4s + 3) of the tile holds a factor; with it the sweep
+  const uint32_t* seg_live;  // [n_tiles] or NULL: bit s = the segment (lanes 4s .. 4s + 3) of the tile holds a factor; with it the sweep
                              // neither loads nor stores the all-pad segments (k_sweep<..., SEG>): graphs of many small cameras, where the unused
                              // tails of the cameras' last rows are a few per cent of all positions
   uint32_t policy;           // kPol* bits: cache policy of the two message streams, chosen per graph shape (gbp_api_ctx.cpp: sweep_policy_for)
@@ -181,7 +188,7 @@ constexpr uint32_t kFlowCam4 = 10;    // camera belief: eta 6, S, lower triangle
 constexpr uint32_t kFlowClin4 = 7;    // CAM_LIN: 20 floats
 constexpr uint32_t kFlowLmk4 = 5;     // landmark belief: eta 3, Lambda 9, the three squared mean changes
 struct PersistFlow {
-  float4* lmsg;    // [2][Ep][4]         eta | Lambda rows 0, 1, 2 of the factor -> landmark message
+  float4* lmsg;    // [2][Ep][4]         eta | Lambda rows 0, 1, 2 of the factor -> landmark message (tagged: NOT the image of LMSG)
   float4* rowp;    // [2][Ep / 16][15]   row sums of the factor -> camera messages
   float4* camb;    // [2][C][10]
   float4* cmu;     // [2][C][2]          hoisted camera mean
@@ -227,6 +234,20 @@ GBP_HD void slice_bounds(uint32_t n_cams, int world, int s, uint32_t* lo, uint32
   *lo = (uint32_t)((uint64_t)n_cams * (uint64_t)s / (uint64_t)world);
   *hi = (uint32_t)((uint64_t)n_cams * ((uint64_t)s + 1u) / (uint64_t)world);
 }
+// The address maps of a tile's landmark messages (kLmsgG * 64 = 192 float4, 3 KiB).  Host and device (gbp_debug_layout_array 11 / 12
+// evaluates them on the host: tests/test_lmsg_split.py).
+//   float4 index i4 of the tile <-> (record = lane of the factor, piece): the message of record r is the float4 3r, 3r + 1, 3r + 2; the
+//   k-th coalesced access of a wave moves i4 = 64k + lane
+GBP_HD uint32_t lmsg_tile_rec(uint32_t i4) { return i4 / (uint32_t)kLmsgG; }
+GBP_HD uint32_t lmsg_tile_piece(uint32_t i4) { return i4 % (uint32_t)kLmsgG; }
+GBP_HD uint32_t lmsg_tile_i4(uint32_t rec, uint32_t piece) { return rec * (uint32_t)kLmsgG + piece; }
+//   float4 slot of (record, piece) in the wave-private LDS stage the tile is transposed through.  Record order, no swizzle: a 16-lane
+//   group of the record-order ds_read_b128 (lane r reads piece q of record r) starts at dword banks 12 r + 4 q mod 64 — sixteen distinct
+//   multiples of 4 — and an 8-lane group of the record-order ds_write_b128 at eight distinct ones mod 32; the tile-order accesses are
+//   consecutive float4
+GBP_HD uint32_t lmsg_lds_slot(uint32_t rec, uint32_t piece) { return rec * (uint32_t)kLmsgG + piece; }
+//   SEG (SweepArgs.seg_live): bit s of a tile's mask = lanes 4s .. 4s + 3 hold a factor; their messages are the float4 12s .. 12s + 11
+GBP_HD bool lmsg_seg_live(uint32_t seg_mask, uint32_t i4) { return ((seg_mask >> (i4 / (4u * (uint32_t)kLmsgG))) & 1u) != 0u; }
 // What an owner leaves per camera of its slice for the other ranks, 18 float4: [0..10] the belief record (CAMB), [11, 12] the hoisted
 // mean (cam_mu[c][0, 1]), [13..17] CAM_LIN.  res: record c - lo of the owner's result buffer (one parity).
 constexpr int kCamRes4 = 18;
@@ -307,7 +328,9 @@ void launch_eval_fold(const EvalRide& ev, uint32_t n_slots, void* out, hipStream
 [[gnu::weak]] void launch_eval_fold_part(const DeviceEval* parts, uint32_t stride, uint32_t nb, uint32_t n_tiles, bool per_wave, uint32_t n_records,
                                          void* out, hipStream_t s);
 // the riding metric of the CURRENT beliefs (a piece's last iteration: no sweep follows) into ring slot counter - 1
-void launch_eval_ride(const EvalRide& ev, const uint32_t* row_cam, const uint32_t* lmk_idx, const float4* lmsg, const float4* fac, const float* K9_dev, hipStream_t s);
+// (weak, with the other launchers that read or write the state planes below: the CPU sanitizer build of the host code links stand-ins of the
+// launchers of the 64-byte record, tests/sanitize/kernel_stubs.cpp; the callers check for a null launcher)
+[[gnu::weak]] void launch_eval_ride_fst(const EvalRide& ev, const uint32_t* row_cam, const uint32_t* lmk_idx, const int* fst_packed, const float4* fac, const float* K9_dev, hipStream_t s);
 int persist_max_resident_blocks();                                            // how many of them this GPU keeps resident at once
 // cooperative != 0: hipLaunchCooperativeKernel — the runtime refuses a grid that cannot be co-resident on the device and the
 // driver never runs two cooperative grids (of any process) side by side; 0: plain launch (the creation-time probe vouches for
@@ -317,12 +340,12 @@ void launch_copy_segments(const CopySegs& t, const unsigned* guard /* abort word
 // runs the placement + barriers of k_persist for this graph once (blocking); false = the workgroups are not co-resident here
 bool persist_probe(uint32_t n_tiles, uint32_t n_cams, uint32_t n_lmks, unsigned* sync, unsigned* status_dev, volatile unsigned* status_host,
                    bool cooperative, hipStream_t s);
-void launch_state_get(const float4* lmsg, float* damping, int* packed, uint32_t n, hipStream_t s);
-void launch_state_set(float4* lmsg, const int* new_count, const uint32_t* ctl, uint32_t n, hipStream_t s);
+[[gnu::weak]] void launch_fst_set(int* fst_packed, const int* new_count, const uint32_t* ctl, uint32_t n, hipStream_t s);
 // WRITE_PROG's per-factor streams (ba.cpp:868-886) from their compact host form — st[p] = {damping, count << 3 | flags, z0, z1}, var[p], both possibly
-// host-mapped — into the records of the device order: the whole LMSG record of position p (zero messages + state) and the measurement
+// host-mapped — into the arrays of the device order: the zero message of position p, its three state planes and the measurement
 // slots of its FAC tile (the rest of FAC is zeroed by the caller)
-void launch_upload_scatter(float4* lmsg, float4* fac, const float4* st, const float* var, uint32_t n, hipStream_t s);
+struct FactorState { int* packed; float* damp; float* var; };      // FST_PACKED, FST_DAMP, FST_VAR
+[[gnu::weak]] void launch_upload_scatter_fst(float4* lmsg, const FactorState& fs, float4* fac, const float4* st, const float* var, uint32_t n, hipStream_t s);
 // ---- device-resident caller arrays (gbp_api_devio.cpp; the kernels: "device-resident caller arrays" in gbp_kernels.hip) ----
 // gbp_upload from device pointers: the caller's file-order arrays (NULL = zeros, as in gbp_state_in) -> the records k_upload_scatter writes
 struct UploadDev {
@@ -330,7 +353,7 @@ struct UploadDev {
   const float* damping; const int* damping_count; const uint32_t* active_flag;
   const float* measurements; const float* meas_variances;
   const float* om;                 // [9E] oldmu (or mu), read only when mu != NULL
-  float4* lmsg; float4* fac;
+  float4* lmsg; FactorState fs; float4* fac;
   float4* mu;                      // the literal mu tensor (per_factor_mu) or NULL
   uint32_t n;                      // device positions (Ep)
 };
@@ -343,14 +366,14 @@ struct RecSegs {                   // see k_rec_copy
   uint32_t w[kMaxRecSegs], stride[kMaxRecSegs], off[kMaxRecSegs];   // words per record in the caller's array / in the device records, offset inside a device record
 };
 void launch_upload_dev(const UploadDev& a, hipStream_t s);
-void launch_read_state_dev(const uint32_t* pos_edge, const float4* lmsg, float* damping, int* damping_count, uint32_t* robust_flag, uint32_t n, hipStream_t s);
-void launch_keyframe_state_dev(const uint32_t* pos_edge, float4* lmsg, const int* new_count, const uint32_t* active_flag, uint32_t n, hipStream_t s);
+void launch_read_state_dev(const uint32_t* pos_edge, const FactorState& fs, float* damping, int* damping_count, uint32_t* robust_flag, uint32_t n, hipStream_t s);
+void launch_keyframe_state_dev(const uint32_t* pos_edge, int* fst_packed, const int* new_count, const uint32_t* active_flag, uint32_t n, hipStream_t s);
 void launch_rec_copy(const RecSegs& t, bool to_rec, hipStream_t s);
 void launch_means(const float4* camb, const float4* lmkb, float* cam_mu, float* lmk_mu, uint32_t n_cams,
                   uint32_t n_lmks, unsigned long long* health2 /* [0] non-finite means, [1] non-PD beliefs: zero on entry */,
                   unsigned long long* health2_next /* zeroed by this launch for the next evaluation */,
                   bool count_cams, hipStream_t s);
-void launch_eval(const uint32_t* row_cam, const uint32_t* lmk_idx, const float4* lmsg, const float4* fac, const float* cam_mu,
+[[gnu::weak]] void launch_eval_fst(const uint32_t* row_cam, const uint32_t* lmk_idx, const int* fst_packed, const float4* fac, const float* cam_mu,
                  const float* lmk_mu, const float* K9_dev, int num_undamped_iters, DeviceEval* partials /* may be mapped host memory */,
                  unsigned long long* health2, unsigned long long* health2_out, uint32_t n_tiles, hipStream_t s);
 uint32_t eval_blocks(uint32_t n_tiles);

@@ -372,8 +372,8 @@ GBP_DEV void cmsg_pack(const float (&oc_eta)[6], const float (&bi)[9], bool acti
 
 // One factor's share of a sweep on register state: PrepMessageVertex + the four Compute*Message*Vertex classes
 // (gbp_codelets.cpp:215-710).  Shared by k_sweep (state streamed from HBM every launch) and k_persist (state kept in
-// registers across iterations).  `means(x0c, x0l, cl)` supplies the hoisted linearisation point and the camera-only Jacobian
-// terms of that point when a lane relinearises.  cm: the previous camera message (cmsg_expand); bi: the 3x3 inverse the new one was
+// registers across iterations).  `means(x0c, x0l, cl, var)` supplies the hoisted linearisation point and the camera-only Jacobian
+// terms of that point when a lane relinearises, and may replace `var` (a caller that fetches the variance only then).  cm: the previous camera message (cmsg_expand); bi: the 3x3 inverse the new one was
 // computed from (written for an active factor only) — with oc_eta what cmsg_pack keeps of it.
 template <bool HOIST, class Means>
 GBP_DEV void factor_update(float (&fac)[56], const float (&cm)[28], float (&mu)[12], const float (&lm)[16], const float (&cb)[44],
@@ -391,6 +391,7 @@ GBP_DEV void factor_update(float (&fac)[56], const float (&cm)[28], float (&mu)[
     float x0c[6], x0l[3];
     CamLin cl;
     float d2;
+    float var_r = var;
     if (HOIST) {
       d2 = cb[6];
       d2 += lb[3];
@@ -414,9 +415,10 @@ GBP_DEV void factor_update(float (&fac)[56], const float (&cm)[28], float (&mu)[
     mu[9] = dmu;
     relin = (dmu < hp.dmu_threshold) && (count > hp.min_linear_iters - hp.num_undamped_iters);
     if (relin) {
-      if (HOIST) {  // linearisation point = the hoisted means + the camera's CAM_LIN record (rare path: loaded only here)
-        means(x0c, x0l, cl);
-      } else {
+      // HOIST: linearisation point = the hoisted means + the camera's CAM_LIN record (rare path: loaded only here); either mode: the
+      // callback may fetch the variance here
+      means(x0c, x0l, cl, var_r);
+      if (!HOIST) {
         const float w[3] = {x0c[3], x0c[4], x0c[5]};
         cam_lin(w, cl);
       }
@@ -426,7 +428,7 @@ GBP_DEV void factor_update(float (&fac)[56], const float (&cm)[28], float (&mu)[
         GBP_UNROLL
         for (int i = 0; i < 54; ++i) fac[i] = 0.f;
       }
-      const bool robust = relin_core(fac, x0c, x0l, K, var, hp.nstds, cl);
+      const bool robust = relin_core(fac, x0c, x0l, K, var_r, hp.nstds, cl);
       flags = robust ? (flags | kFlagRobust) : (flags & ~kFlagRobust);
     }
 
@@ -698,6 +700,60 @@ GBP_DEV void ride_metric(const EvalRide& ev, uint32_t done, uint32_t ws, uint32_
   }
 }
 
+// A wave's 64 landmark messages between LMSG and the lanes' registers.  In memory they are one contiguous 3 KiB block in record
+// order (gbp_kernels.h), moved with kLmsgG coalesced 1 KiB accesses — `ld(k)` / `st(k, v)`: the lane's float4 of access k, float4
+// 64 k + lane of the tile — and transposed through a wave-private LDS stage (>= 192 float4) in the plain record order of
+// lmsg_lds_slot: the tile-order side touches consecutive float4, the record-order side (lane r: piece q of record r) is free of
+// bank conflicts without a swizzle (the maps' comment in gbp_kernels.h).  In registers a message keeps the 16-float shape of a
+// landmark record (eta 0..2, Lambda 4..12); the scalar slots 3, 13, 14, 15 are the caller's.
+// k_beliefs gathers the messages of a landmark by position (random READS are ~2.3x cheaper than random writes of the same size:
+// measured, profiles/HISTORY.md).
+template <class Ld>
+GBP_DEV void lmsg_tile_in(float4* stage, uint32_t lane, Ld&& ld, float (&lm)[16]) {
+  GBP_UNROLL
+  for (int k = 0; k < kLmsgG; ++k) {
+    const uint32_t i4 = (uint32_t)k * 64u + lane;
+    stage[lmsg_lds_slot(lmsg_tile_rec(i4), lmsg_tile_piece(i4))] = ld((uint32_t)k);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  float d[4 * kLmsgG];
+  GBP_UNROLL
+  for (int q = 0; q < kLmsgG; ++q) {
+    // (each piece is ONE ds_read_b128: the empty asm keeps the 16 bytes one value.  Without it the compiler re-cuts the 48 bytes
+    // along the eta | Lambda boundary of the register image — b96, 2 x b32, b32, b64, b128 — and the narrow reads, whose bank rule
+    // is another, conflict at this 48-byte stride: 0.3 M conflict cycles per sweep of the 1M-factor graph)
+    v4f v = *reinterpret_cast<const v4f*>(&stage[lmsg_lds_slot(lane, (uint32_t)q)]);
+    asm volatile("" : "+v"(v));
+    d[4 * q] = v.x; d[4 * q + 1] = v.y; d[4 * q + 2] = v.z; d[4 * q + 3] = v.w;
+  }
+  GBP_UNROLL
+  for (int i = 0; i < 3; ++i) lm[i] = d[i];
+  GBP_UNROLL
+  for (int i = 0; i < 9; ++i) lm[4 + i] = d[3 + i];
+}
+template <class St>
+GBP_DEV void lmsg_tile_out(float4* stage, uint32_t lane, const float (&ol)[16], St&& st) {
+  float d[4 * kLmsgG];
+  GBP_UNROLL
+  for (int i = 0; i < 3; ++i) d[i] = ol[i];
+  GBP_UNROLL
+  for (int i = 0; i < 9; ++i) d[3 + i] = ol[4 + i];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  GBP_UNROLL
+  for (int q = 0; q < kLmsgG; ++q) stage[lmsg_lds_slot(lane, (uint32_t)q)] = make_float4(d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  GBP_UNROLL
+  for (int k = 0; k < kLmsgG; ++k) {
+    const uint32_t i4 = (uint32_t)k * 64u + lane;
+    st((uint32_t)k, stage[lmsg_lds_slot(lmsg_tile_rec(i4), lmsg_tile_piece(i4))]);
+  }
+}
+
 // =================================================================================================
 // k_sweep: one lane = one factor.
 // =================================================================================================
@@ -712,7 +768,8 @@ constexpr int kWpb = 4;      // wavefronts per workgroup of the sweep (the waves
 // POL: cache policy of the two message streams (SweepArgs.policy, chosen per graph shape by gbp_api_ctx.cpp; a template parameter,
 // not a branch on the flag: with both load sequences behind a branch the non-temporal path lost 1.2 %)
 // EV: the metric of the PREVIOUS iteration rides in this sweep (EvalRide in gbp_kernels.h)
-// SEG: the tile's all-pad 64-byte segments are neither loaded nor stored (SweepArgs.seg_live, load_tile_seg above)
+// SEG: the tile's all-pad segments (four lanes) are neither loaded nor stored (SweepArgs.seg_live, load_tile_seg above); the state
+// planes — 4 or 8 bytes per position — are moved whole
 template <bool HOIST, uint32_t POL = 0, bool EV = false, bool SEG = false>
 GBP_DEV void sweep_tile(const SweepArgs& a, const uint32_t wslot) {
   // (the slot is wave-uniform: as an SGPR it turns the permutation look-up into one scalar load)
@@ -736,48 +793,31 @@ GBP_DEV void sweep_tile(const SweepArgs& a, const uint32_t wslot) {
   if (SEG) load_tile_seg<kCmsgG, !(POL & kPolCmsgLoadCached)>(a.cmsg, tile, lane, live8, cmr);
   else load_tile<kCmsgG, !(POL & kPolCmsgLoadCached)>(a.cmsg, tile, lane, cmr);
   if (!HOIST) load_tile<kMuG>(a.mu, tile, lane, mu);
-  // Landmark messages live as 64-byte records in DEVICE (camera-major) order: the wave's 64 records are one
-  // contiguous 4 KiB block, moved with four coalesced 1 KiB accesses and transposed through a wave-private
-  // LDS staging area.  Piece q of record r sits at float4 slot r*4 + (q ^ swz(r)), swz(r) = ((r>>2)&3) ^ (r&2):
-  // a permutation inside each 64-B record, so the tile-order accesses (whole records) and the record-order
-  // accesses (one piece per lane) are both bank-conflict-free for ds_read_b128 (16-lane groups, 64 banks)
-  // and ds_write_b128 (8-lane groups, 32 banks).  k_beliefs gathers the records of a landmark by position
-  // (random 64-B READS are ~2.3x cheaper than random 64-B writes: measured, profiles/HISTORY.md).
-  __shared__ float4 lm_stage[kWpb][64 * 4];
+  // Landmark messages: the wave's 3 KiB block of LMSG through the wave-private LDS stage (lmsg_tile_in above), the two state planes
+  // the sweep reads every time with it.  SEG: a float4 of an all-pad segment (lmsg_seg_live) is given an offset beyond the tile's
+  // descriptor — zeros for the load, nothing for the store, no memory access.
+  __shared__ float4 lm_stage[kWpb][64 * kLmsgG];
   float4* stage = lm_stage[threadIdx.x >> 6];
-  const uint32_t rec_t = lane >> 2;                                   // record handled in tile order (+16k)
-  const uint32_t swz_own = ((lane >> 2) & 3u) ^ (lane & 2u);          // swizzle of the lane's own record
-  float4* lm_tile = a.lmsg + (size_t)tile * 256;
-  // SEG: access k moves the records 16k .. 16k + 15 (four lanes each): lanes 16j .. 16j + 15 the records of segment 4k + j
-  const __amdgpu_buffer_rsrc_t lm_rsrc = tile_rsrc<4>(a.lmsg, SEG ? tile : 0u);
-  GBP_UNROLL
-  for (int k = 0; k < 4; ++k) {
-    // (DEFAULT policy for this one stream unless the shape says otherwise: the tile is rewritten in place ten microseconds later
-    // and gathered by k_beliefs right after the sweep — measured +1.5 % iterations/s on the 1M-factor graph against the
-    // non-temporal hint, with either store policy; the potentials keep the hint on every graph)
-    const uint32_t r = k * 16 + rec_t;
+  float4* lm_tile = a.lmsg + (size_t)tile * (64 * kLmsgG);
+  const __amdgpu_buffer_rsrc_t lm_rsrc = tile_rsrc<kLmsgG>(a.lmsg, SEG ? tile : 0u);
+  // (DEFAULT policy for this one stream unless the shape says otherwise: the tile is rewritten in place ten microseconds later
+  // and gathered by k_beliefs right after the sweep — measured +1.5 % iterations/s on the 1M-factor graph against the
+  // non-temporal hint, with either store policy; the potentials keep the hint on every graph)
+  lmsg_tile_in(stage, lane, [&](uint32_t k) {
     if (SEG) {
       typedef unsigned v4u __attribute__((ext_vector_type(4)));
-      const bool live_k = ((segm >> (4 * k + (int)(lane >> 4))) & 1u) != 0u;
-      const v4u v = __builtin_amdgcn_raw_buffer_load_b128(lm_rsrc, (live_k ? (int)(lane * 16u) : kBufOob) + k * 1024, 0, (POL & kPolLmsgLoadNt) ? 2 : 0);
-      stage[r * 4 + ((lane & 3u) ^ (((r >> 2) & 3u) ^ (r & 2u)))] =
-          make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-    } else {
-      const v4f* src = reinterpret_cast<const v4f*>(lm_tile) + k * 64 + lane;
-      const v4f v = (POL & kPolLmsgLoadNt) ? __builtin_nontemporal_load(src) : *src;
-      stage[r * 4 + ((lane & 3u) ^ (((r >> 2) & 3u) ^ (r & 2u)))] = make_float4(v.x, v.y, v.z, v.w);
+      const bool live_k = lmsg_seg_live(segm, k * 64u + lane);
+      const v4u v = __builtin_amdgcn_raw_buffer_load_b128(lm_rsrc, (live_k ? (int)(lane * 16u) : kBufOob) + (int)k * 1024, 0, (POL & kPolLmsgLoadNt) ? 2 : 0);
+      return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
     }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  GBP_UNROLL
-  for (int q = 0; q < 4; ++q) {
-    const float4 v = stage[lane * 4 + ((uint32_t)q ^ swz_own)];
-    lm[4 * q] = v.x; lm[4 * q + 1] = v.y; lm[4 * q + 2] = v.z; lm[4 * q + 3] = v.w;
-  }
+    const v4f* src = reinterpret_cast<const v4f*>(lm_tile) + k * 64u + lane;
+    const v4f v = (POL & kPolLmsgLoadNt) ? __builtin_nontemporal_load(src) : *src;
+    return make_float4(v.x, v.y, v.z, v.w);
+  }, lm);
   load_rec<kCamRec4>(a.camb + (size_t)cam_i * kCamRec4, cb);
   load_rec<kLmkRec4>(a.lmkb + (size_t)lmk_i * kLmkRec4, lb);
+  const int packed = a.fst_packed[p];      // (behind the gathers: nothing needs them before the gathers have landed)
+  float damping = a.fst_damp[p];
   // EV: the camera's metric record (one address per 16-lane row) and the landmark's metric mean (a 16-byte gather from a table
   // 1/4 the size of the beliefs') go out WITH the belief gathers — unconditionally: pads index 0 — and wait in a wave-private
   // LDS area for the end of the tile, where the registers are free: 16 more live registers in this prologue (50 loads in
@@ -792,15 +832,13 @@ GBP_DEV void sweep_tile(const SweepArgs& a, const uint32_t wslot) {
     // the wait for the metric records)
     asm volatile("" ::: "memory");
   }
-  // per-factor scalar state rides in the pad slots of the landmark-message record (read and rewritten
-  // every sweep anyway): [3] damping, [13] (damping_count << 3) | flags, [14] measurement variance
-  if (SEG && !live8) lm[13] = __int_as_float((int)kFlagPad);      // (the record that was not loaded: a pad, as in memory)
-  float damping = lm[3];
-  const int packed = __float_as_int(lm[13]);
+  // per-factor scalar state: the packed word and the damping from their planes (above); the measurement variance is read by
+  // relin_core only, so the sweep fetches it where a lane relinearises (beside the means below) and never writes it
   int count = packed >> 3;
   uint32_t flags = (uint32_t)packed & 7u;
-  const float var = lm[14];
+  const float var = 0.f;
   const bool active = (flags & kFlagActive) != 0;
+  const bool count_was_0 = count == 0;      // (factor_update then sets the damping: see the store of FST_DAMP below)
 
   float K[9];
   GBP_UNROLL
@@ -820,7 +858,9 @@ GBP_DEV void sweep_tile(const SweepArgs& a, const uint32_t wslot) {
   float oc_eta[6], oc_lam[36], bi[9], ol[16];
   bool relin;
   factor_update<HOIST>(fac, cm, mu, lm, cb, lb, K, a.hp, damping, count, flags, var, active, oc_eta, oc_lam, bi, ol, relin,
-                            [&](float (&x0c)[6], float (&x0l)[3], CamLin& cl) {   // rare path: loaded only by relinearising lanes
+                            [&](float (&x0c)[6], float (&x0l)[3], CamLin& cl, float& var_r) {   // rare path: loaded only by relinearising lanes
+                              var_r = a.fst_var[p];
+                              if (!HOIST) return;      // (the literal mu tensors: the means are the lane's own)
                               // camera side: the hoisted mean and its CAM_LIN record — per-camera tables (C x 144 B) that live in L2
                               const float4 m0 = a.cam_mu[(size_t)cam_i * 4], m1 = a.cam_mu[(size_t)cam_i * 4 + 1];
                               float4 q[kCamLin4];
@@ -836,32 +876,30 @@ GBP_DEV void sweep_tile(const SweepArgs& a, const uint32_t wslot) {
                             });
 
   // ---- outputs --------------------------------------------------------------------------------
-  ol[3] = damping;
-  ol[13] = __int_as_float((int)(((uint32_t)count << 3) | flags));
-  ol[14] = var;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  GBP_UNROLL
-  for (int q = 0; q < 4; ++q)
-    stage[lane * 4 + ((uint32_t)q ^ swz_own)] = make_float4(ol[4 * q], ol[4 * q + 1], ol[4 * q + 2], ol[4 * q + 3]);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  GBP_UNROLL
-  for (int k = 0; k < 4; ++k) {
-    const uint32_t r = k * 16 + rec_t;
-    const float4 f = stage[r * 4 + ((lane & 3u) ^ (((r >> 2) & 3u) ^ (r & 2u)))];
+  lmsg_tile_out(stage, lane, ol, [&](uint32_t k, float4 f) {
     if (SEG) {
       typedef unsigned v4u __attribute__((ext_vector_type(4)));
-      const bool live_k = ((segm >> (4 * k + (int)(lane >> 4))) & 1u) != 0u;
+      const bool live_k = lmsg_seg_live(segm, k * 64u + lane);
       const v4u v = {__float_as_uint(f.x), __float_as_uint(f.y), __float_as_uint(f.z), __float_as_uint(f.w)};
-      __builtin_amdgcn_raw_buffer_store_b128(v, lm_rsrc, (live_k ? (int)(lane * 16u) : kBufOob) + k * 1024, 0, (POL & kPolLmsgStoreNt) ? 2 : 0);
+      __builtin_amdgcn_raw_buffer_store_b128(v, lm_rsrc, (live_k ? (int)(lane * 16u) : kBufOob) + (int)k * 1024, 0, (POL & kPolLmsgStoreNt) ? 2 : 0);
     } else if (POL & kPolLmsgStoreNt) {
       const v4f v = {f.x, f.y, f.z, f.w};
-      __builtin_nontemporal_store(v, reinterpret_cast<v4f*>(lm_tile) + k * 64 + lane);
+      __builtin_nontemporal_store(v, reinterpret_cast<v4f*>(lm_tile) + k * 64u + lane);
     } else {
-      lm_tile[k * 64 + lane] = f;
+      lm_tile[k * 64u + lane] = f;
     }
+  });
+  // the state planes: the packed word every sweep (the count of an active factor moves every sweep); the damping only when a lane
+  // of the wave has written it — factor_update does at a relinearisation and when the count stands at 0, nowhere else — and then from
+  // all 64 lanes (whole lines).  No branch: the store goes through a descriptor of the tile's 256 bytes of the plane, and a wave
+  // that has nothing to say gives every lane an offset beyond it — the hardware drops the store without a memory access, as for an
+  // all-pad segment (load_tile_seg).  (A branch round a plain store cost 10 to 14 VGPRs and the second wave per SIMD of two instantiations.)
+  a.fst_packed[p] = (int)(((uint32_t)count << 3) | flags);
+  {
+    // (the literal-mu instantiation stores every time: with the test it needs 259 registers, one wave per SIMD)
+    const bool wave_wrote = !HOIST || __builtin_amdgcn_ballot_w64(active && (count_was_0 || relin)) != 0ull;
+    const __amdgpu_buffer_rsrc_t dr = __builtin_amdgcn_make_buffer_rsrc(a.fst_damp + (size_t)tile * 64, 0, 256, 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(damping), dr, wave_wrote ? (int)(lane * 4u) : kBufOob, 0, 0);
   }
   {
     float cmo[16];
@@ -898,8 +936,7 @@ __global__ __launch_bounds__(256) void k_linearise(const SweepArgs a) {
   const uint32_t p = blockIdx.x * 256 + threadIdx.x;
   const uint32_t tile = p >> 6, lane = p & 63;
   const uint32_t cam_i = a.row_cam[p >> 4], lmk_i = a.lmk_idx[p];
-  float4 st = a.lmsg[(size_t)p * 4 + 3];   // record slots 12..15: y = packed count/flags, z = variance
-  int packed = __float_as_int(st.y);
+  const int packed = a.fst_packed[p];
   uint32_t flags = (uint32_t)packed & 7u;
   if (flags & kFlagPad) return;
   float fac[56], cb[44], lb[16], K[9], x0c[6], x0l[3];
@@ -930,10 +967,9 @@ __global__ __launch_bounds__(256) void k_linearise(const SweepArgs a) {
   CamLin cl;
   const float wv[3] = {x0c[3], x0c[4], x0c[5]};
   cam_lin(wv, cl);
-  const bool robust = relin_core(fac, x0c, x0l, K, st.z, a.hp.nstds, cl);
+  const bool robust = relin_core(fac, x0c, x0l, K, a.fst_var[p], a.hp.nstds, cl);
   flags = robust ? (flags | kFlagRobust) : (flags & ~kFlagRobust);
-  st.y = __int_as_float((packed & ~7) | (int)flags);
-  a.lmsg[(size_t)p * 4 + 3] = st;
+  a.fst_packed[p] = (packed & ~7) | (int)flags;
   store_tile<kFacG>(a.fac, tile, lane, fac);
 }
 
@@ -946,18 +982,39 @@ __global__ __launch_bounds__(256) void k_linearise(const SweepArgs a) {
 // Landmark beliefs: prior + messages in slot order.  With `hoist` the belief means (inf2mean, bafuncs.cpp:2-15)
 // and the dmu^2 pieces of the next sweep are computed here once per variable (see k_sweep<HOIST>).
 // =================================================================================================
-// float4 #q of the landmark-message record at device position pos, with the per-factor state that rides in
-// the record's pad slots (3, 13, 14, 15) blanked so that it never enters a belief sum.  Two steps, and the loads of a batch are
-// issued UNCONDITIONALLY (unused slots hold position 0: a valid record) before anything looks at a loaded value: written as
-// `k < deg ? load : 0` every gather became a branch with its own `s_waitcnt vmcnt(0)` at the join — ten dependent round trips
-// per wave instead of ten loads in flight (the ISA showed it; `k_persist` had hit the same thing with its sc1 loads).
-GBP_DEV float4 lmsg_load(const float4* lmsg, uint32_t pos, uint32_t q) {
-  return lmsg[(size_t)pos * 4 + q];   // default cache policy: a non-temporal hint here costs 4 us (the 128-B line's other half is a neighbour's record)
+// The landmark sums.  A quad of lanes owns a landmark, lane q its float4 #q of the 16-float record (prior, belief); a message is 12
+// dense floats (LMSG in gbp_kernels.h), so lane q < 3 gathers float4 #q of every message (lane 3 repeats lane 2's address: no further
+// bytes, no branch) and the sums run on the DENSE image: lmk_quad_dense deals the record's twelve payload slots to the lanes 0..2 as
+// the messages hold them, lmk_quad_record deals the sums back (pad slots: zero — a prior's pads are zero, and nothing reads a belief's pad
+// slots but the hoisted dmu^2 pieces the owner writes into them afterwards).  Slot for slot the same additions in the same order.
+// The loads of a batch are issued UNCONDITIONALLY (unused slots hold position 0: a valid message) before anything looks at a loaded
+// value: written as `k < deg ? load : 0` every gather became a branch with its own `s_waitcnt vmcnt(0)` at the join — ten dependent
+// round trips per wave instead of ten loads in flight (the ISA showed it; `k_persist` had hit the same thing with its sc1 loads).
+GBP_DEV uint32_t lmsg_quad_i4(uint32_t pos, uint32_t q) { return pos * (uint32_t)kLmsgG + (q < 2u ? q : 2u); }
+// acc += v, four scalar adds: paired into v_pk_add_f32 the (y, z) halves of messages that arrive in odd-aligned registers are first
+// copied into aligned pairs — 8 registers more at the peak of k_beliefs, its seventh wave per SIMD
+GBP_DEV void lmk_acc_add(float4& acc, const float4 v) {
+  acc.x = acc.x + v.x;
+  acc.y = acc.y + v.y; GBP_SLP_FENCE(acc.y);
+  acc.z = acc.z + v.z; GBP_SLP_FENCE(acc.z);
+  acc.w = acc.w + v.w; GBP_SLP_FENCE(acc.w);
 }
-GBP_DEV float4 lmsg_blank(float4 m, uint32_t q) {
-  if (q == 0) m.w = 0.f;
-  if (q == 3) { m.y = 0.f; m.z = 0.f; m.w = 0.f; }
-  return m;
+GBP_DEV float4 lmsg_load(const float4* lmsg, uint32_t pos, uint32_t q) {
+  return lmsg[lmsg_quad_i4(pos, q)];   // default cache policy: a non-temporal hint here costs 4 us (the line's other part is a neighbour's message)
+}
+// (both are called by whole waves: the DPP moves read the quad's other lanes)
+GBP_DEV float4 lmk_quad_dense(const float4 r, uint32_t q) {      // record float4 r of lane q -> dense float4 q (lanes 0..2; lane 3: unused)
+  // dense 0 = (r0.x r0.y r0.z r1.x)   dense 1 = (r1.y r1.z r1.w r2.x)   dense 2 = (r2.y r2.z r2.w r3.x)
+  // the next lane's .x (lane 3: lane 0's, unused) — a DPP quad permutation [1,2,3,0]: no index register, no trip through the LDS crossbar
+  const float nx = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(r.x), 0x39, 0xF, 0xF, false));
+  return q == 0u ? make_float4(r.x, r.y, r.z, nx) : make_float4(r.y, r.z, r.w, nx);
+}
+GBP_DEV float4 lmk_quad_record(const float4 d, uint32_t q) {      // ... and back; all four lanes call it
+  // r0 = (d0.x d0.y d0.z 0)   r1 = (d0.w d1.x d1.y d1.z)   r2 = (d1.w d2.x d2.y d2.z)   r3 = (d2.w 0 0 0)
+  const float pw = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(d.w), 0x93, 0xF, 0xF, false));      // the previous lane's .w: quad permutation [3,0,1,2] (lane 0: unused)
+  if (q == 0u) return make_float4(d.x, d.y, d.z, 0.f);
+  if (q == 3u) return make_float4(pw, 0.f, 0.f, 0.f);
+  return make_float4(pw, d.x, d.y, d.z);
 }
 
 // mean of a camera belief record (44 floats, in registers or in LDS): inf2mean6x6 (bafuncs.cpp:2-9)
@@ -1182,6 +1239,7 @@ GBP_DEV void beliefs_body(const BeliefArgs& b, const float* const* __restrict__ 
     if (b.hoist && q == 0) used_mu = b.lmk_mu[(size_t)l * 2 + (b.roll ? 0 : 1)];
   }
   const uint32_t deg = (uint32_t)__shfl((int)ix.x, 0, 4);
+  acc = lmk_quad_dense(acc, q);     // the sums run on the dense image of the messages (see lmsg_load)
   {
     // element k + 1 of the index record sits in lane (k + 1) / 4, component (k + 1) % 4 of the quad
     auto slot_pos = [&](int k) -> uint32_t {
@@ -1195,16 +1253,16 @@ GBP_DEV void beliefs_body(const BeliefArgs& b, const float* const* __restrict__ 
     for (int k = 0; k < 10; ++k) m[k] = lmsg_load(b.lmsg, slot_pos(k), q);      // all ten in flight (see lmsg_load)
     GBP_UNROLL
     for (int k = 0; k < 10; ++k) {   // adds in slot order
-      const float4 v = lmsg_blank(m[k], q);
-      if ((uint32_t)k < deg) { acc.x = acc.x + v.x; acc.y = acc.y + v.y; acc.z = acc.z + v.z; acc.w = acc.w + v.w; }
+      const float4 v = m[k];
+      if ((uint32_t)k < deg) lmk_acc_add(acc, v);
     }
     if (__any(deg > 10u)) {
       GBP_UNROLL
       for (int k = 10; k < 15; ++k) m[k - 10] = lmsg_load(b.lmsg, slot_pos(k), q);
       GBP_UNROLL
       for (int k = 10; k < 15; ++k) {
-        const float4 v = lmsg_blank(m[k - 10], q);
-        if ((uint32_t)k < deg) { acc.x = acc.x + v.x; acc.y = acc.y + v.y; acc.z = acc.z + v.z; acc.w = acc.w + v.w; }
+        const float4 v = m[k - 10];
+        if ((uint32_t)k < deg) lmk_acc_add(acc, v);
       }
     }
   }
@@ -1220,11 +1278,12 @@ GBP_DEV void beliefs_body(const BeliefArgs& b, const float* const* __restrict__ 
       for (int k = 0; k < 8; ++k) m[k] = lmsg_load(b.lmsg, pos[k], q);
       GBP_UNROLL
       for (int k = 0; k < 8; ++k) {
-        const float4 v = lmsg_blank(m[k], q);
+        const float4 v = m[k];
         if ((uint32_t)k < nleft) { acc.x = acc.x + v.x; acc.y = acc.y + v.y; acc.z = acc.z + v.z; acc.w = acc.w + v.w; }
       }
     }
   }
+  acc = lmk_quad_record(acc, q);
   if (b.hoist) {
     // gather the 16-float record of the quad into its lane 0 (all lanes execute the shuffles)
     float rec[16];
@@ -1424,12 +1483,7 @@ GBP_DEV void load_rec_xw(const XwBuf& buf, uint32_t i4, float (&out)[G * 4]) {
     out[4 * g] = v.x; out[4 * g + 1] = v.y; out[4 * g + 2] = v.z; out[4 * g + 3] = v.w;
   }
 }
-GBP_DEV float4 lmsg_piece_xw(const XwBuf& lmsg, uint32_t pos, uint32_t q) {
-  float4 m = lmsg.ld4(pos * 4u + q);
-  if (q == 0) m.w = 0.f;
-  if (q == 3) { m.y = 0.f; m.z = 0.f; m.w = 0.f; }
-  return m;
-}
+GBP_DEV float4 lmsg_piece_xw(const XwBuf& lmsg, uint32_t pos, uint32_t q) { return lmsg.ld4(lmsg_quad_i4(pos, q)); }      // (see lmsg_load)
 
 constexpr unsigned long long kBarrierTimeoutTicks = 150000000ull;   // 1.5 s of the 100 MHz wall clock
 // The hand-off in two halves, so that work which needs nothing from the other workgroups can run between the arrival and the
@@ -1495,25 +1549,10 @@ GBP_DEV bool persist_place(const PersistArgs& A, uint32_t& bid, uint32_t& nblk) 
   }
   return true;
 }
-// The wave's 64 landmark-message records through its LDS stage, swizzled as in k_sweep.  In: `ld(k)` is the lane's float4 of the
-// k-th coalesced 1 KiB access; lm receives the lane's own record.
-template <class Ld>
-GBP_DEV void lm_tile_in(float4* stage, uint32_t lane, Ld&& ld, float (&lm)[16]) {
-  const uint32_t rec_t = lane >> 2, swz_own = ((lane >> 2) & 3u) ^ (lane & 2u);
-  GBP_UNROLL
-  for (int k = 0; k < 4; ++k) {
-    const uint32_t r = k * 16 + rec_t;
-    stage[r * 4 + ((lane & 3u) ^ (((r >> 2) & 3u) ^ (r & 2u)))] = ld((uint32_t)k);
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  GBP_UNROLL
-  for (int q = 0; q < 4; ++q) {
-    const float4 v = stage[lane * 4 + ((uint32_t)q ^ swz_own)];
-    lm[4 * q] = v.x; lm[4 * q + 1] = v.y; lm[4 * q + 2] = v.z; lm[4 * q + 3] = v.w;
-  }
-}
+// The tagged landmark messages of k_persist_flow (PersistFlow.lmsg: four 16-byte records per factor) through the wave's LDS stage:
+// piece q of record r sits at float4 slot r*4 + (q ^ swz(r)), swz(r) = ((r>>2)&3) ^ (r&2) — a permutation inside each 64-B record,
+// so the tile-order accesses (whole records) and the record-order accesses (one piece per lane) are both bank-conflict-free for
+// ds_read_b128 (16-lane groups, 64 banks) and ds_write_b128 (8-lane groups, 32 banks).
 // Out: `piece(q)` is float4 #q of the lane's record; `st(k, v)` stores the lane's float4 of the k-th coalesced access.
 template <class Piece, class St>
 GBP_DEV void lm_tile_out(float4* stage, uint32_t lane, Piece&& piece, St&& st) {
@@ -1532,7 +1571,7 @@ GBP_DEV void lm_tile_out(float4* stage, uint32_t lane, Piece&& piece, St&& st) {
   }
 }
 // A tile wave's registers for the whole launch: the potential, the camera messages and — `ld_lm(i4)` = float4 #i4 of LMSG — the
-// landmark messages of tile `tile`.  The camera message stays LITERAL in registers across the iterations: cmsg_expand of the CMSG
+// landmark messages of tile `tile` with the factor's scalars in the pad slots of their register image (gbp_kernels.h).  The camera message stays LITERAL in registers across the iterations: cmsg_expand of the CMSG
 // record once, then each iteration's output; its record is written by the launch's last iteration (tile_cmsg_store)
 template <class LdLm>
 GBP_DEV void tile_regs_load(const SweepArgs& a, uint32_t tile, uint32_t lane, float4* stage, LdLm&& ld_lm, float (&fac)[56], float (&cm)[28],
@@ -1541,7 +1580,9 @@ GBP_DEV void tile_regs_load(const SweepArgs& a, uint32_t tile, uint32_t lane, fl
   float rec[16];
   load_tile<kCmsgG, false>(a.cmsg, tile, lane, rec);
   cmsg_expand(fac, rec, a.cmsg_lit, tile, lane, cm);
-  lm_tile_in(stage, lane, [&](uint32_t k) { return ld_lm(tile * 256u + k * 64u + lane); }, lm);
+  const uint32_t p = tile * 64u + lane;
+  lm[3] = a.fst_damp[p]; lm[13] = __int_as_float(a.fst_packed[p]); lm[14] = a.fst_var[p]; lm[15] = 0.f;
+  lmsg_tile_in(stage, lane, [&](uint32_t k) { return ld_lm(tile * (uint32_t)(64 * kLmsgG) + k * 64u + lane); }, lm);
 }
 // behind factor_update: the factor's scalar state into the pad slots of its new landmark message ol; both new messages become the
 // registers the next iteration starts from
@@ -1568,9 +1609,13 @@ GBP_DEV void tile_cmsg_store(const SweepArgs& a, uint32_t tile, uint32_t lane, c
   cmsg_pack(oc_eta, bi, active, rec);
   store_tile<kCmsgG, false>(a.cmsg, tile, lane, rec);
 }
-// what stayed in registers goes back to its arrays
-GBP_DEV void tile_regs_store(const SweepArgs& a, uint32_t tile, uint32_t lane, const float (&fac)[56], bool fac_dirty) {
+// what stayed in registers goes back to its arrays: the potential where a lane relinearised, the two mutable state planes (lm: the
+// register image the last iteration left)
+GBP_DEV void tile_regs_store(const SweepArgs& a, uint32_t tile, uint32_t lane, const float (&fac)[56], bool fac_dirty, const float (&lm)[16]) {
   if (fac_dirty) store_tile<kFacG, false>(a.fac, tile, lane, fac);
+  const uint32_t p = tile * 64u + lane;
+  a.fst_packed[p] = __float_as_int(lm[13]);
+  a.fst_damp[p] = lm[3];
 }
 // the metric record of a tile wave (DeviceEval slot 1 + wave): its residual sums (zero where the factor is not active) through the lane
 // tree of eval_wave_tree, the counts of ITS factors' flags (packed: the state word as the evaluated sweep left it) through ballots
@@ -1876,7 +1921,7 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
       float oc_eta[6], oc_lam[36], bi[9], ol[16];
       bool relin;
       factor_update<true>(fac, cm, mu, lm, cb, lb, K, a.hp, damping, count, flags, var, active, oc_eta, oc_lam, bi, ol, relin,
-                             [&](float (&x0c)[6], float (&x0l)[3], CamLin& cl) {
+                             [&](float (&x0c)[6], float (&x0l)[3], CamLin& cl, float&) {
                                x0c[0] = m4[0].x; x0c[1] = m4[0].y; x0c[2] = m4[0].z; x0c[3] = m4[1].x; x0c[4] = m4[1].y; x0c[5] = m4[1].z;
                                x0l[0] = u4.x; x0l[1] = u4.y; x0l[2] = u4.z;
                                float f[21];
@@ -1909,9 +1954,8 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
           if (q < 3u) S_rowp.st4(rp + 3u, flow_rec(g2.y, g2.z, g2.w, t_out));
         }
       }
-      if (last)   // the ordinary LMSG tile (with the factor's scalars in its pad slots), as k_sweep leaves it
-        lm_tile_out(stage, lane, [&](uint32_t q) { return make_float4(ol[4 * q], ol[4 * q + 1], ol[4 * q + 2], ol[4 * q + 3]); },
-                    [&](uint32_t k, float4 v) { a.lmsg[lm_tile4 + k * 64u + lane] = v; });
+      if (last)   // the ordinary LMSG tile, as k_sweep leaves it (the state planes: tile_regs_store)
+        lmsg_tile_out(stage, lane, ol, [&](uint32_t k, float4 v) { a.lmsg[tile * (uint32_t)(64 * kLmsgG) + k * 64u + lane] = v; });
     }
 
     // ================= phase B: the belief update (arithmetic of k_beliefs, roll = 1) =================
@@ -2199,7 +2243,7 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
       if (!metric_of((uint32_t)it - 1u, ev_packed, ev_c, ev_l0)) return;
   }
 
-  if (has_tile) tile_regs_store(a, tile, lane, fac, fac_dirty);
+  if (has_tile) tile_regs_store(a, tile, lane, fac, fac_dirty, lm);
 
   // ---- the metric of the last iteration; then the launch's ONE barrier: behind it every owner has counted and block 0 hands the
   // health words of every metric of the launch to the host's slots (and leaves them zero) ----
@@ -2221,52 +2265,41 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
   }
 }
 
-// Per-factor scalar state (damping, damping_count, flags: pad slots 3 / 13 of the LMSG record) <-> compact
-// per-position arrays, so that READ_PROG's damping / damping_count / robust_flag streams (ba.cpp:912-914) and
-// NEW_KEYFRAME's damping_count / active_flag streams (slam.cpp:920,926) move 8 bytes per factor over PCIe instead of the
-// whole 64-byte message record.
-__global__ __launch_bounds__(256) void k_state_get(const float4* __restrict__ lmsg, float* __restrict__ damping,
-                                                   int* __restrict__ packed, uint32_t n) {
-  const uint32_t p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= n) return;
-  damping[p] = lmsg[(size_t)p * 4].w;
-  packed[p] = __float_as_int(lmsg[(size_t)p * 4 + 3].y);
-}
+// Per-factor scalar state lives in compact per-position planes (FST_PACKED, FST_DAMP: gbp_kernels.h), so READ_PROG's damping /
+// damping_count / robust_flag streams (ba.cpp:912-914) are plain copies of them and NEW_KEYFRAME's damping_count / active_flag
+// streams (slam.cpp:920,926) move 8 bytes per factor over PCIe.
 // ctl bit 0: damping_count := new_count;  bit 1: active flag := bit 2
-__global__ __launch_bounds__(256) void k_state_set(float4* __restrict__ lmsg, const int* __restrict__ new_count,
+__global__ __launch_bounds__(256) void k_state_set(int* __restrict__ fst_packed, const int* __restrict__ new_count,
                                                    const uint32_t* __restrict__ ctl, uint32_t n) {
   const uint32_t p = blockIdx.x * 256 + threadIdx.x;
   if (p >= n) return;
   const uint32_t c = ctl[p];
   if (!(c & 3u)) return;
-  float4 st = lmsg[(size_t)p * 4 + 3];
-  const int packed = __float_as_int(st.y);
+  const int packed = fst_packed[p];
   int count = packed >> 3;
   uint32_t flags = (uint32_t)packed & 7u;
   if (flags & kFlagPad) return;
   if (c & 1u) count = new_count[p];
   if (c & 2u) flags = (c & 4u) ? (flags | kFlagActive) : (flags & ~kFlagActive);
-  st.y = __int_as_float((int)(((uint32_t)count << 3) | flags));
-  lmsg[(size_t)p * 4 + 3] = st;
+  fst_packed[p] = (int)(((uint32_t)count << 3) | flags);
 }
 
 // gbp_upload: 20 bytes per position cross PCIe (read here straight out of the pinned staging buffer when they fit it) instead of the 288 bytes
-// of the records they go into
-__global__ __launch_bounds__(256) void k_upload_scatter(float4* __restrict__ lmsg, float4* __restrict__ fac, const float4* __restrict__ st,
+// of the arrays they go into
+__global__ __launch_bounds__(256) void k_upload_scatter(float4* __restrict__ lmsg, const FactorState fs, float4* __restrict__ fac, const float4* __restrict__ st,
                                                         const float* __restrict__ var, uint32_t n) {
   const uint32_t p = blockIdx.x * 256 + threadIdx.x;
   if (p >= n) return;
   const float4 s = st[p];
   const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-  lmsg[(size_t)p * 4] = make_float4(0.f, 0.f, 0.f, s.x);
-  lmsg[(size_t)p * 4 + 1] = z;
-  lmsg[(size_t)p * 4 + 2] = z;
-  lmsg[(size_t)p * 4 + 3] = make_float4(0.f, s.y, var[p], 0.f);
+  GBP_UNROLL
+  for (int q = 0; q < kLmsgG; ++q) lmsg[(size_t)p * kLmsgG + q] = z;
+  fs.damp[p] = s.x; fs.packed[p] = __float_as_int(s.y); fs.var[p] = var[p];
   fac[((size_t)(p >> 6) * kFacG + 13) * 64 + (p & 63)] = make_float4(0.f, 0.f, s.z, s.w);      // floats 52..55: z = .z, .w
 }
 
 // ---- device-resident caller arrays (gbp_api_devio.cpp): gbp_upload / gbp_read / gbp_read_priors / gbp_new_keyframe whose structs hold
-// DEVICE pointers.  The twins of what the host path stages and k_upload_scatter / k_state_get / k_state_set spread: same targets, same
+// DEVICE pointers.  The twins of what the host path stages and k_upload_scatter / k_state_set spread: same targets, same
 // bits, nothing crosses PCIe.  One thread per device POSITION p (pos_edge[p] = file index of its factor, ~0u = pad): the device-order
 // side, which carries 80 (upload) / 8 (read, keyframe) bytes per position in whole 16-byte words, is lane-contiguous; the caller's
 // file-order arrays (4 - 36 bytes per factor) are gathered / scattered through pos_edge, which runs in file order within a camera, so
@@ -2294,10 +2327,9 @@ __global__ __launch_bounds__(256) void k_upload_dev(const UploadDev a) {
     }
   }
   const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-  a.lmsg[(size_t)p * 4] = make_float4(0.f, 0.f, 0.f, damping);
-  a.lmsg[(size_t)p * 4 + 1] = z;
-  a.lmsg[(size_t)p * 4 + 2] = z;
-  a.lmsg[(size_t)p * 4 + 3] = make_float4(0.f, __int_as_float(packed), v, 0.f);
+  GBP_UNROLL
+  for (int q = 0; q < kLmsgG; ++q) a.lmsg[(size_t)p * kLmsgG + q] = z;
+  a.fs.damp[p] = damping; a.fs.packed[p] = packed; a.fs.var[p] = v;
   a.fac[((size_t)(p >> 6) * kFacG + 13) * 64 + (p & 63)] = make_float4(0.f, 0.f, z0, z1);
   if (a.mu) {
     GBP_UNROLL
@@ -2305,33 +2337,31 @@ __global__ __launch_bounds__(256) void k_upload_dev(const UploadDev a) {
   }
 }
 // READ_PROG's damping / damping_count / robust_flag streams into the caller's file-order arrays (NULL = skipped)
-__global__ __launch_bounds__(256) void k_read_state_dev(const uint32_t* __restrict__ pos_edge, const float4* __restrict__ lmsg, float* damping,
+__global__ __launch_bounds__(256) void k_read_state_dev(const uint32_t* __restrict__ pos_edge, const FactorState fs, float* damping,
                                                         int* damping_count, uint32_t* robust_flag, uint32_t n) {
   const uint32_t p = blockIdx.x * 256 + threadIdx.x;
   if (p >= n) return;
   const uint32_t e = pos_edge[p];
   if (e == ~0u) return;
-  const int packed = __float_as_int(lmsg[(size_t)p * 4 + 3].y);
-  if (damping) damping[e] = lmsg[(size_t)p * 4].w;
+  const int packed = fs.packed[p];
+  if (damping) damping[e] = fs.damp[p];
   if (damping_count) damping_count[e] = packed >> 3;
   if (robust_flag) robust_flag[e] = ((uint32_t)packed & kFlagRobust) ? 1u : 0u;
 }
 // NEW_KEYFRAME's damping_count / active_flag streams out of the caller's file-order arrays (NULL = unchanged): what k_state_set does
-__global__ __launch_bounds__(256) void k_keyframe_state_dev(const uint32_t* __restrict__ pos_edge, float4* __restrict__ lmsg,
+__global__ __launch_bounds__(256) void k_keyframe_state_dev(const uint32_t* __restrict__ pos_edge, int* __restrict__ fst_packed,
                                                             const int* __restrict__ new_count, const uint32_t* __restrict__ active_flag, uint32_t n) {
   const uint32_t p = blockIdx.x * 256 + threadIdx.x;
   if (p >= n) return;
   const uint32_t e = pos_edge[p];
   if (e == ~0u) return;
-  float4 st = lmsg[(size_t)p * 4 + 3];
-  const int packed = __float_as_int(st.y);
+  const int packed = fst_packed[p];
   int count = packed >> 3;
   uint32_t flags = (uint32_t)packed & 7u;
   if (flags & kFlagPad) return;
   if (new_count) count = new_count[e];
   if (active_flag) flags = active_flag[e] == 1u ? (flags | kFlagActive) : (flags & ~kFlagActive);
-  st.y = __int_as_float((int)(((uint32_t)count << 3) | flags));
-  lmsg[(size_t)p * 4 + 3] = st;
+  fst_packed[p] = (int)(((uint32_t)count << 3) | flags);
 }
 // Variable records <-> the caller's row-major arrays: word i of the caller's array (record i / w, word i % w) sits at word
 // (i / w) * stride + off + i % w of the padded device records (the element copies pack_cam / pack_lmk and the read paths make on the
@@ -2407,7 +2437,7 @@ uint32_t eval_blocks(uint32_t n_tiles) {
 }
 
 __global__ __launch_bounds__(256) void k_eval(const uint32_t* __restrict__ row_cam, const uint32_t* __restrict__ lmk_idx,
-                                              const float4* __restrict__ lmsg, const float4* __restrict__ fac, const float* __restrict__ cam_mu,
+                                              const int* __restrict__ fst_packed, const float4* __restrict__ fac, const float* __restrict__ cam_mu,
                                               const float* __restrict__ lmk_mu, const float* __restrict__ Kd,
                                               int num_undamped, DeviceEval* partials, unsigned long long* health,
                                               unsigned long long* health_out, uint32_t n_tiles) {
@@ -2422,7 +2452,7 @@ __global__ __launch_bounds__(256) void k_eval(const uint32_t* __restrict__ row_c
   o.sum_norm = 0; o.sum_half_sq = 0; o.n_active = 0; o.n_relin = 0; o.n_robust = 0; o.pad = 0;
   for (uint32_t b = blockIdx.x; b < n_tiles / 4; b += gridDim.x) {
     const uint32_t tile = b * 4 + w, p = tile * 64 + lane;
-    const int packed = __float_as_int(lmsg[(size_t)p * 4 + 3].y);
+    const int packed = fst_packed[p];
     const uint32_t flags = (uint32_t)packed & 7u;
     const bool pad = (flags & kFlagPad) != 0, active = !pad && (flags & kFlagActive) != 0;
     double s_norm = 0, s_half = 0;
@@ -2455,10 +2485,10 @@ __global__ __launch_bounds__(256) void k_eval(const uint32_t* __restrict__ row_c
 // The riding metric of a piece's LAST iteration, which no sweep follows: the same per-tile records from the same metric records
 // (one wave per tile, ride_metric), into slot counter - 1.
 __global__ __launch_bounds__(256) void k_eval_ride(const EvalRide ev, const uint32_t* __restrict__ row_cam, const uint32_t* __restrict__ lmk_idx,
-                                                   const float4* __restrict__ lmsg, const float4* __restrict__ fac, const float* __restrict__ Kd) {
+                                                   const int* __restrict__ fst_packed, const float4* __restrict__ fac, const float* __restrict__ Kd) {
   const uint32_t ws = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, p = ws * 64 + lane;
   const uint32_t cam_i = row_cam[p >> 4], lmk_i = lmk_idx[p];
-  const int packed = __float_as_int(lmsg[(size_t)p * 4 + 3].y);
+  const int packed = fst_packed[p];
   const float4 zg = fac[((size_t)ws * kFacG + 13) * 64 + lane];  // floats 52..55: z = .z, .w
   const float4 q0 = ev.cam_rec[(size_t)cam_i * 3], q1 = ev.cam_rec[(size_t)cam_i * 3 + 1], q2 = ev.cam_rec[(size_t)cam_i * 3 + 2];
   const float4 lq = ev.lmk_mean[lmk_i];
@@ -2639,8 +2669,8 @@ void launch_gather_slices(const float4* const* results, const BeliefArgs& b, int
   hipLaunchKernelGGL(k_gather_slices, dim3((widest * kCamRes4 + 255) / 256, (uint32_t)b.world), dim3(256), 0, s, results,
                      reinterpret_cast<float4*>(b.camb), b.cam_mu, b.cam_lin, b.n_cams, b.world, self, b.hoist, b.roll);
 }
-void launch_eval_ride(const EvalRide& ev, const uint32_t* row_cam, const uint32_t* lmk_idx, const float4* lmsg, const float4* fac, const float* K9_dev, hipStream_t s) {
-  hipLaunchKernelGGL(k_eval_ride, dim3(ev.n_tiles / 4), dim3(256), 0, s, ev, row_cam, lmk_idx, lmsg, fac, K9_dev);
+void launch_eval_ride_fst(const EvalRide& ev, const uint32_t* row_cam, const uint32_t* lmk_idx, const int* fst_packed, const float4* fac, const float* K9_dev, hipStream_t s) {
+  hipLaunchKernelGGL(k_eval_ride, dim3(ev.n_tiles / 4), dim3(256), 0, s, ev, row_cam, lmk_idx, fst_packed, fac, K9_dev);
 }
 void launch_eval_fold(const EvalRide& ev, uint32_t n_slots, void* out, hipStream_t s) {
   if (n_slots == 0) return;
@@ -2767,23 +2797,20 @@ hipError_t launch_persist(PersistArgs A, bool cooperative, hipStream_t s) {
   (void)hipLaunchKernel(f, dim3(grid), dim3(256), args, 0, s);
   return hipGetLastError();
 }
-void launch_state_get(const float4* lmsg, float* damping, int* packed, uint32_t n, hipStream_t s) {
-  hipLaunchKernelGGL(k_state_get, dim3(blocks_for(n)), dim3(256), 0, s, lmsg, damping, packed, n);
+void launch_upload_scatter_fst(float4* lmsg, const FactorState& fs, float4* fac, const float4* st, const float* var, uint32_t n, hipStream_t s) {
+  if (n) hipLaunchKernelGGL(k_upload_scatter, dim3(blocks_for(n)), dim3(256), 0, s, lmsg, fs, fac, st, var, n);
 }
-void launch_upload_scatter(float4* lmsg, float4* fac, const float4* st, const float* var, uint32_t n, hipStream_t s) {
-  if (n) hipLaunchKernelGGL(k_upload_scatter, dim3(blocks_for(n)), dim3(256), 0, s, lmsg, fac, st, var, n);
-}
-void launch_state_set(float4* lmsg, const int* new_count, const uint32_t* ctl, uint32_t n, hipStream_t s) {
-  hipLaunchKernelGGL(k_state_set, dim3(blocks_for(n)), dim3(256), 0, s, lmsg, new_count, ctl, n);
+void launch_fst_set(int* fst_packed, const int* new_count, const uint32_t* ctl, uint32_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_state_set, dim3(blocks_for(n)), dim3(256), 0, s, fst_packed, new_count, ctl, n);
 }
 void launch_upload_dev(const UploadDev& a, hipStream_t s) {
   if (a.n) hipLaunchKernelGGL(k_upload_dev, dim3(blocks_for(a.n)), dim3(256), 0, s, a);
 }
-void launch_read_state_dev(const uint32_t* pos_edge, const float4* lmsg, float* damping, int* damping_count, uint32_t* robust_flag, uint32_t n, hipStream_t s) {
-  if (n) hipLaunchKernelGGL(k_read_state_dev, dim3(blocks_for(n)), dim3(256), 0, s, pos_edge, lmsg, damping, damping_count, robust_flag, n);
+void launch_read_state_dev(const uint32_t* pos_edge, const FactorState& fs, float* damping, int* damping_count, uint32_t* robust_flag, uint32_t n, hipStream_t s) {
+  if (n) hipLaunchKernelGGL(k_read_state_dev, dim3(blocks_for(n)), dim3(256), 0, s, pos_edge, fs, damping, damping_count, robust_flag, n);
 }
-void launch_keyframe_state_dev(const uint32_t* pos_edge, float4* lmsg, const int* new_count, const uint32_t* active_flag, uint32_t n, hipStream_t s) {
-  if (n) hipLaunchKernelGGL(k_keyframe_state_dev, dim3(blocks_for(n)), dim3(256), 0, s, pos_edge, lmsg, new_count, active_flag, n);
+void launch_keyframe_state_dev(const uint32_t* pos_edge, int* fst_packed, const int* new_count, const uint32_t* active_flag, uint32_t n, hipStream_t s) {
+  if (n) hipLaunchKernelGGL(k_keyframe_state_dev, dim3(blocks_for(n)), dim3(256), 0, s, pos_edge, fst_packed, new_count, active_flag, n);
 }
 void launch_rec_copy(const RecSegs& t, bool to_rec, hipStream_t s) {
   uint32_t most = 0;
@@ -2798,10 +2825,10 @@ void launch_means(const float4* camb, const float4* lmkb, float* cam_mu, float* 
   hipLaunchKernelGGL(k_means, dim3(blocks_for((uint64_t)n_cams + n_lmks)), dim3(256), 0, s, (const float*)camb,
                      (const float*)lmkb, cam_mu, lmk_mu, n_cams, n_lmks, health2, health2_next, count_cams ? 1 : 0);
 }
-void launch_eval(const uint32_t* row_cam, const uint32_t* lmk_idx, const float4* lmsg, const float4* fac, const float* cam_mu,
+void launch_eval_fst(const uint32_t* row_cam, const uint32_t* lmk_idx, const int* fst_packed, const float4* fac, const float* cam_mu,
                  const float* lmk_mu, const float* K9_dev, int num_undamped_iters, DeviceEval* partials,
                  unsigned long long* health2, unsigned long long* health2_out, uint32_t n_tiles, hipStream_t s) {
-  hipLaunchKernelGGL(k_eval, dim3(eval_blocks(n_tiles)), dim3(256), 0, s, row_cam, lmk_idx, lmsg, fac, cam_mu, lmk_mu, K9_dev,
+  hipLaunchKernelGGL(k_eval, dim3(eval_blocks(n_tiles)), dim3(256), 0, s, row_cam, lmk_idx, fst_packed, fac, cam_mu, lmk_mu, K9_dev,
                      num_undamped_iters, partials, health2, health2_out, n_tiles);
 }
 

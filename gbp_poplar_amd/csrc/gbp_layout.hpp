@@ -61,6 +61,15 @@ struct Layout {
   std::vector<uint32_t> tile_perm;                    // [n_tiles] wave slot -> tile; EMPTY = identity
 };
 
+// Which segments (four positions: lanes 4s .. 4s + 3) of a tile hold a factor at all: bit s of the result (pos_edge64: the tile's 64 entries)
+inline uint32_t tile_seg_mask(const uint32_t* pos_edge64) {
+  uint32_t m = 0;
+  for (uint32_t s = 0; s < 16; ++s)
+    for (uint32_t k = 0; k < 4; ++k)
+      if (pos_edge64[s * 4 + k] != kNoEdge) { m |= 1u << s; break; }
+  return m;
+}
+
 // Builds the layout of `pr` for shard `sh` (NULL = the whole graph).  tile_order as gbp_params.tile_order.
 // Returns GBP_OK or GBP_ERR_INVALID (+ text in err): null / empty problem, index out of range, bad shard, more than 2^32 positions.
 int layout_build(const gbp_problem* pr, int tile_order, const gbp_shard* sh, const LayoutOptions& opt, Layout& out, std::string& err);

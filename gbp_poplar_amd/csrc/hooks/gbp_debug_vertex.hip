@@ -116,7 +116,7 @@ __global__ __launch_bounds__(64) void k_debug_vertex(const float* __restrict__ i
   } else if (OP == 1) {
     bool relin;
     factor_update<false>(fac, cm, mu, lm, cb, lb, K, hp, damping, count, flags, var, active, oc_eta, oc_lam, bi, ol, relin,
-                         [&](float (&)[6], float (&)[3], CamLin&) {});
+                         [&](float (&)[6], float (&)[3], CamLin&, float&) {});
     GBP_UNROLL
     for (int i = 0; i < 9; ++i) mu_out[i] = mu[i];
   } else {
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(64) void k_debug_vertex(const float* __restrict__ i
     lb[3] = u[0]; lb[13] = u[1]; lb[14] = u[2];
     bool relin;
     factor_update<true>(fac, cm, mu, lm, cb, lb, K, hp, damping, count, flags, var, active, oc_eta, oc_lam, bi, ol, relin,
-                        [&](float (&x0c)[6], float (&x0l)[3], CamLin& cl) {      // as sweep_tile hands them to a relinearising lane
+                        [&](float (&x0c)[6], float (&x0l)[3], CamLin& cl, float&) {      // as sweep_tile hands them to a relinearising lane
                           x0c[0] = m0.x; x0c[1] = m0.y; x0c[2] = m0.z; x0c[3] = m0.w; x0c[4] = m1.x; x0c[5] = m1.y;
                           cam_lin_unpack(q, cl);
                           lmk_mean(lb, x0l);

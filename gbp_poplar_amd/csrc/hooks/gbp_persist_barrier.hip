@@ -28,7 +28,7 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
   // ---- phase-A role: sweep tile w.  State that only this lane ever touches lives in registers for the whole launch.
   const bool has_tile = w < A.n_tiles;
   const uint32_t tile = has_tile ? w : 0u, p = tile * 64 + lane;
-  const uint32_t lm_tile4 = tile * 256u;                        // first float4 of the wave's 64 landmark-message records
+  const uint32_t lm_tile4 = tile * (uint32_t)(64 * kLmsgG);     // first float4 of the wave's 64 landmark messages
   float fac[56], cm[28], lm[16];
   uint32_t cam_i = 0, lmk_i = 0;
   bool fac_dirty = false;
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
       float oc_eta[6], oc_lam[36], bi[9], ol[16];
       bool relin;
       factor_update<true>(fac, cm, mu, lm, cb, lb, K, a.hp, damping, count, flags, var, active, oc_eta, oc_lam, bi, ol, relin,
-                             [&](float (&x0c)[6], float (&x0l)[3], CamLin& cl) {
+                             [&](float (&x0c)[6], float (&x0l)[3], CamLin& cl, float&) {
                                x0c[0] = m0.x; x0c[1] = m0.y; x0c[2] = m0.z; x0c[3] = m0.w; x0c[4] = m1.x; x0c[5] = m1.y;
                                x0l[0] = l0.x; x0l[1] = l0.y; x0l[2] = l0.z;
                                cam_lin_unpack(clq, cl);
@@ -170,8 +170,7 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
       tile_regs_refresh(ol, oc_eta, oc_lam, damping, count, flags, var, lm, cm);
       if (it + 1 == A.n_iters) tile_cmsg_store(a, tile, lane, oc_eta, bi, active);
       // the wave's landmark messages go to memory (phase B gathers them by position); this lane keeps its own copy
-      lm_tile_out(stage, lane, [&](uint32_t q) { return make_float4(ol[4 * q], ol[4 * q + 1], ol[4 * q + 2], ol[4 * q + 3]); },
-                  [&](uint32_t k, float4 v) { X_lmsg.st4(lm_tile4 + k * 64u + lane, v); });
+      lmsg_tile_out(stage, lane, ol, [&](uint32_t k, float4 v) { X_lmsg.st4(lm_tile4 + k * 64u + lane, v); });
       {  // camera half of the belief reduction: per-row tree sums, as in k_sweep
         const uint32_t rp4 = (p >> 4) * (uint32_t)kCamRec4;
         row16_sums_store(oc_eta, oc_lam, lane, [&](uint32_t g, float4 v) { X_rowp.st4(rp4 + g, v); });
@@ -277,7 +276,7 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       if (cam_live && cam_wave) X_camb.st1(v * (uint32_t)kCamRec + cj, sh[wib][cj]);
     } else if (lmk_wave) {
-      float4 acc = lmk_prior4;
+      float4 acc = lmk_quad_dense(lmk_prior4, q4);      // the sums run on the dense image of the messages (lmsg_load in gbp_kernels.hip)
       {  // both batches of loads are issued before the first add (one memory round trip for up to 30 slots: the
          // wave has 512 registers per lane to itself); the adds stay in slot order
         float4 m[15], m2[15];
@@ -311,6 +310,7 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
             if ((uint32_t)k < nleft) { acc.x = acc.x + m[k].x; acc.y = acc.y + m[k].y; acc.z = acc.z + m[k].z; acc.w = acc.w + m[k].w; }
         }
       }
+      acc = lmk_quad_record(acc, q4);
       float rec[16];
       GBP_UNROLL
       for (int k = 0; k < 4; ++k) {
@@ -374,5 +374,5 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
     metric((uint32_t)A.n_iters - 1u, __float_as_int(lm[13]), cmv, lmu);
   }
 
-  if (has_tile) tile_regs_store(a, tile, lane, fac, fac_dirty);
+  if (has_tile) tile_regs_store(a, tile, lane, fac, fac_dirty, lm);
 }

@@ -196,6 +196,7 @@ def tile_order_local(tile_class, window=96, n_classes=8):
 
 
 LAYOUT_DIMS = ("C", "L", "E", "lmk_begin", "lmk_end", "L_loc", "E_loc", "n_rows", "n_tiles", "Ep", "row_window")
+LAYOUT_LMSG_MAPS = ((11, "lmsg_maps"), (12, "lmsg_live"))      # [192][4] record, piece, index rebuilt, LDS slot;  [n_tiles][192] 0 / 1
 LAYOUT_ARRAYS = ("pos_edge", "pos_cam", "pos_lmk_loc", "pos_lpos", "cam_row_ptr", "row_slot", "row_cam", "lmk_ptr", "lmk_fpos",
                  "lmk_ix", "tile_perm")
 
@@ -228,6 +229,10 @@ def layout_build(cam_id, lmk_id, n_cams, n_lmks, tile_order=0, shard=None, optio
             data, n = cabi.c_u32p(), C.c_size_t()
             _chk(lib.gbp_debug_layout_array(h, i, C.byref(data), C.byref(n)), "gbp_debug_layout_array")
             out[name] = np.ctypeslib.as_array(data, shape=(n.value,)).copy() if n.value else np.zeros(0, np.uint32)
+        for i, name in LAYOUT_LMSG_MAPS:      # the address maps of a tile's landmark messages (csrc/gbp_kernels.h), evaluated on the host
+            data, n = cabi.c_u32p(), C.c_size_t()
+            _chk(lib.gbp_debug_layout_array(h, i, C.byref(data), C.byref(n)), "gbp_debug_layout_array")
+            out[name] = np.ctypeslib.as_array(data, shape=(n.value,)).copy()
     finally:
         lib.gbp_debug_layout_free(h)
     return out

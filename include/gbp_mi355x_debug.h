@@ -106,7 +106,10 @@ GBP_API int gbp_debug_layout_build(const gbp_problem* problem, int tile_order, c
 GBP_API int gbp_debug_layout_dims(const gbp_layout* lay, uint32_t* dims);
 /* which: 0 pos_edge [Ep] (~0 = pad), 1 pos_cam [Ep], 2 pos_lmk_loc [Ep], 3 pos_lpos [Ep], 4 cam_row_ptr [C+1], 5 row_slot
  * [n_rows] or empty, 6 row_cam [Ep/16], 7 lmk_ptr [L_loc+1], 8 lmk_fpos [E_loc], 9 lmk_ix [L_loc][16], 10 tile_perm [n_tiles] or
- * empty.  The pointer stays valid until gbp_debug_layout_free. */
+ * empty.  11, 12: the address maps of a tile's landmark messages as the kernels evaluate them (host evaluation; float4 index i4 of
+ * a tile's 192): 11 [192][4] = record, piece, the index rebuilt from (record, piece), LDS stage slot;  12 [n_tiles][192] = 1 where the
+ * float4 belongs to a segment (four positions) of that tile that holds a factor, else 0.
+ * The pointer stays valid until gbp_debug_layout_free. */
 GBP_API int gbp_debug_layout_array(const gbp_layout* lay, int which, const uint32_t** data, size_t* n);
 GBP_API void gbp_debug_layout_free(gbp_layout* lay);
 /* The local XCD-aware execution order of the sweep (gbp_params.tile_order = 3) as a pure function of the tiles' landmark
