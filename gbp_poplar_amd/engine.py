@@ -337,6 +337,13 @@ class GbpEngine:
         self._need_hooks()
         self._chk(self.lib.gbp_debug_persist_flow(self.h, int(bool(on))), "gbp_debug_persist_flow")
 
+    def sweep_variant(self):
+        """(SweepArgs.policy bits, segment-skipping instantiation?) of the sweep this ctx launches on the two-kernel path (test hook)"""
+        self._need_hooks()
+        pol, seg = C.c_uint32(0), C.c_int(0)
+        self._chk(self.lib.gbp_debug_sweep_variant(self.h, C.byref(pol), C.byref(seg)), "gbp_debug_sweep_variant")
+        return int(pol.value), bool(seg.value)
+
     def persist_verify(self, on):
         """redundant records in the persistent kernel (test hook): every tagged record published twice and compared by its consumers;
         returns the mismatches counted since the last call"""

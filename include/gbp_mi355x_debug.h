@@ -80,6 +80,9 @@ GBP_API int gbp_debug_force_sweep_policy(int policy);
 /* the sweep of later gbp_create calls skips the all-pad 64-byte segments of its tiles (k_sweep<..., SEG>): -1 = by shape (the default:
  * graphs of >= 2 048 tiles where they are >= 1 % of the positions), 0 = never, 1 = always; identical results — A/B measurements and tests */
 GBP_API int gbp_debug_force_seg_skip(int mode);
+/* which instantiation of the sweep a ctx launches on the two-kernel path: *policy = its SweepArgs.policy bits (forced or chosen by
+ * shape), *seg_skip = 1 where it is the one that skips the all-pad segments (asked for AND possible: hoisted means, policy 0) */
+GBP_API int gbp_debug_sweep_variant(gbp_ctx* ctx, uint32_t* policy, int* seg_skip);
 /* bursts without the metric on a graph that runs in the persistent kernel: 1 (default) = k_persist_flow (hand-offs through tagged
  * records, no device-wide barrier), 0 = k_persist<false> (counter barriers); identical results — A/B measurements and tests */
 GBP_API int gbp_debug_persist_flow(gbp_ctx* ctx, int on);
