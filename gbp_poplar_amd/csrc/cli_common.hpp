@@ -14,6 +14,7 @@
 #pragma once
 #include "../../include/gbp_mi355x.h"
 #include "../../include/gbp_mi355x_multi.h"       // --ipus N: one forked rank per GPU
+#include "gbp_transport.hpp"                      // --transport: the names of gbp_comm_init's transport numbers
 #include "../../include/gbp_mi355x_compat.h"      // MetricPipe: the metric in two halves (gbp_iterate_eval / gbp_eval_end), so that printing overlaps the next iterations
 
 #include <condition_variable>
@@ -96,7 +97,7 @@ struct Options {
   bool verbose = false;
   unsigned long long seed = 0;
   int eval_every = 1;
-  int transport = 0;            // --transport: 0 auto, 1 RCCL, 2 host-staged (ranks sharing a GPU), 3 p2p (direct peer memory), 4 p2p-slices (the same, cameras reduced in slices)
+  int transport = (int)gbp::Transport::Auto;   // --transport (gbp_transport.hpp): what gbp_comm_init is given
   std::string out_file;         // --out_file: write the refined problem (belief means) in the input's format
   bool force_sharded = false;   // --force_sharded: run the multi-rank code path (fork, shard ctx, communicator) with one rank
 };
@@ -167,7 +168,11 @@ inline int parse(int argc, char** argv, bool slam, Options& o) {
       else if (k == "eval_every") o.eval_every = std::max(1, std::stoi(v));
       else if (k == "force_sharded") o.force_sharded = B(v);
       else if (k == "out_file") o.out_file = v;
-      else if (k == "transport") o.transport = v == "rccl" ? 1 : v == "host" ? 2 : v == "p2p" ? 3 : v == "p2p-slices" ? 4 : v == "auto" ? 0 : std::stoi(v);
+      else if (k == "transport") {
+        using T = gbp::Transport;
+        o.transport = v == "rccl" ? (int)T::Rccl : v == "host" ? (int)T::HostStaged : v == "p2p" ? (int)T::P2p : v == "p2p-slices" ? (int)T::P2pSlices :
+                      v == "auto" ? (int)T::Auto : std::stoi(v);
+      }
       else { std::cerr << "unrecognised option '--" << k << "'\n"; return 2; }
     }
   } catch (const std::exception&) {

@@ -15,48 +15,155 @@ using namespace gbp::api;
 namespace gbp {
 namespace api {
 
-// The direct peer-memory transport exchanges through the communicator's own buffer: send_dev / recv_dev are this rank's slot / the
-// whole [world][C][44] of the parity of the NEXT exchange (re-bound after every exchange).  No-op for the other transports.
-void bind_exchange(gbp_ctx* c) {
-  float* x = c->comm ? c->comm->exchange_buffer() : nullptr;
-  if (!x) return;
-  float* recv = x + (size_t)c->comm->next_parity() * c->world * c->C * kCamRec;
-  c->recv_dev = recv;
-  c->send_dev = recv + (size_t)c->rank * c->C * kCamRec;
+// A peer-memory transport exchanges through the communicator's own buffer: send_dev / recv_dev are this rank's slot / the whole
+// [world][C][44] of the NEXT exchange (re-bound after every exchange).  No-op for the other transports.
+static void bind_exchange(gbp_ctx* c) {
+  if (PeerComm* pc = peers(c->comm)) {
+    c->send_dev = pc->send_slot();
+    c->recv_dev = pc->next_block();
+  }
 }
 
-const float* last_own_slot(gbp_ctx* c) {
-  if (!c->comm || !c->comm->sliced() || c->world != 1) return nullptr;
-  return c->comm->exchange_buffer() + (size_t)(c->comm->next_parity() ^ 1) * c->C * kCamRec;
-}
-
-// p2p: every rank's partials of the LAST exchange, read in place (device table); nullptr for the other transports — and for a 1-rank
-// p2p-slices communicator, which launches no peer kernel: its refreshes read last_own_slot() with the plain combine
-const float* const* last_peers(gbp_ctx* c) {
-  if (last_own_slot(c)) return nullptr;
-  return c->comm && c->comm->exchange_buffer() ? c->comm->peer_table(c->comm->next_parity() ^ 1) : nullptr;
-}
-
-// plain exchange on the ctx's stream (LINEARISE, refreshes): partials in send_dev -> recv_dev of every rank
-int exchange_now(gbp_ctx* c) {
+// plain exchange on the ctx's stream (LINEARISE, refreshes) or on s: partials in send_dev -> recv_dev of every rank
+int exchange_now(gbp_ctx* c, hipStream_t s) {
   COMMCHK(c, c->comm->all_gather(static_cast<const float*>(c->send_dev), static_cast<float*>(c->recv_dev),
-                                 (size_t)c->C * kCamRec, c->stream, e_));
+                                 (size_t)c->C * kCamRec, s ? s : c->stream, e_));
   bind_exchange(c);
   return GBP_OK;
 }
 
-// One iteration of a sharded ctx: sweep + local camera partials, the ALL-GATHER of the partials on the communication
-// stream while the rank-local landmark half of the belief update runs, then the camera combine.  With a stream-ordered
-// transport (RCCL) nothing here blocks the host, so the sequence can be captured into a hipGraph.
+// the exchange without a copy: stream sync + ONE region barrier; *p = the parity it closed, whose slots the readers behind it take in place
+static int advance_exchange(gbp_ctx* c, PeerComm* pc, int* p) {
+  COMMCHK(c, pc->advance(c->stream, p, e_));
+  bind_exchange(c);
+  return GBP_OK;
+}
+
+// a new problem (gbp_upload): what the exchange gathers into starts from zero
+int zero_exchange(gbp_ctx* c) {
+  if (PeerComm* pc = peers(c->comm)) HIPCHK(c, pc->zero(c->stream));
+  else if (exch(c) && c->recv_dev) HIPCHK(c, hipMemsetAsync(c->recv_dev, 0, (size_t)c->world * c->C * kCamRec * 4, c->stream));
+  return GBP_OK;
+}
+
+// ---- who combines the cameras ----------------------------------------------------------------------------------------------------
+// | transport                  | in the iteration (single stream, behind the partial_only launch)                                 | prior-only refresh (refresh_beliefs_from_partials)                                |
+// | RCCL, host-staged          | all_gather into recv_dev, then launch_beliefs(b, true, false) with gathered = recv_dev            | launch_beliefs(b, true, do_lmk) with gathered = recv_dev                           |
+// | p2p                        | advance, then launch_beliefs_cam_peers(b, table of that parity)                                   | launch_beliefs_cam_peers(b, last table), then launch_beliefs(b, false, true) if do_lmk |
+// | p2p-slices, world > 1      | advance (barrier A); launch_beliefs_cam_slice; stream sync; barrier (B); launch_gather_slices     | as p2p                                                                             |
+// | p2p-slices, world = 1      | advance, then launch_beliefs(b, true, false) with gathered = own slot of that parity              | launch_beliefs(b, true, do_lmk) with gathered = own slot of the last parity        |
+// | no communicator, world > 1 | not this path (caller's exchange)                                                                 | gathered = recv_dev; error "exchange buffers not set" without one                  |
+// | no communicator, world = 1 | not this path                                                                                     | gathered = local, b.world = 1                                                      |
+// Return codes by cause: GBP_ERR_HIP (a launch, a synchronisation), GBP_ERR_COMM (the exchange), GBP_ERR_STATE (no device code).
+
+// the iteration's column: the exchange and the camera combine on the ctx's stream; x1 (profiling): recorded behind the all-gather
+static int combine_cameras_in_iteration(gbp_ctx* c, hipEvent_t x1) {
+  BeliefArgs b = belief_args(c);
+  b.roll = 1;
+  PeerComm* pc = peers(c->comm);
+  int p = 0;
+  switch (c->comm->kind()) {
+    case Transport::P2p:
+      if (!launch_beliefs_cam_peers) return fail(c, GBP_ERR_STATE, "no device code for the p2p combine");
+      if (int rc = advance_exchange(c, pc, &p)) return rc;
+      launch_beliefs_cam_peers(b, pc->peer_table(p), c->stream);
+      break;
+    case Transport::P2pSlices:
+      if (c->world == 1) {      // nothing to share: no peer kernel
+        if (int rc = advance_exchange(c, pc, &p)) return rc;
+        b.gathered = pc->last_own_slot();
+        launch_beliefs(b, true, false, c->stream);
+        break;
+      }
+      // the reduce of this rank's slice of the cameras (sums in rank order out of every peer's partials, the camera chain, once per
+      // camera), then the gather of the other slices' finished records — every rank ends with the tables the full combine leaves
+      if (!launch_beliefs_cam_slice || !launch_gather_slices) return fail(c, GBP_ERR_STATE, "no device code for the sliced exchange");
+      if (int rc = advance_exchange(c, pc, &p)) return rc;
+      CamSlice sl;
+      slice_bounds(c->C, c->world, c->rank, &sl.lo, &sl.hi);
+      sl.res = pc->result_buffer(p);
+      launch_beliefs_cam_slice(b, pc->peer_table(p), sl, c->stream);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      COMMCHK(c, c->comm->barrier(e_));
+      launch_gather_slices(pc->result_table(p), b, c->rank, c->stream);
+      break;
+    default:
+      if (int rc = exchange_now(c)) return rc;
+      if (x1) HIPCHK(c, hipEventRecord(x1, c->stream));
+      b.gathered = static_cast<const float*>(c->recv_dev);
+      launch_beliefs(b, true, false, c->stream);
+      break;
+  }
+  HIPCHK(c, hipGetLastError());
+  return GBP_OK;
+}
+
+// the refresh's column: b as the caller set it up (roll, weaken)
+int refresh_cameras(gbp_ctx* c, BeliefArgs& b, bool do_lmk) {
+  PeerComm* pc = peers(c->comm);
+  const Transport kind = c->comm ? c->comm->kind() : Transport::Auto;      // (Auto: no communicator)
+  if (kind == Transport::P2p || (kind == Transport::P2pSlices && c->world > 1)) {
+    // the last exchange's partials are read where they lie; the landmark half, which needs nothing from other ranks, in a launch of its own
+    if (!launch_beliefs_cam_peers) return fail(c, GBP_ERR_STATE, "no device code for the p2p combine");
+    launch_beliefs_cam_peers(b, pc->last_table(), c->stream);
+    if (do_lmk) launch_beliefs(b, false, true, c->stream);
+  } else {
+    if (kind == Transport::P2pSlices) {
+      b.gathered = pc->last_own_slot();      // (recv_dev is the parity of the NEXT exchange)
+    } else if (!exch(c)) {
+      b.gathered = P<float>(c->local); b.world = 1;
+    } else {
+      if (!c->recv_dev) return fail(c, GBP_ERR_STATE, "exchange buffers not set");
+      b.gathered = static_cast<const float*>(c->recv_dev);
+    }
+    launch_beliefs(b, true, do_lmk, c->stream);
+  }
+  HIPCHK(c, hipGetLastError());
+  return GBP_OK;
+}
+
+// The two-stream schedule (RCCL): the communication stream (highest priority) takes the whole camera side of the exchange — local
+// partial sums, then the all-gather — right after the sweep; the landmark half of the belief update, which needs nothing from other
+// ranks, runs beside it on the main stream.  x0 / x1 (profiling): a bracket around the camera side on its stream.
+static int enqueue_cameras_two_streams(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1) {
+  HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
+  HIPCHK(c, hipStreamWaitEvent(c->comm_stream, c->ev_fork, 0));
+  if (x0) HIPCHK(c, hipEventRecord(x0, c->comm_stream));
+  enqueue_cam_partials(c, static_cast<float*>(c->send_dev), c->comm_stream);
+  if (int rc = exchange_now(c, c->comm_stream)) return rc;
+  if (x1) HIPCHK(c, hipEventRecord(x1, c->comm_stream));
+  HIPCHK(c, hipEventRecord(c->ev_join, c->comm_stream));
+  BeliefArgs b = belief_args(c);
+  b.roll = 1;
+  launch_beliefs(b, false, true, c->stream);
+  HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+  b.gathered = static_cast<const float*>(c->recv_dev);
+  launch_beliefs(b, true, false, c->stream);
+  HIPCHK(c, hipGetLastError());
+  return GBP_OK;
+}
+
+// ONE stream: the local camera partial sums ride in the launch of the landmark half (camera blocks write send_dev and leave,
+// landmark blocks do the rank-local belief update), so an iteration is sweep -> beliefs -> exchange -> combine: three kernels and
+// one collective.  Still no host wait with a stream-ordered transport.
+static int enqueue_cameras_one_stream(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1) {
+  BeliefArgs b = belief_args(c);
+  b.cam_local = static_cast<float*>(c->send_dev);
+  b.partial_only = 1;
+  b.roll = 1;
+  launch_beliefs(b, true, true, c->stream);
+  if (x0) HIPCHK(c, hipEventRecord(x0, c->stream));
+  return combine_cameras_in_iteration(c, x1);
+}
+
+// One iteration of a sharded ctx: sweep, then the camera side of the exchange and the belief update in one of the two schedules.
+// With a stream-ordered transport (RCCL) nothing here blocks the host, so the sequence can be captured into a hipGraph.
 static int enqueue_sharded_iteration(gbp_ctx* c, const SweepArgs& a) {
   if (c->profile_stages) {
     if (c->pending_sweep_ev.size() >= 256) drain_sweep_events(c);
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(c, hipEventCreate(&e0));
-    if (hipError_t e_ = hipEventCreate(&e1); e_ != hipSuccess) {
-      (void)hipEventDestroy(e0);
-      return fail(c, GBP_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e_));
-    }
+    if (int rc = event_pair(c, &e0, &e1)) return rc;
     c->pending_sweep_ev.emplace_back(e0, e1);
     HIPCHK(c, hipEventRecord(e0, c->stream));
     launch_sweep(a, c->n_tiles, c->hoist, c->stream);
@@ -64,99 +171,12 @@ static int enqueue_sharded_iteration(gbp_ctx* c, const SweepArgs& a) {
   } else {
     launch_sweep(a, c->n_tiles, c->hoist, c->stream);
   }
-  // The communication stream (highest priority) takes the whole camera side of the exchange — local partial sums, then the
-  // all-gather — right after the sweep; the landmark half of the belief update runs beside it on the main stream.
-  const bool ordered = c->comm->stream_ordered() && !c->comm_single_stream;
   hipEvent_t x0 = nullptr, x1 = nullptr;     // profiling: how long the camera side of the exchange takes on its stream
   if (c->profile_stages && c->comm->stream_ordered()) {
-    HIPCHK(c, hipEventCreate(&x0));
-    if (hipError_t e_ = hipEventCreate(&x1); e_ != hipSuccess) { (void)hipEventDestroy(x0); return fail(c, GBP_ERR_HIP, "hipEventCreate"); }
+    if (int rc = event_pair(c, &x0, &x1)) return rc;
     c->pending_exch_ev.emplace_back(x0, x1);
   }
-  if (ordered) {
-    HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(c->comm_stream, c->ev_fork, 0));
-    if (x0) HIPCHK(c, hipEventRecord(x0, c->comm_stream));
-    enqueue_cam_partials(c, static_cast<float*>(c->send_dev), c->comm_stream);
-    COMMCHK(c, c->comm->all_gather(static_cast<const float*>(c->send_dev), static_cast<float*>(c->recv_dev),
-                                   (size_t)c->C * kCamRec, c->comm_stream, e_));
-    if (x1) HIPCHK(c, hipEventRecord(x1, c->comm_stream));
-    HIPCHK(c, hipEventRecord(c->ev_join, c->comm_stream));
-  }
-  if (ordered) {
-    {  // the landmark half needs nothing from other ranks: it runs beside the all-gather
-      BeliefArgs b = belief_args(c);
-      b.roll = 1;
-      launch_beliefs(b, false, true, c->stream);
-    }
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-  } else {
-    // ONE stream: the local camera partial sums ride in the launch of the landmark half (camera blocks write send_dev and
-    // leave, landmark blocks do the rank-local belief update), so an iteration is sweep -> beliefs -> all-gather -> combine:
-    // three kernels and one collective.  Still no host wait with a stream-ordered transport.
-    {
-      BeliefArgs b = belief_args(c);
-      b.cam_local = static_cast<float*>(c->send_dev);
-      b.partial_only = 1;
-      b.roll = 1;
-      launch_beliefs(b, true, true, c->stream);
-    }
-    if (x0) HIPCHK(c, hipEventRecord(x0, c->stream));
-    if (c->comm->sliced() && c->world > 1) {
-      // p2p-slices: barrier A behind the partials, the reduce of this rank's slice of the cameras (sums in rank order out of every
-      // peer's partials, the camera chain, once per camera), barrier B behind it, then the gather of the other slices' finished
-      // records — every rank ends with the tables the full combine leaves
-      if (!launch_beliefs_cam_slice || !launch_gather_slices) return fail(c, GBP_ERR_STATE, "no device code for the sliced exchange");
-      const int p = c->comm->next_parity();
-      COMMCHK(c, c->comm->exchange_in_place(c->stream, e_));
-      BeliefArgs b = belief_args(c);
-      b.roll = 1;
-      CamSlice sl;
-      slice_bounds(c->C, c->world, c->rank, &sl.lo, &sl.hi);
-      sl.res = c->comm->result_buffer(p);
-      launch_beliefs_cam_slice(b, c->comm->peer_table(p), sl, c->stream);
-      bind_exchange(c);
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      COMMCHK(c, c->comm->barrier(e_));
-      launch_gather_slices(c->comm->result_table(p), b, c->rank, c->stream);
-      HIPCHK(c, hipGetLastError());
-      return GBP_OK;
-    }
-    if (c->comm->sliced()) {
-      // ... with ONE rank: nothing to share — the plain combine over this rank's own slot, no peer kernel
-      const float* mine = static_cast<const float*>(c->send_dev);
-      COMMCHK(c, c->comm->exchange_in_place(c->stream, e_));
-      BeliefArgs b = belief_args(c);
-      b.gathered = mine;
-      b.roll = 1;
-      launch_beliefs(b, true, false, c->stream);
-      bind_exchange(c);
-      HIPCHK(c, hipGetLastError());
-      return GBP_OK;
-    }
-    if (c->comm->exchange_buffer()) {
-      // p2p: stream sync + ONE region barrier, then the combine reads every rank's partials in place — no gather copy
-      if (!launch_beliefs_cam_peers) return fail(c, GBP_ERR_STATE, "no device code for the p2p combine");
-      COMMCHK(c, c->comm->exchange_in_place(c->stream, e_));
-      BeliefArgs b = belief_args(c);
-      b.roll = 1;
-      launch_beliefs_cam_peers(b, last_peers(c), c->stream);
-      bind_exchange(c);
-      HIPCHK(c, hipGetLastError());
-      return GBP_OK;
-    }
-    if (int rc = exchange_now(c)) return rc;
-    if (x1) HIPCHK(c, hipEventRecord(x1, c->stream));
-  }
-  {
-    BeliefArgs b = belief_args(c);
-    b.gathered = static_cast<const float*>(c->recv_dev);
-    b.roll = 1;
-    launch_beliefs(b, true, false, c->stream);
-  }
-  HIPCHK(c, hipGetLastError());
-  return GBP_OK;
+  return c->comm->stream_ordered() && !c->comm_single_stream ? enqueue_cameras_two_streams(c, x0, x1) : enqueue_cameras_one_stream(c, x0, x1);
 }
 
 int iterate_sharded(gbp_ctx* c, int n) {
@@ -208,6 +228,16 @@ int iterate_sharded(gbp_ctx* c, int n) {
 }  // namespace gbp
 
 // ---- communicator: the exchange step owned by the library (RCCL over xGMI from the C++ host) ------------------------
+// the second stream of the two-stream schedule, made when first needed.  Highest priority: the all-gather is issued while the
+// landmark half of k_beliefs fills the GPU; it must not queue behind those blocks (the camera combine of every rank waits for it)
+static int ensure_comm_stream(gbp_ctx* c) {
+  if (c->comm_stream || c->comm_single_stream) return GBP_OK;
+  int least = 0, greatest = 0;
+  HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+  HIPCHK(c, hipStreamCreateWithPriority(&c->comm_stream, hipStreamNonBlocking, greatest));
+  return GBP_OK;
+}
+
 static int comm_attach(gbp_ctx* c, gbp::Comm* comm) {
   if (int rc = settle(c)) { delete comm; return rc; }
   c->comm = comm;
@@ -222,21 +252,14 @@ static int comm_attach(gbp_ctx* c, gbp::Comm* comm) {
   // (sendbuff == recvbuff + rank * count is the in-place form of ncclAllGather: the collective then moves only what comes from
   // other ranks — with a 1-rank communicator nothing at all, where the out-of-place form was a 5 us copy kernel per iteration,
   // profiles/r06_sharded_timeline.md).  (zero-filled on the ctx's stream, in front of everything that uses it)
-  if (comm->exchange_buffer()) {     // p2p: the communicator's own buffer, [2 parities][world][C][44]
-    bind_exchange(c);
-  } else {
+  bind_exchange(c);      // p2p: the communicator's own buffer
+  if (!peers(comm)) {
     if (!c->xrecv.p)
       if (int rc = dev_alloc(c, c->xrecv, (size_t)c->world * c->C * kCamRec * 4)) return rc;
     c->recv_dev = c->xrecv.p;
     c->send_dev = static_cast<float*>(c->xrecv.p) + (size_t)c->rank * c->C * kCamRec;
   }
-  if (!c->comm_stream && !c->comm_single_stream) {
-    // highest priority: the all-gather is issued while the landmark half of k_beliefs fills the GPU; it must not queue
-    // behind those blocks (the camera combine of every rank waits for it)
-    int least = 0, greatest = 0;
-    HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-    HIPCHK(c, hipStreamCreateWithPriority(&c->comm_stream, hipStreamNonBlocking, greatest));
-  }
+  if (int rc = ensure_comm_stream(c)) return rc;
   if (!c->ev_fork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
   if (!c->ev_join) HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
   c->comm_warm = 0;
@@ -277,7 +300,7 @@ GBP_EXPORT(gbp_comm_init, c, (gbp_ctx* c, void* region, int transport), (c, regi
   if (!c || !region) return GBP_ERR_INVALID;
   if (c->comm) return fail(c, GBP_ERR_STATE, "gbp_comm_init: the ctx already has a communicator");
   std::string err;
-  gbp::Comm* comm = gbp::comm_create_from_region(region, c->rank, c->world, transport, c->C, err);
+  gbp::Comm* comm = gbp::comm_create_from_region(region, c->rank, c->world, static_cast<gbp::Transport>(transport), c->C, err);
   if (!comm) return fail(c, GBP_ERR_COMM, "gbp_comm_init: " + err);
   return comm_attach(c, comm);
 }
@@ -324,23 +347,17 @@ GBP_EXPORT(gbp_comm_set_schedule, c, (gbp_ctx* c, int two_streams), (c, two_stre
   if (c->comm_stream) HIPCHK(c, hipStreamSynchronize(c->comm_stream));
   drop_graph(c);
   c->comm_single_stream = two_streams == 0;
-  if (!c->comm_stream && !c->comm_single_stream) {
-    int least = 0, greatest = 0;
-    HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-    HIPCHK(c, hipStreamCreateWithPriority(&c->comm_stream, hipStreamNonBlocking, greatest));
-  }
-  return GBP_OK;
+  return ensure_comm_stream(c);
 }
 
 // `reps` all-gathers of the camera partial buffers back to back on the ctx's stream (collective: every rank calls it);
 // *avg_us = mean duration between two events.  The buffers keep their content (the gather of the same partials).
 GBP_EXPORT(gbp_comm_probe, c, (gbp_ctx* c, int reps, double* avg_us), (c, reps, avg_us)) {
   if (!c || !c->comm || !avg_us || reps < 1) return fail(c, GBP_ERR_STATE, "gbp_comm_probe: needs a communicator, reps >= 1");
-  if (c->comm->exchange_buffer()) {
+  if (PeerComm* pc = peers(c->comm)) {
     // p2p: this rank's slot of the next parity still holds the partials of two exchanges ago — give it the last ones, so that every
     // exchange of the probe (both parities) moves the same partials and leaves what a refresh reads unchanged
-    const float* mine = c->comm->exchange_buffer() + ((size_t)(c->comm->next_parity() ^ 1) * c->world + c->rank) * c->C * kCamRec;
-    HIPCHK(c, hipMemcpyAsync(c->send_dev, mine, (size_t)c->C * kCamRec * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->send_dev, pc->last_own_slot(), (size_t)c->C * kCamRec * 4, hipMemcpyDeviceToDevice, c->stream));
   }
   if (!c->comm->stream_ordered()) {      // host-staged, p2p: wall clock around blocking exchanges
     const auto t0 = std::chrono::steady_clock::now();

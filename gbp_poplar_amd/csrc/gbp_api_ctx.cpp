@@ -459,7 +459,7 @@ GBP_EXPORT(gbp_set_stream, c, (gbp_ctx* c, void* s), (c, s)) {
 
 GBP_EXPORT(gbp_set_exchange_buffers, c, (gbp_ctx* c, void* send_dev, void* recv_dev), (c, send_dev, recv_dev)) {
   if (!c) return GBP_ERR_INVALID;
-  if (c->comm && c->comm->exchange_buffer())
+  if (peers(c->comm))
     return fail(c, GBP_ERR_STATE, "gbp_set_exchange_buffers: the ctx's p2p communicator exchanges through its own buffers");
   c->send_dev = send_dev; c->recv_dev = recv_dev;
   return GBP_OK;
@@ -604,9 +604,7 @@ GBP_EXPORT(gbp_upload, c, (gbp_ctx* c, const gbp_state_in* in), (c, in)) {
   lap("fills, priors, scalings queued");
   if (int rc = up.end()) return rc;
   lap("everything on the device");
-  if (float* x = c->comm ? c->comm->exchange_buffer() : nullptr)      // p2p: both parities of the communicator's buffer
-    HIPCHK(c, hipMemsetAsync(x, 0, (size_t)2 * c->world * c->C * kCamRec * 4, c->stream));
-  else if (exch(c) && c->recv_dev) HIPCHK(c, hipMemsetAsync(c->recv_dev, 0, (size_t)c->world * c->C * kCamRec * 4, c->stream));
+  if (int rc = zero_exchange(c)) return rc;
   c->uploaded = true;
   c->beliefs_valid = false;
   return GBP_OK;

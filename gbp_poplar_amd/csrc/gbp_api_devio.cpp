@@ -76,9 +76,7 @@ int devio_upload(gbp_ctx* c, const gbp_state_in* in) {
   seg(t, in->lmk_weaken_flag, c->lwf.p, c->L, 1, 1, 0);
   launch_rec_copy(t, true, c->stream);
   HIPCHK(c, hipGetLastError());
-  if (float* x = c->comm ? c->comm->exchange_buffer() : nullptr)      // (a 1-rank communicator: as gbp_upload)
-    HIPCHK(c, hipMemsetAsync(x, 0, (size_t)2 * c->world * c->C * kCamRec * 4, c->stream));
-  else if (exch(c) && c->recv_dev) HIPCHK(c, hipMemsetAsync(c->recv_dev, 0, (size_t)c->world * c->C * kCamRec * 4, c->stream));
+  if (int rc = zero_exchange(c)) return rc;      // (as gbp_upload)
   c->uploaded = true;
   c->beliefs_valid = false;
   return GBP_OK;

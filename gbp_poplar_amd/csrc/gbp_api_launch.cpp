@@ -74,28 +74,8 @@ int refresh_beliefs_from_partials(gbp_ctx* c, bool roll, bool do_lmk, bool weake
     b.weaken = 1;
     weaken_args(c, b);
   }
-  if (const float* const* peers = last_peers(c)) {
-    // direct peer-memory transport: the last exchange's partials are read where they lie (the combine of the sharded iteration
-    // gathers nothing into recv_dev); the landmark half, which needs nothing from other ranks, in a launch of its own
-    b.roll = roll ? 1 : 0;
-    if (!launch_beliefs_cam_peers) return fail(c, GBP_ERR_STATE, "no device code for the p2p combine");
-    launch_beliefs_cam_peers(b, peers, c->stream);
-    if (do_lmk) launch_beliefs(b, false, true, c->stream);
-    HIPCHK(c, hipGetLastError());
-    return GBP_OK;
-  }
-  if (const float* own = last_own_slot(c)) {
-    b.gathered = own;      // (recv_dev is the parity of the NEXT exchange)
-  } else if (!exch(c)) {
-    b.gathered = P<float>(c->local); b.world = 1;
-  } else {
-    if (!c->recv_dev) return fail(c, GBP_ERR_STATE, "exchange buffers not set");
-    b.gathered = static_cast<const float*>(c->recv_dev);
-  }
   b.roll = roll ? 1 : 0;
-  launch_beliefs(b, true, do_lmk, c->stream);
-  HIPCHK(c, hipGetLastError());
-  return GBP_OK;
+  return refresh_cameras(c, b, do_lmk);      // (which launches, by transport: gbp_api_comm.cpp)
 }
 
 // one iteration: k_sweep + k_beliefs; ev: the instantiations that carry the metric (a.ev filled in by the caller)

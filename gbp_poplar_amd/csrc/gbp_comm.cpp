@@ -154,7 +154,6 @@ class RcclComm : public Comm {
     if (r != ncclSuccess) { err = nccl_err("ncclAllGather", r); return -1; }
     return 0;
   }
-  bool stream_ordered() const override { return true; }
   int all_gather_host(const double* mine, double* all, int n, std::string& err) override {
     if (peer.h) return peer.gather_host(rank, mine, all, n, err) ? 0 : -1;
     if (n > 16) { err = "all_gather_host: at most 16 values"; return -1; }
@@ -171,7 +170,7 @@ class RcclComm : public Comm {
     double x = 0, all[kCommMaxWorld];
     return all_gather_host(&x, all, 1, err);
   }
-  const char* name() const override { return "rccl"; }
+  Transport kind() const override { return Transport::Rccl; }
   std::string library_path() const override { return rccl().path; }
   int library_version() const override {
     int v = 0;
@@ -184,13 +183,13 @@ class RcclComm : public Comm {
 class StagedComm : public Comm {
  public:
   RegionPeer peer;
-  float* data = nullptr;        // [2][world][n_floats]
-  size_t n_floats = 0;
+  float* data = nullptr;        // the region's staging slots, laid out as X
+  ExchangeLayout l;
   int parity = 0;
   std::vector<float> stage;
   int all_gather(const float* send, float* recv, size_t n, hipStream_t s, std::string& err) override {
-    if (n > n_floats) { err = "all_gather: message larger than the staging region"; return -1; }
-    float* slot = data + ((size_t)parity * world + rank) * n_floats;
+    if (n > l.slot_floats()) { err = "all_gather: message larger than the staging region"; return -1; }
+    float* slot = data + l.slot(parity, rank);
     if (hipMemcpyAsync(slot, send, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
       err = "all_gather: device -> region copy failed";
       return -1;
@@ -199,7 +198,7 @@ class StagedComm : public Comm {
     // a rank can be at most one exchange ahead of the slowest one (the next barrier needs everybody), so the
     // two parities never collide
     stage.resize((size_t)world * n);
-    for (int r = 0; r < world; ++r) std::memcpy(&stage[(size_t)r * n], data + ((size_t)parity * world + r) * n_floats, n * 4);
+    for (int r = 0; r < world; ++r) std::memcpy(&stage[(size_t)r * n], data + l.slot(parity, r), n * 4);
     if (hipMemcpyAsync(recv, stage.data(), stage.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
       err = "all_gather: region -> device copy failed";
       return -1;
@@ -207,29 +206,97 @@ class StagedComm : public Comm {
     parity ^= 1;
     return 0;
   }
-  bool stream_ordered() const override { return false; }
   int all_gather_host(const double* mine, double* all, int n, std::string& err) override {
     return peer.gather_host(rank, mine, all, n, err) ? 0 : -1;
   }
   int barrier(std::string& err) override { return peer.barrier(err) ? 0 : -1; }
-  const char* name() const override { return "host-staged"; }
+  Transport kind() const override { return Transport::HostStaged; }
+  bool setup(RegionHeader* h, int, uint32_t, std::string& err) {      // (the staging slots are the region's, sized by its cameras)
+    data = region_data(h);
+    l = ExchangeLayout{world, h->n_cams};
+    return peer.barrier(err);
+  }
+};
+
+// ---- one IPC-shared device buffer --------------------------------------------------------------------------------------------
+// A rank's hipMalloc'ed buffer that every peer maps through HIP IPC, and the device table of pointers into the ranks' buffers.
+// who / what name the transport and the buffer in the error texts ("p2p" / "exchange buffer").
+struct IpcBuffer {
+  void* own = nullptr;
+  std::vector<void*> mapped;       // [world] IPC mappings of the peers' buffers (nullptr: this rank)
+  void** d_tab = nullptr;          // [2][world] device pointer table
+  IpcBuffer() = default;
+  IpcBuffer(const IpcBuffer&) = delete;
+  IpcBuffer& operator=(const IpcBuffer&) = delete;
+  // (the owner has quiesced: no peer reads this rank's buffer any more) the mappings closed first, this rank's memory freed last
+  ~IpcBuffer() {
+    for (void* p : mapped)
+      if (p) (void)hipIpcCloseMemHandle(p);
+    if (d_tab) (void)hipFree(d_tab);
+    if (own) (void)hipFree(own);
+  }
+  // Collective over the ranks, four region barriers; on failure the caller raises the region's abort flag.  The handle goes into the
+  // region's handle slot of this rank (idle: a barrier lies behind every rank's reads of what it held before).  off(p, r): byte
+  // offset in rank r's buffer of what entry r of parity p's table points to.
+  template <class Off>
+  bool setup(RegionHeader* h, RegionPeer& peer, int rank, const char* who, const char* what, uint32_t tag, uint32_t n_cams, size_t bytes,
+             Off off, std::string& err) {
+    const int world = peer.world;
+    const std::string pre = std::string(who) + ": ";
+    // 1. the buffer, its handle published in the region
+    if (hipMalloc(&own, bytes) != hipSuccess) { own = nullptr; err = pre + "hipMalloc of the " + what + " failed"; return false; }
+    hipIpcMemHandle_t handle;
+    if (hipIpcGetMemHandle(&handle, own) != hipSuccess) { err = pre + "hipIpcGetMemHandle failed"; return false; }
+    std::memcpy(h->ipc[rank], &handle, HIP_IPC_HANDLE_SIZE);
+    if (!peer.barrier(err)) return false;
+    // 2. every peer's buffer mapped (never this rank's own handle)
+    mapped.assign(world, nullptr);
+    for (int r = 0; r < world; ++r) {
+      if (r == rank) continue;
+      std::memcpy(&handle, h->ipc[r], HIP_IPC_HANDLE_SIZE);
+      if (hipIpcOpenMemHandle(&mapped[r], handle, hipIpcMemLazyEnablePeerAccess) != hipSuccess || !mapped[r]) {
+        mapped[r] = nullptr;
+        err = pre + "hipIpcOpenMemHandle of rank " + std::to_string(r) + "'s " + what + " failed";
+        return false;
+      }
+    }
+    auto at = [&](int p, int r) { return static_cast<char*>(r == rank ? own : mapped[r]) + off(p, r); };
+    // 3. every mapping checked with runtime copies before any kernel reads through it: (tag, rank, C, world) where entry (0, r) points
+    const uint32_t pat[4] = {tag, (uint32_t)rank, n_cams, (uint32_t)world};
+    if (hipMemcpy(at(0, rank), pat, sizeof(pat), hipMemcpyHostToDevice) != hipSuccess) { err = pre + "pattern copy failed"; return false; }
+    if (!peer.barrier(err)) return false;
+    for (int r = 0; r < world; ++r) {
+      if (r == rank) continue;
+      uint32_t got[4] = {0, 0, 0, 0};
+      const uint32_t want[4] = {tag, (uint32_t)r, n_cams, (uint32_t)world};
+      if (hipMemcpy(got, at(0, r), sizeof(got), hipMemcpyDeviceToHost) != hipSuccess || std::memcmp(got, want, sizeof(got)) != 0) {
+        err = pre + "the mapping of rank " + std::to_string(r) + "'s " + what + " does not hold its pattern";
+        return false;
+      }
+    }
+    if (!peer.barrier(err)) return false;
+    if (hipMemset(own, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { err = pre + "zero-fill failed"; return false; }
+    // 4. the pointer tables
+    std::vector<void*> tab(2 * (size_t)world);
+    for (int p = 0; p < 2; ++p)
+      for (int r = 0; r < world; ++r) tab[(size_t)p * world + r] = at(p, r);
+    if (hipMalloc(&d_tab, tab.size() * sizeof(void*)) != hipSuccess) { d_tab = nullptr; err = pre + "hipMalloc failed"; return false; }
+    if (hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(void*), hipMemcpyHostToDevice) != hipSuccess) { err = pre + "table upload failed"; return false; }
+    return peer.barrier(err);
+  }
 };
 
 // ---- direct peer-memory transport (p2p) ---------------------------------------------------------------------------------
-// Every rank owns X = [2 parities][world][n] fp32 (its own hipMalloc).  Rank r's partials always go into slot r of the parity of the
+// Every rank owns X (ExchangeLayout; its own hipMalloc).  Rank r's partials always go into slot r of the parity of the
 // exchange; peers read only that slot, through an IPC mapping of X; a rank's gather writes only the other slots of its own X.
 // Exchange k: partials into parity k & 1 (stream-ordered), stream synchronised, ONE region barrier, then the readers
 // (k_gather_peers / k_beliefs_cam_peers) on the stream.  A rank reaches barrier k + 1 only after its stream has finished everything
 // it enqueued before it — its reads of exchange k included — so by the time any rank writes parity k & 1 again (exchange k + 2, after
 // barrier k + 1) every peer is done reading it.
-class P2pComm : public Comm {
+class P2pComm : public PeerComm {
  public:
   RegionPeer peer;
-  size_t n_floats = 0;             // slot: one rank's [C][44]
-  float* X = nullptr;
-  std::vector<void*> mapped;       // [world] IPC mappings of the peers' buffers (nullptr: this rank)
-  float** d_tab = nullptr;         // [2][world] device pointer tables
-  int parity = 0;
+  IpcBuffer x;
   bool armed = false;              // every rank has set up: teardown meets the others at a barrier
   bool quiet = false;              // quiesce() has run
   // first step of every teardown, once: this rank's work done, then (armed) every rank's — no peer reads this rank's buffers any more
@@ -240,46 +307,27 @@ class P2pComm : public Comm {
     std::string err;
     if (armed) (void)peer.barrier(err);
   }
-  ~P2pComm() override {
-    quiesce();
-    for (void* p : mapped)
-      if (p) (void)hipIpcCloseMemHandle(p);
-    if (d_tab) (void)hipFree(d_tab);
-    if (X) (void)hipFree(X);
-  }
-  float* slot(int p, int r) const { return X + ((size_t)p * world + r) * n_floats; }
-  float* exchange_buffer() const override { return X; }
-  const float* const* peer_table(int p) const override { return d_tab + (size_t)(p & 1) * world; }
-  int next_parity() const override { return parity; }
-  int exchange_in_place(hipStream_t s, std::string& err) override {
-    if (hipStreamSynchronize(s) != hipSuccess) { err = "p2p exchange: stream synchronisation failed"; return -1; }
-    if (!peer.barrier(err)) return -1;
-    parity ^= 1;
-    return 0;
-  }
+  ~P2pComm() override { quiesce(); }      // (then the members: mappings closed, memory freed)
+  Transport kind() const override { return Transport::P2p; }
   int all_gather(const float* send, float* recv, size_t n, hipStream_t s, std::string& err) override {
-    if (n != n_floats || send != slot(parity, rank) || recv != slot(parity, 0)) {
+    if (n != xl.slot_floats() || send != send_slot() || recv != next_block()) {
       err = "all_gather: the p2p transport exchanges through its own buffer (send / recv of the current parity)";
       return -1;
     }
     if (!launch_gather_peers) { err = "all_gather: no device code"; return -1; }
-    const int p = parity;
-    if (exchange_in_place(s, err) != 0) return -1;
+    int p = 0;
+    if (advance(s, &p, err) != 0) return -1;
     launch_gather_peers(peer_table(p), recv, (uint32_t)(n / 4), world, rank, s);
     if (hipGetLastError() != hipSuccess) { err = "all_gather: k_gather_peers did not launch"; return -1; }
     return 0;
   }
-  bool stream_ordered() const override { return false; }
   int all_gather_host(const double* mine, double* all, int n, std::string& err) override {
     return peer.gather_host(rank, mine, all, n, err) ? 0 : -1;
   }
   int barrier(std::string& err) override { return peer.barrier(err) ? 0 : -1; }
-  const char* name() const override { return "p2p"; }
 
-  // collective over the ranks; on failure the caller raises the region's abort flag
-  bool setup(RegionHeader* h, int dev, uint32_t n_cams, std::string& err) {
-    n_floats = (size_t)n_cams * 44;
-    // 1. ranks on different GPUs must reach each other's memory
+  virtual bool setup(RegionHeader* h, int dev, uint32_t n_cams, std::string& err) {
+    // ranks on different GPUs must reach each other's memory
     for (int r = 0; r < world; ++r) {
       if (r == rank || std::strncmp(h->gpu_id[r], h->gpu_id[rank], 64) == 0) continue;
       int pdev = -1, can = 0;
@@ -289,59 +337,19 @@ class P2pComm : public Comm {
         return false;
       }
     }
-    // 2. the buffer, its handle published in the region
-    const size_t bytes = 2 * (size_t)world * n_floats * sizeof(float);
-    if (hipMalloc(&X, bytes < 16 ? 16 : bytes) != hipSuccess) { X = nullptr; err = "p2p: hipMalloc of the exchange buffer failed"; return false; }
-    hipIpcMemHandle_t mine;
-    if (hipIpcGetMemHandle(&mine, X) != hipSuccess) { err = "p2p: hipIpcGetMemHandle failed"; return false; }
-    std::memcpy(h->ipc[rank], &mine, HIP_IPC_HANDLE_SIZE);
-    if (!peer.barrier(err)) return false;
-    // 3. every peer's buffer mapped (never this rank's own handle)
-    mapped.assign(world, nullptr);
-    for (int r = 0; r < world; ++r) {
-      if (r == rank) continue;
-      hipIpcMemHandle_t theirs;
-      std::memcpy(&theirs, h->ipc[r], HIP_IPC_HANDLE_SIZE);
-      if (hipIpcOpenMemHandle(&mapped[r], theirs, hipIpcMemLazyEnablePeerAccess) != hipSuccess || !mapped[r]) {
-        mapped[r] = nullptr;
-        err = "p2p: hipIpcOpenMemHandle of rank " + std::to_string(r) + "'s exchange buffer failed";
-        return false;
-      }
-    }
-    auto base = [&](int r) { return r == rank ? X : static_cast<float*>(mapped[r]); };
-    // 4. every mapping checked with runtime copies before any kernel reads through it: (magic, rank, C, world) in slot r of parity 0
-    const uint32_t pat[4] = {kMagic, (uint32_t)rank, n_cams, (uint32_t)world};
-    if (hipMemcpy(slot(0, rank), pat, sizeof(pat), hipMemcpyHostToDevice) != hipSuccess) { err = "p2p: pattern copy failed"; return false; }
-    if (!peer.barrier(err)) return false;
-    for (int r = 0; r < world; ++r) {
-      if (r == rank) continue;
-      uint32_t got[4] = {0, 0, 0, 0};
-      const uint32_t want[4] = {kMagic, (uint32_t)r, n_cams, (uint32_t)world};
-      if (hipMemcpy(got, base(r) + (size_t)r * n_floats, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess ||
-          std::memcmp(got, want, sizeof(got)) != 0) {
-        err = "p2p: the mapping of rank " + std::to_string(r) + "'s exchange buffer does not hold its pattern";
-        return false;
-      }
-    }
-    if (!peer.barrier(err)) return false;
-    if (hipMemset(X, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { err = "p2p: zero-fill failed"; return false; }
-    // 5. the pointer tables: for parity p, slot r of parity p in rank r's buffer
-    std::vector<float*> tab(2 * (size_t)world);
-    for (int p = 0; p < 2; ++p)
-      for (int r = 0; r < world; ++r) tab[(size_t)p * world + r] = base(r) + ((size_t)p * world + r) * n_floats;
-    if (hipMalloc(&d_tab, tab.size() * sizeof(float*)) != hipSuccess) { d_tab = nullptr; err = "p2p: hipMalloc failed"; return false; }
-    if (hipMemcpy(d_tab, tab.data(), tab.size() * sizeof(float*), hipMemcpyHostToDevice) != hipSuccess) { err = "p2p: table upload failed"; return false; }
-    if (!peer.barrier(err)) return false;
-    armed = true;
-    return true;
+    xl = ExchangeLayout{world, n_cams};
+    armed = x.setup(h, peer, rank, "p2p", "exchange buffer", kMagic, n_cams, xl.bytes(), [this](int p, int r) { return xl.slot(p, r) * sizeof(float); }, err);
+    X = static_cast<float*>(x.own);
+    x_tab = reinterpret_cast<const float* const*>(x.d_tab);
+    return armed;
   }
 };
 
 // ---- sliced peer-memory transport (p2p-slices) ---------------------------------------------------------------------------------------
 // P2pComm (its exchange buffer X, its tables, its all_gather for everything outside the iteration) plus a second IPC-mapped buffer per
-// rank, the RESULT buffer R = [2 parities][widest slice][kCamRes4] float4, written only by its owner.  The cameras are cut into `world`
-// slices (slice_bounds, gbp_kernels.h), rank s owns slice s.  Exchange k of the iteration, parity p = k & 1:
-//   partials into X[p][rank]; stream sync; barrier A (exchange_in_place)
+// rank, the RESULT buffer R (ResultLayout), written only by its owner.  The cameras are cut into `world` slices (slice_bounds,
+// gbp_kernels.h), rank s owns slice s.  Exchange k of the iteration, parity p = k & 1:
+//   partials into X[p][rank]; stream sync; barrier A (advance)
 //   reduce: the owner sums its slice out of every peer's X[p] and writes the finished records into its own R[p]; stream sync; barrier B
 //   gather: every rank copies the other slices out of their owners' R[p]
 // A rank reaches the next barrier, whichever it is, only after its stream has finished everything enqueued before it.  So X[p] is written
@@ -349,71 +357,43 @@ class P2pComm : public Comm {
 // k + 2, behind barrier A of k + 2) only after every rank's gather k has ended.
 class P2pSlicesComm : public P2pComm {
  public:
-  size_t res4 = 0;                 // float4 of one parity of R
-  float4* R = nullptr;
-  std::vector<void*> rmapped;      // [world] IPC mappings of the peers' result buffers (nullptr: this rank)
-  float4** d_rtab = nullptr;       // [2][world] device pointer tables: R of rank r, parity p
-  ~P2pSlicesComm() override {
-    quiesce();                     // no peer reads R (or X) any more
-    for (void* p : rmapped)
-      if (p) (void)hipIpcCloseMemHandle(p);
-    if (d_rtab) (void)hipFree(d_rtab);
-    if (R) (void)hipFree(R);
-  }
-  bool sliced() const override { return true; }
-  float4* result_buffer(int p) const override { return R + (size_t)(p & 1) * res4; }
-  const float4* const* result_table(int p) const override { return d_rtab + (size_t)(p & 1) * world; }
-  const char* name() const override { return "p2p-slices"; }
-
-  // collective, behind P2pComm::setup: the same steps for R — handle published in the region's (now idle) handle slots, every peer's
-  // mapping opened and checked with runtime copies before any kernel reads through it
-  bool setup_results(RegionHeader* h, uint32_t n_cams, std::string& err) {
+  IpcBuffer r;                     // (destroyed before P2pComm's x: R's mappings and memory go first)
+  ~P2pSlicesComm() override { quiesce(); }      // no peer reads R (or X) any more
+  Transport kind() const override { return Transport::P2pSlices; }
+  // X as in p2p; then the same steps for R — its handle goes into the region's handle slots only behind the barrier that ended X's
+  // setup, when every rank has opened the handles of X
+  bool setup(RegionHeader* h, int dev, uint32_t n_cams, std::string& err) override {
+    if (!P2pComm::setup(h, dev, n_cams, err)) return false;
     armed = false;                 // (a failure below is met by the region's abort flag, not by a teardown barrier)
-    res4 = ((size_t)n_cams + (size_t)world - 1) / (size_t)world * kCamRes4;
-    const size_t bytes = 2 * res4 * sizeof(float4);
-    if (hipMalloc(&R, bytes < 16 ? 16 : bytes) != hipSuccess) { R = nullptr; err = "p2p-slices: hipMalloc of the result buffer failed"; return false; }
-    hipIpcMemHandle_t mine;
-    if (hipIpcGetMemHandle(&mine, R) != hipSuccess) { err = "p2p-slices: hipIpcGetMemHandle failed"; return false; }
-    std::memcpy(h->ipc[rank], &mine, HIP_IPC_HANDLE_SIZE);      // every rank has opened the handles of X: setup() ended with barriers behind that
-    if (!peer.barrier(err)) return false;
-    rmapped.assign(world, nullptr);
-    for (int r = 0; r < world; ++r) {
-      if (r == rank) continue;
-      hipIpcMemHandle_t theirs;
-      std::memcpy(&theirs, h->ipc[r], HIP_IPC_HANDLE_SIZE);
-      if (hipIpcOpenMemHandle(&rmapped[r], theirs, hipIpcMemLazyEnablePeerAccess) != hipSuccess || !rmapped[r]) {
-        rmapped[r] = nullptr;
-        err = "p2p-slices: hipIpcOpenMemHandle of rank " + std::to_string(r) + "'s result buffer failed";
-        return false;
-      }
-    }
-    auto base = [&](int r) { return r == rank ? R : static_cast<float4*>(rmapped[r]); };
-    const uint32_t pat[4] = {~kMagic, (uint32_t)rank, n_cams, (uint32_t)world};      // (~magic: not the pattern of X)
-    if (hipMemcpy(R, pat, sizeof(pat), hipMemcpyHostToDevice) != hipSuccess) { err = "p2p-slices: pattern copy failed"; return false; }
-    if (!peer.barrier(err)) return false;
-    for (int r = 0; r < world; ++r) {
-      if (r == rank) continue;
-      uint32_t got[4] = {0, 0, 0, 0};
-      const uint32_t want[4] = {~kMagic, (uint32_t)r, n_cams, (uint32_t)world};
-      if (hipMemcpy(got, base(r), sizeof(got), hipMemcpyDeviceToHost) != hipSuccess || std::memcmp(got, want, sizeof(got)) != 0) {
-        err = "p2p-slices: the mapping of rank " + std::to_string(r) + "'s result buffer does not hold its pattern";
-        return false;
-      }
-    }
-    if (!peer.barrier(err)) return false;
-    if (hipMemset(R, 0, bytes < 16 ? 16 : bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { err = "p2p-slices: zero-fill failed"; return false; }
-    std::vector<float4*> tab(2 * (size_t)world);
-    for (int p = 0; p < 2; ++p)
-      for (int r = 0; r < world; ++r) tab[(size_t)p * world + r] = base(r) + (size_t)p * res4;
-    if (hipMalloc(&d_rtab, tab.size() * sizeof(float4*)) != hipSuccess) { d_rtab = nullptr; err = "p2p-slices: hipMalloc failed"; return false; }
-    if (hipMemcpy(d_rtab, tab.data(), tab.size() * sizeof(float4*), hipMemcpyHostToDevice) != hipSuccess) { err = "p2p-slices: table upload failed"; return false; }
-    if (!peer.barrier(err)) return false;
-    armed = true;
-    return true;
+    rl = ResultLayout{world, n_cams};
+    armed = r.setup(h, peer, rank, "p2p-slices", "result buffer", ~kMagic, n_cams, rl.bytes(), [this](int p, int) { return rl.parity_offset(p) * sizeof(float4); }, err);
+    R = static_cast<float4*>(r.own);
+    r_tab = reinterpret_cast<const float4* const*>(r.d_tab);
+    return armed;
   }
 };
 
+// a communicator of a launcher-made group: constructed, given its place in the group, set up — or the region's abort flag raised
+template <class T>
+Comm* create_in_region(RegionHeader* h, const RegionPeer& peer, int rank, int world, int dev, uint32_t n_cams, std::string& err) {
+  T* c = new (std::nothrow) T();
+  if (c) { c->rank = rank; c->world = world; c->peer = peer; }
+  else err = "out of memory";
+  if (c && c->setup(h, dev, n_cams, err)) return c;
+  h->abort_flag.store(1);
+  delete c;
+  return nullptr;
+}
+
 }  // namespace
+
+int PeerComm::advance(hipStream_t s, int* closed, std::string& err) {
+  if (hipStreamSynchronize(s) != hipSuccess) { err = "p2p exchange: stream synchronisation failed"; return -1; }
+  if (barrier(err) != 0) return -1;
+  *closed = parity;
+  parity ^= 1;
+  return 0;
+}
 
 int comm_unique_id(void* id128, std::string& err) {
   RcclApi& api = rccl();
@@ -483,7 +463,7 @@ int comm_region_selftest(void* region, int rank, int world, int rounds, std::str
   return 0;
 }
 
-Comm* comm_create_from_region(void* region, int rank, int world, int transport, uint32_t n_cams, std::string& err) {
+Comm* comm_create_from_region(void* region, int rank, int world, Transport transport, uint32_t n_cams, std::string& err) {
   RegionHeader* h = static_cast<RegionHeader*>(region);
   if (!h || h->magic != kMagic || (int)h->world != world || rank < 0 || rank >= world) { err = "bad communication region"; return nullptr; }
   RegionPeer peer;
@@ -498,31 +478,14 @@ Comm* comm_create_from_region(void* region, int rank, int world, int transport, 
   for (int a = 0; a < world; ++a)
     for (int b = a + 1; b < world; ++b)
       if (std::strncmp(h->gpu_id[a], h->gpu_id[b], 64) == 0) shared = true;
-  if (transport == 1 && shared) { err = "RCCL needs one GPU per rank, but two ranks share a GPU"; h->abort_flag.store(1); return nullptr; }
-  if (transport == 3) {
-    P2pComm* c = new (std::nothrow) P2pComm();
-    if (!c) { err = "out of memory"; h->abort_flag.store(1); return nullptr; }
-    c->rank = rank; c->world = world; c->peer = peer;
-    if (!c->setup(h, dev, n_cams, err)) { h->abort_flag.store(1); delete c; return nullptr; }
-    return c;
+  if (transport == Transport::Auto) transport = shared ? Transport::HostStaged : Transport::Rccl;
+  switch (transport) {
+    case Transport::P2p: return create_in_region<P2pComm>(h, peer, rank, world, dev, n_cams, err);
+    case Transport::P2pSlices: return create_in_region<P2pSlicesComm>(h, peer, rank, world, dev, n_cams, err);
+    case Transport::Rccl: break;
+    default: return create_in_region<StagedComm>(h, peer, rank, world, dev, n_cams, err);      // (any other number: as before, host-staged)
   }
-  if (transport == 4) {
-    P2pSlicesComm* c = new (std::nothrow) P2pSlicesComm();
-    if (!c) { err = "out of memory"; h->abort_flag.store(1); return nullptr; }
-    c->rank = rank; c->world = world; c->peer = peer;
-    if (!c->setup(h, dev, n_cams, err) || !c->setup_results(h, n_cams, err)) { h->abort_flag.store(1); delete c; return nullptr; }
-    return c;
-  }
-  const bool use_rccl = transport == 1 || (transport == 0 && !shared);
-  if (!use_rccl) {
-    StagedComm* c = new (std::nothrow) StagedComm();
-    if (!c) { err = "out of memory"; return nullptr; }
-    c->rank = rank; c->world = world; c->peer = peer;
-    c->data = region_data(region);
-    c->n_floats = (size_t)h->n_cams * 44;
-    if (!c->peer.barrier(err)) { delete c; return nullptr; }
-    return c;
-  }
+  if (shared) { err = "RCCL needs one GPU per rank, but two ranks share a GPU"; h->abort_flag.store(1); return nullptr; }
   // 2. RCCL: rank 0 draws the unique id, the region hands it to the others
   if (rank == 0) {
     if (comm_unique_id(h->id, err) != 0) { h->abort_flag.store(1); return nullptr; }

@@ -326,11 +326,10 @@ int struct_kind(gbp_ctx* c, const char* fn, const void* const* members, const ch
 [[gnu::weak]] int devio_refresh_active_shadow(gbp_ctx* c);   // c->active_host from the device (after a device-pointer call changed the flags)
 
 // ---- gbp_api_comm.cpp -------------------------------------------------------------------------------------------------------
-int exchange_now(gbp_ctx* c);                               // plain all-gather of the camera partials on the ctx's stream
+int exchange_now(gbp_ctx* c, hipStream_t s = nullptr);      // plain all-gather of the camera partials on the ctx's stream (or on s)
 int iterate_sharded(gbp_ctx* c, int n);
-void bind_exchange(gbp_ctx* c);                             // p2p: send_dev / recv_dev := the parity of the next exchange
-const float* last_own_slot(gbp_ctx* c);                     // 1-rank p2p-slices: this rank's partials of the last exchange (else nullptr)
-const float* const* last_peers(gbp_ctx* c);                 // p2p: device table of the last exchange's partials (else nullptr)
+int zero_exchange(gbp_ctx* c);                              // gbp_upload: the gathered partials (of both parities) cleared on the ctx's stream
+int refresh_cameras(gbp_ctx* c, BeliefArgs& b, bool do_lmk);   // the launches of refresh_beliefs_from_partials, by transport
 
 }  // namespace api
 }  // namespace gbp

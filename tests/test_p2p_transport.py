@@ -6,6 +6,7 @@ import ctypes
 import json
 import mmap
 import os
+import shutil
 import subprocess
 import sys
 import time
@@ -45,6 +46,20 @@ def test_transport_p2p_is_parsed():
         assert rc == 1 and "--bal_file" in err and "invalid option value" not in err, (value, err)
     rc, _, err = run([BA, "--bal_file", "/nonexistent/file.txt", "--transport", "p2p"])
     assert rc == 1 and "unable to open file" in err and "invalid option value" not in err
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_exchange_layout_under_asan_ubsan(tmp_path):
+    """The layouts of the exchange buffer X and the result buffer R (csrc/gbp_comm.hpp) for world in {1, 2, 3, 8, 64} x C in {0, 1, 3, 5,
+    1000}: X's 2 * world slots disjoint and tiling the buffer, parity 1 world * C * 44 floats behind parity 0, at least 16 bytes; R's
+    parity ceil(C / world) records, every slice of slice_bounds fitting it — a stand-alone program under ASan + UBSan
+    (tests/sanitize/exchange_layout_main.cpp)."""
+    exe = str(tmp_path / "exchange_layout")
+    subprocess.check_call(["g++", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1",
+                           os.path.join(ROOT, "tests", "sanitize", "exchange_layout_main.cpp"), "-o", exe], cwd=ROOT)
+    p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert p.returncode == 0 and "exchange_layout: ok (25 shapes)" in p.stdout, (p.returncode, p.stdout[-500:], p.stderr[-3000:])
 
 
 # ---- GPU: the executables ----------------------------------------------------------------------------------------------------------
