@@ -50,6 +50,7 @@ struct Phases {
   double exec_to_main_s = 0;                                  // exec -> main(): the dynamic loader (libamdhip64 and what it pulls in)
   std::vector<std::pair<std::string, double>> v;              // phase, seconds — in order
   std::string create_info;                                    // gbp_create's own breakdown (gbp_last_error(ctx) right after it)
+  std::string comm_info;                                      // gbp_comm_describe of a sharded run (JSON): the transport, who chose it, what was measured
   Phases() {
     // start time of the process (clock ticks since boot, /proc/self/stat field 22) against the time since boot now: 10 ms resolution
     double up = 0;
@@ -124,7 +125,8 @@ inline void usage(bool slam) {
                "  --v arg (=0)                   Verbose: print beliefs\n"
                "  --seed arg (=0)                seed of the initialisation noise (0 = from the clock)\n"
                "  --eval_every arg (=1)          read back + evaluate every K iterations\n"
-               "  --transport arg (=auto)        exchange between ranks: auto | rccl | host | p2p | p2p-slices (host, p2p, p2p-slices: ranks may share a GPU)\n"
+               "  --transport arg (=auto)        exchange between ranks: auto | rccl | host | p2p | p2p-slices | measured (host, p2p, p2p-slices: ranks may\n"
+               "                                 share a GPU; measured: time every transport the ranks can form, keep the fastest)\n"
                "  --out_file arg                 write the refined cameras / landmarks (belief means) in the input's format\n";
 }
 
@@ -171,7 +173,7 @@ inline int parse(int argc, char** argv, bool slam, Options& o) {
       else if (k == "transport") {
         using T = gbp::Transport;
         o.transport = v == "rccl" ? (int)T::Rccl : v == "host" ? (int)T::HostStaged : v == "p2p" ? (int)T::P2p : v == "p2p-slices" ? (int)T::P2pSlices :
-                      v == "auto" ? (int)T::Auto : std::stoi(v);
+                      v == "measured" ? (int)T::Measured : v == "auto" ? (int)T::Auto : std::stoi(v);
       }
       else { std::cerr << "unrecognised option '--" << k << "'\n"; return 2; }
     }
@@ -397,6 +399,11 @@ inline int create_rank_ctx(const Options& o, const Problem& P, RankCtx& rk, gbp_
     }
     std::cout << "Exchange between the " << rk.world << " ranks: " << gbp_comm_transport(*ctx)
               << (ndev < rk.world ? " (fewer GPUs than ranks: ranks share a GPU)" : "") << "\n";
+    if (o.transport == (int)gbp::Transport::Measured)
+      if (const char* info = gbp_last_error(*ctx))
+        if (const char* m = std::strstr(info, "info: gbp_comm_init:")) std::cout << m + 6 << "\n";
+    std::vector<char> desc(16384);
+    if (gbp_comm_describe(*ctx, desc.data(), desc.size()) == GBP_OK) phases().comm_info = desc.data();
   }
   if (const char* info = gbp_last_error(*ctx)) phases().create_info = info;
   phases().mark("create_s");
@@ -610,6 +617,7 @@ inline void write_profile(const gbp_timing_out& t, int graph_state, const char* 
       std::string info = ph.create_info;
       for (char& ch : info) if (ch == '"' || ch == '\\') ch = '\'';
       std::fprintf(f, ", \"create\": \"%s\"}", info.c_str());
+      if (!ph.comm_info.empty()) std::fprintf(f, ", \"comm\": %s", ph.comm_info.c_str());
     }
     std::fprintf(f, "}\n");
     std::fclose(f);

@@ -8,6 +8,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <vector>
 
 using namespace gbp;
 using namespace gbp::api;
@@ -56,10 +57,11 @@ int zero_exchange(gbp_ctx* c) {
 // | no communicator, world = 1 | not this path                                                                                     | gathered = local, b.world = 1                                                      |
 // Return codes by cause: GBP_ERR_HIP (a launch, a synchronisation), GBP_ERR_COMM (the exchange), GBP_ERR_STATE (no device code).
 
-// the iteration's column: the exchange and the camera combine on the ctx's stream; x1 (profiling): recorded behind the all-gather
-static int combine_cameras_in_iteration(gbp_ctx* c, hipEvent_t x1) {
+// the iteration's column: the exchange and the camera combine on the ctx's stream; x1 (profiling): recorded behind the all-gather.
+// roll = 1: the end of an iteration; 0: the same launches as a recomputation of what the ctx holds (the measured transport's rounds)
+static int combine_cameras_in_iteration(gbp_ctx* c, hipEvent_t x1, int roll) {
   BeliefArgs b = belief_args(c);
-  b.roll = 1;
+  b.roll = roll;
   PeerComm* pc = peers(c->comm);
   int p = 0;
   switch (c->comm->kind()) {
@@ -126,7 +128,7 @@ int refresh_cameras(gbp_ctx* c, BeliefArgs& b, bool do_lmk) {
 // The two-stream schedule (RCCL): the communication stream (highest priority) takes the whole camera side of the exchange — local
 // partial sums, then the all-gather — right after the sweep; the landmark half of the belief update, which needs nothing from other
 // ranks, runs beside it on the main stream.  x0 / x1 (profiling): a bracket around the camera side on its stream.
-static int enqueue_cameras_two_streams(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1) {
+static int enqueue_cameras_two_streams(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1, int roll = 1) {
   HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
   HIPCHK(c, hipStreamWaitEvent(c->comm_stream, c->ev_fork, 0));
   if (x0) HIPCHK(c, hipEventRecord(x0, c->comm_stream));
@@ -135,7 +137,7 @@ static int enqueue_cameras_two_streams(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1)
   if (x1) HIPCHK(c, hipEventRecord(x1, c->comm_stream));
   HIPCHK(c, hipEventRecord(c->ev_join, c->comm_stream));
   BeliefArgs b = belief_args(c);
-  b.roll = 1;
+  b.roll = roll;
   launch_beliefs(b, false, true, c->stream);
   HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
   b.gathered = static_cast<const float*>(c->recv_dev);
@@ -147,14 +149,14 @@ static int enqueue_cameras_two_streams(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1)
 // ONE stream: the local camera partial sums ride in the launch of the landmark half (camera blocks write send_dev and leave,
 // landmark blocks do the rank-local belief update), so an iteration is sweep -> beliefs -> exchange -> combine: three kernels and
 // one collective.  Still no host wait with a stream-ordered transport.
-static int enqueue_cameras_one_stream(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1) {
+static int enqueue_cameras_one_stream(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1, int roll = 1) {
   BeliefArgs b = belief_args(c);
   b.cam_local = static_cast<float*>(c->send_dev);
   b.partial_only = 1;
-  b.roll = 1;
+  b.roll = roll;
   launch_beliefs(b, true, true, c->stream);
   if (x0) HIPCHK(c, hipEventRecord(x0, c->stream));
-  return combine_cameras_in_iteration(c, x1);
+  return combine_cameras_in_iteration(c, x1, roll);
 }
 
 // One iteration of a sharded ctx: sweep, then the camera side of the exchange and the belief update in one of the two schedules.
@@ -296,12 +298,202 @@ GBP_EXPORT(gbp_comm_region_selftest, nullptr, (void* region, int rank, int world
   return GBP_OK;
 }
 
+// ---- transport 5: the exchange chosen by measurement -------------------------------------------------------------------------------
+// Which transport is fastest depends on the machine (ranks sharing a GPU, PCIe or xGMI between them, how many processes the device
+// schedules), and the rules of transport 0 were written without one to measure on.  gbp_comm_init(ctx, region, 5) therefore forms, one
+// after the other, every communicator this group of ranks CAN form (eligible_candidates, from facts published before any exists: a
+// creation that fails raises the region's abort flag for good), attaches each to the ctx as comm_attach does and times what differs
+// between them — the camera side of the sharded iteration (local partials, exchange, combine, the landmark half beside them) — with
+// roll = 0: the launches recompute, from the same row sums, messages and priors, the tables the ctx already holds, as a prior-only
+// refresh does.  What transport 0 would have attached (the baseline) is timed first and last; choose_transport (gbp_transport.hpp)
+// decides from the table every rank has gathered.  Collective; every rank leaves with the same transport and schedule.
+namespace {
+
+constexpr int kMeasureWarmup = 3;      // untimed rounds (RCCL sets its channels up lazily; iterate_sharded waits for as many)
+constexpr int kMeasureReps = 10;       // timed rounds
+constexpr int kMeasureCappedReps = 2;  // ... of a candidate whose warm-up alone outlasted the baseline's whole first measurement
+
+using clk = std::chrono::steady_clock;
+inline double us_since(clk::time_point t0) { return std::chrono::duration<double, std::micro>(clk::now() - t0).count(); }
+
+// n rounds back to back; *us = wall clock from the first enqueue until the ctx's stream has drained (what a rank waits for)
+int time_rounds(gbp_ctx* c, bool two_streams, int n, double* us) {
+  const auto t0 = clk::now();
+  for (int i = 0; i < n; ++i)
+    if (int rc = two_streams ? enqueue_cameras_two_streams(c, nullptr, nullptr, 0) : enqueue_cameras_one_stream(c, nullptr, nullptr, 0)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *us = us_since(t0);
+  return GBP_OK;
+}
+
+struct Measurement {
+  int reps = 0;
+  double mine = 0;          // us per exchange on this rank
+  double total_max = 0;     // warm-up + timed rounds, us, MAX over the ranks
+};
+
+// One measurement of the attached communicator in one schedule.  cap_us > 0: the baseline's first total — a candidate whose warm-up
+// alone took longer on some rank gets kMeasureCappedReps timed rounds (agreed through the gather: every rank runs the same rounds).
+// row[r] = rank r's figure.
+int measure_attached(gbp_ctx* c, bool two_streams, double cap_us, Measurement* m, double* row) {
+  c->comm_single_stream = !two_streams;
+  if (int rc = ensure_comm_stream(c)) return rc;
+  double warm = 0, timed = 0, all[2 * gbp::kCommMaxWorld];
+  if (int rc = time_rounds(c, two_streams, kMeasureWarmup, &warm)) return rc;
+  COMMCHK(c, c->comm->all_gather_host(&warm, all, 1, e_));      // (ends in a barrier: the timed rounds start together)
+  double warm_max = 0;
+  for (int r = 0; r < c->world; ++r) warm_max = std::max(warm_max, all[r]);
+  m->reps = cap_us > 0 && warm_max > cap_us ? kMeasureCappedReps : kMeasureReps;
+  if (int rc = time_rounds(c, two_streams, m->reps, &timed)) return rc;
+  m->mine = timed / m->reps;
+  const double out[2] = {m->mine, warm + timed};
+  COMMCHK(c, c->comm->all_gather_host(out, all, 2, e_));
+  m->total_max = 0;
+  for (int r = 0; r < c->world; ++r) { row[r] = all[2 * r]; m->total_max = std::max(m->total_max, all[2 * r + 1]); }
+  return GBP_OK;
+}
+
+// the ctx without its communicator, which the caller keeps or (destroy) drops the way gbp_destroy does, behind a barrier of the group
+int comm_detach(gbp_ctx* c, bool destroy) {
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->comm_stream) HIPCHK(c, hipStreamSynchronize(c->comm_stream));
+  gbp::Comm* k = c->comm;
+  c->comm = nullptr; c->send_dev = nullptr; c->recv_dev = nullptr;
+  if (!destroy || !k) return GBP_OK;
+  std::string e;
+  const int rc = k->barrier(e);      // nobody is inside an exchange of it any more
+  delete k;
+  return rc == 0 ? GBP_OK : fail(c, GBP_ERR_COMM, "exchange: " + e);
+}
+
+std::string candidate_name(const gbp::Candidate& k) {
+  std::string n = gbp::transport_name(k.transport);
+  if (k.transport == gbp::Transport::Rccl) n += k.two_streams ? " (two streams)" : " (one stream)";
+  return n;
+}
+
+int comm_init_measured_body(gbp_ctx* c, void* region, gbp::Comm** kept) {
+  using gbp::Transport;
+  std::string err;
+  gbp::RankFacts facts[gbp::kCommMaxWorld];
+  if (gbp::comm_region_facts(region, c->rank, c->world, facts, err) != 0) return fail(c, GBP_ERR_COMM, "gbp_comm_init: " + err);
+  const char* ss = std::getenv("GBP_COMM_SINGLE_STREAM");
+  const gbp::Candidates cl = gbp::eligible_candidates(facts, c->world, ss ? (ss[0] == '1' ? 1 : 0) : -1);
+  const gbp::Candidate& base = cl.c[cl.baseline];
+  // (RCCL is made at most once: it is eligible only where it is also the baseline's transport, whose communicator is kept)
+  auto attach_new = [&](Transport t) -> int {
+    gbp::Comm* k = gbp::comm_create_in_region(region, c->rank, c->world, t, c->C, err);
+    if (!k) return fail(c, GBP_ERR_COMM, "gbp_comm_init: " + err);
+    return comm_attach(c, k);
+  };
+  if (c->world == 1) {      // nothing to measure
+    if (int rc = attach_new(base.transport)) return rc;
+    c->comm_selected_by = "rule";
+    c->comm_measured = "[]";
+    return GBP_OK;
+  }
+  // the order: the baseline; what else runs on its communicator (RCCL's other schedule); the other transports, each made once; the baseline again
+  std::vector<int> order{cl.baseline};
+  for (int pass = 0; pass < 2; ++pass)
+    for (int i = 0; i < cl.n; ++i)
+      if (i != cl.baseline && cl.c[i].eligible && (cl.c[i].transport == base.transport) == (pass == 0)) order.push_back(i);
+  order.push_back(cl.baseline);
+  std::vector<double> table((size_t)(cl.n + 1) * (size_t)c->world, 0.0);
+  Measurement ms[gbp::kMaxCandidates + 1];
+  double cap_us = 0;
+  for (size_t step = 0; step < order.size(); ++step) {
+    const gbp::Candidate& k = cl.c[order[step]];
+    const int row = step + 1 == order.size() ? cl.n : order[step];
+    if (!c->comm || c->comm->kind() != k.transport) {
+      if (c->comm) {      // the baseline's communicator waits for its second measurement, every other one has had its only
+        const bool keep = c->comm->kind() == base.transport;
+        if (keep) *kept = c->comm;
+        if (int rc = comm_detach(c, !keep)) return rc;
+      }
+      if (k.transport == base.transport && *kept) {
+        gbp::Comm* b = *kept;
+        *kept = nullptr;
+        if (int rc = comm_attach(c, b)) return rc;
+      } else if (int rc = attach_new(k.transport)) {
+        return rc;
+      }
+    }
+    if (int rc = measure_attached(c, k.two_streams, cap_us, &ms[row], &table[(size_t)row * c->world])) return rc;
+    if (step == 0) cap_us = ms[row].total_max;
+  }
+  const gbp::Choice ch = gbp::choose_transport(cl, table.data(), c->world);
+  const gbp::Candidate& win = cl.c[ch.winner];
+  if (c->comm->kind() != win.transport) {
+    if (int rc = comm_detach(c, true)) return rc;
+    if (int rc = attach_new(win.transport)) return rc;
+  }
+  c->comm_single_stream = !win.two_streams;
+  if (int rc = ensure_comm_stream(c)) return rc;
+  if (c->comm_single_stream && c->comm_stream) {      // the second queue was only measured: it would slow every dispatch of the first
+    HIPCHK(c, hipStreamSynchronize(c->comm_stream));
+    HIPCHK(c, hipStreamDestroy(c->comm_stream));
+    c->comm_stream = nullptr;
+  }
+  if (c->uploaded) {      // the winner's exchange buffers hold the partials the ctx's camera tables were made from, as after an iteration
+    double us = 0;
+    if (int rc = time_rounds(c, win.two_streams, 1, &us)) return rc;
+  }
+  c->comm_warm = 0;
+  // the record
+  const int base_row = ch.base_first <= ch.base_last ? cl.baseline : cl.n;
+  std::string js = "[";
+  char buf[320];
+  for (int i = 0; i < cl.n; ++i) {
+    const gbp::Candidate& k = cl.c[i];
+    std::snprintf(buf, sizeof(buf), "%s{\"transport\": \"%s\", \"two_streams\": %s, \"eligible\": %s", i ? ", " : "", gbp::transport_name(k.transport),
+                  k.two_streams ? "true" : "false", k.eligible ? "true" : "false");
+    js += buf;
+    if (!k.eligible) {
+      js += std::string(", \"reason\": \"") + k.reason + "\"}";
+      continue;
+    }
+    const int row = i == cl.baseline ? base_row : i;
+    std::snprintf(buf, sizeof(buf), ", \"us_per_exchange\": %.3f, \"us_this_rank\": %.3f, \"reps\": %d", ch.figure[i], table[(size_t)row * c->world + c->rank], ms[row].reps);
+    js += buf;
+    if (i == cl.baseline) {
+      std::snprintf(buf, sizeof(buf), ", \"baseline\": true, \"us_first\": %.3f, \"us_last\": %.3f", ch.base_first, ch.base_last);
+      js += buf;
+    }
+    if (i == ch.winner) js += ", \"chosen\": true";
+    js += "}";
+  }
+  c->comm_measured = js + "]";
+  c->comm_selected_by = "measurement";
+  std::snprintf(buf, sizeof(buf), "info: gbp_comm_init: measured %d rounds each, chose %s at %.1f us per exchange", kMeasureReps, candidate_name(win).c_str(), ch.figure[ch.winner]);
+  std::string info = buf;
+  if (ch.runner_up >= 0) {
+    std::snprintf(buf, sizeof(buf), ", runner-up %s at %.1f us", candidate_name(cl.c[ch.runner_up]).c_str(), ch.figure[ch.runner_up]);
+    info += buf;
+  }
+  std::snprintf(buf, sizeof(buf), "; what transport 0 attaches (%s): %.1f us first, %.1f us last", candidate_name(base).c_str(), ch.base_first, ch.base_last);
+  info += buf;
+  c->err = c->err.rfind("info:", 0) == 0 ? c->err + " | " + info : info;      // (behind gbp_create's own line, if the ctx still holds it)
+  return GBP_OK;
+}
+
+int comm_init_measured(gbp_ctx* c, void* region) {
+  gbp::Comm* kept = nullptr;
+  const int rc = comm_init_measured_body(c, region, &kept);
+  if (rc != GBP_OK) gbp::comm_region_abort(region);      // the other ranks leave their barriers with an error instead of waiting
+  if (kept && kept != c->comm) delete kept;
+  return rc;
+}
+
+}  // namespace
+
 GBP_EXPORT(gbp_comm_init, c, (gbp_ctx* c, void* region, int transport), (c, region, transport)) {
   if (!c || !region) return GBP_ERR_INVALID;
   if (c->comm) return fail(c, GBP_ERR_STATE, "gbp_comm_init: the ctx already has a communicator");
+  if (transport == (int)gbp::Transport::Measured) return comm_init_measured(c, region);
   std::string err;
   gbp::Comm* comm = gbp::comm_create_from_region(region, c->rank, c->world, static_cast<gbp::Transport>(transport), c->C, err);
   if (!comm) return fail(c, GBP_ERR_COMM, "gbp_comm_init: " + err);
+  c->comm_selected_by = transport == (int)gbp::Transport::Auto ? "rule" : "caller";
   return comm_attach(c, comm);
 }
 
@@ -329,10 +521,15 @@ GBP_EXPORT(gbp_comm_describe, c, (gbp_ctx* c, char* buf, size_t cap), (c, buf, c
   (void)hipGetDevice(&dev);
   (void)hipDeviceGetPCIBusId(bus, sizeof(bus), dev);
   const std::string lib = c->comm ? c->comm->library_path() : "";
-  std::snprintf(buf, cap, "{\"rank\": %d, \"world\": %d, \"device\": %d, \"pci_bus_id\": \"%s\", \"transport\": \"%s\", \"library\": \"%s\", "
-                          "\"library_version\": %d, \"two_streams\": %s}",
+  char head[1024];
+  std::snprintf(head, sizeof(head), "{\"rank\": %d, \"world\": %d, \"device\": %d, \"pci_bus_id\": \"%s\", \"transport\": \"%s\", \"library\": \"%s\", "
+                                    "\"library_version\": %d, \"two_streams\": %s, \"selected_by\": \"%s\"",
                 c->rank, c->world, dev, bus, c->comm ? c->comm->name() : "none", lib.c_str(), c->comm ? c->comm->library_version() : 0,
-                (c->comm && !c->comm_single_stream) ? "true" : "false");
+                (c->comm && !c->comm_single_stream) ? "true" : "false", c->comm_selected_by);
+  // transport 5: what gbp_comm_init timed, one entry per candidate (an empty list with one rank: nothing to measure)
+  const std::string text = std::string(head) + (c->comm_measured.empty() ? "" : ", \"measured\": " + c->comm_measured) + "}";
+  std::snprintf(buf, cap, "%s", text.c_str());
+  if (text.size() + 1 > cap) return fail(c, GBP_ERR_INVALID, "gbp_comm_describe: the text needs " + std::to_string(text.size() + 1) + " bytes");
   return GBP_OK;
 }
 

@@ -89,12 +89,14 @@ struct RegionHeader {
   uint32_t magic, world, n_cams, pad;
   std::atomic<uint32_t> bar_count, bar_sense, abort_flag, id_ready;
   char id[kCommIdBytes];
-  char gpu_id[kCommMaxWorld][64];
+  RankFacts facts[kCommMaxWorld];                    // every rank's GPU (all transports); peer access and librccl (the measured transport)
   double scratch[kCommMaxWorld][16];
   char ipc[kCommMaxWorld][HIP_IPC_HANDLE_SIZE];     // p2p: every rank's IPC handle of its exchange buffer (fixed size: the region's
                                                      // size stays linear in world x cams)
 };
 static_assert(std::atomic<uint32_t>::is_always_lock_free, "cross-process barrier needs lock-free atomics");
+static_assert(sizeof(RegionHeader) == 32 + kCommIdBytes + kCommMaxWorld * (64 + 16 * sizeof(double) + HIP_IPC_HANDLE_SIZE),
+              "the header's size is part of gbp_comm_region_bytes");
 
 inline size_t header_bytes() { return (sizeof(RegionHeader) + 255) / 256 * 256; }
 inline float* region_data(void* region) { return reinterpret_cast<float*>(static_cast<char*>(region) + header_bytes()); }
@@ -121,8 +123,11 @@ struct RegionPeer {   // one rank's view of the region: sense-reversing barrier,
     }
     return true;
   }
+  // The sense of a barrier is the opposite of the last one's, which the region still shows when a rank arrives: it changes only once
+  // every rank has arrived at the NEXT barrier, this one included.  So any copy of a RegionPeer may take the next barrier, whichever
+  // copy took the last (the measured transport makes and drops communicators on one region).
   bool barrier(std::string& err) {
-    sense ^= 1u;
+    sense = h->bar_sense.load(std::memory_order_acquire) ^ 1u;
     if (h->bar_count.fetch_add(1, std::memory_order_acq_rel) + 1 == (uint32_t)world) {
       h->bar_count.store(0, std::memory_order_relaxed);
       h->bar_sense.store(sense, std::memory_order_release);
@@ -329,11 +334,11 @@ class P2pComm : public PeerComm {
   virtual bool setup(RegionHeader* h, int dev, uint32_t n_cams, std::string& err) {
     // ranks on different GPUs must reach each other's memory
     for (int r = 0; r < world; ++r) {
-      if (r == rank || std::strncmp(h->gpu_id[r], h->gpu_id[rank], 64) == 0) continue;
+      if (r == rank || same_gpu(h->facts[r], h->facts[rank])) continue;
       int pdev = -1, can = 0;
-      if (hipDeviceGetByPCIBusId(&pdev, h->gpu_id[r]) != hipSuccess || hipDeviceCanAccessPeer(&can, dev, pdev) != hipSuccess || !can) {
-        err = std::string("p2p: the GPU of rank ") + std::to_string(rank) + " (" + h->gpu_id[rank] + ") cannot access the GPU of rank " +
-              std::to_string(r) + " (" + h->gpu_id[r] + ")";
+      if (hipDeviceGetByPCIBusId(&pdev, h->facts[r].bus) != hipSuccess || hipDeviceCanAccessPeer(&can, dev, pdev) != hipSuccess || !can) {
+        err = std::string("p2p: the GPU of rank ") + std::to_string(rank) + " (" + h->facts[rank].bus + ") cannot access the GPU of rank " +
+              std::to_string(r) + " (" + h->facts[r].bus + ")";
         return false;
       }
     }
@@ -435,7 +440,7 @@ int comm_region_init(void* region, size_t bytes, uint32_t n_cams, int world) {
   h->magic = kMagic; h->world = (uint32_t)world; h->n_cams = n_cams; h->pad = 0;
   h->bar_count.store(0); h->bar_sense.store(0); h->abort_flag.store(0); h->id_ready.store(0);
   std::memset(h->id, 0, sizeof(h->id));
-  std::memset(h->gpu_id, 0, sizeof(h->gpu_id));
+  std::memset(h->facts, 0, sizeof(h->facts));
   std::memset(h->ipc, 0, sizeof(h->ipc));
   return 0;
 }
@@ -463,34 +468,39 @@ int comm_region_selftest(void* region, int rank, int world, int rounds, std::str
   return 0;
 }
 
-Comm* comm_create_from_region(void* region, int rank, int world, Transport transport, uint32_t n_cams, std::string& err) {
+namespace {
+
+RegionHeader* checked_region(void* region, int rank, int world, std::string& err) {
   RegionHeader* h = static_cast<RegionHeader*>(region);
   if (!h || h->magic != kMagic || (int)h->world != world || rank < 0 || rank >= world) { err = "bad communication region"; return nullptr; }
-  RegionPeer peer;
-  peer.h = h; peer.world = world;
-  // 1. every rank publishes the identity of its GPU; a GPU shared by two ranks rules RCCL out
-  int dev = 0;
-  char bus[64] = {0};
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetPCIBusId(bus, sizeof(bus), dev) != hipSuccess) { err = "hipDeviceGetPCIBusId failed"; return nullptr; }
-  std::memcpy(h->gpu_id[rank], bus, sizeof(bus));
-  if (!peer.barrier(err)) return nullptr;
-  bool shared = false;
-  for (int a = 0; a < world; ++a)
-    for (int b = a + 1; b < world; ++b)
-      if (std::strncmp(h->gpu_id[a], h->gpu_id[b], 64) == 0) shared = true;
-  if (transport == Transport::Auto) transport = shared ? Transport::HostStaged : Transport::Rccl;
+  return h;
+}
+
+// this rank's GPU into its slot of the region's table (the rest of the slot cleared)
+bool publish_gpu(RegionHeader* h, int rank, int* dev, std::string& err) {
+  RankFacts mine;
+  std::memset(&mine, 0, sizeof(mine));
+  if (hipGetDevice(dev) != hipSuccess || hipDeviceGetPCIBusId(mine.bus, sizeof(mine.bus), *dev) != hipSuccess) { err = "hipDeviceGetPCIBusId failed"; return false; }
+  mine.bus[sizeof(mine.bus) - 1] = 0;
+  std::memcpy(&h->facts[rank], &mine, sizeof(mine));
+  return true;
+}
+
+// every rank knows every rank's GPU: the communicator of one transport (any number but Rccl, P2p, P2pSlices: host-staged)
+Comm* create_transport(RegionHeader* h, const RegionPeer& peer, int rank, int world, int dev, Transport transport, uint32_t n_cams,
+                       std::string& err) {
   switch (transport) {
     case Transport::P2p: return create_in_region<P2pComm>(h, peer, rank, world, dev, n_cams, err);
     case Transport::P2pSlices: return create_in_region<P2pSlicesComm>(h, peer, rank, world, dev, n_cams, err);
     case Transport::Rccl: break;
     default: return create_in_region<StagedComm>(h, peer, rank, world, dev, n_cams, err);      // (any other number: as before, host-staged)
   }
-  if (shared) { err = "RCCL needs one GPU per rank, but two ranks share a GPU"; h->abort_flag.store(1); return nullptr; }
-  // 2. RCCL: rank 0 draws the unique id, the region hands it to the others
+  if (any_shared_gpu(h->facts, world)) { err = "RCCL needs one GPU per rank, but two ranks share a GPU"; h->abort_flag.store(1); return nullptr; }
+  // RCCL: rank 0 draws the unique id, the region hands it to the others
   if (rank == 0) {
     if (comm_unique_id(h->id, err) != 0) { h->abort_flag.store(1); return nullptr; }
     h->id_ready.store(1, std::memory_order_release);
-  } else if (!peer.wait_until(h->id_ready, 1u, err, "RCCL unique id")) {
+  } else if (!RegionPeer(peer).wait_until(h->id_ready, 1u, err, "RCCL unique id")) {
     return nullptr;
   }
   Comm* c = comm_create_rccl(h->id, rank, world, err);
@@ -498,6 +508,55 @@ Comm* comm_create_from_region(void* region, int rank, int world, Transport trans
   static_cast<RcclComm*>(c)->peer = peer;
   if (!static_cast<RcclComm*>(c)->peer.barrier(err)) { delete c; return nullptr; }
   return c;
+}
+
+}  // namespace
+
+Comm* comm_create_from_region(void* region, int rank, int world, Transport transport, uint32_t n_cams, std::string& err) {
+  RegionHeader* h = checked_region(region, rank, world, err);
+  if (!h) return nullptr;
+  RegionPeer peer;
+  peer.h = h; peer.world = world;
+  // every rank publishes the identity of its GPU; a GPU shared by two ranks rules RCCL out
+  int dev = 0;
+  if (!publish_gpu(h, rank, &dev, err)) return nullptr;
+  if (!peer.barrier(err)) return nullptr;
+  if (transport == Transport::Auto) transport = any_shared_gpu(h->facts, world) ? Transport::HostStaged : Transport::Rccl;
+  return create_transport(h, peer, rank, world, dev, transport, n_cams, err);
+}
+
+int comm_region_facts(void* region, int rank, int world, RankFacts* table, std::string& err) {
+  RegionHeader* h = checked_region(region, rank, world, err);
+  if (!h) return -1;
+  RegionPeer peer;
+  peer.h = h; peer.world = world;
+  int dev = 0;
+  if (!publish_gpu(h, rank, &dev, err)) { h->abort_flag.store(1); return -1; }
+  if (!peer.barrier(err)) return -1;
+  // every rank's GPU is known: what this rank can reach, and (own GPUs only) whether it has the collective library
+  RankFacts& mine = h->facts[rank];
+  uint64_t mask = 0;
+  for (int r = 0; r < world; ++r) {
+    int pdev = -1, can = 0;
+    if (r == rank || same_gpu(h->facts[r], mine)) can = 1;
+    else if (hipDeviceGetByPCIBusId(&pdev, h->facts[r].bus) != hipSuccess || hipDeviceCanAccessPeer(&can, dev, pdev) != hipSuccess) { can = 0; (void)hipGetLastError(); }
+    if (can) mask |= (uint64_t)1 << r;
+  }
+  mine.peer_mask = mask;
+  mine.has_rccl = !any_shared_gpu(h->facts, world) && rccl().handle != nullptr ? 1u : 0u;
+  if (!peer.barrier(err)) return -1;
+  std::memcpy(table, h->facts, sizeof(RankFacts) * (size_t)world);
+  return peer.barrier(err) ? 0 : -1;      // nobody republishes (a later comm_create_from_region on this region) before everyone has read
+}
+
+Comm* comm_create_in_region(void* region, int rank, int world, Transport transport, uint32_t n_cams, std::string& err) {
+  RegionHeader* h = checked_region(region, rank, world, err);
+  if (!h) return nullptr;
+  RegionPeer peer;
+  peer.h = h; peer.world = world;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) { err = "hipGetDevice failed"; h->abort_flag.store(1); return nullptr; }
+  return create_transport(h, peer, rank, world, dev, transport, n_cams, err);
 }
 
 }  // namespace gbp

@@ -5,7 +5,7 @@
 // buffer of camera partial sums; one ALL-GATHER per iteration gives every rank all of them, and each rank adds
 // prior + partials in rank order (k_beliefs) — deterministic, bit-identical camera beliefs on all ranks.
 //
-// Four transports (Transport, gbp_transport.hpp).  Comm::kind() says which one a communicator is; its name, whether it is
+// Four transports (Transport, gbp_transport.hpp; a fifth value, Measured, is a way to choose among them: gbp_api_comm.cpp).  Comm::kind() says which one a communicator is; its name, whether it is
 // stream-ordered and whether it exchanges through buffers of its own follow from that:
 //   * Rccl (xGMI): ncclAllGather on a HIP stream — stream-ordered, capturable into the iteration's hipGraph.  librccl
 //     is dlopen'ed on first use (no link-time dependency: a single-GPU user never loads it, and inside a PyTorch
@@ -37,7 +37,7 @@
 namespace gbp {
 
 constexpr int kCommIdBytes = 128;      // NCCL_UNIQUE_ID_BYTES
-constexpr int kCommMaxWorld = 64;
+// (kCommMaxWorld: gbp_transport.hpp)
 
 // X = [2 parities][world][C][kCamRec] fp32: rank r's partials of an exchange go into slot r of the exchange's parity
 struct ExchangeLayout {
@@ -59,10 +59,7 @@ class Comm {
  public:
   virtual ~Comm() {}
   virtual Transport kind() const = 0;      // never Auto
-  const char* name() const {
-    static const char* const names[] = {"none", "rccl", "host-staged", "p2p", "p2p-slices"};      // by Transport
-    return names[(int)kind()];
-  }
+  const char* name() const { return transport_name(kind()); }
   // stream-ordered: all_gather only enqueues on its stream (the others synchronise it, exchange and return with recv complete)
   bool stream_ordered() const { return kind() == Transport::Rccl; }
   // recv[r][0..n) = send of rank r, for all r
@@ -123,5 +120,15 @@ void comm_region_abort(void* region);      // a supervisor saw a rank die: wake 
 int comm_region_selftest(void* region, int rank, int world, int rounds, std::string& err);   // protocol check, no device
 // n_cams: the ctx's cameras, the size of a rank's slot in X
 Comm* comm_create_from_region(void* region, int rank, int world, Transport transport, uint32_t n_cams, std::string& err);
+
+// The measured transport (Transport::Measured, gbp_api_comm.cpp: comm_init_measured) takes the two steps of comm_create_from_region apart.
+// 1. Collective: every rank publishes its facts in the region — its GPU; then, knowing every rank's GPU, peer access towards each and
+//    (only where no two ranks share a GPU: RCCL is out otherwise, and the library is not loaded to learn nothing) whether librccl
+//    resolves — and leaves with the same table[world] as every other rank.  No communicator exists yet, nothing can have failed in one.
+int comm_region_facts(void* region, int rank, int world, RankFacts* table, std::string& err);
+// 2. Collective: a communicator of ONE given transport (Rccl, HostStaged, P2p, P2pSlices) that eligible_candidates(table) allows.
+//    Rccl at most once per region (its unique id is handed over once): the measured transport keeps that communicator between its
+//    two measurements.  A failure raises the region's abort flag, as in comm_create_from_region.
+Comm* comm_create_in_region(void* region, int rank, int world, Transport transport, uint32_t n_cams, std::string& err);
 
 }  // namespace gbp

@@ -90,6 +90,8 @@ struct gbp_ctx {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   int comm_warm = 0;                   // sharded iterations run directly so far (RCCL must have run before a capture)
   bool comm_single_stream = false;     // all-gather on the main stream, no second queue (default for world <= 2)
+  const char* comm_selected_by = "caller";   // gbp_comm_describe: who chose the transport — "caller", "rule" (transport 0) or "measurement" (5)
+  std::string comm_measured;           // transport 5: the JSON list of what gbp_comm_init timed, one entry per candidate ("" for the others)
   hipStream_t own_stream = nullptr, stream = nullptr;
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;

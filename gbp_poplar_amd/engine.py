@@ -288,11 +288,19 @@ class GbpEngine:
         buf = C.create_string_buffer(bytes(id128), 128)
         self._chk(self.lib.gbp_comm_init_rccl(self.h, buf), "gbp_comm_init_rccl")
 
+    def comm_init(self, region_address, transport=0):
+        """Collective over the ranks of a launcher-made group: attaches the library's communicator over `transport` (0 auto, 1 rccl,
+        2 host-staged, 3 p2p, 4 p2p-slices, 5 measured: the library times what the ranks can form and keeps the fastest — see
+        comm_describe()["measured"]).  region_address: the address of the shared region (gbp_comm_region_bytes / gbp_comm_region_init)
+        as this process maps it."""
+        self._chk(self.lib.gbp_comm_init(self.h, C.c_void_p(int(region_address)), int(transport)), "gbp_comm_init")
+
     def comm_describe(self):
-        """dict: rank, world, device, pci_bus_id, transport, library (resolved path of librccl), library_version, two_streams"""
+        """dict: rank, world, device, pci_bus_id, transport, library (resolved path of librccl), library_version, two_streams,
+        selected_by ("caller", "rule", "measurement") and, after comm_init(..., 5), measured: one dict per candidate"""
         import json
-        buf = C.create_string_buffer(1024)
-        self._chk(self.lib.gbp_comm_describe(self.h, buf, 1024), "gbp_comm_describe")
+        buf = C.create_string_buffer(16384)
+        self._chk(self.lib.gbp_comm_describe(self.h, buf, 16384), "gbp_comm_describe")
         return json.loads(buf.value.decode())
 
     def comm_set_schedule(self, two_streams):

@@ -59,6 +59,19 @@ GBP_API int gbp_linearise_factors(gbp_ctx* ctx);  /* the factor half of LINEARIS
  * gather them: two host barriers per exchange, a third of p2p's bytes at 8 ranks, the same bits.  Outside the iteration
  * (gbp_linearise's exchange, gbp_new_keyframe's and the prior-only refreshes, gbp_comm_probe) it uses p2p's full peer gather unchanged;
  * gbp_comm_set_schedule has no effect on either.
+ * 5 = measured: gbp_comm_init itself finds out which of the above is fastest HERE.  Every rank first publishes facts in the region (its
+ * GPU, peer access towards every other rank's GPU, whether librccl resolves); from that table every rank derives the same list of
+ * transports the group can form (RCCL: one GPU per rank and librccl everywhere; p2p, p2p-slices: mutual peer access or one shared GPU;
+ * host-staged: always) — one that it cannot form is never tried.  Each of the others is created once, attached, and timed on the camera
+ * side of the sharded iteration (local partials, exchange, combine, the landmark half beside them; RCCL in both stream schedules, or in
+ * the one GBP_COMM_SINGLE_STREAM names): 3 warm-up and 10 timed rounds that recompute the tables the ctx already holds, so an uploaded
+ * ctx keeps every bit and a fresh one is refilled by gbp_upload.  A transport's figure is the maximum over the ranks.  What transport 0
+ * would have attached is timed first and last; another one is taken only if it beats the better of those two figures by more than
+ * their difference, so ties and noise keep today's choice, and every rank decides from the same gathered table.  gbp_comm_transport
+ * then names the transport that won; gbp_comm_describe adds "selected_by": "measurement" and "measured", a list with one entry per
+ * candidate (transport, two_streams, eligible, reason | us_per_exchange, us_this_rank, reps); gbp_last_error holds an "info:" line with
+ * the winner and the runner-up.  With one rank there is nothing to measure: transport 0's choice, "measured": [].  For the other
+ * transports "selected_by" is "caller" (1 - 4, gbp_comm_init_rccl) or "rule" (0).
  * Launchers with their own rendezvous (torchrun, MPI) pass the 128-byte RCCL id around themselves:
  * gbp_comm_unique_id on rank 0, gbp_comm_init_rccl on every rank.  All calls are collective over the ranks.
  * Scheduling: with 4 ranks or more the camera side of the exchange (local partial sums, all-gather) runs on a second,
@@ -81,7 +94,8 @@ GBP_API int gbp_comm_init_rccl(gbp_ctx* ctx, const void* id128);
 GBP_API const char* gbp_comm_transport(const gbp_ctx* ctx);            /* "rccl", "host-staged", "p2p", "p2p-slices" or "none" */
 GBP_API int gbp_comm_barrier(gbp_ctx* ctx);
 /* What a first multi-GPU run puts on record next to its numbers (bench.py's preflight block): gbp_comm_describe writes one
- * JSON object (rank, world, device, PCI bus id, transport, the collective library's resolved path and version, schedule);
+ * JSON object (rank, world, device, PCI bus id, transport, the collective library's resolved path and version, schedule, who chose
+ * the transport and — transport 5 — what was measured: give it 8 KiB; GBP_ERR_INVALID names the size when `cap` is too small);
  * gbp_comm_probe times `reps` all-gathers of the camera partial buffers back to back (collective); gbp_comm_set_schedule
  * switches between the one-stream and the two-stream form of the sharded iteration (identical results) so that a launcher can
  * MEASURE both and keep the faster one instead of trusting the ">= 4 ranks" rule (ba.cpp:617-649 has no such choice to make:
