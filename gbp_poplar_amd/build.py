@@ -109,7 +109,7 @@ def build(force=False, verbose=False, test_hooks=True):
         build_experiments(force, verbose)
     os.makedirs(BIN, exist_ok=True)
     inc = os.path.join(HERE, "..", "include")
-    cli_deps = [os.path.join(CSRC, f) for f in ("cli_common.hpp", "gbp_transport.hpp")] + [os.path.join(inc, f) for f in os.listdir(inc)] + [LIB]
+    cli_deps = [os.path.join(CSRC, f) for f in ("cli_common.hpp", "gbp_transport.hpp", "gbp_metric_gather.hpp")] + [os.path.join(inc, f) for f in os.listdir(inc)] + [LIB]
     for name, src in CLI_SRCS.items():
         path = os.path.join(CSRC, src)
         exe = os.path.join(BIN, name)

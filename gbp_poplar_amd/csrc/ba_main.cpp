@@ -35,6 +35,9 @@ static int run(const cli::Options& o, cli::Problem& P, cli::RankCtx& rk) {
   cli::MetricPipe pipe;
   pipe.ctx = ctx;
   pipe.on = !rk.region && !o.verbose;
+  // the bursts of the default loop (--eval_every 1, no --v): a multi-rank run issues them like a single process — the metric rides in the
+  // sharded iterations where the transport allows (gbp_comm_describe: "metric") — and sums each burst's records over the ranks
+  const bool bursts = !o.verbose && o.eval_every == 1;
   unsigned iter = 0;
   cli::RunReport rep;
   const auto write_iter = [](unsigned it_now, const gbp_eval_out& e) {   // ba.cpp:1020-1024
@@ -52,14 +55,15 @@ static int run(const cli::Options& o, cli::Problem& P, cli::RankCtx& rk) {
   // the reference's default (the metric after EVERY iteration) with a whole number of --steps: the loop's body goes down as
   // gbp_ba_loop — prior weakening, iteration and metric of many passes in one call (ONE launch on a graph that runs in the persistent
   // kernel, which weakens the priors itself); the lines are written from the results, "Weakening priors" where the loop weakens
-  const bool whole_loop = pipe.on && o.eval_every == 1 && cli::whole_steps(o.steps);
+  const bool whole_loop = bursts && cli::whole_steps(o.steps);
   for (int i = 0; i < o.n_iters; ++i) {
     if (whole_loop) {
-      const int cap = gbp_graph_state(ctx) == 2 ? 512 : 128;      // (so that the lines keep coming on a large graph)
+      const int cap = !rk.region && gbp_graph_state(ctx) == 2 ? 512 : gbp::kMetricBurstMax;      // (so that the lines keep coming on a large graph)
       int burst = std::min(cap, o.n_iters - i);
       if (cap == 512 && i + burst == o.n_iters && burst > 96) burst -= 64;      // the run ends with a short burst: its lines are the ones no launch overlaps
       series.resize((size_t)burst);
       CLI_CHECK(ctx, gbp_ba_loop(ctx, burst, iter, (unsigned)o.steps, series.data()));
+      CLI_CHECK(ctx, cli::sum_burst_over_ranks(ctx, rk, series.data(), burst));
       rep.last = series.back(); rep.have_metric = true;
       lines.post([first = iter, steps2 = 2u * (unsigned)o.steps, batch = series, &write_iter] {
         for (size_t k = 0; k < batch.size(); ++k) {
@@ -93,21 +97,22 @@ static int run(const cli::Options& o, cli::Problem& P, cli::RankCtx& rk) {
       continue;
     }
     if (((iter + 1) % 2 == 0) && (iter < o.steps * 2)) {       // ba.cpp:1003-1006
-      if (pipe.on && o.eval_every == 1) lines.post([] { std::cout << "Weakening priors \n"; });      // in order, behind the lines of the burst before it
+      if (bursts) lines.post([] { std::cout << "Weakening priors \n"; });      // in order, behind the lines of the burst before it
       else pipe.line("Weakening priors \n");
       CLI_CHECK(ctx, gbp_weaken_priors(ctx));
     }
-    if (pipe.on && o.eval_every == 1) {
+    if (bursts) {
       // the reference's default: the metric after EVERY iteration.  All iterations up to the next prior weakening go down in
       // one call (gbp_ba_loop: one launch on a graph that runs in the persistent kernel), at most 128 at a time so
       // that the lines keep coming on a large graph — 512 where an iteration takes microseconds (the persistent kernel: every
       // launch boundary is ~60 us of idle GPU), but the LAST burst of the run short: its lines are the ones no launch overlaps
-      const int cap = gbp_graph_state(ctx) == 2 ? 512 : 128;
+      const int cap = !rk.region && gbp_graph_state(ctx) == 2 ? 512 : gbp::kMetricBurstMax;
       int burst = 1;
       while (burst < cap && i + burst < o.n_iters && !(((iter + burst + 1) % 2 == 0) && (iter + burst < o.steps * 2))) ++burst;
       if (cap == 512 && i + burst == o.n_iters && burst > 96) burst -= 64;      // ... so the run ends with a burst of 64
       series.resize((size_t)burst);
       CLI_CHECK(ctx, gbp_ba_loop(ctx, burst, iter, 0u, series.data()));      // steps = 0: the weakenings are this loop's own calls
+      CLI_CHECK(ctx, cli::sum_burst_over_ranks(ctx, rk, series.data(), burst));
       rep.last = series.back(); rep.have_metric = true;
       lines.post([first = iter, batch = series, &write_iter] {
         for (size_t k = 0; k < batch.size(); ++k) write_iter(first + (unsigned)k, batch[k]);

@@ -15,6 +15,7 @@
 #include "../../include/gbp_mi355x.h"
 #include "../../include/gbp_mi355x_multi.h"       // --ipus N: one forked rank per GPU
 #include "gbp_transport.hpp"                      // --transport: the names of gbp_comm_init's transport numbers
+#include "gbp_metric_gather.hpp"                  // --ipus N: the cross-rank sum of a burst's metric records
 #include "../../include/gbp_mi355x_compat.h"      // MetricPipe: the metric in two halves (gbp_iterate_eval / gbp_eval_end), so that printing overlaps the next iterations
 
 #include <condition_variable>
@@ -126,7 +127,8 @@ inline void usage(bool slam) {
                "  --seed arg (=0)                seed of the initialisation noise (0 = from the clock)\n"
                "  --eval_every arg (=1)          read back + evaluate every K iterations\n"
                "  --transport arg (=auto)        exchange between ranks: auto | rccl | host | p2p | p2p-slices | measured (host, p2p, p2p-slices: ranks may\n"
-               "                                 share a GPU; measured: time every transport the ranks can form, keep the fastest)\n"
+               "                                 share a GPU; host is also spelled host-staged; measured: time every transport the ranks\n"
+               "                                 can form, keep the fastest)\n"
                "  --out_file arg                 write the refined cameras / landmarks (belief means) in the input's format\n";
 }
 
@@ -172,7 +174,7 @@ inline int parse(int argc, char** argv, bool slam, Options& o) {
       else if (k == "out_file") o.out_file = v;
       else if (k == "transport") {
         using T = gbp::Transport;
-        o.transport = v == "rccl" ? (int)T::Rccl : v == "host" ? (int)T::HostStaged : v == "p2p" ? (int)T::P2p : v == "p2p-slices" ? (int)T::P2pSlices :
+        o.transport = v == "rccl" ? (int)T::Rccl : (v == "host" || v == "host-staged") ? (int)T::HostStaged : v == "p2p" ? (int)T::P2p : v == "p2p-slices" ? (int)T::P2pSlices :
                       v == "measured" ? (int)T::Measured : v == "auto" ? (int)T::Auto : std::stoi(v);
       }
       else { std::cerr << "unrecognised option '--" << k << "'\n"; return 2; }
@@ -319,6 +321,8 @@ inline int write_solution(const Options& o, const Problem& P, gbp_ctx* ctx, bool
 struct RankCtx {
   int rank = 0, world = 1;
   void* region = nullptr;       // shared rendezvous / staging region (gbp_comm_region_*), world > 1 only
+  void* metric_area = nullptr;  // shared [2 parities][world][gbp::kMetricBurstMax] metric records (gbp_metric_gather.hpp), mapped with the region
+  unsigned bursts = 0;          // bursts summed so far: the parity of the next one
   gbp_shard shard{0, 1, 0, 0};
 };
 
@@ -422,6 +426,13 @@ template <class F> int run_ranks(int world, uint32_t n_cams, bool force, F&& bod
     std::cerr << "could not create the shared region of the ranks\n";
     return 1;
   }
+  const size_t metric_bytes = gbp::metric_area_bytes(world);
+  void* metric_area = mmap(nullptr, metric_bytes, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
+  if (metric_area == MAP_FAILED) {
+    std::cerr << "could not create the shared metric records of the ranks\n";
+    munmap(region, bytes);
+    return 1;
+  }
   std::cout.flush();
   std::fflush(nullptr);
   std::vector<pid_t> pid((size_t)world, -1);
@@ -430,7 +441,7 @@ template <class F> int run_ranks(int world, uint32_t n_cams, bool force, F&& bod
     pid[r] = fork();
     if (pid[r] < 0) { std::cerr << "fork failed\n"; gbp_comm_region_abort(region); fork_failed = true; break; }
     if (pid[r] == 0) {
-      rk.rank = r; rk.world = world; rk.region = region;
+      rk.rank = r; rk.world = world; rk.region = region; rk.metric_area = metric_area;
       if (r != 0 && !std::freopen("/dev/null", "w", stdout)) std::_Exit(1);     // rank 0 prints (ba.cpp:996,1026-1028)
       int rc = 1;
       try { rc = body(rk); } catch (const std::exception& e) { std::cerr << "rank " << r << ": " << e.what() << "\n"; }
@@ -471,6 +482,7 @@ template <class F> int run_ranks(int world, uint32_t n_cams, bool force, F&& bod
     }
     usleep(20000);
   }
+  munmap(metric_area, metric_bytes);
   munmap(region, bytes);
   return first_bad;
 }
@@ -478,7 +490,8 @@ template <class F> int run_ranks(int world, uint32_t n_cams, bool force, F&& bod
 // The reference's loop prints the metric after every iteration (ba.cpp:1009-1028).  To keep that output without making
 // the GPU wait for the host every iteration, the metric of iteration i is queued (gbp_eval_begin) and printed only after
 // iteration i+1 has been queued too; lines that belong after it ("Weakening priors") are deferred with it, so stdout is
-// byte-identical to the unpipelined loop.  Off for multi-rank runs (the metric needs a gather) and for --v.
+// byte-identical to the unpipelined loop.  Off for --v, and for multi-rank runs: at the default --eval_every 1 those issue the same bursts
+// as a single process and sum the records over the ranks (sum_burst_over_ranks); otherwise every metric is a gbp_eval_global.
 struct MetricPipe {
   gbp_ctx* ctx = nullptr;
   bool on = false, pending = false;
@@ -567,6 +580,18 @@ struct AsyncLines {
   }
 };
 
+// A multi-rank run's burst (gbp_ba_loop with a host `out`: the LOCAL shard's sums of n <= gbp::kMetricBurstMax passes) -> the sums over all
+// ranks, in place: this rank's row of the burst's parity, ONE barrier, the rows added in rank order (gbp_metric_gather.hpp: what
+// gbp_eval_global returns, pass for pass).  A single-process run: nothing to do.
+inline int sum_burst_over_ranks(gbp_ctx* ctx, RankCtx& rk, gbp_eval_out* series, int n) {
+  if (!rk.region) return GBP_OK;
+  const int parity = (int)(rk.bursts++ & 1u);
+  std::memcpy(gbp::metric_row(rk.metric_area, rk.world, parity, rk.rank), series, sizeof(gbp_eval_out) * (size_t)n);
+  if (const int rc = gbp_comm_barrier(ctx)) return rc;
+  gbp::metric_sum_ranks(gbp::metric_row(rk.metric_area, rk.world, parity, 0), rk.world, n, series);
+  return GBP_OK;
+}
+
 #define CLI_CHECK(ctx, call)                                                              \
   do {                                                                                    \
     const int rc_ = (call);                                                               \
@@ -628,6 +653,10 @@ inline void write_profile(const gbp_timing_out& t, int graph_state, const char* 
 // The end of a run, shared by ./ba and ./slam: the ctx is destroyed FIRST (its teardown is part of what the user waits for), then the
 // "Total time" line — which covers the process from exec to here — and the --profile report.
 inline int finish_run(const Options& o, const Problem& P, gbp_ctx* ctx, const RankCtx& rk, const char* tool, RunReport& rep, long iters) {
+  if (rk.region) {      // the communicator's record as the run leaves it: its "metric" member says which path the loop's bursts took
+    std::vector<char> desc(16384);
+    if (gbp_comm_describe(ctx, desc.data(), desc.size()) == GBP_OK) phases().comm_info = desc.data();
+  }
   gbp_timing_out tm{};
   gbp_timing(ctx, &tm, 0);
   const int gs = gbp_graph_state(ctx);

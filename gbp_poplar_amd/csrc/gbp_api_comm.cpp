@@ -59,24 +59,33 @@ int zero_exchange(gbp_ctx* c) {
 
 // the iteration's column: the exchange and the camera combine on the ctx's stream; x1 (profiling): recorded behind the all-gather.
 // roll = 1: the end of an iteration; 0: the same launches as a recomputation of what the ctx holds (the measured transport's rounds)
-static int combine_cameras_in_iteration(gbp_ctx* c, hipEvent_t x1, int roll) {
+// ev: the iteration carries the metric — the combine is the iteration's LAST belief launch: it leaves the cameras' metric records and
+// advances the burst's counter (gbp_kernels.h: BeliefArgs.ev_split).  Never with roll = 0, never on the sliced transport with world > 1.
+static void ride_args(gbp_ctx* c, BeliefArgs& b, const EvalRide* ev, bool last) {
+  if (!ev) return;
+  b.ev = *ev;
+  b.ev_split = (last ? 0 : kEvNotLast) | (c->rank == 0 ? 0 : kEvNoCamHealth);
+}
+static int combine_cameras_in_iteration(gbp_ctx* c, hipEvent_t x1, int roll, const EvalRide* ev) {
   BeliefArgs b = belief_args(c);
   b.roll = roll;
+  ride_args(c, b, ev, true);
   PeerComm* pc = peers(c->comm);
   int p = 0;
   switch (c->comm->kind()) {
     case Transport::P2p:
       if (!launch_beliefs_cam_peers) return fail(c, GBP_ERR_STATE, "no device code for the p2p combine");
       if (int rc = advance_exchange(c, pc, &p)) return rc;
-      launch_beliefs_cam_peers(b, pc->peer_table(p), c->stream);
+      launch_beliefs_cam_peers(b, pc->peer_table(p), c->stream, ev != nullptr);
       break;
     case Transport::P2pSlices:
       if (c->world == 1) {      // nothing to share: no peer kernel
         if (int rc = advance_exchange(c, pc, &p)) return rc;
         b.gathered = pc->last_own_slot();
-        launch_beliefs(b, true, false, c->stream);
+        launch_beliefs(b, true, false, c->stream, ev != nullptr);
         break;
       }
+      if (ev) return fail(c, GBP_ERR_STATE, "the sliced exchange carries no metric records");      // (metric_rides keeps such a ctx per-pass)
       // the reduce of this rank's slice of the cameras (sums in rank order out of every peer's partials, the camera chain, once per
       // camera), then the gather of the other slices' finished records — every rank ends with the tables the full combine leaves
       if (!launch_beliefs_cam_slice || !launch_gather_slices) return fail(c, GBP_ERR_STATE, "no device code for the sliced exchange");
@@ -94,7 +103,7 @@ static int combine_cameras_in_iteration(gbp_ctx* c, hipEvent_t x1, int roll) {
       if (int rc = exchange_now(c)) return rc;
       if (x1) HIPCHK(c, hipEventRecord(x1, c->stream));
       b.gathered = static_cast<const float*>(c->recv_dev);
-      launch_beliefs(b, true, false, c->stream);
+      launch_beliefs(b, true, false, c->stream, ev != nullptr);
       break;
   }
   HIPCHK(c, hipGetLastError());
@@ -128,7 +137,8 @@ int refresh_cameras(gbp_ctx* c, BeliefArgs& b, bool do_lmk) {
 // The two-stream schedule (RCCL): the communication stream (highest priority) takes the whole camera side of the exchange — local
 // partial sums, then the all-gather — right after the sweep; the landmark half of the belief update, which needs nothing from other
 // ranks, runs beside it on the main stream.  x0 / x1 (profiling): a bracket around the camera side on its stream.
-static int enqueue_cameras_two_streams(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1, int roll = 1) {
+// ev: the landmark half leaves its metric means and health counts, the combine behind the join is the iteration's last belief launch.
+static int enqueue_cameras_two_streams(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1, int roll = 1, const EvalRide* ev = nullptr) {
   HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
   HIPCHK(c, hipStreamWaitEvent(c->comm_stream, c->ev_fork, 0));
   if (x0) HIPCHK(c, hipEventRecord(x0, c->comm_stream));
@@ -138,10 +148,12 @@ static int enqueue_cameras_two_streams(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1,
   HIPCHK(c, hipEventRecord(c->ev_join, c->comm_stream));
   BeliefArgs b = belief_args(c);
   b.roll = roll;
-  launch_beliefs(b, false, true, c->stream);
+  ride_args(c, b, ev, false);
+  launch_beliefs(b, false, true, c->stream, ev != nullptr);
   HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
   b.gathered = static_cast<const float*>(c->recv_dev);
-  launch_beliefs(b, true, false, c->stream);
+  ride_args(c, b, ev, true);
+  launch_beliefs(b, true, false, c->stream, ev != nullptr);
   HIPCHK(c, hipGetLastError());
   return GBP_OK;
 }
@@ -149,36 +161,50 @@ static int enqueue_cameras_two_streams(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1,
 // ONE stream: the local camera partial sums ride in the launch of the landmark half (camera blocks write send_dev and leave,
 // landmark blocks do the rank-local belief update), so an iteration is sweep -> beliefs -> exchange -> combine: three kernels and
 // one collective.  Still no host wait with a stream-ordered transport.
-static int enqueue_cameras_one_stream(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1, int roll = 1) {
+// ev: the partial_only launch carries the landmarks' share of the metric (its camera blocks none), the combine the cameras'.
+static int enqueue_cameras_one_stream(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1, int roll = 1, const EvalRide* ev = nullptr) {
   BeliefArgs b = belief_args(c);
   b.cam_local = static_cast<float*>(c->send_dev);
   b.partial_only = 1;
   b.roll = roll;
-  launch_beliefs(b, true, true, c->stream);
+  ride_args(c, b, ev, false);
+  launch_beliefs(b, true, true, c->stream, ev != nullptr);
   if (x0) HIPCHK(c, hipEventRecord(x0, c->stream));
-  return combine_cameras_in_iteration(c, x1, roll);
+  return combine_cameras_in_iteration(c, x1, roll, ev);
 }
 
 // One iteration of a sharded ctx: sweep, then the camera side of the exchange and the belief update in one of the two schedules.
 // With a stream-ordered transport (RCCL) nothing here blocks the host, so the sequence can be captured into a hipGraph.
-static int enqueue_sharded_iteration(gbp_ctx* c, const SweepArgs& a) {
+// ev: the iteration carries the metric (a.ev set by the caller: eval_each_ride) — the sweep collects the metric of the iteration before
+// it, the belief launches leave this one's metric records.  Such iterations are launched directly, never from sharded_graph.
+static int enqueue_sharded_iteration(gbp_ctx* c, const SweepArgs& a, bool ev = false) {
   if (c->profile_stages) {
     if (c->pending_sweep_ev.size() >= 256) drain_sweep_events(c);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (int rc = event_pair(c, &e0, &e1)) return rc;
     c->pending_sweep_ev.emplace_back(e0, e1);
     HIPCHK(c, hipEventRecord(e0, c->stream));
-    launch_sweep(a, c->n_tiles, c->hoist, c->stream);
+    launch_sweep(a, c->n_tiles, c->hoist, c->stream, ev);
     HIPCHK(c, hipEventRecord(e1, c->stream));
   } else {
-    launch_sweep(a, c->n_tiles, c->hoist, c->stream);
+    launch_sweep(a, c->n_tiles, c->hoist, c->stream, ev);
   }
   hipEvent_t x0 = nullptr, x1 = nullptr;     // profiling: how long the camera side of the exchange takes on its stream
   if (c->profile_stages && c->comm->stream_ordered()) {
     if (int rc = event_pair(c, &x0, &x1)) return rc;
     c->pending_exch_ev.emplace_back(x0, x1);
   }
-  return c->comm->stream_ordered() && !c->comm_single_stream ? enqueue_cameras_two_streams(c, x0, x1) : enqueue_cameras_one_stream(c, x0, x1);
+  const EvalRide* r = ev ? &a.ev : nullptr;
+  return c->comm->stream_ordered() && !c->comm_single_stream ? enqueue_cameras_two_streams(c, x0, x1, 1, r) : enqueue_cameras_one_stream(c, x0, x1, 1, r);
+}
+
+// n sharded iterations that carry the metric, inside a piece of eval_each_ride (which owns the ring, the counter and the timing bracket)
+int iterate_sharded_ev(gbp_ctx* c, const SweepArgs& a, int n) {
+  for (int k = 0; k < n; ++k) {
+    if (int rc = enqueue_sharded_iteration(c, a, true)) return rc;
+    c->comm_warm++;
+  }
+  return GBP_OK;
 }
 
 int iterate_sharded(gbp_ctx* c, int n) {
@@ -261,6 +287,7 @@ static int comm_attach(gbp_ctx* c, gbp::Comm* comm) {
     c->recv_dev = c->xrecv.p;
     c->send_dev = static_cast<float*>(c->xrecv.p) + (size_t)c->rank * c->C * kCamRec;
   }
+  c->metric_last = 0; c->metric_riding = c->metric_per_pass = 0; c->metric_reason = "";
   if (int rc = ensure_comm_stream(c)) return rc;
   if (!c->ev_fork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
   if (!c->ev_join) HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
@@ -527,7 +554,13 @@ GBP_EXPORT(gbp_comm_describe, c, (gbp_ctx* c, char* buf, size_t cap), (c, buf, c
                 c->rank, c->world, dev, bus, c->comm ? c->comm->name() : "none", lib.c_str(), c->comm ? c->comm->library_version() : 0,
                 (c->comm && !c->comm_single_stream) ? "true" : "false", c->comm_selected_by);
   // transport 5: what gbp_comm_init timed, one entry per candidate (an empty list with one rank: nothing to measure)
-  const std::string text = std::string(head) + (c->comm_measured.empty() ? "" : ", \"measured\": " + c->comm_measured) + "}";
+  // how the loops with the metric (gbp_ba_loop, gbp_iterate_eval_each) have run on this ctx since gbp_comm_init: the path of the last burst
+  char metric[512];
+  const bool rides = c->metric_last == 1;
+  std::snprintf(metric, sizeof(metric), ", \"metric\": {\"path\": \"%s\", \"passes_riding\": %llu, \"passes_per_pass\": %llu, \"reason\": \"%s\"}",
+                c->metric_last == 0 ? "none" : rides ? "riding" : "per-pass", (unsigned long long)c->metric_riding,
+                (unsigned long long)c->metric_per_pass, rides ? "" : c->metric_reason);
+  const std::string text = std::string(head) + (c->comm_measured.empty() ? "" : ", \"measured\": " + c->comm_measured) + metric + "}";
   std::snprintf(buf, cap, "%s", text.c_str());
   if (text.size() + 1 > cap) return fail(c, GBP_ERR_INVALID, "gbp_comm_describe: the text needs " + std::to_string(text.size() + 1) + " bytes");
   return GBP_OK;

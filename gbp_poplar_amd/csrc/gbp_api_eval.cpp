@@ -241,7 +241,8 @@ static int iterate_eval(gbp_ctx* c, int n) {
 }
 
 // gbp_iterate_eval_each on a graph that does not run in k_persist: the metric of iteration k rides in the sweep of iteration
-// k + 1 (k_sweep<EV>, k_beliefs<EV>: EvalRide in gbp_kernels.h), the iterations replay from a hipGraph like gbp_iterate's, the
+// k + 1 (k_sweep<EV>, k_beliefs<EV>: EvalRide in gbp_kernels.h), the iterations replay from a hipGraph like gbp_iterate's (a ctx with a
+// communicator: the sharded iteration with its belief update of two launches, launched directly — gbp_api_comm.cpp), the
 // host is not involved until the burst has ended: per piece of at most ev_depth iterations (the ring of per-tile records) one
 // k_eval_ride for the piece's last iteration and one k_eval_fold, which reduces every slot to one 56-byte result in host-mapped
 // memory.  Bit-identical to gbp_iterate(1) + gbp_eval per iteration (same operations, same order of the sums).
@@ -279,7 +280,7 @@ static int eval_each_ride(gbp_ctx* c, int n, gbp_eval_out* out, bool dev = false
   for (int done = 0; done < n;) {         // pieces of at most ev_depth iterations, queued behind each other: no host wait in between
     const int m = std::min(n - done, (int)c->ev_depth);
     HIPCHK(c, hipMemsetAsync(c->ev_ctl.p, 0, 64, c->stream));      // iteration counter and health words of this piece
-    if (int rc = iterate_plain(c, a, m, true)) return rc;
+    if (int rc = c->comm ? iterate_sharded_ev(c, a, m) : iterate_plain(c, a, m, true)) return rc;      // (a sharded ctx: launched directly, both schedules)
     if (!launch_eval_ride_fst) return fail(c, GBP_ERR_STATE, "gbp_iterate_eval_each: no device code");
     launch_eval_ride_fst(a.ev, P<uint32_t>(c->row_cam), P<uint32_t>(c->lmk_idx), P<int>(c->fst_packed), P<float4>(c->fac), P<float>(c->dK), c->stream);
     launch_eval_fold(a.ev, (uint32_t)m, results + done, c->stream);
@@ -334,7 +335,7 @@ static int series_burst_dev(gbp_ctx* c, int m, unsigned i, unsigned steps2, gbp_
   return sp.commit((uint64_t)m);
 }
 
-// per_factor_mu = 1, per-stage timing, a ctx with a communicator: the loop the riding path replaces, with device records — per pass
+// per_factor_mu = 1, per-stage timing, a ctx with a communicator whose metric does not ride: the loop the riding path replaces, with device records — per pass
 // gbp_iterate(1), k_means + k_eval into the device scratch, its fold (stream order keeps the scratch until its fold has read it)
 static int eval_each_plain_dev(gbp_ctx* c, int m, gbp_eval_out* out) {
   if (int rc = eval_scratch(c)) return rc;
@@ -350,7 +351,8 @@ static int eval_each_plain_dev(gbp_ctx* c, int m, gbp_eval_out* out) {
 // GBP_PROG, the metric.  On a graph that runs in the persistent kernel the passes are launches of at most kSeriesMax (persist_burst):
 // k_persist_flow applies WeakenPriorVertex itself in front of its later passes, only a weakening in front of a launch's first pass is
 // a launch of its own.  Everywhere else — and after a recovered time-out — each run of passes up to the next weakening carries the
-// metric in its sweeps (eval_each_ride), or is the loop it replaces, two metrics in flight.
+// metric in its sweeps (eval_each_ride; a ctx with a communicator: where metric_rides says so, gbp_transport.hpp), or is the loop it
+// replaces, two metrics in flight.
 // dev: out[] is memory of the ctx's GPU and nothing here blocks — launches of the persistent kernel queue behind the unvalidated ones
 // as gbp_iterate's do (persist_ready), the other paths wait for those first (settle) as every other kind of device work does.
 static int iterate_passes_eval(gbp_ctx* c, int n, unsigned i0, unsigned steps2, gbp_eval_out* out, bool dev = false) {
@@ -372,7 +374,13 @@ static int iterate_passes_eval(gbp_ctx* c, int n, unsigned i0, unsigned steps2, 
     if (dev)
       if (int rc = settle(c)) return rc;
     const int m = weakening_free_run(n - done, i, steps2);
-    if (!c->comm && c->world == 1 && c->hoist && !c->profile_stages && !stream_is_capturing(c)) {
+    bool ride = !c->comm && c->world == 1 && c->hoist && !c->profile_stages && !stream_is_capturing(c);
+    if (c->comm) {      // a ctx with a communicator: the decision and its record (gbp_comm_describe: "metric")
+      ride = metric_rides(c->comm->kind(), c->world, c->hoist, c->profile_stages, stream_is_capturing(c), &c->metric_reason);
+      c->metric_last = ride ? 1 : 2;
+      (ride ? c->metric_riding : c->metric_per_pass) += (uint64_t)m;
+    }
+    if (ride) {
       if (int rc = eval_each_ride(c, m, out + done, dev)) return rc;
     } else if (dev) {
       if (int rc = eval_each_plain_dev(c, m, out + done)) return rc;

@@ -92,6 +92,10 @@ struct gbp_ctx {
   bool comm_single_stream = false;     // all-gather on the main stream, no second queue (default for world <= 2)
   const char* comm_selected_by = "caller";   // gbp_comm_describe: who chose the transport — "caller", "rule" (transport 0) or "measurement" (5)
   std::string comm_measured;           // transport 5: the JSON list of what gbp_comm_init timed, one entry per candidate ("" for the others)
+  // gbp_comm_describe's "metric" member: passes with the metric since gbp_comm_init, by path (gbp_transport.hpp: metric_rides)
+  int metric_last = 0;                 // 0 none yet, 1 the last burst rode in the sharded iteration, 2 it ran the per-pass loop
+  uint64_t metric_riding = 0, metric_per_pass = 0;
+  const char* metric_reason = "";      // why the last per-pass burst did not ride (static text)
   hipStream_t own_stream = nullptr, stream = nullptr;
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
@@ -330,6 +334,7 @@ int struct_kind(gbp_ctx* c, const char* fn, const void* const* members, const ch
 // ---- gbp_api_comm.cpp -------------------------------------------------------------------------------------------------------
 int exchange_now(gbp_ctx* c, hipStream_t s = nullptr);      // plain all-gather of the camera partials on the ctx's stream (or on s)
 int iterate_sharded(gbp_ctx* c, int n);
+int iterate_sharded_ev(gbp_ctx* c, const SweepArgs& a, int n);   // n iterations with the metric riding (a.ev set), launched directly
 int zero_exchange(gbp_ctx* c);                              // gbp_upload: the gathered partials (of both parities) cleared on the ctx's stream
 int refresh_cameras(gbp_ctx* c, BeliefArgs& b, bool do_lmk);   // the launches of refresh_beliefs_from_partials, by transport
 

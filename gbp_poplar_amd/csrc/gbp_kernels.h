@@ -132,6 +132,12 @@ constexpr uint32_t kPolCmsgLoadCached = 1u;   // camera-message tiles LOADED wit
 constexpr uint32_t kPolLmsgLoadNt = 2u;       // landmark-message tiles loaded with the non-temporal hint (default: default policy — k_beliefs gathers them next)
 constexpr uint32_t kPolLmsgStoreNt = 4u;      // ... and stored with it
 
+// BeliefArgs.ev_split: a belief update made of two launches round an exchange (the sharded iteration, gbp_api_comm.cpp).  The burst's
+// iteration counter advances ONCE per iteration, in the last belief launch — the camera combine; every launch before it carries kEvNotLast.
+// Camera blocks of a partial_only launch leave no metric record and touch no health word (they hold partial sums, not beliefs); its
+// landmark blocks leave their metric means and health counts as k_beliefs_ev does.  kEvNoCamHealth: the camera beliefs are replicated over
+// the ranks and rank 0 alone counts their health (k_means: count_cams) — every rank still writes the metric records, which its sweep reads.
+constexpr int kEvNotLast = 1, kEvNoCamHealth = 2;
 struct BeliefArgs {
   // camera part
   const float* rowp; const uint32_t* cam_row_ptr; const float* cam_prior;
@@ -139,6 +145,7 @@ struct BeliefArgs {
   float* cam_local;          // [C][44] local row sums (kept for prior-only refreshes / the exchange buffer)
   const float* gathered;     // != nullptr: belief = prior + sum_r gathered[r] ([world][C][44]) instead of the row sums
   int world;
+  int ev_split;              // k_beliefs<EV> only, kEv* bits; 0 = the belief update is this ONE launch (the slot the struct's alignment left free)
   float* camb; float4* cam_mu; float4* cam_lin; uint32_t n_cams;
   // landmark part
   const float4* lmk_prior; const float4* lmsg; const uint32_t* lmk_ptr; const uint32_t* lmk_fpos;
@@ -303,7 +310,7 @@ void launch_linearise(const SweepArgs& a, uint32_t n_tiles, hipStream_t s);
 // the camera messages as the reference stores them, out[p] = 28 floats (eta 6, Lambda lower triangle 21, 0) of device position p (test hooks;
 // weak, as the launchers below: the CPU sanitizer build of the host code has no device code behind it, the caller checks for a null launcher)
 [[gnu::weak]] void launch_cmsg_expand(const SweepArgs& a, uint32_t n_tiles, float* out, hipStream_t s);
-void launch_beliefs(BeliefArgs b, bool do_cam, bool do_lmk, hipStream_t s, bool ev = false);
+void launch_beliefs(BeliefArgs b, bool do_cam, bool do_lmk, hipStream_t s, bool ev = false);      // ev: k_beliefs_ev, or k_beliefs_cam_ev for a launch without landmark blocks
 // The direct peer-memory transport (gbp_comm.cpp: p2p).  peers: device table of `world` pointers, peers[r] = slot r of one parity in
 // rank r's exchange buffer (an IPC mapping for r != self).  Both kernels begin with a system-scope acquire.
 //   launch_beliefs_cam_peers  the camera combine of launch_beliefs(b, true, false) with partial r read from peers[r] in place of
@@ -311,7 +318,7 @@ void launch_beliefs(BeliefArgs b, bool do_cam, bool do_lmk, hipStream_t s, bool 
 //   launch_gather_peers       dst[r][0..n4) = peers[r][0..n4) (float4) for every r != self: an all-gather into this rank's buffer
 // Declared weak: the CPU sanitizer build of the host code links stand-ins of the launchers it may reach, and a p2p communicator needs a
 // device; the callers check for a null launcher.
-[[gnu::weak]] void launch_beliefs_cam_peers(BeliefArgs b, const float* const* peers, hipStream_t s);
+[[gnu::weak]] void launch_beliefs_cam_peers(BeliefArgs b, const float* const* peers, hipStream_t s, bool ev = false);      // ev: k_beliefs_cam_peers_ev
 [[gnu::weak]] void launch_gather_peers(const float* const* peers, float* dst, uint32_t n4, int world, int self, hipStream_t s);
 // The sliced peer-memory transport (gbp_comm.cpp: p2p-slices), the two kernels of its iteration (weak for the same reason):
 //   launch_beliefs_cam_slice  launch_beliefs_cam_peers over the cameras [sl.lo, sl.hi) only, every finished camera also written as a

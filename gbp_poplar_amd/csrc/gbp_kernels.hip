@@ -1036,7 +1036,9 @@ template <bool EV, bool CAM_ONLY = false, bool PEERS = false, bool SLICE = false
 GBP_DEV void beliefs_body(const BeliefArgs& b, const float* const* __restrict__ peers = nullptr, const CamSlice sl = CamSlice{}) {
   __shared__ float sh[4][48];
   __shared__ float lrec[EV ? 64 : 1][13];      // EV: the beliefs of the workgroup's 64 landmarks (eta 3, Lambda 9; 13: bank spread)
-  if (EV && blockIdx.x == 0 && threadIdx.x == 0) *b.ev.counter = *b.ev.counter + 1u;     // one more iteration of the burst done (read by the NEXT sweep)
+  // one more iteration of the burst done (read by the NEXT sweep) — counted by the LAST belief launch of the iteration: where the update is
+  // two launches round an exchange (a sharded ctx), the first carries kEvNotLast and the camera combine behind the exchange counts
+  if (EV && !(b.ev_split & kEvNotLast) && blockIdx.x == 0 && threadIdx.x == 0) *b.ev.counter = *b.ev.counter + 1u;
   // Which blocks are the cameras'?  The FIRST cam_blocks of the grid where a camera block ends in the serial chain of its means (long
   // latency: started first, hidden under the landmark blocks) — the LAST ones where it only adds up rows (partial_only, before the
   // exchange of a sharded iteration): short work that fills the slots the landmark blocks free as they drain, instead of holding the
@@ -1134,7 +1136,7 @@ GBP_DEV void beliefs_body(const BeliefArgs& b, const float* const* __restrict__ 
       sh[w][j] = bel;
       if (j == 0 && wf >= 1u && wf <= 5u) b.cam_wflag[c] = wf - 1u;
     }
-    if (b.partial_only) return;
+    if (b.partial_only) return;      // (EV too: a partial sum is no belief — no camera metric record, no health word; the combine leaves them)
     __syncthreads();
     // The 6x6 mean of a camera is one serial instruction stream on ONE lane.  The four cameras of the workgroup share a
     // single stream (lanes 0..3 of wave 0) instead of issuing it from four wavefronts: with thousands of cameras the
@@ -1179,6 +1181,7 @@ GBP_DEV void beliefs_body(const BeliefArgs& b, const float* const* __restrict__ 
       // pinned at 7 (the tableau spills: 20.1 us against 18.3), the tableau in LDS (21.4 - 25.1 us: the camera chain then sets the
       // kernel's length) — profiles/r05_default_loop.md.
       const uint32_t cj = cam0 + cblk * 4 + j;
+      const bool count_cams = !(b.ev_split & kEvNoCamHealth);      // cameras are replicated over the ranks: rank 0 counts them (as k_means: count_cams)
       if (cj < cam1) {
         if (w == 1) {
           float xm[6], R[9];
@@ -1186,13 +1189,13 @@ GBP_DEV void beliefs_body(const BeliefArgs& b, const float* const* __restrict__ 
           bool finite = true;
           GBP_UNROLL
           for (int i = 0; i < 6; ++i) finite &= (xm[i] - xm[i] == 0.f);
-          if (!finite) atomicAdd(&b.ev.health[0], 1ull);
+          if (!finite && count_cams) atomicAdd(&b.ev.health[0], 1ull);
           eval_cam_rot(xm, R);
           float4* rec = b.ev.cam_rec + (size_t)cj * 3;
           rec[0] = make_float4(R[0], R[1], R[2], xm[0]);
           rec[1] = make_float4(R[3], R[4], R[5], xm[1]);
           rec[2] = make_float4(R[6], R[7], R[8], xm[2]);
-        } else if (!ldl_pivots_positive<6>(sh[j] + 8, 6)) {
+        } else if (count_cams && !ldl_pivots_positive<6>(sh[j] + 8, 6)) {
           atomicAdd(&b.ev.health[1], 1ull);
         }
       }
@@ -1338,6 +1341,10 @@ GBP_DEV void beliefs_body(const BeliefArgs& b, const float* const* __restrict__ 
 __global__ __launch_bounds__(256) void k_beliefs(const BeliefArgs b) { beliefs_body<false>(b); }      // (held at 8 waves per SIMD: S1 +0.1 %, config-5 shape +0.2 %: noise — profiles/HISTORY.md)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_beliefs_cam(const BeliefArgs b) { beliefs_body<false, true>(b); }
 __global__ __launch_bounds__(256) void k_beliefs_ev(const BeliefArgs b) { beliefs_body<true>(b); }
+// The camera combine of a sharded iteration that carries the metric (behind the exchange; BeliefArgs.ev_split): each camera's metric record
+// from the finished belief.  Not pinned at 8 waves per SIMD like k_beliefs_cam: the fp64 tableau of the metric's solve would spill there
+// (see the EV block of beliefs_body), so the compiler chooses — resources in profiles/sharded_metric.md.
+__global__ __launch_bounds__(256) void k_beliefs_cam_ev(const BeliefArgs b) { beliefs_body<true, true>(b); }
 // The direct peer-memory exchange.  The peers' partials were written by kernels of OTHER processes, whose completion the
 // host has observed before the region barrier that let this launch be enqueued; the system-scope acquire in front of the first peer
 // access drops whatever stale copy of those lines this agent's caches still hold (the read of two exchanges ago, same parity).
@@ -1346,6 +1353,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                                                                                                      const float* const* __restrict__ peers) {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
   beliefs_body<false, true, true>(b, peers);
+}
+__global__ __launch_bounds__(256) void k_beliefs_cam_peers_ev(const BeliefArgs b, const float* const* __restrict__ peers) {
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+  beliefs_body<true, true, true>(b, peers);
 }
 // dst[r] = peers[r] for every rank r != self, 16 bytes per lane (a camera record is 11 float4); grid.y = rank
 __global__ __launch_bounds__(256) void k_gather_peers(const float* const* __restrict__ peers, float* __restrict__ dst, uint32_t n4,
@@ -2641,16 +2652,18 @@ void launch_beliefs(BeliefArgs b, bool do_cam, bool do_lmk, hipStream_t s, bool 
   const uint32_t lmk_blocks = do_lmk ? blocks_for((uint64_t)b.n_lmks * 4) : 0;
   b.lmk_blocks = lmk_blocks;
   if (b.cam_blocks + lmk_blocks == 0) return;
-  if (ev) hipLaunchKernelGGL(k_beliefs_ev, dim3(b.cam_blocks + lmk_blocks), dim3(256), 0, s, b);
+  if (ev && lmk_blocks == 0) hipLaunchKernelGGL(k_beliefs_cam_ev, dim3(b.cam_blocks), dim3(256), 0, s, b);
+  else if (ev) hipLaunchKernelGGL(k_beliefs_ev, dim3(b.cam_blocks + lmk_blocks), dim3(256), 0, s, b);
   else if (lmk_blocks == 0) hipLaunchKernelGGL(k_beliefs_cam, dim3(b.cam_blocks), dim3(256), 0, s, b);
   else hipLaunchKernelGGL(k_beliefs, dim3(b.cam_blocks + lmk_blocks), dim3(256), 0, s, b);
 }
-void launch_beliefs_cam_peers(BeliefArgs b, const float* const* peers, hipStream_t s) {
+void launch_beliefs_cam_peers(BeliefArgs b, const float* const* peers, hipStream_t s, bool ev) {
   b.cam_blocks = (b.n_cams + 3) / 4;
   b.lmk_blocks = 0;
   b.gathered = nullptr;
   if (b.cam_blocks == 0) return;
-  hipLaunchKernelGGL(k_beliefs_cam_peers, dim3(b.cam_blocks), dim3(256), 0, s, b, peers);
+  if (ev) hipLaunchKernelGGL(k_beliefs_cam_peers_ev, dim3(b.cam_blocks), dim3(256), 0, s, b, peers);
+  else hipLaunchKernelGGL(k_beliefs_cam_peers, dim3(b.cam_blocks), dim3(256), 0, s, b, peers);
 }
 void launch_gather_peers(const float* const* peers, float* dst, uint32_t n4, int world, int self, hipStream_t s) {
   if (n4 == 0 || world < 2) return;

@@ -1,7 +1,8 @@
 // gbp_transport.hpp — the transports of the sharded exchange by name, and how the measured transport chooses between them.  The values
 // are those of the public gbp_comm_init(ctx, region, transport) argument (include/gbp_mi355x_multi.h).  No HIP in here: the CLIs, plain
-// C++ on top of the C-ABI, include it next to the library (gbp_comm.hpp), and the two pure functions at the end — who may run
-// (eligible_candidates), who won (choose_transport) — are tested as a stand-alone host program (tests/sanitize/transport_choice_main.cpp).
+// C++ on top of the C-ABI, include it next to the library (gbp_comm.hpp), and the pure functions at the end — who may run
+// (eligible_candidates), who won (choose_transport), whether the metric rides in the sharded iteration (metric_rides) — are tested as
+// stand-alone host programs (tests/sanitize/transport_choice_main.cpp, metric_gather_main.cpp).
 #pragma once
 
 #include <cstdint>
@@ -90,6 +91,24 @@ inline Candidates eligible_candidates(const RankFacts* f, int world, int single_
   add(Transport::P2pSlices, false, no_peer);
   cl.baseline = !shared && cl.c[rccl_rule].eligible ? rccl_rule : host;
   return cl;
+}
+
+// Does the metric of a loop with the metric after every pass (gbp_ba_loop, gbp_iterate_eval_each) ride in the iterations of a ctx WITH a
+// communicator — the metric of iteration k collected by the sweep of iteration k + 1, nothing of a burst waiting for the metric — or does
+// the ctx run the per-pass loop (gbp_iterate(1), k_means, k_eval, a fold and a host wait per pass)?  It rides when the means are hoisted,
+// per-stage profiling is off, the caller is not capturing the ctx's stream, and the transport's camera combine can leave the cameras'
+// metric records: every one but the sliced peer-memory transport with more than one rank, whose gathered cameras arrive as finished
+// records without them.  *why (may be NULL) = "" when it rides, the reason (static text) when it does not.
+inline bool metric_rides(Transport kind, int world, bool hoist, bool profile_stages, bool capturing, const char** why) {
+  const char* r = "";
+  if (!hoist) r = "per_factor_mu = 1: the belief update computes no hoisted means for the metric to ride with";
+  else if (profile_stages) r = "per-stage profiling brackets every launch of a pass";
+  else if (capturing) r = "the caller is capturing the ctx's stream";
+  else if (kind == Transport::P2pSlices && world > 1) r = "transport p2p-slices with more than one rank: the gathered camera records carry no metric records";
+  else if (kind != Transport::Rccl && kind != Transport::HostStaged && kind != Transport::P2p && kind != Transport::P2pSlices)
+    r = "the ctx has no communicator of a known transport";
+  if (why) *why = r;
+  return r[0] == 0;
 }
 
 struct Choice {

@@ -41,6 +41,7 @@ static int run(const cli::Options& o, cli::Problem& P, cli::RankCtx& rk) {
   cli::MetricPipe pipe;
   pipe.ctx = ctx;
   pipe.on = !rk.region && !o.verbose;
+  const bool bursts = !o.verbose && o.eval_every == 1;      // multi-rank runs too: the records summed over the ranks (see ba_main.cpp)
   cli::RunReport rep;
   const auto write_iter = [](unsigned total, unsigned since, const gbp_eval_out& e) {
     std::cout << "Iters " << total;
@@ -67,7 +68,7 @@ static int run(const cli::Options& o, cli::Problem& P, cli::RankCtx& rk) {
         std::cout << "\n Adding " << n_new << " new landmarks";
         std::cout << "\n**********************************************************\n\n";
       };
-      if (pipe.on && o.eval_every == 1) lines.post(banner);     // through the writer: in order behind the lines of the burst before it
+      if (bursts) lines.post(banner);     // through the writer: in order behind the lines of the burst before it
       else banner();
       CLI_CHECK(ctx, gbp_read_priors(ctx, &po));
       CLI_CHECK(ctx, gbp_read(ctx, &rb.out));
@@ -80,14 +81,15 @@ static int run(const cli::Options& o, cli::Problem& P, cli::RankCtx& rk) {
       up.active_flag = P.active.data(); up.cam_weaken_flag = P.cwf.data(); up.lmk_weaken_flag = P.lwf.data();
       CLI_CHECK(ctx, gbp_new_keyframe(ctx, &up));
     }
-    if (pipe.on && o.eval_every == 1 && cli::whole_steps(o.steps)) {
+    if (bursts && cli::whole_steps(o.steps)) {
       // the loop's body up to the next keyframe as gbp_ba_loop (see ba_main.cpp): prior weakening, iteration, metric — one call
-      const unsigned cap = gbp_graph_state(ctx) == 2 ? 512u : 128u;
+      const unsigned cap = !rk.region && gbp_graph_state(ctx) == 2 ? 512u : (unsigned)gbp::kMetricBurstMax;
       unsigned nb = 1;
       while (nb < cap && i + nb < niters && (i + nb + 1) % (unsigned)o.iters_between_kfs != 0) ++nb;
       if (cap == 512u && i + nb == niters && nb > 96u) nb -= 64u;
       series.resize(nb);
       CLI_CHECK(ctx, gbp_ba_loop(ctx, (int)nb, iter, (unsigned)o.steps, series.data()));
+      CLI_CHECK(ctx, cli::sum_burst_over_ranks(ctx, rk, series.data(), (int)nb));
       rep.last = series.back(); rep.have_metric = true;
       lines.post([total0 = (unsigned)o.iters_between_kfs * data_counter + iter, since0 = iter, steps2 = 2u * (unsigned)o.steps, batch = series, &write_iter] {
         for (size_t k = 0; k < batch.size(); ++k) {
@@ -120,14 +122,14 @@ static int run(const cli::Options& o, cli::Problem& P, cli::RankCtx& rk) {
       continue;
     }
     if (((iter + 1) % 2 == 0) && (iter < o.steps * 2)) {
-      if (pipe.on && o.eval_every == 1) lines.post([] { std::cout << "Weakening priors \n"; });
+      if (bursts) lines.post([] { std::cout << "Weakening priors \n"; });
       else { lines.drain(); pipe.line("Weakening priors \n"); }
       CLI_CHECK(ctx, gbp_weaken_priors(ctx));
     }
-    if (pipe.on && o.eval_every == 1) {
+    if (bursts) {
       // the reference's default, the metric after EVERY iteration: everything up to the next keyframe / prior weakening in
       // one call (gbp_ba_loop, see ba_main.cpp)
-      const unsigned cap = gbp_graph_state(ctx) == 2 ? 512u : 128u;      // (see ba_main.cpp)
+      const unsigned cap = !rk.region && gbp_graph_state(ctx) == 2 ? 512u : (unsigned)gbp::kMetricBurstMax;      // (see ba_main.cpp)
       unsigned nb = 1;
       while (nb < cap && i + nb < niters && (i + nb + 1) % (unsigned)o.iters_between_kfs != 0 &&
              !(((iter + nb + 1) % 2 == 0) && (iter + nb < o.steps * 2)))
@@ -135,6 +137,7 @@ static int run(const cli::Options& o, cli::Problem& P, cli::RankCtx& rk) {
       if (cap == 512u && i + nb == niters && nb > 96u) nb -= 64u;      // the run ends with a burst of 64 (its lines are the ones no launch overlaps)
       series.resize(nb);
       CLI_CHECK(ctx, gbp_ba_loop(ctx, (int)nb, iter, 0u, series.data()));      // steps = 0: the weakenings are this loop's own calls
+      CLI_CHECK(ctx, cli::sum_burst_over_ranks(ctx, rk, series.data(), (int)nb));
       rep.last = series.back(); rep.have_metric = true;
       lines.post([total0 = (unsigned)o.iters_between_kfs * data_counter + iter, since0 = iter, batch = series, &write_iter] {
         for (size_t k = 0; k < batch.size(); ++k) write_iter(total0 + (unsigned)k, since0 + (unsigned)k, batch[k]);

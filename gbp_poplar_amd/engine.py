@@ -297,7 +297,9 @@ class GbpEngine:
 
     def comm_describe(self):
         """dict: rank, world, device, pci_bus_id, transport, library (resolved path of librccl), library_version, two_streams,
-        selected_by ("caller", "rule", "measurement") and, after comm_init(..., 5), measured: one dict per candidate"""
+        selected_by ("caller", "rule", "measurement"), after comm_init(..., 5) measured: one dict per candidate, and metric: how the
+        loops with the metric (ba_loop, iterate_eval_each) have run on this ctx — path ("riding" in the sharded iterations, "per-pass",
+        "none"), passes_riding, passes_per_pass, reason (why the last burst did not ride)"""
         import json
         buf = C.create_string_buffer(16384)
         self._chk(self.lib.gbp_comm_describe(self.h, buf, 16384), "gbp_comm_describe")

@@ -100,6 +100,18 @@ GBP_API int gbp_comm_barrier(gbp_ctx* ctx);
  * switches between the one-stream and the two-stream form of the sharded iteration (identical results) so that a launcher can
  * MEASURE both and keep the faster one instead of trusting the ">= 4 ranks" rule (ba.cpp:617-649 has no such choice to make:
  * Poplar compiles the exchange into the program). */
+/* The loops with the metric on a ctx with a communicator.  gbp_ba_loop and gbp_iterate_eval_each (host `out`; a device `out` stays
+ * refused on a landmark-sharded ctx) return the LOCAL shard's sums, one record per pass, bit-identical to gbp_iterate(1) + gbp_eval per
+ * pass; a launcher adds the ranks' records in rank order, every field as a double (gbp_eval_global's arithmetic — the CLIs do it through a
+ * shared area, csrc/gbp_metric_gather.hpp).  Where the means are hoisted (per_factor_mu = 0), per-stage profiling is off, the caller is
+ * not capturing the ctx's stream and the transport is rccl, host-staged, p2p, or p2p-slices with ONE rank, the metric RIDES in the sharded
+ * iterations: the metric of iteration k is collected by the sweep of iteration k + 1, the belief launches on either side of the exchange
+ * leave its records, and nothing of a burst waits for the metric (a transport that is not stream-ordered still synchronises inside each
+ * exchange).  Everywhere else — p2p-slices with more than one rank: its gathered cameras carry no metric records — the call runs the
+ * per-pass loop.  gbp_comm_describe reports it in one more member,
+ *   "metric": {"path": "riding" | "per-pass" | "none", "passes_riding": n, "passes_per_pass": m, "reason": "..."}
+ * path = that of the last burst ("none": no such loop has run), the counts run since gbp_comm_init, reason = why the last burst did not
+ * ride ("" when it did).  Every other member keeps its name and value. */
 GBP_API int gbp_comm_describe(gbp_ctx* ctx, char* json_buf, size_t cap);
 GBP_API int gbp_comm_set_schedule(gbp_ctx* ctx, int two_streams);
 GBP_API int gbp_comm_probe(gbp_ctx* ctx, int reps, double* avg_us);
