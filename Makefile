@@ -11,7 +11,8 @@ LIB     := $(PKG)/libgbp_mi355x.so
 HIPFLAGS := -O3 -std=c++17 -fPIC -ffp-contract=off -fvisibility=hidden -Wall -Wno-unused-function
 OBJDIR  := $(PKG)/_obj/make
 # device code: host + gfx950 pass; the C-ABI (gbp_api_*.cpp, see gbp_ctx.hpp), the device order, the transports, the host helpers: plain C++
-HOST_SRCS := gbp_api_ctx.cpp gbp_api_launch.cpp gbp_api_persist.cpp gbp_api_eval.cpp gbp_api_comm.cpp gbp_api_debug.cpp gbp_layout.cpp gbp_comm.cpp gbp_host.cpp
+# (the rule of gbp_poplar_amd/build.py: every csrc/*.cpp that is not the main of a CLI)
+HOST_SRCS := $(filter-out %_main.cpp,$(notdir $(wildcard $(CSRC)/*.cpp)))
 OBJS    := $(OBJDIR)/gbp_kernels.o $(HOST_SRCS:%.cpp=$(OBJDIR)/%.o)
 HDRS    := $(wildcard $(CSRC)/*.h $(CSRC)/*.hpp $(CSRC)/hooks/* $(CSRC)/experiments/* include/*.h)
 
@@ -28,7 +29,7 @@ $(OBJDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
 $(LIB): $(OBJS)
 	$(HIPCC) -shared -o $@ --offload-arch=$(ARCH) $(OBJS) -ldl -pthread -Wl,--version-script=$(CSRC)/gbp_exports.map
 
-$(PKG)/bin/%: $(CSRC)/%_main.cpp $(CSRC)/cli_common.hpp $(CSRC)/gbp_transport.hpp include/gbp_mi355x.h include/gbp_mi355x_multi.h include/gbp_mi355x_compat.h $(LIB)
+$(PKG)/bin/%: $(CSRC)/%_main.cpp $(CSRC)/cli_common.hpp $(CSRC)/gbp_transport.hpp $(CSRC)/gbp_metric_gather.hpp include/gbp_mi355x.h include/gbp_mi355x_multi.h include/gbp_mi355x_compat.h $(LIB)
 	@mkdir -p $(PKG)/bin
 	$(CXX) -o $@ -O2 -std=c++17 -ffp-contract=off -pthread $< -L$(PKG) -lgbp_mi355x '-Wl,-rpath,$$ORIGIN/..'
 

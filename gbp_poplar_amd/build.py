@@ -31,9 +31,9 @@ ARCH = "gfx950"
 # -fvisibility=hidden: the library exports the gbp_* functions of include/*.h (GBP_API) and nothing else
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 DEVICE_SRCS = ["gbp_kernels.hip"]                        # HIP: host + gfx950 device pass
-# the C-ABI (gbp_ctx.hpp names what each holds), the device order, the exchange transports, the host helpers: plain C++
-HOST_SRCS = ["gbp_api_ctx.cpp", "gbp_api_launch.cpp", "gbp_api_persist.cpp", "gbp_api_eval.cpp", "gbp_api_comm.cpp", "gbp_api_debug.cpp",
-             "gbp_api_devio.cpp", "gbp_layout.cpp", "gbp_comm.cpp", "gbp_host.cpp"]
+# the C-ABI (gbp_ctx.hpp names what each holds), the device order, the exchange transports, the host helpers: plain C++.
+# The rule (the Makefile states the same one): every csrc/*.cpp that is not the main of a CLI
+HOST_SRCS = sorted(f for f in os.listdir(CSRC) if f.endswith(".cpp") and not f.endswith("_main.cpp"))
 LIB_SRCS = DEVICE_SRCS + HOST_SRCS
 CLI_SRCS = {"ba": "ba_main.cpp", "slam": "slam_main.cpp", "bal_convert": "bal_convert_main.cpp"}
 
@@ -88,7 +88,7 @@ def _build_lib(target, variant, defines, force, verbose):
         if force or _stale(obj, hdr + [os.path.join(CSRC, s)]):
             todo.append((s, obj))
     if todo:
-        workers = max(1, min(len(todo), (os.cpu_count() or 2)))
+        workers = min(len(todo), 16, os.cpu_count() or 1)
         with concurrent.futures.ThreadPoolExecutor(workers) as ex:
             for f in [ex.submit(_compile, s, o, defines, verbose) for s, o in todo]:
                 f.result()

@@ -55,7 +55,7 @@ int zero_exchange(gbp_ctx* c) {
 // | p2p-slices, world = 1      | advance, then launch_beliefs(b, true, false) with gathered = own slot of that parity              | launch_beliefs(b, true, do_lmk) with gathered = own slot of the last parity        |
 // | no communicator, world > 1 | not this path (caller's exchange)                                                                 | gathered = recv_dev; error "exchange buffers not set" without one                  |
 // | no communicator, world = 1 | not this path                                                                                     | gathered = local, b.world = 1                                                      |
-// Return codes by cause: GBP_ERR_HIP (a launch, a synchronisation), GBP_ERR_COMM (the exchange), GBP_ERR_STATE (no device code).
+// Return codes by cause: GBP_ERR_HIP (a launch, a synchronisation), GBP_ERR_COMM (the exchange).
 
 // the iteration's column: the exchange and the camera combine on the ctx's stream; x1 (profiling): recorded behind the all-gather.
 // roll = 1: the end of an iteration; 0: the same launches as a recomputation of what the ctx holds (the measured transport's rounds)
@@ -74,7 +74,6 @@ static int combine_cameras_in_iteration(gbp_ctx* c, hipEvent_t x1, int roll, con
   int p = 0;
   switch (c->comm->kind()) {
     case Transport::P2p:
-      if (!launch_beliefs_cam_peers) return fail(c, GBP_ERR_STATE, "no device code for the p2p combine");
       if (int rc = advance_exchange(c, pc, &p)) return rc;
       launch_beliefs_cam_peers(b, pc->peer_table(p), c->stream, ev != nullptr);
       break;
@@ -88,7 +87,6 @@ static int combine_cameras_in_iteration(gbp_ctx* c, hipEvent_t x1, int roll, con
       if (ev) return fail(c, GBP_ERR_STATE, "the sliced exchange carries no metric records");      // (metric_rides keeps such a ctx per-pass)
       // the reduce of this rank's slice of the cameras (sums in rank order out of every peer's partials, the camera chain, once per
       // camera), then the gather of the other slices' finished records — every rank ends with the tables the full combine leaves
-      if (!launch_beliefs_cam_slice || !launch_gather_slices) return fail(c, GBP_ERR_STATE, "no device code for the sliced exchange");
       if (int rc = advance_exchange(c, pc, &p)) return rc;
       CamSlice sl;
       slice_bounds(c->C, c->world, c->rank, &sl.lo, &sl.hi);
@@ -116,7 +114,6 @@ int refresh_cameras(gbp_ctx* c, BeliefArgs& b, bool do_lmk) {
   const Transport kind = c->comm ? c->comm->kind() : Transport::Auto;      // (Auto: no communicator)
   if (kind == Transport::P2p || (kind == Transport::P2pSlices && c->world > 1)) {
     // the last exchange's partials are read where they lie; the landmark half, which needs nothing from other ranks, in a launch of its own
-    if (!launch_beliefs_cam_peers) return fail(c, GBP_ERR_STATE, "no device code for the p2p combine");
     launch_beliefs_cam_peers(b, pc->last_table(), c->stream);
     if (do_lmk) launch_beliefs(b, false, true, c->stream);
   } else {

@@ -185,7 +185,6 @@ int struct_kind(gbp_ctx* c, const char* fn, const void* const* members, const ch
   if (k0 != kPtrDevice) return GBP_OK;
   if (c->L_loc != c->L || c->world != 1)
     return fail(c, GBP_ERR_INVALID, std::string(fn) + ": " + names[first] + " is device memory: device pointers are not supported on a landmark-sharded ctx");
-  if (!devio_upload) return fail(c, GBP_ERR_INVALID, std::string(fn) + ": " + names[first] + " is device memory: built without device I/O");
   *device = true;
   return GBP_OK;
 }
@@ -566,11 +565,7 @@ GBP_EXPORT(gbp_upload, c, (gbp_ctx* c, const gbp_state_in* in), (c, in)) {
       if (e2 != hipSuccess) { (void)hipFree(tmp.p); HIPCHK(c, e2); }
       st_dev = static_cast<const float4*>(tmp.p); var_dev = reinterpret_cast<const float*>(static_cast<char*>(tmp.p) + Ep * 16);
     }
-    if (!launch_upload_scatter_fst) {
-      if (tmp.p) (void)hipFree(tmp.p);
-      return fail(c, GBP_ERR_STATE, "gbp_upload: no device code");
-    }
-    launch_upload_scatter_fst(P<float4>(c->lmsg), factor_state(c), P<float4>(c->fac), st_dev, var_dev, (uint32_t)Ep, c->stream);
+    launch_upload_scatter(P<float4>(c->lmsg), factor_state(c), P<float4>(c->fac), st_dev, var_dev, (uint32_t)Ep, c->stream);
     const hipError_t le = hipGetLastError();
     if (tmp.p) { (void)hipStreamSynchronize(c->stream); (void)hipFree(tmp.p); }
     HIPCHK(c, le);
@@ -700,7 +695,7 @@ GBP_EXPORT(gbp_new_keyframe, c, (gbp_ctx* c, const gbp_kf_update* u), (c, u)) {
     if (dev) return devio_new_keyframe(c, u);
   }
   if (int rc = gbp_sync(c)) return rc;
-  if (c->active_host_stale && u->active_flag && devio_refresh_active_shadow)      // device-pointer calls came before: the shadow of the flags is on the device
+  if (c->active_host_stale && u->active_flag)      // device-pointer calls came before: the shadow of the flags is on the device
     if (int rc = devio_refresh_active_shadow(c)) return rc;
   if (u->damping_count || u->active_flag) {
     // edit the per-factor scalars in place on the device: 8 bytes per factor go over PCIe, not the 64-byte records
@@ -728,8 +723,7 @@ GBP_EXPORT(gbp_new_keyframe, c, (gbp_ctx* c, const gbp_kf_update* u), (c, u)) {
     if (int rc = up.put(c->st_b.p, cnt.data(), (size_t)c->Ep * 4)) return rc;
     if (int rc = up.put(c->st_a.p, ctl.data(), (size_t)c->Ep * 4)) return rc;
     if (int rc = up.end()) return rc;
-    if (!launch_fst_set) return fail(c, GBP_ERR_STATE, "gbp_new_keyframe: no device code");
-    launch_fst_set(P<int>(c->fst_packed), P<int>(c->st_b), P<uint32_t>(c->st_a), c->Ep, c->stream);
+    launch_state_set(P<int>(c->fst_packed), P<int>(c->st_b), P<uint32_t>(c->st_a), c->Ep, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (u->active_flag)

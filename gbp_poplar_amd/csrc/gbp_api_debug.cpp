@@ -44,7 +44,6 @@ GBP_EXPORT(gbp_debug_get, c, (gbp_ctx* c, int what, float* a, float* b), (c, wha
   } else if (what == 1) {
     // the CMSG records keep eta and the 3x3 inverse the message's Lambda derives from (gbp_kernels.h): expanded on the device, by the
     // code the sweeps expand them with, into 28 floats per position (eta 6, lower triangle 21, 0)
-    if (!launch_cmsg_expand) return fail(c, GBP_ERR_STATE, "gbp_debug_get: no device code for the camera messages");
     std::vector<float> f((size_t)c->Ep * 28);
     float* tmp = nullptr;
     HIPCHK(c, hipMalloc(&tmp, f.size() * 4));

@@ -42,8 +42,7 @@ int eval_enqueue(gbp_ctx* c, int area, DeviceEval* dev_slots) {
   unsigned long long* h_next = P<unsigned long long>(c->health) + 2 * (area ^ 1);
   launch_means(P<float4>(c->camb), P<float4>(c->lmkb), P<float>(c->cam_mu), P<float>(c->lmk_mu), c->C, c->L_loc,
                h_cur, h_next, /*count_cams=*/c->rank == 0, c->stream);
-  if (!launch_eval_fst) return fail(c, GBP_ERR_STATE, "gbp_eval: no device code");
-  launch_eval_fst(P<uint32_t>(c->row_cam), P<uint32_t>(c->lmk_idx), P<int>(c->fst_packed), P<float4>(c->fac), P<float>(c->cam_mu), P<float>(c->lmk_mu),
+  launch_eval(P<uint32_t>(c->row_cam), P<uint32_t>(c->lmk_idx), P<int>(c->fst_packed), P<float4>(c->fac), P<float>(c->cam_mu), P<float>(c->lmk_mu),
               P<float>(c->dK), c->prm.num_undamped_iters, slots + 1, h_cur, reinterpret_cast<unsigned long long*>(slots), c->n_tiles, c->stream);
   HIPCHK(c, hipGetLastError());
   if (dev_slots) return GBP_OK;
@@ -61,7 +60,6 @@ static int out_kind(gbp_ctx* c, const char* fn, const void* out, bool* device) {
   if (int rc = struct_kind(c, fn, members, names, 1, device)) return rc;
   if (!*device) return GBP_OK;
   *device = false;
-  if (!launch_eval_fold_part) return fail(c, GBP_ERR_INVALID, std::string(fn) + ": out is device memory: built without the device metric");
   if (reinterpret_cast<uintptr_t>(out) % 8 != 0)
     return fail(c, GBP_ERR_INVALID, std::string(fn) + ": out is device memory that is not 8-byte aligned (a record holds doubles and 64-bit counters)");
   if (stream_is_capturing(c))
@@ -281,8 +279,7 @@ static int eval_each_ride(gbp_ctx* c, int n, gbp_eval_out* out, bool dev = false
     const int m = std::min(n - done, (int)c->ev_depth);
     HIPCHK(c, hipMemsetAsync(c->ev_ctl.p, 0, 64, c->stream));      // iteration counter and health words of this piece
     if (int rc = c->comm ? iterate_sharded_ev(c, a, m) : iterate_plain(c, a, m, true)) return rc;      // (a sharded ctx: launched directly, both schedules)
-    if (!launch_eval_ride_fst) return fail(c, GBP_ERR_STATE, "gbp_iterate_eval_each: no device code");
-    launch_eval_ride_fst(a.ev, P<uint32_t>(c->row_cam), P<uint32_t>(c->lmk_idx), P<int>(c->fst_packed), P<float4>(c->fac), P<float>(c->dK), c->stream);
+    launch_eval_ride(a.ev, P<uint32_t>(c->row_cam), P<uint32_t>(c->lmk_idx), P<int>(c->fst_packed), P<float4>(c->fac), P<float>(c->dK), c->stream);
     launch_eval_fold(a.ev, (uint32_t)m, results + done, c->stream);
     HIPCHK(c, hipGetLastError());
     done += m;

@@ -319,7 +319,6 @@ class P2pComm : public PeerComm {
       err = "all_gather: the p2p transport exchanges through its own buffer (send / recv of the current parity)";
       return -1;
     }
-    if (!launch_gather_peers) { err = "all_gather: no device code"; return -1; }
     int p = 0;
     if (advance(s, &p, err) != 0) return -1;
     launch_gather_peers(peer_table(p), recv, (uint32_t)(n / 4), world, rank, s);

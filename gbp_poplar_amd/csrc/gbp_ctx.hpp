@@ -323,13 +323,12 @@ inline PtrKind ptr_kind(const gbp_ctx* c, const void* p) {
 // One struct of a call: every non-NULL member must be of the kind of the first.  *device = the struct holds device pointers.
 // GBP_ERR_INVALID (text names the member): a mix, another GPU's memory, managed memory, a landmark-sharded ctx.
 int struct_kind(gbp_ctx* c, const char* fn, const void* const* members, const char* const* names, int n, bool* device);
-// The device-pointer forms of the four programs.  Weak: the CPU sanitizer build of the host code is linked without gbp_api_devio.cpp
-// and the kernels; the callers (gbp_api_ctx.cpp) check for a null function.
-[[gnu::weak]] int devio_upload(gbp_ctx* c, const gbp_state_in* in);
-[[gnu::weak]] int devio_read(gbp_ctx* c, gbp_state_out* out);
-[[gnu::weak]] int devio_read_priors(gbp_ctx* c, gbp_priors_out* out);
-[[gnu::weak]] int devio_new_keyframe(gbp_ctx* c, const gbp_kf_update* upd);
-[[gnu::weak]] int devio_refresh_active_shadow(gbp_ctx* c);   // c->active_host from the device (after a device-pointer call changed the flags)
+// The device-pointer forms of the four programs (gbp_api_devio.cpp).
+int devio_upload(gbp_ctx* c, const gbp_state_in* in);
+int devio_read(gbp_ctx* c, gbp_state_out* out);
+int devio_read_priors(gbp_ctx* c, gbp_priors_out* out);
+int devio_new_keyframe(gbp_ctx* c, const gbp_kf_update* upd);
+int devio_refresh_active_shadow(gbp_ctx* c);   // c->active_host from the device (after a device-pointer call changed the flags)
 
 // ---- gbp_api_comm.cpp -------------------------------------------------------------------------------------------------------
 int exchange_now(gbp_ctx* c, hipStream_t s = nullptr);      // plain all-gather of the camera partials on the ctx's stream (or on s)

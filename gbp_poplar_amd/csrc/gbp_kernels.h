@@ -305,39 +305,36 @@ struct DeviceEval {  // per-block partials, summed on the host in block order
   unsigned long long n_active, n_relin, n_robust, pad;
 };
 
+// ---- the launchers ------------------------------------------------------------------------------
+// Every function declared from here on (and persist_grid above) is defined exactly once per link: by gbp_kernels.hip, or — the CPU
+// sanitizer build of the host code — by tests/sanitize/kernel_stubs.cpp, which fails to link when one is missing or declared otherwise.
 void launch_sweep(const SweepArgs& a, uint32_t n_tiles, bool hoist, hipStream_t s, bool ev = false);
 void launch_linearise(const SweepArgs& a, uint32_t n_tiles, hipStream_t s);
-// the camera messages as the reference stores them, out[p] = 28 floats (eta 6, Lambda lower triangle 21, 0) of device position p (test hooks;
-// weak, as the launchers below: the CPU sanitizer build of the host code has no device code behind it, the caller checks for a null launcher)
-[[gnu::weak]] void launch_cmsg_expand(const SweepArgs& a, uint32_t n_tiles, float* out, hipStream_t s);
+// the camera messages as the reference stores them, out[p] = 28 floats (eta 6, Lambda lower triangle 21, 0) of device position p (test hooks)
+void launch_cmsg_expand(const SweepArgs& a, uint32_t n_tiles, float* out, hipStream_t s);
 void launch_beliefs(BeliefArgs b, bool do_cam, bool do_lmk, hipStream_t s, bool ev = false);      // ev: k_beliefs_ev, or k_beliefs_cam_ev for a launch without landmark blocks
 // The direct peer-memory transport (gbp_comm.cpp: p2p).  peers: device table of `world` pointers, peers[r] = slot r of one parity in
 // rank r's exchange buffer (an IPC mapping for r != self).  Both kernels begin with a system-scope acquire.
 //   launch_beliefs_cam_peers  the camera combine of launch_beliefs(b, true, false) with partial r read from peers[r] in place of
 //                             b.gathered[r] (b.gathered unused): the same additions in the same order
 //   launch_gather_peers       dst[r][0..n4) = peers[r][0..n4) (float4) for every r != self: an all-gather into this rank's buffer
-// Declared weak: the CPU sanitizer build of the host code links stand-ins of the launchers it may reach, and a p2p communicator needs a
-// device; the callers check for a null launcher.
-[[gnu::weak]] void launch_beliefs_cam_peers(BeliefArgs b, const float* const* peers, hipStream_t s, bool ev = false);      // ev: k_beliefs_cam_peers_ev
-[[gnu::weak]] void launch_gather_peers(const float* const* peers, float* dst, uint32_t n4, int world, int self, hipStream_t s);
-// The sliced peer-memory transport (gbp_comm.cpp: p2p-slices), the two kernels of its iteration (weak for the same reason):
+void launch_beliefs_cam_peers(BeliefArgs b, const float* const* peers, hipStream_t s, bool ev = false);      // ev: k_beliefs_cam_peers_ev
+void launch_gather_peers(const float* const* peers, float* dst, uint32_t n4, int world, int self, hipStream_t s);
+// The sliced peer-memory transport (gbp_comm.cpp: p2p-slices), the two kernels of its iteration:
 //   launch_beliefs_cam_slice  launch_beliefs_cam_peers over the cameras [sl.lo, sl.hi) only, every finished camera also written as a
 //                             result record into sl.res (nothing is launched for an empty slice)
 //   launch_gather_slices      the records of every slice but `self`'s out of results[s] (device table of `world` pointers: the result
 //                             buffer of rank s, one parity) into b.camb / b.cam_mu / b.cam_lin (b.n_cams, b.world, b.hoist, b.roll)
-[[gnu::weak]] void launch_beliefs_cam_slice(BeliefArgs b, const float* const* peers, const CamSlice& sl, hipStream_t s);
-[[gnu::weak]] void launch_gather_slices(const float4* const* results, const BeliefArgs& b, int self, hipStream_t s);
+void launch_beliefs_cam_slice(BeliefArgs b, const float* const* peers, const CamSlice& sl, hipStream_t s);
+void launch_gather_slices(const float4* const* results, const BeliefArgs& b, int self, hipStream_t s);
 // per-tile records of ring slots [0, n_slots) -> out[slot]: one gbp_eval_out-shaped result per slot (may be mapped host memory)
 void launch_eval_fold(const EvalRide& ev, uint32_t n_slots, void* out, hipStream_t s);
 // sum_eval (gbp_api_eval.cpp) on the device, for gbp_eval_out records that live on the GPU: metric r of n_records = the DeviceEval records
 // parts + r * stride ([0] = health words, then nb <= 1 024 block sums — or, per_wave, one record per tile wave of n_tiles <= 4 096) -> out[r].
-// Weak: the CPU sanitizer build of the host code links stand-ins of the launchers it may reach; the callers check for a null launcher.
-[[gnu::weak]] void launch_eval_fold_part(const DeviceEval* parts, uint32_t stride, uint32_t nb, uint32_t n_tiles, bool per_wave, uint32_t n_records,
-                                         void* out, hipStream_t s);
+void launch_eval_fold_part(const DeviceEval* parts, uint32_t stride, uint32_t nb, uint32_t n_tiles, bool per_wave, uint32_t n_records,
+                           void* out, hipStream_t s);
 // the riding metric of the CURRENT beliefs (a piece's last iteration: no sweep follows) into ring slot counter - 1
-// (weak, with the other launchers that read or write the state planes below: the CPU sanitizer build of the host code links stand-ins of the
-// launchers of the 64-byte record, tests/sanitize/kernel_stubs.cpp; the callers check for a null launcher)
-[[gnu::weak]] void launch_eval_ride_fst(const EvalRide& ev, const uint32_t* row_cam, const uint32_t* lmk_idx, const int* fst_packed, const float4* fac, const float* K9_dev, hipStream_t s);
+void launch_eval_ride(const EvalRide& ev, const uint32_t* row_cam, const uint32_t* lmk_idx, const int* fst_packed, const float4* fac, const float* K9_dev, hipStream_t s);
 int persist_max_resident_blocks();                                            // how many of them this GPU keeps resident at once
 // cooperative != 0: hipLaunchCooperativeKernel — the runtime refuses a grid that cannot be co-resident on the device and the
 // driver never runs two cooperative grids (of any process) side by side; 0: plain launch (the creation-time probe vouches for
@@ -347,12 +344,12 @@ void launch_copy_segments(const CopySegs& t, const unsigned* guard /* abort word
 // runs the placement + barriers of k_persist for this graph once (blocking); false = the workgroups are not co-resident here
 bool persist_probe(uint32_t n_tiles, uint32_t n_cams, uint32_t n_lmks, unsigned* sync, unsigned* status_dev, volatile unsigned* status_host,
                    bool cooperative, hipStream_t s);
-[[gnu::weak]] void launch_fst_set(int* fst_packed, const int* new_count, const uint32_t* ctl, uint32_t n, hipStream_t s);
+void launch_state_set(int* fst_packed, const int* new_count, const uint32_t* ctl, uint32_t n, hipStream_t s);
 // WRITE_PROG's per-factor streams (ba.cpp:868-886) from their compact host form — st[p] = {damping, count << 3 | flags, z0, z1}, var[p], both possibly
 // host-mapped — into the arrays of the device order: the zero message of position p, its three state planes and the measurement
 // slots of its FAC tile (the rest of FAC is zeroed by the caller)
 struct FactorState { int* packed; float* damp; float* var; };      // FST_PACKED, FST_DAMP, FST_VAR
-[[gnu::weak]] void launch_upload_scatter_fst(float4* lmsg, const FactorState& fs, float4* fac, const float4* st, const float* var, uint32_t n, hipStream_t s);
+void launch_upload_scatter(float4* lmsg, const FactorState& fs, float4* fac, const float4* st, const float* var, uint32_t n, hipStream_t s);
 // ---- device-resident caller arrays (gbp_api_devio.cpp; the kernels: "device-resident caller arrays" in gbp_kernels.hip) ----
 // gbp_upload from device pointers: the caller's file-order arrays (NULL = zeros, as in gbp_state_in) -> the records k_upload_scatter writes
 struct UploadDev {
@@ -380,7 +377,7 @@ void launch_means(const float4* camb, const float4* lmkb, float* cam_mu, float* 
                   uint32_t n_lmks, unsigned long long* health2 /* [0] non-finite means, [1] non-PD beliefs: zero on entry */,
                   unsigned long long* health2_next /* zeroed by this launch for the next evaluation */,
                   bool count_cams, hipStream_t s);
-[[gnu::weak]] void launch_eval_fst(const uint32_t* row_cam, const uint32_t* lmk_idx, const int* fst_packed, const float4* fac, const float* cam_mu,
+void launch_eval(const uint32_t* row_cam, const uint32_t* lmk_idx, const int* fst_packed, const float4* fac, const float* cam_mu,
                  const float* lmk_mu, const float* K9_dev, int num_undamped_iters, DeviceEval* partials /* may be mapped host memory */,
                  unsigned long long* health2, unsigned long long* health2_out, uint32_t n_tiles, hipStream_t s);
 uint32_t eval_blocks(uint32_t n_tiles);

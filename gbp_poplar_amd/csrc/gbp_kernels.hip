@@ -2682,7 +2682,7 @@ void launch_gather_slices(const float4* const* results, const BeliefArgs& b, int
   hipLaunchKernelGGL(k_gather_slices, dim3((widest * kCamRes4 + 255) / 256, (uint32_t)b.world), dim3(256), 0, s, results,
                      reinterpret_cast<float4*>(b.camb), b.cam_mu, b.cam_lin, b.n_cams, b.world, self, b.hoist, b.roll);
 }
-void launch_eval_ride_fst(const EvalRide& ev, const uint32_t* row_cam, const uint32_t* lmk_idx, const int* fst_packed, const float4* fac, const float* K9_dev, hipStream_t s) {
+void launch_eval_ride(const EvalRide& ev, const uint32_t* row_cam, const uint32_t* lmk_idx, const int* fst_packed, const float4* fac, const float* K9_dev, hipStream_t s) {
   hipLaunchKernelGGL(k_eval_ride, dim3(ev.n_tiles / 4), dim3(256), 0, s, ev, row_cam, lmk_idx, fst_packed, fac, K9_dev);
 }
 void launch_eval_fold(const EvalRide& ev, uint32_t n_slots, void* out, hipStream_t s) {
@@ -2810,10 +2810,10 @@ hipError_t launch_persist(PersistArgs A, bool cooperative, hipStream_t s) {
   (void)hipLaunchKernel(f, dim3(grid), dim3(256), args, 0, s);
   return hipGetLastError();
 }
-void launch_upload_scatter_fst(float4* lmsg, const FactorState& fs, float4* fac, const float4* st, const float* var, uint32_t n, hipStream_t s) {
+void launch_upload_scatter(float4* lmsg, const FactorState& fs, float4* fac, const float4* st, const float* var, uint32_t n, hipStream_t s) {
   if (n) hipLaunchKernelGGL(k_upload_scatter, dim3(blocks_for(n)), dim3(256), 0, s, lmsg, fs, fac, st, var, n);
 }
-void launch_fst_set(int* fst_packed, const int* new_count, const uint32_t* ctl, uint32_t n, hipStream_t s) {
+void launch_state_set(int* fst_packed, const int* new_count, const uint32_t* ctl, uint32_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_state_set, dim3(blocks_for(n)), dim3(256), 0, s, fst_packed, new_count, ctl, n);
 }
 void launch_upload_dev(const UploadDev& a, hipStream_t s) {
@@ -2838,7 +2838,7 @@ void launch_means(const float4* camb, const float4* lmkb, float* cam_mu, float* 
   hipLaunchKernelGGL(k_means, dim3(blocks_for((uint64_t)n_cams + n_lmks)), dim3(256), 0, s, (const float*)camb,
                      (const float*)lmkb, cam_mu, lmk_mu, n_cams, n_lmks, health2, health2_next, count_cams ? 1 : 0);
 }
-void launch_eval_fst(const uint32_t* row_cam, const uint32_t* lmk_idx, const int* fst_packed, const float4* fac, const float* cam_mu,
+void launch_eval(const uint32_t* row_cam, const uint32_t* lmk_idx, const int* fst_packed, const float4* fac, const float* cam_mu,
                  const float* lmk_mu, const float* K9_dev, int num_undamped_iters, DeviceEval* partials,
                  unsigned long long* health2, unsigned long long* health2_out, uint32_t n_tiles, hipStream_t s) {
   hipLaunchKernelGGL(k_eval, dim3(eval_blocks(n_tiles)), dim3(256), 0, s, row_cam, lmk_idx, fst_packed, fac, cam_mu, lmk_mu, K9_dev,

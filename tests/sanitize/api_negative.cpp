@@ -70,8 +70,8 @@ static int null_ctx_calls() {
 }
 
 static int create_without_a_device() {
-  // a valid 2 x 3 problem: the device order is built and validated on the host, then gbp_create finds no GPU (this harness runs on
-  // the CPU box; on a GPU box the call succeeds and the ctx is destroyed again)
+  // a valid 2 x 3 problem: the device order is built and validated on the host, then gbp_create finds no GPU (the test hides them from
+  // this process; a ctx on a device would run into the aborting launchers of kernel_stubs.cpp)
   const uint32_t cam[6] = {0, 0, 0, 1, 1, 1}, lmk[6] = {0, 1, 2, 0, 1, 2};
   gbp_problem pr{};
   pr.n_cams = 2; pr.n_lmks = 3; pr.n_edges = 6; pr.cam_id = cam; pr.lmk_id = lmk;
@@ -88,14 +88,12 @@ static int create_without_a_device() {
   REQUIRE(gbp_create(&bad, nullptr, nullptr, &c) == GBP_ERR_INVALID && std::strlen(gbp_last_error(nullptr)) > 0);
   gbp_shard sh{2, 2, 0, 3};                                 // rank >= world
   REQUIRE(gbp_create(&pr, nullptr, &sh, &c) == GBP_ERR_INVALID);
-  const int rc = gbp_create(&pr, nullptr, nullptr, &c);
-  if (gbp_device_count() == 0) {
-    REQUIRE(rc == GBP_ERR_NO_DEVICE && c == nullptr && std::strstr(gbp_last_error(nullptr), "no HIP device") != nullptr);
-    REQUIRE(gbp_set_device(0) == GBP_ERR_NO_DEVICE);
-  } else {
-    REQUIRE(rc == GBP_OK && c != nullptr);
-    gbp_destroy(c);
+  if (gbp_device_count() != 0) {
+    std::printf("api_negative: %d HIP device(s) visible: gbp_create without a device skipped\n", gbp_device_count());
+    return 0;
   }
+  REQUIRE(gbp_create(&pr, nullptr, nullptr, &c) == GBP_ERR_NO_DEVICE && c == nullptr && std::strstr(gbp_last_error(nullptr), "no HIP device") != nullptr);
+  REQUIRE(gbp_set_device(0) == GBP_ERR_NO_DEVICE);
   return 0;
 }
 
