@@ -1,6 +1,6 @@
 """One rank of the sharded-metric comparisons in tests/test_gpu_sharded_metric.py, run as a fresh process:
 
-    python -m tests.metric_worker REGION RANK WORLD TRANSPORT OUT_DIR SCENARIO MODE
+    python -m tests.metric_worker REGION RANK WORLD OUT_DIR TRANSPORT SCENARIO MODE
 
 REGION is a file (in /dev/shm) that the test created and initialised with gbp_comm_region_init for WORLD ranks and the scenario's camera
 count ("-": the scenario makes its own 1-rank regions).  MODE is `ride` — the loops with the metric as the library runs them
@@ -19,7 +19,6 @@ touch (gbp_weaken_priors, gbp_iterate(1), gbp_eval, gbp_eval_global per pass).  
 Every metric record is written as the hex of its 56 bytes; the whole gbp_read state as OUT_DIR/<array>_r<RANK>.npy (one_rank: one set per
 engine, <array>_<engine>.npy), everything else as OUT_DIR/info_r<RANK>.json."""
 import ctypes
-import json
 import mmap
 import os
 import struct
@@ -27,7 +26,8 @@ import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.rank_group import ROOT, rank_engine, write_rank
+
 FIELDS = ("sum_norm", "sum_half_sq", "n_active", "n_relin", "n_robust", "n_nonfinite", "n_nonpd")
 
 
@@ -179,34 +179,24 @@ def one_rank(out_dir):
     run("each_ride", behind(2), "ride", each=260)
     run("each_perpass", behind(2), "perpass", each=260)
     run("health_plain", plain, "perpass", st=no_information(bal, state), n=6)
-    with open(os.path.join(out_dir, "info_r0.json"), "w") as f:
-        json.dump(info, f)
+    write_rank(out_dir, 0, {}, info)
     return 0
 
 
 def main(argv):
-    region_path, rank, world, transport, out_dir, scenario, mode = argv[0], int(argv[1]), int(argv[2]), int(argv[3]), argv[4], argv[5], argv[6]
+    region_path, rank, world, out_dir, transport, scenario, mode = argv[0], int(argv[1]), int(argv[2]), argv[3], int(argv[4]), argv[5], argv[6]
     if scenario == "one_rank":
         return one_rank(out_dir)
     from gbp_poplar_amd import driver, hostlib
-    from gbp_poplar_amd.engine import GbpEngine
     bal = graph(scenario)
-    C, L = int(bal["n_cams"]), int(bal["n_lmks"])
     opts = driver.Options()
     steps = int(opts.steps)
     K, state, extra = driver.build_inputs(bal, opts, hostlib, slam=scenario == "slam")
     if scenario == "health":
         state = no_information(bal, state)
     bounds = bounds_of(bal, scenario, world)
-    eng = GbpEngine(bal["cam_id"], bal["lmk_id"], C, L, K, shard=(rank, world, int(bounds[rank]), int(bounds[rank + 1])))
-    size = int(eng.lib.gbp_comm_region_bytes(C, world))
-    fd = os.open(region_path, os.O_RDWR)
-    mm = mmap.mmap(fd, size)
-    os.close(fd)
-    buf = (ctypes.c_char * size).from_buffer(mm)
-    try:
-        eng._chk(eng.lib.gbp_comm_init(eng.h, ctypes.addressof(buf), transport), "gbp_comm_init")
-        info = {"transport": eng.comm_transport(), "bounds": [int(b) for b in bounds]}
+    with rank_engine(region_path, rank, world, transport, bal, K, bounds) as (eng, info):
+        info["bounds"] = [int(b) for b in bounds]
         if scenario == "slam":
             info["traj"] = driver.run_slam(eng if mode == "ride" else PerPass(eng), hostlib, bal, state, extra, opts, iters_between_kfs=8, max_iters=23)
         else:
@@ -219,17 +209,8 @@ def main(argv):
                 info["records"] += more
                 if more_glob is not None:
                     info["global"] += more_glob
-        info["describe"] = eng.comm_describe()
-        save_state(eng, out_dir, "r%d" % rank)
-        with open(os.path.join(out_dir, "info_r%d.json" % rank), "w") as f:
-            json.dump(info, f)
-    except BaseException:
-        eng.lib.gbp_comm_region_abort(ctypes.addressof(buf))     # wake the other ranks out of their barriers with an error
-        raise
-    finally:
-        eng.close()              # collective with a communicator: the peer transports meet the other ranks before they free their buffers
-        del buf
-        mm.close()
+        info["describe"] = eng.comm_describe()      # after the loops: its "metric" member says how they ran
+        write_rank(out_dir, rank, eng.read(), info)
     return 0
 
 

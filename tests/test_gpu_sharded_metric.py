@@ -2,21 +2,20 @@
 metric of iteration k is collected by the sweep of iteration k + 1, the belief update is two launches round the exchange, nothing of a burst
 waits for the metric.  Whatever it runs must leave, byte for byte, the records and the state of the loop it replaces — gbp_iterate(1) +
 gbp_eval per pass on the same kind of engine, calls this path does not touch — and the state of the N-shard oracle.  Every rank is a fresh
-process (tests/metric_worker.py) under a time limit; nothing is run twice."""
-import ctypes
+process (tests/metric_worker.py) started by the launcher the multi-process suites share (tests/rank_group.py), under a time limit;
+nothing is run twice."""
 import json
-import mmap
 import os
 import struct
 import subprocess
-import sys
-import time
 
 import numpy as np
 import pytest
 
 from tests.conftest import seq_path
-from tests.test_cli import BA, LINE, ROOT, SLAM
+from tests.metric_worker import graph
+from tests.rank_group import GROUPS
+from tests.test_cli import BA, LINE, SLAM
 
 STATE = ("cam_beliefs_eta", "cam_beliefs_lambda", "lmk_beliefs_eta", "lmk_beliefs_lambda", "damping", "damping_count", "robust_flag")
 HOST, P2P, SLICES = 2, 3, 4
@@ -30,67 +29,14 @@ def _built():
         build.build()
 
 
-_RUNS = {}      # (world, transport, scenario, mode) -> (per rank info, out_dir), or the exception of the one attempt
-
-
-def _run_workers(out_dir, world, transport, scenario, mode, timeout=180):
-    from gbp_poplar_amd._lib import load
-    from tests.metric_worker import graph
-    os.makedirs(out_dir)
-    region = "-"
-    if scenario != "one_rank":
-        lib = load()
-        C = int(graph(scenario)["n_cams"])
-        size = int(lib.gbp_comm_region_bytes(C, world))
-        region = "/dev/shm/gbp_test_metric_%d_%d_%d_%s" % (os.getpid(), world, transport, mode)
-        with open(region, "wb") as f:
-            f.truncate(size)
-    procs = []
-    try:
-        if region != "-":
-            fd = os.open(region, os.O_RDWR)
-            mm = mmap.mmap(fd, size)
-            os.close(fd)
-            buf = (ctypes.c_char * size).from_buffer(mm)
-            rc = lib.gbp_comm_region_init(ctypes.addressof(buf), size, C, world)
-            del buf
-            mm.close()
-            assert rc == 0
-        cmd = [sys.executable, "-m", "tests.metric_worker", region]
-        procs = [subprocess.Popen(cmd + [str(r), str(world), str(transport), out_dir, scenario, mode], cwd=ROOT, stdout=subprocess.PIPE,
-                                  stderr=subprocess.PIPE, text=True) for r in range(world)]
-        deadline = time.monotonic() + timeout
-        for r, p in enumerate(procs):
-            _, err = p.communicate(timeout=max(1.0, deadline - time.monotonic()))
-            assert p.returncode == 0, "rank %d of %d (transport %d, %s, %s): %s" % (r, world, transport, scenario, mode, err[-2000:])
-    finally:
-        for p in procs:                   # one rank failed or hung: end the others
-            if p.poll() is None:
-                p.kill()
-                p.communicate()
-        if region != "-":
-            os.unlink(region)
-    infos = []
-    for r in range(world):
-        with open(os.path.join(out_dir, "info_r%d.json" % r)) as f:
-            infos.append(json.load(f))
-    return infos, out_dir
-
-
 @pytest.fixture(scope="module")
 def ranks_of(tmp_path_factory):
-    """ranks_of(world, transport, scenario, mode): the run, made once and shared by the tests that read it"""
+    """ranks_of(world, transport, scenario, mode): the run, made once and shared by the tests that read it -> (per rank info, out_dir)"""
     def get(world, transport, scenario, mode):
-        key = (world, transport, scenario, mode)
-        if key not in _RUNS:
-            out_dir = str(tmp_path_factory.mktemp("metric") / "run")
-            try:
-                _RUNS[key] = _run_workers(out_dir, world, transport, scenario, mode)
-            except BaseException as e:
-                _RUNS[key] = e
-        if isinstance(_RUNS[key], BaseException):
-            raise _RUNS[key]
-        return _RUNS[key]
+        ranks, out_dir = GROUPS.ranks_of("tests.metric_worker", world, (transport, scenario, mode),
+                                         lambda: str(tmp_path_factory.mktemp("metric") / "run"),
+                                         lambda: None if scenario == "one_rank" else int(graph(scenario)["n_cams"]), 180)
+        return [info for _, info in ranks], out_dir
     return get
 
 

@@ -2,21 +2,19 @@
 every transport the ranks can form — host-staged, p2p, p2p-slices, RCCL in both schedules — on the camera side of the sharded iteration
 and attaches the fastest, every rank deciding from the same gathered table.  What is claimed and checked: the ranks agree, the record
 says what was measured, and whatever wins leaves the bits of the host-staged transport (2).  Which transport wins is a timing and is not
-asserted anywhere."""
-import ctypes
+asserted anywhere.  The ranks are fresh processes (tests/rank_worker.py) started by the launcher the multi-process suites share
+(tests/rank_group.py); nothing is run twice."""
 import json
 import math
-import mmap
 import os
 import shutil
 import subprocess
-import sys
-import time
 
 import numpy as np
 import pytest
 
 from tests.conftest import seq_path
+from tests.rank_group import GROUPS
 from tests.test_cli import BA, LINE, ROOT, SLAM
 
 STATE = ("cam_beliefs_eta", "cam_beliefs_lambda", "lmk_beliefs_eta", "lmk_beliefs_lambda", "damping", "damping_count", "robust_flag")
@@ -74,96 +72,13 @@ def test_choice_and_eligibility_under_asan_ubsan(tmp_path):
 
 # ---- GPU: real processes on the one GPU ------------------------------------------------------------------------------------------------
 
-_RUNS = {}          # (world, transport, scenario) -> per rank (arrays, info), or the exception of the one attempt (nothing is run twice)
-_STOP = []          # a rank failed or hung once: nothing further is started
-
-
-def _run_workers(out_dir, world, transport, scenario, timeout=150):
-    """`world` fresh processes (tests/measured_worker.py) sharing one /dev/shm region.  The first rank to fail, or the deadline, aborts
-    the region (the others leave their barriers with an error), ends the remaining ranks and bars every later run."""
-    from gbp_poplar_amd import hostlib
-    from gbp_poplar_amd._lib import load
-    assert not _STOP, "an earlier run failed: %s" % _STOP[0]
-    lib = load()
-    C = int(hostlib.bal_read(seq_path("fr2robot2"))["n_cams"])
-    size = int(lib.gbp_comm_region_bytes(C, world))
-    region = "/dev/shm/gbp_test_measured_%d_%d_%d_%s" % (os.getpid(), world, transport, scenario)
-    os.makedirs(out_dir)
-    with open(region, "wb") as f:
-        f.truncate(size)
-    fd = os.open(region, os.O_RDWR)
-    mm = mmap.mmap(fd, size)
-    os.close(fd)
-    buf = (ctypes.c_char * size).from_buffer(mm)
-    procs, failure = [], None
-    try:
-        assert lib.gbp_comm_region_init(ctypes.addressof(buf), size, C, world) == 0
-        cmd = [sys.executable, "-m", "tests.measured_worker", region]
-        for r in range(world):
-            with open(os.path.join(out_dir, "stderr_r%d.txt" % r), "w") as log:
-                procs.append(subprocess.Popen(cmd + [str(r), str(world), str(transport), out_dir, scenario], cwd=ROOT,
-                                              stdout=subprocess.DEVNULL, stderr=log))
-        deadline = time.monotonic() + timeout
-        left = set(range(world))
-        while left and failure is None:
-            for r in sorted(left):
-                rc = procs[r].poll()
-                if rc is None:
-                    continue
-                left.discard(r)
-                if rc != 0:
-                    failure = "rank %d of %d exited with %d" % (r, world, rc)
-                    break
-            if left and failure is None:
-                if time.monotonic() > deadline:
-                    failure = "ranks %s of %d still running after %d s" % (sorted(left), world, timeout)
-                else:
-                    time.sleep(0.02)      # (waiting for processes, not for a time)
-        if failure is not None:
-            lib.gbp_comm_region_abort(ctypes.addressof(buf))
-            for p in procs:
-                if p.poll() is None:
-                    try:
-                        p.wait(timeout=10)          # the abort flag lets a waiting rank leave by itself
-                    except subprocess.TimeoutExpired:
-                        p.kill()
-                        p.wait()
-            tails = []
-            for r in range(world):
-                with open(os.path.join(out_dir, "stderr_r%d.txt" % r)) as f:
-                    tails.append("rank %d: %s" % (r, f.read()[-1500:]))
-            _STOP.append("%s (transport %d, %s)" % (failure, transport, scenario))
-            raise AssertionError(_STOP[0] + "\n" + "\n".join(tails))
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-                p.wait()
-        del buf
-        mm.close()
-        os.unlink(region)
-    ranks = []
-    for r in range(world):
-        arrays = {f[:-len("_r%d.npy" % r)]: np.load(os.path.join(out_dir, f)) for f in os.listdir(out_dir) if f.endswith("_r%d.npy" % r)}
-        with open(os.path.join(out_dir, "info_r%d.json" % r)) as f:
-            ranks.append((arrays, json.load(f)))
-    return ranks
-
-
 @pytest.fixture(scope="module")
 def ranks_of(tmp_path_factory):
     """ranks_of(world, transport, scenario): the run, made once and shared by the tests that read it"""
     def get(world, transport, scenario):
-        key = (world, transport, scenario)
-        if key not in _RUNS:
-            out_dir = str(tmp_path_factory.mktemp("measured") / "run")
-            try:
-                _RUNS[key] = _run_workers(out_dir, world, transport, scenario)
-            except BaseException as e:
-                _RUNS[key] = e
-        if isinstance(_RUNS[key], BaseException):
-            raise _RUNS[key]
-        return _RUNS[key]
+        from gbp_poplar_amd import hostlib
+        return GROUPS.ranks_of("tests.rank_worker", world, (transport, scenario), lambda: str(tmp_path_factory.mktemp("measured") / "run"),
+                               lambda: int(hostlib.bal_read(seq_path("fr2robot2"))["n_cams"]), 150)[0]
     return get
 
 

@@ -2,20 +2,19 @@
 are cut into `world` slices, rank s alone sums slice s out of its peers' partial sums (HIP IPC) and runs the camera chain behind the sum,
 the other ranks gather the finished records — two host barriers per exchange.  Whatever it runs must leave the bits of the host-staged
 transport (2) on the same shards: forked ranks on one GPU are separate processes, so IPC maps one process's buffers into another's
-exactly as across peer GPUs."""
-import ctypes
+exactly as across peer GPUs.  The ranks are fresh processes (tests/rank_worker.py) started by the launcher the multi-process suites
+share (tests/rank_group.py); nothing is run twice."""
 import json
-import mmap
 import os
 import shutil
 import subprocess
-import sys
-import time
 
 import numpy as np
 import pytest
 
 from tests.conftest import seq_path
+from tests.rank_group import GROUPS
+from tests.rank_worker import graph
 from tests.test_cli import BA, LINE, ROOT, SLAM
 
 STATE = ("cam_beliefs_eta", "cam_beliefs_lambda", "lmk_beliefs_eta", "lmk_beliefs_lambda", "damping", "damping_count", "robust_flag")
@@ -71,65 +70,12 @@ def test_transport_p2p_slices_is_parsed():
 
 # ---- GPU: real processes, the whole state bit for bit --------------------------------------------------------------------------------
 
-_RUNS = {}      # (world, transport, scenario) -> per rank (arrays, info), or the exception of the one attempt (nothing is run twice)
-
-
-def _run_workers(out_dir, world, transport, scenario, timeout=240):
-    """`world` fresh processes (tests/slices_worker.py), forked before anything touches HIP, sharing one /dev/shm region"""
-    from gbp_poplar_amd._lib import load
-    from tests.slices_worker import graph
-    lib = load()
-    C = int(graph(scenario)["n_cams"])
-    size = int(lib.gbp_comm_region_bytes(C, world))
-    region = "/dev/shm/gbp_test_slices_%d_%d_%d" % (os.getpid(), world, transport)
-    os.makedirs(out_dir)
-    with open(region, "wb") as f:
-        f.truncate(size)
-    procs = []
-    try:
-        fd = os.open(region, os.O_RDWR)
-        mm = mmap.mmap(fd, size)
-        os.close(fd)
-        buf = (ctypes.c_char * size).from_buffer(mm)
-        rc = lib.gbp_comm_region_init(ctypes.addressof(buf), size, C, world)
-        del buf
-        mm.close()
-        assert rc == 0
-        cmd = [sys.executable, "-m", "tests.slices_worker", region]
-        procs = [subprocess.Popen(cmd + [str(r), str(world), str(transport), out_dir, scenario], cwd=ROOT, stdout=subprocess.PIPE,
-                                  stderr=subprocess.PIPE, text=True) for r in range(world)]
-        deadline = time.monotonic() + timeout
-        for r, p in enumerate(procs):
-            _, err = p.communicate(timeout=max(1.0, deadline - time.monotonic()))
-            assert p.returncode == 0, "rank %d of %d (transport %d, %s): %s" % (r, world, transport, scenario, err[-2000:])
-    finally:
-        for p in procs:                   # one rank failed or hung: end the others
-            if p.poll() is None:
-                p.kill()
-                p.communicate()
-        os.unlink(region)
-    ranks = []
-    for r in range(world):
-        arrays = {f[:-len("_r%d.npy" % r)]: np.load(os.path.join(out_dir, f)) for f in os.listdir(out_dir) if f.endswith("_r%d.npy" % r)}
-        with open(os.path.join(out_dir, "info_r%d.json" % r)) as f:
-            ranks.append((arrays, json.load(f)))
-    return ranks
-
-
 @pytest.fixture(scope="module")
 def ranks_of(tmp_path_factory):
     """ranks_of(world, transport, scenario): the run, made once and shared by the tests that read it"""
     def get(world, transport, scenario):
-        key = (world, transport, scenario)
-        if key not in _RUNS:
-            out_dir = str(tmp_path_factory.mktemp("slices") / "run")
-            try:
-                _RUNS[key] = _run_workers(out_dir, world, transport, scenario)
-            except BaseException as e:
-                _RUNS[key] = e
-        if isinstance(_RUNS[key], BaseException):
-            raise _RUNS[key]
-        return _RUNS[key]
+        return GROUPS.ranks_of("tests.rank_worker", world, (transport, scenario), lambda: str(tmp_path_factory.mktemp("slices") / "run"),
+                               lambda: int(graph(scenario)["n_cams"]), 240)[0]
     return get
 
 

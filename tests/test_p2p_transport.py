@@ -1,20 +1,17 @@
 """The direct peer-memory transport of the sharded camera exchange (`gbp_comm_init(ctx, region, 3)`, `--transport p2p`): every rank reads
 its peers' partial sums straight out of their device memory (HIP IPC), one host barrier per exchange.  On one GPU the forked ranks are
 separate processes, so IPC maps one process's buffer into another's exactly as across peer GPUs: every run here must compute what the
-host-staged transport computes, bit for bit."""
-import ctypes
-import json
-import mmap
+host-staged transport computes, bit for bit.  The ranks of the state comparison are fresh processes (tests/rank_worker.py) started by
+the launcher the multi-process suites share (tests/rank_group.py)."""
 import os
 import shutil
 import subprocess
-import sys
-import time
 
 import numpy as np
 import pytest
 
 from tests.conftest import seq_path
+from tests.rank_group import GROUPS
 from tests.test_cli import BA, LINE, ROOT, SLAM, run
 
 
@@ -108,46 +105,11 @@ def test_p2p_with_one_forked_rank_equals_plain_run():
 
 # ---- GPU: the whole state, bit for bit, against the host-staged transport ---------------------------------------------------------
 
-def _run_workers(out_dir, world, transport, timeout=300):
-    """`world` fresh processes (tests/p2p_worker.py) sharing one /dev/shm region; returns per rank (arrays, info)"""
+def _ranks(out_dir, world, transport):
+    """`world` fresh processes (tests/rank_worker.py, scenario `iterate`) through the shared launcher; per rank (arrays, info)"""
     from gbp_poplar_amd import hostlib
-    from gbp_poplar_amd._lib import load
-    lib = load()
-    C = int(hostlib.bal_read(seq_path("fr2robot2"))["n_cams"])
-    size = int(lib.gbp_comm_region_bytes(C, world))
-    region = "/dev/shm/gbp_test_p2p_%d_%d_%d" % (os.getpid(), world, transport)
-    os.makedirs(out_dir)
-    with open(region, "wb") as f:
-        f.truncate(size)
-    procs = []
-    try:
-        fd = os.open(region, os.O_RDWR)
-        mm = mmap.mmap(fd, size)
-        os.close(fd)
-        buf = (ctypes.c_char * size).from_buffer(mm)
-        rc = lib.gbp_comm_region_init(ctypes.addressof(buf), size, C, world)
-        del buf
-        mm.close()
-        assert rc == 0
-        cmd = [sys.executable, "-m", "tests.p2p_worker", region]
-        procs = [subprocess.Popen(cmd + [str(r), str(world), str(transport), out_dir], cwd=ROOT, stdout=subprocess.PIPE,
-                                  stderr=subprocess.PIPE, text=True) for r in range(world)]
-        deadline = time.monotonic() + timeout
-        for r, p in enumerate(procs):
-            _, err = p.communicate(timeout=max(1.0, deadline - time.monotonic()))
-            assert p.returncode == 0, "rank %d of %d (transport %d): %s" % (r, world, transport, err[-2000:])
-    finally:
-        for p in procs:                   # one rank failed or hung: end the others
-            if p.poll() is None:
-                p.kill()
-                p.communicate()
-        os.unlink(region)
-    ranks = []
-    for r in range(world):
-        arrays = {f[:-len("_r%d.npy" % r)]: np.load(os.path.join(out_dir, f)) for f in os.listdir(out_dir) if f.endswith("_r%d.npy" % r)}
-        with open(os.path.join(out_dir, "info_r%d.json" % r)) as f:
-            ranks.append((arrays, json.load(f)))
-    return ranks
+    return GROUPS.ranks_of("tests.rank_worker", world, (transport, "iterate"), lambda: out_dir,
+                           lambda: int(hostlib.bal_read(seq_path("fr2robot2"))["n_cams"]), 300)[0]
 
 
 @pytest.mark.gpu
@@ -155,8 +117,8 @@ def _run_workers(out_dir, world, transport, timeout=300):
 def test_p2p_state_bit_identical_to_host_staged(world, tmp_path):
     """LINEARISE, 30 iterations, WEAKEN_PRIORS, 5 more, gbp_eval_global, gbp_comm_probe on `world` real processes: every rank's
     beliefs, damping, damping counts and robust flags are the host-staged transport's, bit for bit, and so are the global metric sums."""
-    host = _run_workers(str(tmp_path / "host"), world, 2)
-    p2p = _run_workers(str(tmp_path / "p2p"), world, 3)
+    host = _ranks(str(tmp_path / "host"), world, 2)
+    p2p = _ranks(str(tmp_path / "p2p"), world, 3)
     names = ("cam_beliefs_eta", "cam_beliefs_lambda", "lmk_beliefs_eta", "lmk_beliefs_lambda", "damping", "damping_count", "robust_flag")
     for r, ((a_h, i_h), (a_p, i_p)) in enumerate(zip(host, p2p)):
         assert i_h["describe"]["transport"] == "host-staged" and i_p["describe"]["transport"] == "p2p"
