@@ -110,38 +110,161 @@ def belief_means(eta, lam, width):
 
 
 def rodrigues(w):
-    """rotation matrix of a rotation vector; the identity below 1e-6"""
-    w = np.asarray(w, np.float64)
-    th = np.sqrt(w @ w)
-    if th < 1e-6:
-        return np.eye(3)
-    W = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
-    return np.eye(3) + (np.sin(th) / th) * W + ((1.0 - np.cos(th)) / (th * th)) * (W @ W)
+    """Rotation matrices of rotation vectors (..., 3) -> (..., 3, 3); the identity below 1e-6.  The angle is sqrt(w . w) without a
+    conjugate, so a complex w is carried analytically (the complex step of linearise_factor)."""
+    w = np.asarray(w)
+    w = w if np.iscomplexobj(w) else w.astype(np.float64)
+    th2 = w[..., 0] * w[..., 0] + w[..., 1] * w[..., 1] + w[..., 2] * w[..., 2]
+    small = np.real(th2) < 1e-12
+    th = np.sqrt(np.where(small, 1.0, th2))
+    W = np.zeros(w.shape[:-1] + (3, 3), w.dtype)
+    W[..., 0, 1], W[..., 0, 2] = -w[..., 2], w[..., 1]
+    W[..., 1, 0], W[..., 1, 2] = w[..., 2], -w[..., 0]
+    W[..., 2, 0], W[..., 2, 1] = -w[..., 1], w[..., 0]
+    a = np.where(small, 0.0, np.sin(th) / th)[..., None, None]
+    b = np.where(small, 0.0, (1.0 - np.cos(th)) / (th * th))[..., None, None]
+    return np.eye(3) + a * W + b * (W @ W)
+
+
+def project(x9, K, rotation_transposed=False):
+    """pi(K (R(w) y + t)) of factors' nine unknowns (..., 9) = [t 3, w 3, y 3] -> (..., 2); real or complex"""
+    x9 = np.asarray(x9)
+    Km = _f64(K, 3, 3)
+    R = rodrigues(x9[..., 3:6])
+    if rotation_transposed:
+        R = np.swapaxes(R, -1, -2)
+    p = np.einsum("...ij,...j->...i", R, x9[..., 6:9]) + x9[..., 0:3]
+    q = np.einsum("ij,...j->...i", Km, p)
+    return q[..., :2] / p[..., 2:3]
+
+
+def jacobian(x0, K, method="complex", h=None):
+    """d project / d x at x0 (N, 9) -> (N, 2, 9), numerically: by complex step (h = 1e-30: no subtraction, exact to round-off) or by
+    central differences (h = 1e-6 by default).  Not a restatement of any closed form."""
+    x0 = _f64(x0, -1, 9)
+    J = np.empty((x0.shape[0], 2, 9))
+    for k in range(9):
+        if method == "complex":
+            d = 1e-30 if h is None else h
+            xc = x0.astype(np.complex128)
+            xc[:, k] += 1j * d
+            J[:, :, k] = np.imag(project(xc, K)) / d
+        else:
+            d = 1e-6 if h is None else h
+            xp, xm = x0.copy(), x0.copy()
+            xp[:, k] += d
+            xm[:, k] -= d
+            J[:, :, k] = (project(xp, K) - project(xm, K)) / (2 * d)
+    return J
+
+
+def _hat(y):
+    H = np.zeros(y.shape[:-1] + (3, 3))
+    H[..., 0, 1], H[..., 0, 2] = -y[..., 2], y[..., 1]
+    H[..., 1, 0], H[..., 1, 2] = y[..., 2], -y[..., 0]
+    H[..., 2, 0], H[..., 2, 1] = -y[..., 1], y[..., 0]
+    return H
+
+
+def huber_mvar(err, var, nstds, no_huber=False):
+    """(robust decision err > nstds sqrt(var), the variance the factor is scaled by)"""
+    err, var = np.asarray(err, np.float64), np.asarray(var, np.float64)
+    s = nstds * np.sqrt(var)
+    robust = err > s
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mv = var * err * err / (2.0 * (s * err - 0.5 * nstds * nstds * var))
+    mvar = np.where(robust & (not no_huber), mv, var)
+    return robust, mvar
+
+
+def linearise_factor(x0, K, z, var, nstds, first_order_rotation=False, no_huber=False, flip_residual=False):
+    """The linearisation of N reprojection factors at x0 (N, 9), measurements z (N, 2), variances var (N): a dict of
+      eta     J^T (J x0 + z - h(x0)), unscaled (N, 9)
+      lam     J^T J, unscaled (N, 9, 9)
+      err     ||h - z||
+      robust  err > nstds sqrt(var)
+      mvar    var err^2 / (2 (nstds sqrt(var) err - nstds^2 var / 2)) when robust, else var
+      J, h    the Jacobian (complex step) and the prediction.
+    The switches deliberately compute something wrong, for the blindness tests: the rotation block taken as the first-order
+    -R [y]x (through the landmark block, d pi / d y = (d pi / d p) R); no Huber rescale; the sign of z - h flipped.  (The fourth wrong
+    variant, landmark l + 1 in place of l, is the caller's choice of x0.)"""
+    x0, z = _f64(x0, -1, 9), _f64(z, -1, 2)
+    var = np.broadcast_to(np.asarray(var, np.float64), (x0.shape[0],))
+    J = jacobian(x0, K)
+    if first_order_rotation:
+        J = J.copy()
+        J[:, :, 3:6] = -np.einsum("nij,njk->nik", J[:, :, 6:9], _hat(x0[:, 6:9]))
+    h = project(x0, K)
+    r = h - z if flip_residual else z - h
+    rhs = np.einsum("nij,nj->ni", J, x0) + r
+    eta = np.einsum("nij,ni->nj", J, rhs)
+    lam = np.einsum("nij,nik->njk", J, J)
+    err = np.sqrt(np.sum((h - z) ** 2, axis=1))
+    robust, mvar = huber_mvar(err, var, nstds, no_huber)
+    return {"eta": eta, "lam": lam, "err": err, "robust": robust, "mvar": mvar, "J": J, "h": h}
+
+
+def factor_points(cam_mean, lmk_mean, bal, lmk_shift=0):
+    """x0 (E, 9) of every factor from per-variable means (C, 6), (L, 3); lmk_shift: landmark l + shift in place of l (wrong on purpose)"""
+    cam_id, lmk_id = np.asarray(bal["cam_id"], np.int64), np.asarray(bal["lmk_id"], np.int64)
+    L = int(bal["n_lmks"])
+    return np.concatenate([_f64(cam_mean, -1, 6)[cam_id], _f64(lmk_mean, -1, 3)[(lmk_id + lmk_shift) % L]], axis=1)
+
+
+def blocks_of(lam81):
+    """(E, 9, 9) from the four blocks in a row of the C-ABI (E, 81): factor_block for every factor"""
+    f = _f64(lam81, -1, 81)
+    out = np.empty((f.shape[0], 9, 9))
+    out[:, :6, :6] = f[:, :36].reshape(-1, 6, 6)
+    out[:, :6, 6:] = f[:, 36:54].reshape(-1, 6, 3)
+    out[:, 6:, :6] = f[:, 54:72].reshape(-1, 3, 6)
+    out[:, 6:, 6:] = f[:, 72:].reshape(-1, 3, 3)
+    return out
+
+
+def cost_gradient(means, bal, K, state, nstds=2.5, lmk_shift=0, **wrong):
+    """Gradient of  1/2 x^T Lp x - ep^T x + sum over active factors of rho_Huber(||h - z||)  at means = (cam (C, 6), lmk (L, 3)):
+    the prior's Lp x - ep, and per factor J^T (h - z) / mvar(err) (rho' / err = 1 / mvar on both sides of the Huber threshold).
+    Returns (gradient, scale): per unknown, the sum of the terms and the sum of their absolute values (the prior's products taken one
+    by one), the scale of a relative measure.  lmk_shift and the switches of linearise_factor compute something wrong on purpose."""
+    C, L = int(bal["n_cams"]), int(bal["n_lmks"])
+    cam_id, lmk_id = np.asarray(bal["cam_id"], np.int64), np.asarray(bal["lmk_id"], np.int64)
+    cm, lm = _f64(means[0], C, 6), _f64(means[1], L, 3)
+    g, s = np.zeros(6 * C + 3 * L), np.zeros(6 * C + 3 * L)
+    cpl, cpe = _f64(state["cam_priors_lambda"], C, 6, 6), _f64(state["cam_priors_eta"], C, 6)
+    lpl, lpe = _f64(state["lmk_priors_lambda"], L, 3, 3), _f64(state["lmk_priors_eta"], L, 3)
+    g[:6 * C] = (np.einsum("vij,vj->vi", cpl, cm) - cpe).ravel()
+    s[:6 * C] = (np.einsum("vij,vj->vi", np.abs(cpl), np.abs(cm)) + np.abs(cpe)).ravel()
+    g[6 * C:] = (np.einsum("vij,vj->vi", lpl, lm) - lpe).ravel()
+    s[6 * C:] = (np.einsum("vij,vj->vi", np.abs(lpl), np.abs(lm)) + np.abs(lpe)).ravel()
+    lin = linearise_factor(factor_points(cm, lm, bal, lmk_shift), K, state["measurements"], state["meas_variances"], nstds, **wrong)
+    res = (lin["h"] - _f64(state["measurements"], -1, 2)) * (-1.0 if wrong.get("flip_residual") else 1.0)
+    t = np.einsum("nij,ni->nj", lin["J"], res) / lin["mvar"][:, None]
+    act = np.asarray(state["active_flag"]) == 1 if "active_flag" in state else np.ones(cam_id.size, bool)
+    ci = (6 * cam_id[:, None] + np.arange(6))[act]
+    li = (6 * C + 3 * lmk_id[:, None] + np.arange(3))[act]
+    np.add.at(g, ci, t[act, :6])
+    np.add.at(g, li, t[act, 6:])
+    np.add.at(s, ci, np.abs(t[act, :6]))
+    np.add.at(s, li, np.abs(t[act, 6:]))
+    return g, s
 
 
 def metric_terms(beliefs, bal, K, measurements, active, rotation_transposed=False, lmk_shift=0):
     """Per factor: the norm of the reprojection residual and half its square, 0 for inactive factors.  Means by solve() of the
-    float32 beliefs promoted to float64, p = R(w) y + t, prediction = (K p)[:2] / p_z, residual = measurement - prediction.
+    float32 beliefs promoted to float64, prediction = project(), residual = measurement - prediction.
     rotation_transposed / lmk_shift deliberately compute something wrong (the rotation's transpose; landmark l + shift in place
     of l): what the test's tolerance must be able to tell from the right answer."""
-    C, L = int(bal["n_cams"]), int(bal["n_lmks"])
-    cam_id, lmk_id = np.asarray(bal["cam_id"], np.int64), np.asarray(bal["lmk_id"], np.int64)
+    L = int(bal["n_lmks"])
     cm = belief_means(beliefs["cam_beliefs_eta"], beliefs["cam_beliefs_lambda"], 6)
     with np.errstate(invalid="ignore", divide="ignore"):
         lm = belief_means(beliefs["lmk_beliefs_eta"], beliefs["lmk_beliefs_lambda"], 3) if L else np.zeros((0, 3))
-    Km = _f64(K, 3, 3)
     z = _f64(measurements, -1, 2)
-    act = np.asarray(active)
-    norm, half = np.zeros(cam_id.size), np.zeros(cam_id.size)
-    R = {}
-    for e in np.nonzero(act == 1)[0]:
-        c, l = cam_id[e], (lmk_id[e] + lmk_shift) % L
-        if c not in R:
-            R[c] = rodrigues(cm[c, 3:])
-        Rc = R[c].T if rotation_transposed else R[c]
-        p = Rc @ lm[l] + cm[c, :3]
-        pr = (Km @ p) / p[2]
-        r = z[e] - pr[:2]
-        norm[e] = np.sqrt(r @ r)
-        half[e] = 0.5 * (r @ r)
+    act = np.asarray(active) == 1
+    norm, half = np.zeros(z.shape[0]), np.zeros(z.shape[0])
+    if act.any():
+        with np.errstate(invalid="ignore", divide="ignore"):
+            r = z[act] - project(factor_points(cm, lm, bal, lmk_shift)[act], K, rotation_transposed=rotation_transposed)
+        sq = np.sum(r * r, axis=1)
+        norm[act], half[act] = np.sqrt(sq), 0.5 * sq
     return norm, half

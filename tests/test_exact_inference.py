@@ -210,6 +210,29 @@ class _Shards:
             self.fake.gather_all()
             self._all("iterate_end")
 
+    def weaken_priors(self):
+        for sh in self.shards:
+            sh.weaken_priors()                   # priors are replicated / local: the partials of the last exchange still hold
+
+    def new_keyframe(self, upd):
+        for sh in self.shards:
+            sh.new_keyframe(upd)
+
+    def eval(self):
+        """the shards' local sums added in rank order, as ShardedGbp.eval does over a process group"""
+        evs = [sh.eval() for sh in self.shards]
+        return {k: sum(ev[k] for ev in evs) for k in evs[0]}
+
+    def read_priors(self):
+        out = self.shards[0].read_priors()
+        for r, sh in enumerate(self.shards):
+            g = sh.read_priors()
+            assert np.array_equal(g["cam_priors_eta"], out["cam_priors_eta"]) and np.array_equal(g["cam_priors_lambda"], out["cam_priors_lambda"])
+            lo, hi, _ = self._own(r)
+            out["lmk_priors_eta"][3 * lo:3 * hi] = g["lmk_priors_eta"][3 * lo:3 * hi]
+            out["lmk_priors_lambda"][9 * lo:9 * hi] = g["lmk_priors_lambda"][9 * lo:9 * hi]
+        return out
+
     def _own(self, r):
         lo, hi = int(self.bounds[r]), int(self.bounds[r + 1])
         lmk = np.asarray(self.bal["lmk_id"])
@@ -313,23 +336,31 @@ class _Exact:
     """One graph of A / B: its inputs and, per set of potentials, the joint's exact marginals.  The dense inverse is computed once and
     kept: every path holds the same potentials bit for bit, which run() checks before it uses them."""
 
-    def __init__(self, name, bal, sweeps, **params):
+    def __init__(self, name, bal, sweeps, state=None, cond_limit=None, **params):
+        """state: what the run uploads and the joint takes its priors and active flags from (default: the inputs of _inputs, every
+        factor active, the priors as uploaded); members given replace those of _inputs"""
         self.name, self.bal, self.sweeps = name, bal, sweeps
-        self.params = dict(dmu_threshold=0.0, **params)      # relin = dmu < 0 never fires
-        self.K, self.state = _inputs(bal)                    # (no weaken_priors anywhere: the priors stay as uploaded)
-        self._pot, self._exact = None, None
+        self.params = {"dmu_threshold": 0.0, **params}             # by default relin = dmu < 0 never fires
+        self.K, self.state = _inputs(bal)
+        if state is not None:
+            self.state = dict(self.state, **state)
+        self.cond_limit = COND_LIMIT[name[0]] if cond_limit is None else cond_limit
+        self._kept = {}
 
-    def exact(self, fac_eta, fac_lambda):
-        if self._pot is None or not (np.array_equal(self._pot[0], fac_eta) and np.array_equal(self._pot[1], fac_lambda)):
-            Lam, eta = ref64.joint(self.bal, self.state, fac_eta, fac_lambda)
+    def exact(self, fac_eta, fac_lambda, state=None, key=None):
+        """the exact marginals of the joint of `state`'s priors (default: the uploaded state's) and its active factors' potentials.  The
+        last joint of each `key` (a name the caller gives a state) is kept and used again for the same potentials"""
+        kept = self._kept.get(key)
+        if kept is None or not (np.array_equal(kept[0], fac_eta) and np.array_equal(kept[1], fac_lambda)):
+            Lam, eta = ref64.joint(self.bal, self.state if state is None else state, fac_eta, fac_lambda)
             w = np.linalg.eigvalsh(Lam)
             cond = float(w[-1] / w[0])
             print("%s: joint of %d unknowns, condition %.1f" % (self.name, eta.size, cond))
-            assert w[0] > 0 and cond <= COND_LIMIT[self.name[0]], cond
+            assert w[0] > 0 and cond <= self.cond_limit, cond
             ex = ref64.marginals(Lam, eta, self.bal["n_cams"], self.bal["n_lmks"])
             ex["cond"] = cond
-            self._pot, self._exact = (np.array(fac_eta), np.array(fac_lambda)), ex
-        return self._exact
+            kept = self._kept[key] = (np.array(fac_eta), np.array(fac_lambda), ex)
+        return kept[2]
 
     def errors(self, beliefs, ex):
         cm = ref64.belief_means(beliefs["cam_beliefs_eta"], beliefs["cam_beliefs_lambda"], 6)
