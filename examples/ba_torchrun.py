@@ -4,7 +4,7 @@ sets.  The product's multi-GPU path is `bin/ba --ipus N` / `bin/slam --ipus N`: 
 owned by the C++ library (csrc/gbp_comm.cpp, RCCL).
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-           examples/ba_torchrun.py --bal_file F [--n_iters K] [--eval_every E] [... the ba flags]
+           examples/ba_torchrun.py --bal_file F [--n_iters K] [--eval_every E] [--out_file G] [... the ba flags]
 
 One process per GPU; landmarks are sharded over the ranks (gbp_poplar_amd.distributed), rank 0 prints the
 same lines as `./ba` (ba.cpp:996,1004,1026-1028) or, with `--slam`, as `./slam` (slam.cpp:1073-1076; keyframes
@@ -36,6 +36,7 @@ def main(argv=None):
     ap.add_argument("--eval_every", type=int, default=1)
     ap.add_argument("--slam", action="store_true", help="incremental SLAM flow of ./slam instead of batch BA")
     ap.add_argument("--iters_between_kfs", type=int, default=700)
+    ap.add_argument("--out_file", default="", help="write the refined cameras / landmarks (belief means) in the input's format")
     a = ap.parse_args(argv)
 
     rank = int(os.environ.get("RANK", "0"))
@@ -88,10 +89,23 @@ def main(argv=None):
         n_done = a.n_iters
     run.sync()
     log("\n Finished GBP.\nTotal time: %.3f s (%d iterations, %d GPUs)" % (time.perf_counter() - t0, n_done, world))
+    rc = 0 if traj else 1
+    if a.out_file:
+        # every rank owns a landmark range: the gathered read (collective) hands every rank the complete beliefs, rank 0 writes
+        bel = run.read(gather=True)
+        if rank == 0:
+            cams, pts = hostlib.belief_means(C, L, bel["cam_beliefs_eta"], bel["cam_beliefs_lambda"],
+                                             bel["lmk_beliefs_eta"], bel["lmk_beliefs_lambda"])
+            try:
+                hostlib.bal_write(a.out_file, dict(bal, cameras=cams, points=pts))
+                log("Refined problem written to %s" % a.out_file)
+            except RuntimeError:
+                print("ERROR: unable to write %s" % a.out_file, file=sys.stderr)
+                rc = 1
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
-    return 0 if traj else 1
+    return rc
 
 
 if __name__ == "__main__":

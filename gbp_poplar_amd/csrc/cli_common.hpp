@@ -298,11 +298,50 @@ inline void print_verbose(const Readback& r) {  // ba.cpp:1030-1051
   std::fflush(stdout);
 }
 
-// --out_file: the solution (belief means) in the format of the input, observations unchanged.  Single-process runs only:
-// a rank of a sharded run holds the landmarks of its own range.
-inline int write_solution(const Options& o, const Problem& P, gbp_ctx* ctx, bool sharded) {
+// ---- one process per GPU (`--ipus N` / `--gpus N`) -------------------------------------------------------------------
+struct RankCtx {
+  int rank = 0, world = 1;
+  void* region = nullptr;       // shared rendezvous / staging region (gbp_comm_region_*), world > 1 only
+  void* metric_area = nullptr;  // shared [2 parities][world][gbp::kMetricBurstMax] metric records (gbp_metric_gather.hpp), mapped with the region
+  float* result = nullptr;      // --out_file of a forked run: the shared belief arrays (result_floats), mapped with the region
+  unsigned bursts = 0;          // bursts summed so far: the parity of the next one
+  gbp_shard shard{0, 1, 0, 0};
+};
+
+// The result area of a forked run with --out_file: cam_beliefs_eta [6C], cam_beliefs_lambda [36C], lmk_beliefs_eta [3L], lmk_beliefs_lambda [9L]
+inline size_t result_floats(uint32_t C, uint32_t L) { return 42 * (size_t)C + 12 * (size_t)L; }
+
+constexpr int kLeaveNow = 2;      // write_solution: this rank failed where the others still wait for it — it leaves without meeting them again
+
+// --out_file of a forked run.  Every rank reads its beliefs into the SHARED arrays: gbp_read on a sharded ctx writes the landmarks of the
+// rank's own range at their global indices, so the ranks fill disjoint bytes; the cameras, replicated and bit-identical, are rank 0's.
+// ONE barrier (the region's: release / acquire on its shared words, whatever the transport) lies between every rank's writes and rank 0's
+// reads.  A rank whose read or barrier fails writes nothing and does not reach another barrier: the file never holds arrays that some
+// rank has not filled.
+inline int write_solution_ranks(const Options& o, const Problem& P, gbp_ctx* ctx, const RankCtx& rk) {
+  const uint32_t C = P.bal.n_cams, L = P.bal.n_lmks;
+  if (!rk.result) { std::cerr << "rank " << rk.rank << ": no shared result area for --out_file\n"; return kLeaveNow; }
+  float *cbe = rk.result, *cbl = cbe + 6 * (size_t)C, *lbe = cbl + 36 * (size_t)C, *lbl = lbe + 3 * (size_t)L;
+  gbp_state_out out{};
+  out.lmk_beliefs_eta = lbe; out.lmk_beliefs_lambda = lbl;
+  if (rk.rank == 0) { out.cam_beliefs_eta = cbe; out.cam_beliefs_lambda = cbl; }
+  if (gbp_read(ctx, &out) != GBP_OK) { std::cerr << "rank " << rk.rank << ": gbp_read failed: " << gbp_last_error(ctx) << "\n"; return kLeaveNow; }
+  if (gbp_comm_barrier(ctx) != GBP_OK) { std::cerr << "rank " << rk.rank << ": gbp_comm_barrier failed: " << gbp_last_error(ctx) << "\n"; return kLeaveNow; }
+  if (rk.rank != 0) return 0;
+  std::vector<double> cams(6 * (size_t)C), pts(3 * (size_t)L);
+  gbp_belief_means(C, L, cbe, cbl, lbe, lbl, cams.data(), pts.data());
+  gbp_bal res = P.bal;
+  res.cameras = cams.data(); res.points = pts.data();
+  if (gbp_bal_write(o.out_file.c_str(), &res) != GBP_OK) { std::cerr << "ERROR: unable to write " << o.out_file << "\n"; return 1; }
+  std::cout << "Refined problem written to " << o.out_file << "\n";
+  return 0;
+}
+
+// --out_file: the solution (belief means) in the format of the input, observations unchanged.  A forked run (--ipus N, --force_sharded):
+// write_solution_ranks.
+inline int write_solution(const Options& o, const Problem& P, gbp_ctx* ctx, const RankCtx& rk) {
   if (o.out_file.empty()) return 0;
-  if (sharded) { std::cout << "--out_file is ignored with --ipus N > 1 (each rank holds its own landmark range)\n"; return 0; }
+  if (rk.region) return write_solution_ranks(o, P, ctx, rk);
   const uint32_t C = P.bal.n_cams, L = P.bal.n_lmks;
   std::vector<float> cbe(6 * (size_t)C), cbl(36 * (size_t)C), lbe(3 * (size_t)L), lbl(9 * (size_t)L);
   gbp_state_out out{};
@@ -316,15 +355,6 @@ inline int write_solution(const Options& o, const Problem& P, gbp_ctx* ctx, bool
   std::cout << "Refined problem written to " << o.out_file << "\n";
   return 0;
 }
-
-// ---- one process per GPU (`--ipus N` / `--gpus N`) -------------------------------------------------------------------
-struct RankCtx {
-  int rank = 0, world = 1;
-  void* region = nullptr;       // shared rendezvous / staging region (gbp_comm_region_*), world > 1 only
-  void* metric_area = nullptr;  // shared [2 parities][world][gbp::kMetricBurstMax] metric records (gbp_metric_gather.hpp), mapped with the region
-  unsigned bursts = 0;          // bursts summed so far: the parity of the next one
-  gbp_shard shard{0, 1, 0, 0};
-};
 
 // A single-process run brings the HIP runtime up (120 - 240 ms: the first call that needs it) on a second thread WHILE the main thread
 // reads the file and builds the priors — nothing for the shipped sequences (4 ms of host work), the runtime's whole start-up for a
@@ -415,8 +445,9 @@ inline int create_rank_ctx(const Options& o, const Problem& P, RankCtx& rk, gbp_
 }
 
 // Runs body(rank) in `world` processes forked from this one — which must not have touched HIP yet — and supervises them:
-// the exit status is the first failing rank's, and a rank that dies wakes the others out of their barriers.
-template <class F> int run_ranks(int world, uint32_t n_cams, bool force, F&& body) {
+// the exit status is the first failing rank's, and a rank that dies wakes the others out of their barriers.  result_count > 0 (--out_file):
+// that many shared floats for the beliefs the ranks end with (result_floats, write_solution_ranks).
+template <class F> int run_ranks(int world, uint32_t n_cams, bool force, size_t result_count, F&& body) {
   RankCtx rk;
   if (world <= 1 && !force) return body(rk);
   if (!std::getenv("HSA_ENABLE_IPC_MODE_LEGACY")) setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0", 1);   // dmabuf IPC for RCCL
@@ -433,6 +464,17 @@ template <class F> int run_ranks(int world, uint32_t n_cams, bool force, F&& bod
     munmap(region, bytes);
     return 1;
   }
+  const size_t result_bytes = result_count * sizeof(float);
+  void* result = nullptr;
+  if (result_bytes) {
+    result = mmap(nullptr, result_bytes, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
+    if (result == MAP_FAILED) {
+      std::cerr << "could not create the shared result arrays of the ranks (--out_file: " << result_bytes << " bytes)\n";
+      munmap(metric_area, metric_bytes);
+      munmap(region, bytes);
+      return 1;
+    }
+  }
   std::cout.flush();
   std::fflush(nullptr);
   std::vector<pid_t> pid((size_t)world, -1);
@@ -441,7 +483,7 @@ template <class F> int run_ranks(int world, uint32_t n_cams, bool force, F&& bod
     pid[r] = fork();
     if (pid[r] < 0) { std::cerr << "fork failed\n"; gbp_comm_region_abort(region); fork_failed = true; break; }
     if (pid[r] == 0) {
-      rk.rank = r; rk.world = world; rk.region = region; rk.metric_area = metric_area;
+      rk.rank = r; rk.world = world; rk.region = region; rk.metric_area = metric_area; rk.result = static_cast<float*>(result);
       if (r != 0 && !std::freopen("/dev/null", "w", stdout)) std::_Exit(1);     // rank 0 prints (ba.cpp:996,1026-1028)
       int rc = 1;
       try { rc = body(rk); } catch (const std::exception& e) { std::cerr << "rank " << r << ": " << e.what() << "\n"; }
@@ -482,6 +524,7 @@ template <class F> int run_ranks(int world, uint32_t n_cams, bool force, F&& bod
     }
     usleep(20000);
   }
+  if (result) munmap(result, result_bytes);
   munmap(metric_area, metric_bytes);
   munmap(region, bytes);
   return first_bad;
@@ -661,7 +704,8 @@ inline int finish_run(const Options& o, const Problem& P, gbp_ctx* ctx, const Ra
   gbp_timing(ctx, &tm, 0);
   const int gs = gbp_graph_state(ctx);
   print_warning(ctx);
-  const int wrc = write_solution(o, P, ctx, rk.region != nullptr);
+  const int wrc = write_solution(o, P, ctx, rk);
+  if (wrc == kLeaveNow) return 1;      // like a failed call of the loop: the process ends, the supervisor wakes the other ranks
   phases().mark("loop_s");
   gbp_destroy(ctx);
   phases().mark("teardown_s");

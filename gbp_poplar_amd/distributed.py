@@ -17,7 +17,9 @@ incident to it; factor potentials, per-factor state, both message directions and
 rank-local.  Cameras are replicated: per iteration each rank reduces its factor->camera messages to a
 [C x 44] partial, ONE all-gather moves the partials, and every rank adds prior + partials in rank order
 (deterministic, bit-identical camera beliefs on all ranks; no float atomics, no ring all-reduce whose
-association order would differ between ranks).
+association order would differ between ranks).  So a rank's read() / read_priors() hold the cameras and the
+landmark and per-factor entries of its own range; read(gather=True) / read_priors(gather=True) fetch every other
+entry from its owner and return complete arrays on every rank.
 
 `engine` is a rank-local object with the split-phase verbs of the C-ABI (gbp_iterate_begin/_end,
 gbp_refresh_begin/_end, gbp_linearise_factors, ...): the product passes GbpEngine (HIP); the CPU gloo
@@ -45,12 +47,19 @@ def landmark_partition(lmk_id, n_lmks, world):
 class ShardedGbp:
     """The Poplar program list over `world` ranks.  Same verbs as GbpEngine / the oracle."""
 
-    def __init__(self, engine, n_cams, rank, world, dist=None, device="cpu", always_collective=False, use_graph=False):
+    def __init__(self, engine, n_cams, rank, world, dist=None, device="cpu", always_collective=False, use_graph=False,
+                 lmk_id=None, lmk_range=None):
+        """lmk_id [E], lmk_range (begin, end): the landmark of every factor and this rank's own landmark range — what
+        read(gather=True) / read_priors(gather=True) need to know who owns which entry.  Left out, they are taken from the
+        engine where it keeps them (GbpEngine and the oracle engines do: `problem`, `shard`)."""
         import torch
         self.torch = torch
         self.e = engine
         self.C, self.rank, self.world = int(n_cams), int(rank), int(world)
         self.dist = dist
+        self._lmk_id = None if lmk_id is None else np.ascontiguousarray(lmk_id, dtype=np.int64)
+        self._lmk_range = None if lmk_range is None else (int(lmk_range[0]), int(lmk_range[1]))
+        self._owners = None                          # (ranges [world, 2], factors of every rank): made by the first gathered read
         self.always_collective = always_collective   # run the all-gather even for world == 1 (exercises RCCL in tests)
         self.use_graph = use_graph                   # capture kernels + collective of `graph_unroll` iterations
         self.graph_unroll = 10
@@ -149,11 +158,89 @@ class ShardedGbp:
     def new_keyframe(self, upd):
         self.e.new_keyframe(upd)
 
-    def read(self):
-        return self.e.read()
+    def read(self, gather=False):
+        """The local rank's view: landmark and per-factor entries outside its range are left untouched.  gather=True
+        (collective: every rank calls it): COMPLETE arrays on every rank — the cameras from its own copy, every landmark
+        entry from the rank that owns it, every per-factor entry from the rank that owns the factor's landmark."""
+        out = self.e.read()
+        if gather and self._several_ranks():
+            self._gather_owned(out, (("lmk_beliefs_eta", 3), ("lmk_beliefs_lambda", 9)),
+                               ("damping", "damping_count", "robust_flag"))
+        return out
 
-    def read_priors(self):
-        return self.e.read_priors()
+    def read_priors(self, gather=False):
+        """as read(): the local view, or with gather=True the landmark priors of every range from its owner"""
+        out = self.e.read_priors()
+        if gather and self._several_ranks():
+            self._gather_owned(out, (("lmk_priors_eta", 3), ("lmk_priors_lambda", 9)), ())
+        return out
+
+    def _several_ranks(self):
+        return self.dist is not None and self.world > 1
+
+    def _ownership(self):
+        """(ranges [world][2], factors [world] -> edge indices in ascending order); the ranges are all-gathered once."""
+        if self._owners is not None:
+            return self._owners
+        rng, lmk = self._lmk_range, self._lmk_id
+        shard = getattr(self.e, "shard", None)
+        if rng is None and shard is not None:
+            rng = (int(shard.lmk_begin), int(shard.lmk_end)) if hasattr(shard, "lmk_begin") else (int(shard[2]), int(shard[3]))
+        problem = getattr(self.e, "problem", None)
+        if lmk is None and problem is not None and int(problem.n_edges) > 0:
+            lmk = np.ctypeslib.as_array(problem.lmk_id, shape=(int(problem.n_edges),)).astype(np.int64)
+        if rng is None or lmk is None:
+            raise ValueError("read(gather=True) needs to know who owns which entry: pass lmk_id= (the landmark of every factor) "
+                             "and lmk_range= (this rank's landmark range) to ShardedGbp, or an engine that keeps `problem` and `shard`")
+        torch = self.torch
+        with self._on_stream():
+            mine = torch.tensor(rng, dtype=torch.int64, device=self.send.device)
+            allr = torch.zeros(2 * self.world, dtype=torch.int64, device=self.send.device)
+            self.dist.all_gather_into_tensor(allr, mine)
+        if self.stream is not None:
+            self.stream.synchronize()
+        ranges = [(int(a), int(b)) for a, b in allr.view(self.world, 2).cpu().numpy()]
+        factors = [np.nonzero((lmk >= lo) & (lmk < hi))[0] for lo, hi in ranges]
+        self._owners = (ranges, factors)
+        return self._owners
+
+    def _gather_owned(self, out, lmk_members, factor_members):
+        """Fills the other ranks' entries of out[...] in place.  Every rank packs what it owns — the bit patterns, as int32 — into
+        one buffer padded to the longest, ONE all-gather moves them, and the entries are COPIED to their places: a belief may be
+        -0.0 or a NaN and arrives with its bits (a sum over zero-filled arrays would lose them)."""
+        torch = self.torch
+        ranges, factors = self._ownership()
+        words = [sum(w for _, w in lmk_members) * (hi - lo) + len(factor_members) * len(f) for (lo, hi), f in zip(ranges, factors)]
+        longest = max(words)
+        if longest == 0:
+            return
+        bits = {k: out[k].view(np.int32) for k in [m for m, _ in lmk_members] + list(factor_members)}
+
+        def pieces(r):      # (member, where its entries of rank r lie in the member's array), in the order they are packed
+            lo, hi = ranges[r]
+            return [(k, slice(w * lo, w * hi)) for k, w in lmk_members] + [(k, factors[r]) for k in factor_members]
+
+        mine = np.zeros(longest, np.int32)
+        at = 0
+        for k, where in pieces(self.rank):
+            part = bits[k][where]
+            mine[at:at + part.size] = part
+            at += part.size
+        with self._on_stream():
+            send = torch.from_numpy(mine).to(self.send.device)
+            recv = torch.zeros(self.world * longest, dtype=torch.int32, device=self.send.device)
+            self.dist.all_gather_into_tensor(recv, send)
+        if self.stream is not None:
+            self.stream.synchronize()
+        recv = recv.view(self.world, longest).cpu().numpy()
+        for r in range(self.world):
+            if r == self.rank:
+                continue
+            at = 0
+            for k, where in pieces(r):
+                n = where.stop - where.start if isinstance(where, slice) else len(where)
+                bits[k][where] = recv[r, at:at + n]
+                at += n
 
     def eval(self):
         """Local shard sums, added over ranks (integers and fp64 partials; rank order fixed by all_gather)."""
