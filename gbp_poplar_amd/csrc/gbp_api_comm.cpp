@@ -19,15 +19,15 @@ namespace api {
 // A peer-memory transport exchanges through the communicator's own buffer: send_dev / recv_dev are this rank's slot / the whole
 // [world][C][44] of the NEXT exchange (re-bound after every exchange).  No-op for the other transports.
 static void bind_exchange(gbp_ctx* c) {
-  if (PeerComm* pc = peers(c->comm)) {
-    c->send_dev = pc->send_slot();
-    c->recv_dev = pc->next_block();
+  if (PeerComm* pc = peers(c->xch.comm)) {
+    c->xch.send_dev = pc->send_slot();
+    c->xch.recv_dev = pc->next_block();
   }
 }
 
 // plain exchange on the ctx's stream (LINEARISE, refreshes) or on s: partials in send_dev -> recv_dev of every rank
 int exchange_now(gbp_ctx* c, hipStream_t s) {
-  COMMCHK(c, c->comm->all_gather(static_cast<const float*>(c->send_dev), static_cast<float*>(c->recv_dev),
+  COMMCHK(c, c->xch.comm->all_gather(static_cast<const float*>(c->xch.send_dev), static_cast<float*>(c->xch.recv_dev),
                                  (size_t)c->C * kCamRec, s ? s : c->stream, e_));
   bind_exchange(c);
   return GBP_OK;
@@ -42,8 +42,8 @@ static int advance_exchange(gbp_ctx* c, PeerComm* pc, int* p) {
 
 // a new problem (gbp_upload): what the exchange gathers into starts from zero
 int zero_exchange(gbp_ctx* c) {
-  if (PeerComm* pc = peers(c->comm)) HIPCHK(c, pc->zero(c->stream));
-  else if (exch(c) && c->recv_dev) HIPCHK(c, hipMemsetAsync(c->recv_dev, 0, (size_t)c->world * c->C * kCamRec * 4, c->stream));
+  if (PeerComm* pc = peers(c->xch.comm)) HIPCHK(c, pc->zero(c->stream));
+  else if (exch(c) && c->xch.recv_dev) HIPCHK(c, hipMemsetAsync(c->xch.recv_dev, 0, (size_t)c->world * c->C * kCamRec * 4, c->stream));
   return GBP_OK;
 }
 
@@ -70,9 +70,9 @@ static int combine_cameras_in_iteration(gbp_ctx* c, hipEvent_t x1, int roll, con
   BeliefArgs b = belief_args(c);
   b.roll = roll;
   ride_args(c, b, ev, true);
-  PeerComm* pc = peers(c->comm);
+  PeerComm* pc = peers(c->xch.comm);
   int p = 0;
-  switch (c->comm->kind()) {
+  switch (c->xch.comm->kind()) {
     case Transport::P2p:
       if (int rc = advance_exchange(c, pc, &p)) return rc;
       launch_beliefs_cam_peers(b, pc->peer_table(p), c->stream, ev != nullptr);
@@ -94,13 +94,13 @@ static int combine_cameras_in_iteration(gbp_ctx* c, hipEvent_t x1, int roll, con
       launch_beliefs_cam_slice(b, pc->peer_table(p), sl, c->stream);
       HIPCHK(c, hipGetLastError());
       HIPCHK(c, hipStreamSynchronize(c->stream));
-      COMMCHK(c, c->comm->barrier(e_));
+      COMMCHK(c, c->xch.comm->barrier(e_));
       launch_gather_slices(pc->result_table(p), b, c->rank, c->stream);
       break;
     default:
       if (int rc = exchange_now(c)) return rc;
       if (x1) HIPCHK(c, hipEventRecord(x1, c->stream));
-      b.gathered = static_cast<const float*>(c->recv_dev);
+      b.gathered = static_cast<const float*>(c->xch.recv_dev);
       launch_beliefs(b, true, false, c->stream, ev != nullptr);
       break;
   }
@@ -110,8 +110,8 @@ static int combine_cameras_in_iteration(gbp_ctx* c, hipEvent_t x1, int roll, con
 
 // the refresh's column: b as the caller set it up (roll, weaken)
 int refresh_cameras(gbp_ctx* c, BeliefArgs& b, bool do_lmk) {
-  PeerComm* pc = peers(c->comm);
-  const Transport kind = c->comm ? c->comm->kind() : Transport::Auto;      // (Auto: no communicator)
+  PeerComm* pc = peers(c->xch.comm);
+  const Transport kind = c->xch.comm ? c->xch.comm->kind() : Transport::Auto;      // (Auto: no communicator)
   if (kind == Transport::P2p || (kind == Transport::P2pSlices && c->world > 1)) {
     // the last exchange's partials are read where they lie; the landmark half, which needs nothing from other ranks, in a launch of its own
     launch_beliefs_cam_peers(b, pc->last_table(), c->stream);
@@ -120,10 +120,10 @@ int refresh_cameras(gbp_ctx* c, BeliefArgs& b, bool do_lmk) {
     if (kind == Transport::P2pSlices) {
       b.gathered = pc->last_own_slot();      // (recv_dev is the parity of the NEXT exchange)
     } else if (!exch(c)) {
-      b.gathered = P<float>(c->local); b.world = 1;
+      b.gathered = P<float>(c->arr.local); b.world = 1;
     } else {
-      if (!c->recv_dev) return fail(c, GBP_ERR_STATE, "exchange buffers not set");
-      b.gathered = static_cast<const float*>(c->recv_dev);
+      if (!c->xch.recv_dev) return fail(c, GBP_ERR_STATE, "exchange buffers not set");
+      b.gathered = static_cast<const float*>(c->xch.recv_dev);
     }
     launch_beliefs(b, true, do_lmk, c->stream);
   }
@@ -136,19 +136,19 @@ int refresh_cameras(gbp_ctx* c, BeliefArgs& b, bool do_lmk) {
 // ranks, runs beside it on the main stream.  x0 / x1 (profiling): a bracket around the camera side on its stream.
 // ev: the landmark half leaves its metric means and health counts, the combine behind the join is the iteration's last belief launch.
 static int enqueue_cameras_two_streams(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1, int roll = 1, const EvalRide* ev = nullptr) {
-  HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-  HIPCHK(c, hipStreamWaitEvent(c->comm_stream, c->ev_fork, 0));
-  if (x0) HIPCHK(c, hipEventRecord(x0, c->comm_stream));
-  enqueue_cam_partials(c, static_cast<float*>(c->send_dev), c->comm_stream);
-  if (int rc = exchange_now(c, c->comm_stream)) return rc;
-  if (x1) HIPCHK(c, hipEventRecord(x1, c->comm_stream));
-  HIPCHK(c, hipEventRecord(c->ev_join, c->comm_stream));
+  HIPCHK(c, hipEventRecord(c->xch.ev_fork, c->stream));
+  HIPCHK(c, hipStreamWaitEvent(c->xch.stream, c->xch.ev_fork, 0));
+  if (x0) HIPCHK(c, hipEventRecord(x0, c->xch.stream));
+  enqueue_cam_partials(c, static_cast<float*>(c->xch.send_dev), c->xch.stream);
+  if (int rc = exchange_now(c, c->xch.stream)) return rc;
+  if (x1) HIPCHK(c, hipEventRecord(x1, c->xch.stream));
+  HIPCHK(c, hipEventRecord(c->xch.ev_join, c->xch.stream));
   BeliefArgs b = belief_args(c);
   b.roll = roll;
   ride_args(c, b, ev, false);
   launch_beliefs(b, false, true, c->stream, ev != nullptr);
-  HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-  b.gathered = static_cast<const float*>(c->recv_dev);
+  HIPCHK(c, hipStreamWaitEvent(c->stream, c->xch.ev_join, 0));
+  b.gathered = static_cast<const float*>(c->xch.recv_dev);
   ride_args(c, b, ev, true);
   launch_beliefs(b, true, false, c->stream, ev != nullptr);
   HIPCHK(c, hipGetLastError());
@@ -161,7 +161,7 @@ static int enqueue_cameras_two_streams(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1,
 // ev: the partial_only launch carries the landmarks' share of the metric (its camera blocks none), the combine the cameras'.
 static int enqueue_cameras_one_stream(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1, int roll = 1, const EvalRide* ev = nullptr) {
   BeliefArgs b = belief_args(c);
-  b.cam_local = static_cast<float*>(c->send_dev);
+  b.cam_local = static_cast<float*>(c->xch.send_dev);
   b.partial_only = 1;
   b.roll = roll;
   ride_args(c, b, ev, false);
@@ -173,13 +173,13 @@ static int enqueue_cameras_one_stream(gbp_ctx* c, hipEvent_t x0, hipEvent_t x1, 
 // One iteration of a sharded ctx: sweep, then the camera side of the exchange and the belief update in one of the two schedules.
 // With a stream-ordered transport (RCCL) nothing here blocks the host, so the sequence can be captured into a hipGraph.
 // ev: the iteration carries the metric (a.ev set by the caller: eval_each_ride) — the sweep collects the metric of the iteration before
-// it, the belief launches leave this one's metric records.  Such iterations are launched directly, never from sharded_graph.
+// it, the belief launches leave this one's metric records.  Such iterations are launched directly, never from the captured graph (graph.sharded).
 static int enqueue_sharded_iteration(gbp_ctx* c, const SweepArgs& a, bool ev = false) {
-  if (c->profile_stages) {
-    if (c->pending_sweep_ev.size() >= 256) drain_sweep_events(c);
+  if (c->tm.profile_stages) {
+    if (c->tm.pending_sweep_ev.size() >= 256) drain_sweep_events(c);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (int rc = event_pair(c, &e0, &e1)) return rc;
-    c->pending_sweep_ev.emplace_back(e0, e1);
+    c->tm.pending_sweep_ev.push_back({e0, e1});
     HIPCHK(c, hipEventRecord(e0, c->stream));
     launch_sweep(a, c->n_tiles, c->hoist, c->stream, ev);
     HIPCHK(c, hipEventRecord(e1, c->stream));
@@ -187,19 +187,19 @@ static int enqueue_sharded_iteration(gbp_ctx* c, const SweepArgs& a, bool ev = f
     launch_sweep(a, c->n_tiles, c->hoist, c->stream, ev);
   }
   hipEvent_t x0 = nullptr, x1 = nullptr;     // profiling: how long the camera side of the exchange takes on its stream
-  if (c->profile_stages && c->comm->stream_ordered()) {
+  if (c->tm.profile_stages && c->xch.comm->stream_ordered()) {
     if (int rc = event_pair(c, &x0, &x1)) return rc;
-    c->pending_exch_ev.emplace_back(x0, x1);
+    c->tm.pending_exch_ev.push_back({x0, x1});
   }
   const EvalRide* r = ev ? &a.ev : nullptr;
-  return c->comm->stream_ordered() && !c->comm_single_stream ? enqueue_cameras_two_streams(c, x0, x1, 1, r) : enqueue_cameras_one_stream(c, x0, x1, 1, r);
+  return c->xch.comm->stream_ordered() && !c->xch.single_stream ? enqueue_cameras_two_streams(c, x0, x1, 1, r) : enqueue_cameras_one_stream(c, x0, x1, 1, r);
 }
 
 // n sharded iterations that carry the metric, inside a piece of eval_each_ride (which owns the ring, the counter and the timing bracket)
 int iterate_sharded_ev(gbp_ctx* c, const SweepArgs& a, int n) {
   for (int k = 0; k < n; ++k) {
     if (int rc = enqueue_sharded_iteration(c, a, true)) return rc;
-    c->comm_warm++;
+    c->xch.warm++;
   }
   return GBP_OK;
 }
@@ -211,42 +211,42 @@ int iterate_sharded(gbp_ctx* c, int n) {
   int left = n;
   // Measured (config-5 shard shape, 1-rank communicator): direct launches 0.186 ms per iteration, the captured graph with
   // its cross-stream fork/join nodes 0.191 ms — the path is not host-bound, so the graph is opt-in (graph_unroll > 0).
-  const bool can_graph = c->comm->stream_ordered() && !c->profile_stages && c->sharded_graph && !c->graph_failed &&
+  const bool can_graph = c->xch.comm->stream_ordered() && !c->tm.profile_stages && c->graph.sharded && !c->graph.failed &&
                          c->stream == c->own_stream;
   // RCCL sets itself up lazily (channels, proxy threads): a few direct iterations must have run before a capture
-  while (left > 0 && (!can_graph || c->comm_warm < 3 || left < c->prm.graph_unroll)) {
+  while (left > 0 && (!can_graph || c->xch.warm < 3 || left < c->prm.graph_unroll)) {
     if (int rc = enqueue_sharded_iteration(c, a)) return rc;
-    c->comm_warm++;
+    c->xch.warm++;
     --left;
   }
   if (left >= c->prm.graph_unroll && can_graph) {
-    if (!c->graph_exec) {
+    if (!c->graph.exec) {
       HIPCHK(c, hipStreamSynchronize(c->stream));
       hipError_t e = hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed);
       int rc = GBP_OK;
       if (e == hipSuccess) {
         for (int i = 0; i < c->prm.graph_unroll && rc == GBP_OK; ++i) rc = enqueue_sharded_iteration(c, a);
-        e = hipStreamEndCapture(c->stream, &c->graph);
-        if (e == hipSuccess && rc == GBP_OK) e = hipGraphInstantiate(&c->graph_exec, c->graph, nullptr, nullptr, 0);
+        e = hipStreamEndCapture(c->stream, &c->graph.g);
+        if (e == hipSuccess && rc == GBP_OK) e = hipGraphInstantiate(&c->graph.exec, c->graph.g, nullptr, nullptr, 0);
       }
       if (e != hipSuccess || rc != GBP_OK) {     // no graph for this ctx: direct launches (identical results)
         (void)hipGetLastError();
         drop_graph(c);
-        c->graph_failed = true;
+        c->graph.failed = true;
       } else {
-        c->graph_iters = c->prm.graph_unroll;
+        c->graph.iters = c->prm.graph_unroll;
       }
     }
-    while (c->graph_exec && left >= c->graph_iters) {
-      HIPCHK(c, hipGraphLaunch(c->graph_exec, c->stream));
-      left -= c->graph_iters;
+    while (c->graph.exec && left >= c->graph.iters) {
+      HIPCHK(c, hipGraphLaunch(c->graph.exec, c->stream));
+      left -= c->graph.iters;
     }
   }
   for (; left > 0; --left)
     if (int rc = enqueue_sharded_iteration(c, a)) return rc;
   if (int rc = sp.end()) return rc;
-  if (!c->comm->stream_ordered() || c->profile_stages) HIPCHK(c, hipStreamSynchronize(c->stream));
-  return sp.commit(c->profile_stages ? 0 : (uint64_t)n);    // with profiling the sweep brackets count the iterations
+  if (!c->xch.comm->stream_ordered() || c->tm.profile_stages) HIPCHK(c, hipStreamSynchronize(c->stream));
+  return sp.commit(c->tm.profile_stages ? 0 : (uint64_t)n);    // with profiling the sweep brackets count the iterations
 }
 
 }  // namespace api
@@ -256,22 +256,22 @@ int iterate_sharded(gbp_ctx* c, int n) {
 // the second stream of the two-stream schedule, made when first needed.  Highest priority: the all-gather is issued while the
 // landmark half of k_beliefs fills the GPU; it must not queue behind those blocks (the camera combine of every rank waits for it)
 static int ensure_comm_stream(gbp_ctx* c) {
-  if (c->comm_stream || c->comm_single_stream) return GBP_OK;
+  if (c->xch.stream || c->xch.single_stream) return GBP_OK;
   int least = 0, greatest = 0;
   HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-  HIPCHK(c, hipStreamCreateWithPriority(&c->comm_stream, hipStreamNonBlocking, greatest));
+  HIPCHK(c, hipStreamCreateWithPriority(&c->xch.stream, hipStreamNonBlocking, greatest));
   return GBP_OK;
 }
 
 static int comm_attach(gbp_ctx* c, gbp::Comm* comm) {
   if (int rc = settle(c)) { delete comm; return rc; }
-  c->comm = comm;
+  c->xch.comm = comm;
   // A second HSA queue makes every dispatch of the main queue slower (measured: +10 us per sharded iteration on the
   // config-5 shard shape, 0.183 vs 0.174 ms with a 1-rank communicator), so overlapping the all-gather with the
   // landmark beliefs (~20 us of cover) only pays once the all-gather itself takes longer than that: 4 ranks and more.
   // GBP_COMM_SINGLE_STREAM=0/1 overrides the rule (measurements).
   const char* ss = std::getenv("GBP_COMM_SINGLE_STREAM");
-  c->comm_single_stream = ss ? ss[0] == '1' : c->world <= 2;
+  c->xch.single_stream = ss ? ss[0] == '1' : c->world <= 2;
   drop_graph(c);
   // IN-PLACE all-gather: this rank's partial sums are written straight into its own slot of the gathered buffer
   // (sendbuff == recvbuff + rank * count is the in-place form of ncclAllGather: the collective then moves only what comes from
@@ -279,16 +279,18 @@ static int comm_attach(gbp_ctx* c, gbp::Comm* comm) {
   // profiles/r06_sharded_timeline.md).  (zero-filled on the ctx's stream, in front of everything that uses it)
   bind_exchange(c);      // p2p: the communicator's own buffer
   if (!peers(comm)) {
-    if (!c->xrecv.p)
-      if (int rc = dev_alloc(c, c->xrecv, (size_t)c->world * c->C * kCamRec * 4)) return rc;
-    c->recv_dev = c->xrecv.p;
-    c->send_dev = static_cast<float*>(c->xrecv.p) + (size_t)c->rank * c->C * kCamRec;
+    if (!c->xch.xrecv.p)
+      if (int rc = dev_alloc(c, c->xch.xrecv, (size_t)c->world * c->C * kCamRec * 4)) return rc;
+    c->xch.recv_dev = c->xch.xrecv.p;
+    c->xch.send_dev = static_cast<float*>(c->xch.xrecv.p) + (size_t)c->rank * c->C * kCamRec;
   }
-  c->metric_last = 0; c->metric_riding = c->metric_per_pass = 0; c->metric_reason = "";
+  c->xch.metric_last = 0; c->xch.metric_riding = c->xch.metric_per_pass = 0; c->xch.metric_reason = "";
   if (int rc = ensure_comm_stream(c)) return rc;
-  if (!c->ev_fork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-  if (!c->ev_join) HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-  c->comm_warm = 0;
+  if (!c->xch.ev_fork)
+    if (int rc = event_create(c, &c->xch.ev_fork, hipEventDisableTiming)) return rc;
+  if (!c->xch.ev_join)
+    if (int rc = event_create(c, &c->xch.ev_join, hipEventDisableTiming)) return rc;
+  c->xch.warm = 0;
   return GBP_OK;
 }
 
@@ -360,18 +362,18 @@ struct Measurement {
 // alone took longer on some rank gets kMeasureCappedReps timed rounds (agreed through the gather: every rank runs the same rounds).
 // row[r] = rank r's figure.
 int measure_attached(gbp_ctx* c, bool two_streams, double cap_us, Measurement* m, double* row) {
-  c->comm_single_stream = !two_streams;
+  c->xch.single_stream = !two_streams;
   if (int rc = ensure_comm_stream(c)) return rc;
   double warm = 0, timed = 0, all[2 * gbp::kCommMaxWorld];
   if (int rc = time_rounds(c, two_streams, kMeasureWarmup, &warm)) return rc;
-  COMMCHK(c, c->comm->all_gather_host(&warm, all, 1, e_));      // (ends in a barrier: the timed rounds start together)
+  COMMCHK(c, c->xch.comm->all_gather_host(&warm, all, 1, e_));      // (ends in a barrier: the timed rounds start together)
   double warm_max = 0;
   for (int r = 0; r < c->world; ++r) warm_max = std::max(warm_max, all[r]);
   m->reps = cap_us > 0 && warm_max > cap_us ? kMeasureCappedReps : kMeasureReps;
   if (int rc = time_rounds(c, two_streams, m->reps, &timed)) return rc;
   m->mine = timed / m->reps;
   const double out[2] = {m->mine, warm + timed};
-  COMMCHK(c, c->comm->all_gather_host(out, all, 2, e_));
+  COMMCHK(c, c->xch.comm->all_gather_host(out, all, 2, e_));
   m->total_max = 0;
   for (int r = 0; r < c->world; ++r) { row[r] = all[2 * r]; m->total_max = std::max(m->total_max, all[2 * r + 1]); }
   return GBP_OK;
@@ -380,9 +382,9 @@ int measure_attached(gbp_ctx* c, bool two_streams, double cap_us, Measurement* m
 // the ctx without its communicator, which the caller keeps or (destroy) drops the way gbp_destroy does, behind a barrier of the group
 int comm_detach(gbp_ctx* c, bool destroy) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->comm_stream) HIPCHK(c, hipStreamSynchronize(c->comm_stream));
-  gbp::Comm* k = c->comm;
-  c->comm = nullptr; c->send_dev = nullptr; c->recv_dev = nullptr;
+  if (c->xch.stream) HIPCHK(c, hipStreamSynchronize(c->xch.stream));
+  gbp::Comm* k = c->xch.comm;
+  c->xch.comm = nullptr; c->xch.send_dev = nullptr; c->xch.recv_dev = nullptr;
   if (!destroy || !k) return GBP_OK;
   std::string e;
   const int rc = k->barrier(e);      // nobody is inside an exchange of it any more
@@ -412,8 +414,8 @@ int comm_init_measured_body(gbp_ctx* c, void* region, gbp::Comm** kept) {
   };
   if (c->world == 1) {      // nothing to measure
     if (int rc = attach_new(base.transport)) return rc;
-    c->comm_selected_by = "rule";
-    c->comm_measured = "[]";
+    c->xch.selected_by = "rule";
+    c->xch.measured = "[]";
     return GBP_OK;
   }
   // the order: the baseline; what else runs on its communicator (RCCL's other schedule); the other transports, each made once; the baseline again
@@ -428,10 +430,10 @@ int comm_init_measured_body(gbp_ctx* c, void* region, gbp::Comm** kept) {
   for (size_t step = 0; step < order.size(); ++step) {
     const gbp::Candidate& k = cl.c[order[step]];
     const int row = step + 1 == order.size() ? cl.n : order[step];
-    if (!c->comm || c->comm->kind() != k.transport) {
-      if (c->comm) {      // the baseline's communicator waits for its second measurement, every other one has had its only
-        const bool keep = c->comm->kind() == base.transport;
-        if (keep) *kept = c->comm;
+    if (!c->xch.comm || c->xch.comm->kind() != k.transport) {
+      if (c->xch.comm) {      // the baseline's communicator waits for its second measurement, every other one has had its only
+        const bool keep = c->xch.comm->kind() == base.transport;
+        if (keep) *kept = c->xch.comm;
         if (int rc = comm_detach(c, !keep)) return rc;
       }
       if (k.transport == base.transport && *kept) {
@@ -447,22 +449,22 @@ int comm_init_measured_body(gbp_ctx* c, void* region, gbp::Comm** kept) {
   }
   const gbp::Choice ch = gbp::choose_transport(cl, table.data(), c->world);
   const gbp::Candidate& win = cl.c[ch.winner];
-  if (c->comm->kind() != win.transport) {
+  if (c->xch.comm->kind() != win.transport) {
     if (int rc = comm_detach(c, true)) return rc;
     if (int rc = attach_new(win.transport)) return rc;
   }
-  c->comm_single_stream = !win.two_streams;
+  c->xch.single_stream = !win.two_streams;
   if (int rc = ensure_comm_stream(c)) return rc;
-  if (c->comm_single_stream && c->comm_stream) {      // the second queue was only measured: it would slow every dispatch of the first
-    HIPCHK(c, hipStreamSynchronize(c->comm_stream));
-    HIPCHK(c, hipStreamDestroy(c->comm_stream));
-    c->comm_stream = nullptr;
+  if (c->xch.single_stream && c->xch.stream) {      // the second queue was only measured: it would slow every dispatch of the first
+    HIPCHK(c, hipStreamSynchronize(c->xch.stream));
+    HIPCHK(c, hipStreamDestroy(c->xch.stream));
+    c->xch.stream = nullptr;
   }
   if (c->uploaded) {      // the winner's exchange buffers hold the partials the ctx's camera tables were made from, as after an iteration
     double us = 0;
     if (int rc = time_rounds(c, win.two_streams, 1, &us)) return rc;
   }
-  c->comm_warm = 0;
+  c->xch.warm = 0;
   // the record
   const int base_row = ch.base_first <= ch.base_last ? cl.baseline : cl.n;
   std::string js = "[";
@@ -486,8 +488,8 @@ int comm_init_measured_body(gbp_ctx* c, void* region, gbp::Comm** kept) {
     if (i == ch.winner) js += ", \"chosen\": true";
     js += "}";
   }
-  c->comm_measured = js + "]";
-  c->comm_selected_by = "measurement";
+  c->xch.measured = js + "]";
+  c->xch.selected_by = "measurement";
   std::snprintf(buf, sizeof(buf), "info: gbp_comm_init: measured %d rounds each, chose %s at %.1f us per exchange", kMeasureReps, candidate_name(win).c_str(), ch.figure[ch.winner]);
   std::string info = buf;
   if (ch.runner_up >= 0) {
@@ -504,7 +506,7 @@ int comm_init_measured(gbp_ctx* c, void* region) {
   gbp::Comm* kept = nullptr;
   const int rc = comm_init_measured_body(c, region, &kept);
   if (rc != GBP_OK) gbp::comm_region_abort(region);      // the other ranks leave their barriers with an error instead of waiting
-  if (kept && kept != c->comm) delete kept;
+  if (kept && kept != c->xch.comm) delete kept;
   return rc;
 }
 
@@ -512,12 +514,12 @@ int comm_init_measured(gbp_ctx* c, void* region) {
 
 GBP_EXPORT(gbp_comm_init, c, (gbp_ctx* c, void* region, int transport), (c, region, transport)) {
   if (!c || !region) return GBP_ERR_INVALID;
-  if (c->comm) return fail(c, GBP_ERR_STATE, "gbp_comm_init: the ctx already has a communicator");
+  if (c->xch.comm) return fail(c, GBP_ERR_STATE, "gbp_comm_init: the ctx already has a communicator");
   if (transport == (int)gbp::Transport::Measured) return comm_init_measured(c, region);
   std::string err;
   gbp::Comm* comm = gbp::comm_create_from_region(region, c->rank, c->world, static_cast<gbp::Transport>(transport), c->C, err);
   if (!comm) return fail(c, GBP_ERR_COMM, "gbp_comm_init: " + err);
-  c->comm_selected_by = transport == (int)gbp::Transport::Auto ? "rule" : "caller";
+  c->xch.selected_by = transport == (int)gbp::Transport::Auto ? "rule" : "caller";
   return comm_attach(c, comm);
 }
 
@@ -530,7 +532,7 @@ GBP_EXPORT(gbp_comm_unique_id, nullptr, (void* id128), (id128)) {
 
 GBP_EXPORT(gbp_comm_init_rccl, c, (gbp_ctx* c, const void* id128), (c, id128)) {
   if (!c || !id128) return GBP_ERR_INVALID;
-  if (c->comm) return fail(c, GBP_ERR_STATE, "gbp_comm_init_rccl: the ctx already has a communicator");
+  if (c->xch.comm) return fail(c, GBP_ERR_STATE, "gbp_comm_init_rccl: the ctx already has a communicator");
   std::string err;
   gbp::Comm* comm = gbp::comm_create_rccl(id128, c->rank, c->world, err);
   if (!comm) return fail(c, GBP_ERR_COMM, "gbp_comm_init_rccl: " + err);
@@ -544,20 +546,20 @@ GBP_EXPORT(gbp_comm_describe, c, (gbp_ctx* c, char* buf, size_t cap), (c, buf, c
   char bus[64] = {0};
   (void)hipGetDevice(&dev);
   (void)hipDeviceGetPCIBusId(bus, sizeof(bus), dev);
-  const std::string lib = c->comm ? c->comm->library_path() : "";
+  const std::string lib = c->xch.comm ? c->xch.comm->library_path() : "";
   char head[1024];
   std::snprintf(head, sizeof(head), "{\"rank\": %d, \"world\": %d, \"device\": %d, \"pci_bus_id\": \"%s\", \"transport\": \"%s\", \"library\": \"%s\", "
                                     "\"library_version\": %d, \"two_streams\": %s, \"selected_by\": \"%s\"",
-                c->rank, c->world, dev, bus, c->comm ? c->comm->name() : "none", lib.c_str(), c->comm ? c->comm->library_version() : 0,
-                (c->comm && !c->comm_single_stream) ? "true" : "false", c->comm_selected_by);
+                c->rank, c->world, dev, bus, c->xch.comm ? c->xch.comm->name() : "none", lib.c_str(), c->xch.comm ? c->xch.comm->library_version() : 0,
+                (c->xch.comm && !c->xch.single_stream) ? "true" : "false", c->xch.selected_by);
   // transport 5: what gbp_comm_init timed, one entry per candidate (an empty list with one rank: nothing to measure)
   // how the loops with the metric (gbp_ba_loop, gbp_iterate_eval_each) have run on this ctx since gbp_comm_init: the path of the last burst
   char metric[512];
-  const bool rides = c->metric_last == 1;
+  const bool rides = c->xch.metric_last == 1;
   std::snprintf(metric, sizeof(metric), ", \"metric\": {\"path\": \"%s\", \"passes_riding\": %llu, \"passes_per_pass\": %llu, \"reason\": \"%s\"}",
-                c->metric_last == 0 ? "none" : rides ? "riding" : "per-pass", (unsigned long long)c->metric_riding,
-                (unsigned long long)c->metric_per_pass, rides ? "" : c->metric_reason);
-  const std::string text = std::string(head) + (c->comm_measured.empty() ? "" : ", \"measured\": " + c->comm_measured) + metric + "}";
+                c->xch.metric_last == 0 ? "none" : rides ? "riding" : "per-pass", (unsigned long long)c->xch.metric_riding,
+                (unsigned long long)c->xch.metric_per_pass, rides ? "" : c->xch.metric_reason);
+  const std::string text = std::string(head) + (c->xch.measured.empty() ? "" : ", \"measured\": " + c->xch.measured) + metric + "}";
   std::snprintf(buf, cap, "%s", text.c_str());
   if (text.size() + 1 > cap) return fail(c, GBP_ERR_INVALID, "gbp_comm_describe: the text needs " + std::to_string(text.size() + 1) + " bytes");
   return GBP_OK;
@@ -568,25 +570,25 @@ GBP_EXPORT(gbp_comm_describe, c, (gbp_ctx* c, char* buf, size_t cap), (c, buf, c
 // identical; which is faster depends on what the all-gather costs against ~10 us of second-queue overhead — measure
 // (bench.py does, 20 iterations each) instead of guessing.
 GBP_EXPORT(gbp_comm_set_schedule, c, (gbp_ctx* c, int two_streams), (c, two_streams)) {
-  if (!c || !c->comm) return fail(c, GBP_ERR_STATE, "gbp_comm_set_schedule: the ctx has no communicator");
+  if (!c || !c->xch.comm) return fail(c, GBP_ERR_STATE, "gbp_comm_set_schedule: the ctx has no communicator");
   if (int rc = settle(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->comm_stream) HIPCHK(c, hipStreamSynchronize(c->comm_stream));
+  if (c->xch.stream) HIPCHK(c, hipStreamSynchronize(c->xch.stream));
   drop_graph(c);
-  c->comm_single_stream = two_streams == 0;
+  c->xch.single_stream = two_streams == 0;
   return ensure_comm_stream(c);
 }
 
 // `reps` all-gathers of the camera partial buffers back to back on the ctx's stream (collective: every rank calls it);
 // *avg_us = mean duration between two events.  The buffers keep their content (the gather of the same partials).
 GBP_EXPORT(gbp_comm_probe, c, (gbp_ctx* c, int reps, double* avg_us), (c, reps, avg_us)) {
-  if (!c || !c->comm || !avg_us || reps < 1) return fail(c, GBP_ERR_STATE, "gbp_comm_probe: needs a communicator, reps >= 1");
-  if (PeerComm* pc = peers(c->comm)) {
+  if (!c || !c->xch.comm || !avg_us || reps < 1) return fail(c, GBP_ERR_STATE, "gbp_comm_probe: needs a communicator, reps >= 1");
+  if (PeerComm* pc = peers(c->xch.comm)) {
     // p2p: this rank's slot of the next parity still holds the partials of two exchanges ago — give it the last ones, so that every
     // exchange of the probe (both parities) moves the same partials and leaves what a refresh reads unchanged
-    HIPCHK(c, hipMemcpyAsync(c->send_dev, pc->last_own_slot(), (size_t)c->C * kCamRec * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->xch.send_dev, pc->last_own_slot(), (size_t)c->C * kCamRec * 4, hipMemcpyDeviceToDevice, c->stream));
   }
-  if (!c->comm->stream_ordered()) {      // host-staged, p2p: wall clock around blocking exchanges
+  if (!c->xch.comm->stream_ordered()) {      // host-staged, p2p: wall clock around blocking exchanges
     const auto t0 = std::chrono::steady_clock::now();
     for (int i = 0; i < reps; ++i)
       if (int rc = exchange_now(c)) return rc;
@@ -594,23 +596,23 @@ GBP_EXPORT(gbp_comm_probe, c, (gbp_ctx* c, int reps, double* avg_us), (c, reps, 
     return GBP_OK;
   }
   if (int rc = exchange_now(c)) return rc;     // warm (lazy channel set-up)
-  HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+  HIPCHK(c, hipEventRecord(c->tm.reps_begin, c->stream));
   for (int i = 0; i < reps; ++i)
     if (int rc = exchange_now(c)) return rc;
-  HIPCHK(c, hipEventRecord(c->ev2, c->stream));
-  HIPCHK(c, hipEventSynchronize(c->ev2));
+  HIPCHK(c, hipEventRecord(c->tm.reps_end, c->stream));
+  HIPCHK(c, hipEventSynchronize(c->tm.reps_end));
   float ms = 0;
-  HIPCHK(c, hipEventElapsedTime(&ms, c->ev1, c->ev2));
+  HIPCHK(c, hipEventElapsedTime(&ms, c->tm.reps_begin, c->tm.reps_end));
   *avg_us = 1e3 * ms / reps;
   return GBP_OK;
 }
 
-GBP_EXPORT_T(const char*, "none", gbp_comm_transport, (const gbp_ctx* c), (c)) { return (c && c->comm) ? c->comm->name() : "none"; }
+GBP_EXPORT_T(const char*, "none", gbp_comm_transport, (const gbp_ctx* c), (c)) { return (c && c->xch.comm) ? c->xch.comm->name() : "none"; }
 
 GBP_EXPORT(gbp_comm_barrier, c, (gbp_ctx* c), (c)) {
-  if (!c || !c->comm) return GBP_ERR_STATE;
+  if (!c || !c->xch.comm) return GBP_ERR_STATE;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  COMMCHK(c, c->comm->barrier(e_));
+  COMMCHK(c, c->xch.comm->barrier(e_));
   return GBP_OK;
 }
 
@@ -618,11 +620,11 @@ GBP_EXPORT(gbp_comm_barrier, c, (gbp_ctx* c), (c)) {
 GBP_EXPORT(gbp_eval_global, c, (gbp_ctx* c, gbp_eval_out* o), (c, o)) {
   if (!c || !o) return GBP_ERR_INVALID;
   const int rc = eval(c, o);
-  if (rc != GBP_OK || !c->comm) return rc;
+  if (rc != GBP_OK || !c->xch.comm) return rc;
   const double mine[7] = {o->sum_norm, o->sum_half_sq, (double)o->n_active, (double)o->n_relin, (double)o->n_robust,
                           (double)o->n_nonfinite, (double)o->n_nonpd};
   double all[7 * gbp::kCommMaxWorld];
-  COMMCHK(c, c->comm->all_gather_host(mine, all, 7, e_));
+  COMMCHK(c, c->xch.comm->all_gather_host(mine, all, 7, e_));
   double acc[7] = {0, 0, 0, 0, 0, 0, 0};
   for (int r = 0; r < c->world; ++r)
     for (int i = 0; i < 7; ++i) acc[i] = acc[i] + all[r * 7 + i];

@@ -46,28 +46,63 @@ int dev_alloc(gbp_ctx* c, DevBuf& b, size_t bytes) {
   return GBP_OK;
 }
 
+static void mapped_free(MappedBuf& b) { if (b.host) (void)hipHostFree(b.host); b = MappedBuf{}; }
+int mapped_alloc(gbp_ctx* c, MappedBuf& b, size_t bytes) {
+  if (b.host && b.bytes >= bytes) return GBP_OK;
+  mapped_free(b);
+  if (std::find(c->mapped.begin(), c->mapped.end(), &b) == c->mapped.end()) c->mapped.push_back(&b);
+  HIPCHK(c, hipHostMalloc(&b.host, bytes, hipHostMallocMapped));
+  HIPCHK(c, hipHostGetDevicePointer(&b.dev, b.host, 0));
+  b.bytes = bytes;
+  return GBP_OK;
+}
+
+static void event_destroy(hipEvent_t& e) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+int event_create(gbp_ctx* c, hipEvent_t* e, unsigned flags) {
+  HIPCHK(c, hipEventCreateWithFlags(e, flags));
+  c->events.push_back(e);
+  return GBP_OK;
+}
+int event_pair(gbp_ctx* c, hipEvent_t* a, hipEvent_t* b, unsigned flags) {
+  HIPCHK(c, hipEventCreateWithFlags(a, flags));
+  if (hipError_t e_ = hipEventCreateWithFlags(b, flags); e_ != hipSuccess) {
+    event_destroy(*a);
+    return fail(c, GBP_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e_));
+  }
+  return GBP_OK;
+}
+int event_pair_owned(gbp_ctx* c, hipEvent_t* a, hipEvent_t* b, unsigned flags) {
+  if (int rc = event_pair(c, a, b, flags)) return rc;
+  c->events.push_back(a);
+  c->events.push_back(b);
+  return GBP_OK;
+}
+// gbp_destroy: the named events, then the pairs in the ring, the pool and the two profiling lists
+static void destroy_events(gbp_ctx* c) {
+  for (hipEvent_t* e : c->events) event_destroy(*e);
+  for (auto* v : {&c->tm.spans, &c->tm.span_pool, &c->tm.pending_sweep_ev, &c->tm.pending_exch_ev})
+    for (gbp_ctx::Span& sp : *v) { event_destroy(sp.a); event_destroy(sp.b); }
+}
+
 // timing brackets of gbp_iterate calls: read the finished ones without blocking anything that is still queued
 int resolve_spans(gbp_ctx* c, bool wait) {
   size_t done = 0;
-  for (; done < c->spans.size(); ++done) {
-    const gbp_ctx::Span sp = c->spans[done];
+  for (; done < c->tm.spans.size(); ++done) {
+    const gbp_ctx::Span sp = c->tm.spans[done];
     if (wait) { if (hipEventSynchronize(sp.b) != hipSuccess) break; }
     else if (hipEventQuery(sp.b) != hipSuccess) break;
     float ms = 0;
-    if (hipEventElapsedTime(&ms, sp.a, sp.b) == hipSuccess) c->total_ms += ms;
-    c->span_pool.push_back(sp);
+    if (hipEventElapsedTime(&ms, sp.a, sp.b) == hipSuccess) c->tm.total_ms += ms;
+    c->tm.span_pool.push_back(sp);
   }
-  c->spans.erase(c->spans.begin(), c->spans.begin() + (long)done);
+  c->tm.spans.erase(c->tm.spans.begin(), c->tm.spans.begin() + (long)done);
   return GBP_OK;
 }
 int TimedSpan::begin() {
   gbp_ctx* c = c_;
-  if (c->spans.size() >= 64) resolve_spans(c, true);
-  if (!c->span_pool.empty()) { sp_ = c->span_pool.back(); c->span_pool.pop_back(); }
-  else {
-    HIPCHK(c, hipEventCreate(&sp_.a));
-    if (hipError_t e_ = hipEventCreate(&sp_.b); e_ != hipSuccess) { (void)hipEventDestroy(sp_.a); return fail(c, GBP_ERR_HIP, "hipEventCreate"); }
-  }
+  if (c->tm.spans.size() >= 64) resolve_spans(c, true);
+  if (!c->tm.span_pool.empty()) { sp_ = c->tm.span_pool.back(); c->tm.span_pool.pop_back(); }
+  else if (int rc = event_pair(c, &sp_.a, &sp_.b)) return rc;
   open_ = true;
   HIPCHK(c, hipEventRecord(sp_.a, c->stream));
   return GBP_OK;
@@ -75,13 +110,13 @@ int TimedSpan::begin() {
 int TimedSpan::end() {
   if (!open_) return GBP_OK;
   HIPCHK(c_, hipEventRecord(sp_.b, c_->stream));
-  c_->spans.push_back(sp_);
+  c_->tm.spans.push_back(sp_);
   open_ = false;
   return GBP_OK;
 }
 int TimedSpan::commit(uint64_t n) {
   if (int rc = end()) return rc;
-  c_->timed_iters += n;
+  c_->tm.timed_iters += n;
   c_->beliefs_valid = true;
   return GBP_OK;
 }
@@ -91,12 +126,10 @@ int H2D::begin(gbp_ctx* ctx, size_t total_bytes, int pieces) {
   const size_t need = total_bytes + 16 * (size_t)pieces;
   direct = need > kStageMax;
   if (direct) return GBP_OK;
-  if (c->stage_cap < need) {
-    if (c->stage_host) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipHostFree(c->stage_host); c->stage_host = nullptr; c->stage_cap = 0; }
-    const size_t cap = std::max<size_t>(std::max(need, c->stage_hint <= kStageMax ? c->stage_hint : 0), (size_t)1 << 20);
-    HIPCHK(c, hipHostMalloc(&c->stage_host, cap, hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer(&c->stage_dev, c->stage_host, 0));
-    c->stage_cap = cap;
+  if (c->stage.buf.bytes < need) {
+    if (c->stage.buf.host) HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t cap = std::max<size_t>(std::max(need, c->stage.hint <= kStageMax ? c->stage.hint : 0), (size_t)1 << 20);
+    if (int rc = mapped_alloc(c, c->stage.buf, cap)) return rc;
   }
   return GBP_OK;
 }
@@ -110,24 +143,31 @@ int H2D::flush() {
 int H2D::put(void* dst_dev, const void* src, size_t bytes) {
   if (bytes == 0) return GBP_OK;
   if (direct) { HIPCHK(c, hipMemcpy(dst_dev, src, bytes, hipMemcpyHostToDevice)); return GBP_OK; }
-  const size_t padded = (bytes + 15) / 16 * 16;
-  if (used + padded > c->stage_cap) return fail(c, GBP_ERR_INVALID, "H2D: staging buffer too small (internal)");
-  char* h = static_cast<char*>(c->stage_host) + used;
+  size_t off = 0;
+  if (int rc = queue(bytes, dst_dev, nullptr, &off)) return rc;
+  char* h = static_cast<char*>(c->stage.buf.host) + off;
   std::memcpy(h, src, bytes);
-  if (padded > bytes) std::memset(h + bytes, 0, padded - bytes);
+  std::memset(h + bytes, 0, used - off - bytes);      // the pad of the last float4
+  return GBP_OK;
+}
+int H2D::queue(size_t bytes, void* dst_dev, const void* src_dev, size_t* off) {
+  const size_t padded = (bytes + 15) / 16 * 16;
+  if (used + padded > c->stage.buf.bytes) return fail(c, GBP_ERR_INVALID, "H2D: staging buffer too small (internal)");
   if (segs.n == kMaxCopySegs)
     if (int rc = flush()) return rc;
-  segs.src[segs.n] = static_cast<char*>(c->stage_dev) + used; segs.dst[segs.n] = dst_dev; segs.n4[segs.n] = padded / 16;
+  char* here = static_cast<char*>(c->stage.buf.dev) + used;
+  segs.src[segs.n] = dst_dev ? here : src_dev; segs.dst[segs.n] = dst_dev ? dst_dev : here; segs.n4[segs.n] = padded / 16;
   segs.n += 1;
+  *off = used;
   used += padded;
   return GBP_OK;
 }
 // bytes into the staging buffer for a kernel of the caller's to read (no copy segment): *dev = their device address, valid until end()
 int H2D::stage(const void* src, size_t bytes, const void** dev) {
   const size_t padded = (bytes + 15) / 16 * 16;
-  if (direct || used + padded > c->stage_cap) return fail(c, GBP_ERR_INVALID, "H2D: staging buffer too small (internal)");
-  std::memcpy(static_cast<char*>(c->stage_host) + used, src, bytes);
-  *dev = static_cast<const char*>(c->stage_dev) + used;
+  if (direct || used + padded > c->stage.buf.bytes) return fail(c, GBP_ERR_INVALID, "H2D: staging buffer too small (internal)");
+  std::memcpy(static_cast<char*>(c->stage.buf.host) + used, src, bytes);
+  *dev = static_cast<const char*>(c->stage.buf.dev) + used;
   used += padded;
   return GBP_OK;
 }
@@ -144,26 +184,17 @@ int D2H::begin(gbp_ctx* ctx, size_t total_bytes, int pieces) {
   return GBP_OK;
 }
 int D2H::get(void* dst_host, const void* src_dev, size_t bytes) {
-  gbp_ctx* c = up.c;
   if (bytes == 0) return GBP_OK;
-  if (up.direct) { HIPCHK(c, hipMemcpy(dst_host, src_dev, bytes, hipMemcpyDeviceToHost)); return GBP_OK; }
-  const size_t padded = (bytes + 15) / 16 * 16;
-  if (up.used + padded > c->stage_cap) return fail(c, GBP_ERR_INVALID, "D2H: staging buffer too small (internal)");
-  if (up.segs.n == kMaxCopySegs) {
-    launch_copy_segments(up.segs, nullptr, c->stream);
-    HIPCHK(c, hipGetLastError());
-    up.segs.n = 0;
-  }
-  up.segs.src[up.segs.n] = src_dev; up.segs.dst[up.segs.n] = static_cast<char*>(c->stage_dev) + up.used; up.segs.n4[up.segs.n] = padded / 16;
-  up.segs.n += 1;
-  pending.push_back(Out{dst_host, up.used, bytes});
-  up.used += padded;
+  if (up.direct) { HIPCHK(up.c, hipMemcpy(dst_host, src_dev, bytes, hipMemcpyDeviceToHost)); return GBP_OK; }
+  size_t off = 0;
+  if (int rc = up.queue(bytes, nullptr, src_dev, &off)) return rc;
+  pending.push_back(Out{dst_host, off, bytes});
   return GBP_OK;
 }
 int D2H::end() {
   if (int rc = up.end()) return rc;      // launches what is queued, synchronises the stream
   if (!up.direct)
-    for (const Out& o : pending) std::memcpy(o.dst, static_cast<const char*>(up.c->stage_host) + o.off, o.bytes);
+    for (const Out& o : pending) std::memcpy(o.dst, static_cast<const char*>(up.c->stage.buf.host) + o.off, o.bytes);
   pending.clear();
   return GBP_OK;
 }
@@ -189,35 +220,21 @@ int struct_kind(gbp_ctx* c, const char* fn, const void* const* members, const ch
   return GBP_OK;
 }
 
-int event_pair(gbp_ctx* c, hipEvent_t* a, hipEvent_t* b) {
-  HIPCHK(c, hipEventCreate(a));
-  if (hipError_t e_ = hipEventCreate(b); e_ != hipSuccess) {
-    (void)hipEventDestroy(*a);
-    *a = nullptr;
-    return fail(c, GBP_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e_));
-  }
-  return GBP_OK;
-}
-
 // split-phase profiling: read (and free) the sweep brackets recorded by gbp_iterate_begin
 void drain_sweep_events(gbp_ctx* c) {
-  for (auto& pr : c->pending_sweep_ev) {
-    float ms = 0;
-    if (hipEventSynchronize(pr.second) == hipSuccess && hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) {
-      c->sweep_ms += ms;
-      c->timed_iters += 1;
+  for (auto* v : {&c->tm.pending_sweep_ev, &c->tm.pending_exch_ev}) {
+    const bool sweep = v == &c->tm.pending_sweep_ev;      // a sweep bracket counts one timed iteration, an exchange bracket none
+    for (gbp_ctx::Span& sp : *v) {
+      float ms = 0;
+      if (hipEventSynchronize(sp.b) == hipSuccess && hipEventElapsedTime(&ms, sp.a, sp.b) == hipSuccess) {
+        (sweep ? c->tm.sweep_ms : c->tm.exchange_ms) += ms;
+        if (sweep) c->tm.timed_iters += 1;
+      }
+      event_destroy(sp.a);
+      event_destroy(sp.b);
     }
-    (void)hipEventDestroy(pr.first);
-    (void)hipEventDestroy(pr.second);
+    v->clear();
   }
-  c->pending_sweep_ev.clear();
-  for (auto& pr : c->pending_exch_ev) {
-    float ms = 0;
-    if (hipEventSynchronize(pr.second) == hipSuccess && hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) c->exchange_ms += ms;
-    (void)hipEventDestroy(pr.first);
-    (void)hipEventDestroy(pr.second);
-  }
-  c->pending_exch_ev.clear();
 }
 
 }  // namespace api
@@ -273,31 +290,15 @@ GBP_EXPORT_T(const char*, "", gbp_last_error, (const gbp_ctx* ctx), (ctx)) { ret
 
 GBP_EXPORT_VOID(gbp_destroy, (gbp_ctx* c), (c)) {
   if (!c) return;
+  persist_forget(c);      // (synchronises the ctx's stream where launches of the persistent kernel may be in flight)
+  if (c->xch.comm) { (void)hipStreamSynchronize(c->stream); if (c->xch.stream) (void)hipStreamSynchronize(c->xch.stream); delete c->xch.comm; c->xch.comm = nullptr; }
   drop_graph(c);
-  persist_forget(c);
-  if (c->comm) { (void)hipStreamSynchronize(c->stream); if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream); delete c->comm; c->comm = nullptr; }
-  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-  if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-  if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
-  for (auto* v : {&c->pending_sweep_ev, &c->pending_exch_ev})
-    for (auto& pr : *v) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
+  destroy_events(c);
   for (DevBuf* b : c->all) if (b->p) (void)hipFree(b->p);
-  for (auto& v : {&c->spans, &c->span_pool})
-    for (auto& sp : *v) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
-  if (c->stage_host) (void)hipHostFree(c->stage_host);
-  if (c->eval_host) (void)hipHostFree(c->eval_host);
-  if (c->ev_host) (void)hipHostFree(c->ev_host);
-  if (c->series_host) (void)hipHostFree(c->series_host);
-  if (c->pstatus_host) (void)hipHostFree(c->pstatus_host);
-  for (hipEvent_t e : c->eval_ev) if (e) (void)hipEventDestroy(e);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  if (c->ev2) (void)hipEventDestroy(c->ev2);
-  if (c->ev3) (void)hipEventDestroy(c->ev3);
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+  for (MappedBuf* b : c->mapped) mapped_free(*b);
+  for (hipStream_t s : {c->xch.stream, c->own_stream}) if (s) (void)hipStreamDestroy(s);
   delete c;
 }
-
 
 GBP_EXPORT(gbp_create, nullptr, (const gbp_problem* pr, const gbp_params* prm, const gbp_shard* sh, gbp_ctx** out), (pr, prm, sh, out)) {
   if (!pr || !out || !pr->cam_id || !pr->lmk_id || pr->n_cams == 0 || pr->n_lmks == 0 || pr->n_edges == 0)
@@ -332,13 +333,18 @@ GBP_EXPORT(gbp_create, nullptr, (const gbp_problem* pr, const gbp_params* prm, c
   t_phase = clk::now();
   step("hipGetDeviceCount");
   gbp_ctx* c = new gbp_ctx();
-  struct Owner { gbp_ctx* p; ~Owner() { if (p) gbp_destroy(p); } } owner{c};   // released on success only
+  // released on success only; a failing return leaves the ctx's error text as the thread's (gbp_last_error(NULL)) and destroys the ctx
+  create_error().clear();
+  struct Owner {
+    gbp_ctx* p;
+    ~Owner() { if (p) { if (create_error().empty()) create_error() = p->err; gbp_destroy(p); } }
+  } owner{c};
   c->lay = std::move(lay);
   c->C = pr->n_cams; c->L = pr->n_lmks; c->E = pr->n_edges;
   std::memcpy(c->K, pr->K, sizeof(c->K));
   if (prm) c->prm = *prm; else gbp_default_params(&c->prm);
   if (const char* gu = prm ? nullptr : std::getenv("GBP_GRAPH_UNROLL")) c->prm.graph_unroll = std::atoi(gu);   // measurements through callers that pass NO params (the CLIs); explicit params always win
-  c->sharded_graph = c->prm.graph_unroll > 0;                // a sharded iteration is captured only on explicit request
+  c->graph.sharded = c->prm.graph_unroll > 0;                // a sharded iteration is captured only on explicit request
   if (c->prm.graph_unroll == 0) c->prm.graph_unroll = 10;   // < 0: never capture, always direct launches
   c->hoist = c->prm.per_factor_mu == 0;
   c->rank = sh ? sh->rank : 0;
@@ -352,26 +358,19 @@ GBP_EXPORT(gbp_create, nullptr, (const gbp_problem* pr, const gbp_params* prm, c
   const uint32_t C = c->C;
   c->sweep_policy = g_force_sweep_policy >= 0 ? (uint32_t)g_force_sweep_policy : sweep_policy_for(c->C, c->n_tiles);
 
-
-  int rc = GBP_OK;
-  auto CK = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && rc == GBP_OK) { create_error() = std::string(what) + ": " + hipGetErrorString(e); rc = GBP_ERR_HIP; }
-  };
-  CK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking), "hipStreamCreate");
-  if (rc != GBP_OK) return rc;
+  HIPCHK(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
   c->stream = c->own_stream;
   if (hipGetDevice(&c->device) != hipSuccess) { (void)hipGetLastError(); c->device = 0; }
   step("hipStreamCreate");
   // ---- device allocations (zero-filled on the ctx's stream) ----
-  auto A = [&](DevBuf& b, size_t bytes) { if (rc == GBP_OK) rc = dev_alloc(c, b, bytes); };
   const size_t Ep = c->Ep;
   // The index arrays of the device order live in ONE allocation and go up in ONE copy (H2D, gbp_ctx.hpp)
   struct Piece { DevBuf* b; const void* src; size_t bytes; size_t off; };
-  Piece pieces[] = {{&c->row_cam, y.row_cam.data(), y.row_cam.size() * 4, 0}, {&c->lmk_idx, y.pos_lmk_loc.data(), Ep * 4, 0},
-                    {&c->d_lmk_fpos, y.lmk_fpos.data(), (size_t)c->E_loc * 4, 0}, {&c->d_lmk_ix, y.lmk_ix.data(), (size_t)c->L_loc * 64, 0},
-                    {&c->d_cam_row_ptr, y.cam_row_ptr.data(), (size_t)(C + 1) * 4, 0}, {&c->d_lmk_ptr, y.lmk_ptr.data(), (size_t)(c->L_loc + 1) * 4, 0},
-                    {&c->d_row_slot, y.row_slot.data(), y.row_slot.size() * 4, 0}, {&c->dK, c->K, 9 * 4, 0},
-                    {&c->tile_perm, y.tile_perm.data(), y.tile_perm.size() * 4, 0}, {&c->seg_live, nullptr, 0, 0}};
+  Piece pieces[] = {{&c->arr.row_cam, y.row_cam.data(), y.row_cam.size() * 4, 0}, {&c->arr.lmk_idx, y.pos_lmk_loc.data(), Ep * 4, 0},
+                    {&c->arr.d_lmk_fpos, y.lmk_fpos.data(), (size_t)c->E_loc * 4, 0}, {&c->arr.d_lmk_ix, y.lmk_ix.data(), (size_t)c->L_loc * 64, 0},
+                    {&c->arr.d_cam_row_ptr, y.cam_row_ptr.data(), (size_t)(C + 1) * 4, 0}, {&c->arr.d_lmk_ptr, y.lmk_ptr.data(), (size_t)(c->L_loc + 1) * 4, 0},
+                    {&c->arr.d_row_slot, y.row_slot.data(), y.row_slot.size() * 4, 0}, {&c->arr.dK, c->K, 9 * 4, 0},
+                    {&c->arr.tile_perm, y.tile_perm.data(), y.tile_perm.size() * 4, 0}, {&c->arr.seg_live, nullptr, 0, 0}};
   // Which segments (four positions) of a tile hold a factor at all?  A camera is padded to whole rows of 16: the tail of its
   // last row is empty — on a graph of many small cameras (BASELINE config 5: ~156 factors per camera and rank) the all-pad segments
   // are 3.7 % of all positions, which the sweep then neither streams in nor out (k_sweep<..., SEG>).  Used where it is worth a kernel
@@ -389,25 +388,26 @@ GBP_EXPORT(gbp_create, nullptr, (const gbp_problem* pr, const gbp_params* prm, c
   if (use_seg) { pieces[9].src = seg_live.data(); pieces[9].bytes = seg_live.size() * 4; }
   size_t idx_bytes = 0;
   for (Piece& pc : pieces) { pc.off = idx_bytes; idx_bytes += (std::max<size_t>(pc.bytes, 256) + 255) / 256 * 256; }      // (>= 256 B each: pad lanes of an empty shard read index 0)
-  A(c->idx_arena, idx_bytes);
+  if (int rc = dev_alloc(c, c->arr.idx_arena, idx_bytes)) return rc;
   step("first hipMalloc + fill");
-  for (Piece& pc : pieces) { pc.b->p = rc == GBP_OK ? static_cast<char*>(c->idx_arena.p) + pc.off : nullptr; pc.b->bytes = pc.bytes; }      // views: freed with the arena
-  A(c->fac, Ep * kFacG * 16); A(c->cmsg, Ep * kCmsgG * 16);
-  A(c->mu, c->hoist ? 0 : Ep * kMuG * 16);   // literal mu/oldmu tensor: only with per_factor_mu
-  A(c->lmsg, Ep * kLmsgG * 16); A(c->fst_packed, Ep * 4); A(c->fst_damp, Ep * 4); A(c->fst_var, Ep * 4);
-  A(c->camb, (size_t)C * kCamRec * 4); A(c->camp, (size_t)C * kCamRec * 4); A(c->local, (size_t)C * kCamRec * 4);
-  A(c->lmkb, (size_t)c->L_loc * 64); A(c->lmkp, (size_t)c->L_loc * 64);
-  A(c->rowp, (Ep / kRow) * kCamRec * 4);
-  A(c->cwf, (size_t)C * 4); A(c->lwf, (size_t)c->L_loc * 4); A(c->cscale, (size_t)C * 4); A(c->lscale, (size_t)c->L_loc * 4);
-  A(c->cam_mu, (size_t)C * 6 * 4 * 2); A(c->lmk_mu, (size_t)c->L_loc * 3 * 4 * 2);   // metric means; k_persist alternates between the two halves
-  A(c->evalp, sizeof(DeviceEval) * 16); A(c->health, 32);
-  A(c->hmu_c, (size_t)C * 4 * 16); A(c->hmu_l, (size_t)c->L_loc * 2 * 16); A(c->clin, (size_t)C * 5 * 16);
-  A(c->st_a, Ep * 4); A(c->st_b, Ep * 4);
-  if (rc != GBP_OK) { create_error() = c->err; return rc; }
+  for (Piece& pc : pieces) { pc.b->p = static_cast<char*>(c->arr.idx_arena.p) + pc.off; pc.b->bytes = pc.bytes; }      // views: freed with the arena
+  const std::pair<DevBuf*, size_t> arrays[] = {
+      {&c->arr.fac, Ep * kFacG * 16}, {&c->arr.cmsg, Ep * kCmsgG * 16},
+      {&c->arr.mu, c->hoist ? 0 : Ep * kMuG * 16},   // literal mu/oldmu tensor: only with per_factor_mu
+      {&c->arr.lmsg, Ep * kLmsgG * 16}, {&c->arr.fst_packed, Ep * 4}, {&c->arr.fst_damp, Ep * 4}, {&c->arr.fst_var, Ep * 4},
+      {&c->arr.camb, (size_t)C * kCamRec * 4}, {&c->arr.camp, (size_t)C * kCamRec * 4}, {&c->arr.local, (size_t)C * kCamRec * 4},
+      {&c->arr.lmkb, (size_t)c->L_loc * 64}, {&c->arr.lmkp, (size_t)c->L_loc * 64},
+      {&c->arr.rowp, (Ep / kRow) * kCamRec * 4},
+      {&c->arr.cwf, (size_t)C * 4}, {&c->arr.lwf, (size_t)c->L_loc * 4}, {&c->arr.cscale, (size_t)C * 4}, {&c->arr.lscale, (size_t)c->L_loc * 4},
+      {&c->arr.cam_mu, (size_t)C * 6 * 4 * 2}, {&c->arr.lmk_mu, (size_t)c->L_loc * 3 * 4 * 2},   // metric means; k_persist alternates between the two halves
+      {&c->arr.health, 32},
+      {&c->arr.hmu_c, (size_t)C * 4 * 16}, {&c->arr.hmu_l, (size_t)c->L_loc * 2 * 16}, {&c->arr.clin, (size_t)C * 5 * 16},
+      {&c->arr.st_a, Ep * 4}, {&c->arr.st_b, Ep * 4}};
+  for (const auto& ar : arrays)
+    if (int rc = dev_alloc(c, *ar.first, ar.second)) return rc;
   step("the other allocations");
-  CK(hipEventCreate(&c->ev0), "hipEventCreate"); CK(hipEventCreate(&c->ev1), "hipEventCreate");
-  CK(hipEventCreate(&c->ev2), "hipEventCreate"); CK(hipEventCreate(&c->ev3), "hipEventCreate");
-  CK(hipStreamSynchronize(c->stream), "hipStreamSynchronize");      // the fills have landed: blocking copies into the fresh buffers follow
+  if (int rc = event_pair_owned(c, &c->tm.reps_begin, &c->tm.reps_end, hipEventDefault)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // the fills have landed: blocking copies into the fresh buffers follow
   const double alloc_ms = ms_since(t_phase);
   t_phase = clk::now();
   step("events + stream sync");
@@ -416,31 +416,27 @@ GBP_EXPORT(gbp_create, nullptr, (const gbp_problem* pr, const gbp_params* prm, c
     for (const Piece& pc : pieces)
       if (pc.bytes) std::memcpy(stage.data() + pc.off, pc.src, pc.bytes);
     // (pinned once, large enough for the gbp_upload that follows: pinning costs ~0.5 ms per MB, a second buffer would cost that again)
-    c->stage_hint = upload_stage_bytes(c) + 16 * 9;
+    c->stage.hint = upload_stage_bytes(c) + 16 * 9;
     H2D up;
-    if (rc == GBP_OK) rc = up.begin(c, idx_bytes, 1);
-    if (rc == GBP_OK) rc = up.put(c->idx_arena.p, stage.data(), idx_bytes);
-    if (rc == GBP_OK) rc = up.end();
-    if (rc != GBP_OK) create_error() = c->err;
+    if (int rc = up.begin(c, idx_bytes, 1)) return rc;
+    if (int rc = up.put(c->arr.idx_arena.p, stage.data(), idx_bytes)) return rc;
+    if (int rc = up.end()) return rc;
   }
   step("the copy of the device order");
   // the XCD-aware execution order of the sweep: wave slot -> tile (gbp_layout.cpp); read once per wave with a scalar load
-  c->use_tile_perm = rc == GBP_OK && !y.tile_perm.empty();
-  c->use_seg_live = rc == GBP_OK && use_seg;
-  if (rc != GBP_OK) return rc;
+  c->use_tile_perm = !y.tile_perm.empty();
+  c->use_seg_live = use_seg;
   const double upload_ms = ms_since(t_phase);
   t_phase = clk::now();
   // ---- persistent iteration kernel: only where every workgroup of the graph is resident at once (gbp_api_persist.cpp) ----
-  rc = persist_setup(c, prm, sh != nullptr);
-  if (rc != GBP_OK) { if (create_error().empty()) create_error() = c->err; return rc; }
-  CK(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
-  if (rc != GBP_OK) return rc;
+  if (int rc = persist_setup(c, prm, sh != nullptr)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   step("persistent kernel set-up");
   {
     char info[320];
     std::snprintf(info, sizeof(info), "info: gbp_create: device order %.3f ms, runtime %.3f ms, allocation %.3f ms, layout upload %.3f ms, "
                                       "persistent kernel %.3f ms (probe %.3f ms)",
-                  layout_ms, runtime_ms, alloc_ms, upload_ms, ms_since(t_phase), c->probe_ms);
+                  layout_ms, runtime_ms, alloc_ms, upload_ms, ms_since(t_phase), c->persist.probe_ms);
     c->err = c->err.empty() ? std::string(info) : c->err + " | " + info;      // (a probe that failed has left its reason in front)
   }
   owner.p = nullptr;
@@ -458,9 +454,9 @@ GBP_EXPORT(gbp_set_stream, c, (gbp_ctx* c, void* s), (c, s)) {
 
 GBP_EXPORT(gbp_set_exchange_buffers, c, (gbp_ctx* c, void* send_dev, void* recv_dev), (c, send_dev, recv_dev)) {
   if (!c) return GBP_ERR_INVALID;
-  if (peers(c->comm))
+  if (peers(c->xch.comm))
     return fail(c, GBP_ERR_STATE, "gbp_set_exchange_buffers: the ctx's p2p communicator exchanges through its own buffers");
-  c->send_dev = send_dev; c->recv_dev = recv_dev;
+  c->xch.send_dev = send_dev; c->xch.recv_dev = recv_dev;
   return GBP_OK;
 }
 
@@ -515,8 +511,8 @@ GBP_EXPORT(gbp_upload, c, (gbp_ctx* c, const gbp_state_in* in), (c, in)) {
   static_assert(sizeof(St) == 16, "k_upload_scatter reads one float4 per position");
   std::vector<St> st(Ep);
   std::vector<float> var(Ep), mu(c->hoist ? 0 : Ep * kMuG * 4, 0.f);
-  c->active_host.assign(Ep, 0);
-  c->active_host_stale = false;
+  c->arr.active_host.assign(Ep, 0);
+  c->arr.active_host_stale = false;
   const float* om = in->oldmu ? in->oldmu : in->mu;
   const unsigned T = gbp::host::host_threads(Ep, 1u << 17);      // (a gather by device position: every position is written by one thread)
   gbp::host::on_threads(T, [&](unsigned t) {
@@ -526,7 +522,7 @@ GBP_EXPORT(gbp_upload, c, (gbp_ctx* c, const gbp_state_in* in), (c, in)) {
       float v = 0.f;
       if (e != ~0u) {
         const bool on = in->active_flag[e] == 1;
-        c->active_host[p] = on;
+        c->arr.active_host[p] = on;
         const int32_t count = in->damping_count ? in->damping_count[e] : 0;
         o.damping = in->damping ? in->damping[e] : 0.f;
         o.packed = (int32_t)(((uint32_t)count << 3) | (on ? kFlagActive : 0u));
@@ -540,7 +536,7 @@ GBP_EXPORT(gbp_upload, c, (gbp_ctx* c, const gbp_state_in* in), (c, in)) {
     }
   });
   lap("gather by device position");
-  HIPCHK(c, hipMemsetAsync(c->fac.p, 0, c->fac.bytes, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->arr.fac.p, 0, c->arr.fac.bytes, c->stream));
   lap("FAC fill queued");
   H2D up;
   if (int rc = up.begin(c, upload_stage_bytes(c), 9)) return rc;
@@ -565,36 +561,36 @@ GBP_EXPORT(gbp_upload, c, (gbp_ctx* c, const gbp_state_in* in), (c, in)) {
       if (e2 != hipSuccess) { (void)hipFree(tmp.p); HIPCHK(c, e2); }
       st_dev = static_cast<const float4*>(tmp.p); var_dev = reinterpret_cast<const float*>(static_cast<char*>(tmp.p) + Ep * 16);
     }
-    launch_upload_scatter(P<float4>(c->lmsg), factor_state(c), P<float4>(c->fac), st_dev, var_dev, (uint32_t)Ep, c->stream);
+    launch_upload_scatter(P<float4>(c->arr.lmsg), factor_state(c), P<float4>(c->arr.fac), st_dev, var_dev, (uint32_t)Ep, c->stream);
     const hipError_t le = hipGetLastError();
     if (tmp.p) { (void)hipStreamSynchronize(c->stream); (void)hipFree(tmp.p); }
     HIPCHK(c, le);
   }
   lap("staging + k_upload_scatter queued");
   if (!c->hoist)
-    if (int rc = up.put(c->mu.p, mu.data(), mu.size() * 4)) return rc;
-  HIPCHK(c, hipMemsetAsync(c->cmsg.p, 0, c->cmsg.bytes, c->stream));      // every record kCmsgZero
-  c->cmsg_zero = true;
-  HIPCHK(c, hipMemsetAsync(c->rowp.p, 0, c->rowp.bytes, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->local.p, 0, c->local.bytes, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->camb.p, 0, c->camb.bytes, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->lmkb.p, 0, c->lmkb.bytes, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->hmu_c.p, 0, c->hmu_c.bytes, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->hmu_l.p, 0, c->hmu_l.bytes, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->clin.p, 0, c->clin.bytes, c->stream));
+    if (int rc = up.put(c->arr.mu.p, mu.data(), mu.size() * 4)) return rc;
+  HIPCHK(c, hipMemsetAsync(c->arr.cmsg.p, 0, c->arr.cmsg.bytes, c->stream));      // every record kCmsgZero
+  c->arr.cmsg_zero = true;
+  HIPCHK(c, hipMemsetAsync(c->arr.rowp.p, 0, c->arr.rowp.bytes, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->arr.local.p, 0, c->arr.local.bytes, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->arr.camb.p, 0, c->arr.camb.bytes, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->arr.lmkb.p, 0, c->arr.lmkb.bytes, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->arr.hmu_c.p, 0, c->arr.hmu_c.bytes, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->arr.hmu_l.p, 0, c->arr.hmu_l.bytes, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->arr.clin.p, 0, c->arr.clin.bytes, c->stream));
   std::vector<float> rec;
   pack_cam(in->cam_priors_eta, in->cam_priors_lambda, c->C, rec);
-  if (int rc = up.put(c->camp.p, rec.data(), rec.size() * 4)) return rc;
+  if (int rc = up.put(c->arr.camp.p, rec.data(), rec.size() * 4)) return rc;
   pack_lmk(in->lmk_priors_eta, in->lmk_priors_lambda, c->lmk_begin, c->L_loc, rec);
   if (c->L_loc)
-    if (int rc = up.put(c->lmkp.p, rec.data(), rec.size() * 4)) return rc;
+    if (int rc = up.put(c->arr.lmkp.p, rec.data(), rec.size() * 4)) return rc;
   std::vector<float> zf(std::max(c->C, c->L), 0.f);
   std::vector<uint32_t> zu(std::max(c->C, c->L), 0u);
-  if (int rc = up.put(c->cscale.p, in->cam_scaling ? in->cam_scaling : zf.data(), (size_t)c->C * 4)) return rc;
-  if (int rc = up.put(c->cwf.p, in->cam_weaken_flag ? in->cam_weaken_flag : zu.data(), (size_t)c->C * 4)) return rc;
+  if (int rc = up.put(c->arr.cscale.p, in->cam_scaling ? in->cam_scaling : zf.data(), (size_t)c->C * 4)) return rc;
+  if (int rc = up.put(c->arr.cwf.p, in->cam_weaken_flag ? in->cam_weaken_flag : zu.data(), (size_t)c->C * 4)) return rc;
   if (c->L_loc) {
-    if (int rc = up.put(c->lscale.p, in->lmk_scaling ? in->lmk_scaling + c->lmk_begin : zf.data(), (size_t)c->L_loc * 4)) return rc;
-    if (int rc = up.put(c->lwf.p, in->lmk_weaken_flag ? in->lmk_weaken_flag + c->lmk_begin : zu.data(), (size_t)c->L_loc * 4)) return rc;
+    if (int rc = up.put(c->arr.lscale.p, in->lmk_scaling ? in->lmk_scaling + c->lmk_begin : zf.data(), (size_t)c->L_loc * 4)) return rc;
+    if (int rc = up.put(c->arr.lwf.p, in->lmk_weaken_flag ? in->lmk_weaken_flag + c->lmk_begin : zu.data(), (size_t)c->L_loc * 4)) return rc;
   }
   lap("fills, priors, scalings queued");
   if (int rc = up.end()) return rc;
@@ -622,10 +618,10 @@ GBP_EXPORT(gbp_read, c, (gbp_ctx* c, gbp_state_out* o), (c, o)) {
   std::vector<int32_t> packed(want_state ? c->Ep : 0);
   D2H down;      // (the per-factor scalars: their planes as they are, FST_DAMP and FST_PACKED)
   if (int rc = down.begin(c, (rec_c.size() + rec_l.size() + damp.size() + packed.size()) * 4, 4)) return rc;
-  if (int rc = down.get(rec_c.data(), c->camb.p, rec_c.size() * 4)) return rc;
-  if (int rc = down.get(rec_l.data(), c->lmkb.p, rec_l.size() * 4)) return rc;
-  if (int rc = down.get(damp.data(), c->fst_damp.p, damp.size() * 4)) return rc;
-  if (int rc = down.get(packed.data(), c->fst_packed.p, packed.size() * 4)) return rc;
+  if (int rc = down.get(rec_c.data(), c->arr.camb.p, rec_c.size() * 4)) return rc;
+  if (int rc = down.get(rec_l.data(), c->arr.lmkb.p, rec_l.size() * 4)) return rc;
+  if (int rc = down.get(damp.data(), c->arr.fst_damp.p, damp.size() * 4)) return rc;
+  if (int rc = down.get(packed.data(), c->arr.fst_packed.p, packed.size() * 4)) return rc;
   if (int rc = down.end()) return rc;
   if (want_cam) {
     const std::vector<float>& rec = rec_c;
@@ -667,8 +663,8 @@ GBP_EXPORT(gbp_read_priors, c, (gbp_ctx* c, gbp_priors_out* o), (c, o)) {
   std::vector<float> rec((size_t)c->C * kCamRec), rec_l((size_t)c->L_loc * 16);
   D2H down;
   if (int rc = down.begin(c, (rec.size() + rec_l.size()) * 4, 2)) return rc;
-  if (int rc = down.get(rec.data(), c->camp.p, rec.size() * 4)) return rc;
-  if (int rc = down.get(rec_l.data(), c->lmkp.p, rec_l.size() * 4)) return rc;
+  if (int rc = down.get(rec.data(), c->arr.camp.p, rec.size() * 4)) return rc;
+  if (int rc = down.get(rec_l.data(), c->arr.lmkp.p, rec_l.size() * 4)) return rc;
   if (int rc = down.end()) return rc;
   for (uint32_t k = 0; k < c->C; ++k) {
     if (o->cam_priors_eta) std::memcpy(o->cam_priors_eta + (size_t)k * 6, &rec[(size_t)k * kCamRec], 6 * 4);
@@ -695,7 +691,7 @@ GBP_EXPORT(gbp_new_keyframe, c, (gbp_ctx* c, const gbp_kf_update* u), (c, u)) {
     if (dev) return devio_new_keyframe(c, u);
   }
   if (int rc = gbp_sync(c)) return rc;
-  if (c->active_host_stale && u->active_flag)      // device-pointer calls came before: the shadow of the flags is on the device
+  if (c->arr.active_host_stale && u->active_flag)      // device-pointer calls came before: the shadow of the flags is on the device
     if (int rc = devio_refresh_active_shadow(c)) return rc;
   if (u->damping_count || u->active_flag) {
     // edit the per-factor scalars in place on the device: 8 bytes per factor go over PCIe, not the 64-byte records
@@ -712,7 +708,7 @@ GBP_EXPORT(gbp_new_keyframe, c, (gbp_ctx* c, const gbp_kf_update* u), (c, u)) {
         // mean where the reference measures it against the factor's own zero-initialised oldmu (ba.cpp:582-583).  The
         // two agree as long as that sweep cannot relinearise, i.e. count + 1 <= min_linear_iters - num_undamped_iters
         // (gbp_codelets.cpp:280) — true for the reference's re-arm value -15 (slam.cpp:1040) and its defaults.
-        if (c->hoist && on && !c->active_host[p] && u->damping_count && u->damping_count[e] + 1 > thr)
+        if (c->hoist && on && !c->arr.active_host[p] && u->damping_count && u->damping_count[e] + 1 > thr)
           return fail(c, GBP_ERR_INVALID, "gbp_new_keyframe: a factor activated with damping_count + 1 > min_linear_iters - "
                                           "num_undamped_iters could relinearise on its first sweep; that needs gbp_params.per_factor_mu = 1");
         ctl[p] |= 2u | (on ? 4u : 0u);
@@ -720,32 +716,32 @@ GBP_EXPORT(gbp_new_keyframe, c, (gbp_ctx* c, const gbp_kf_update* u), (c, u)) {
     }
     H2D up;
     if (int rc = up.begin(c, (size_t)c->Ep * 8, 2)) return rc;
-    if (int rc = up.put(c->st_b.p, cnt.data(), (size_t)c->Ep * 4)) return rc;
-    if (int rc = up.put(c->st_a.p, ctl.data(), (size_t)c->Ep * 4)) return rc;
+    if (int rc = up.put(c->arr.st_b.p, cnt.data(), (size_t)c->Ep * 4)) return rc;
+    if (int rc = up.put(c->arr.st_a.p, ctl.data(), (size_t)c->Ep * 4)) return rc;
     if (int rc = up.end()) return rc;
-    launch_state_set(P<int>(c->fst_packed), P<int>(c->st_b), P<uint32_t>(c->st_a), c->Ep, c->stream);
+    launch_state_set(P<int>(c->arr.fst_packed), P<int>(c->arr.st_b), P<uint32_t>(c->arr.st_a), c->Ep, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (u->active_flag)
       for (size_t p = 0; p < c->Ep; ++p)
-        if (c->lay.pos_edge[p] != ~0u) c->active_host[p] = u->active_flag[c->lay.pos_edge[p]] == 1;
+        if (c->lay.pos_edge[p] != ~0u) c->arr.active_host[p] = u->active_flag[c->lay.pos_edge[p]] == 1;
   }
   H2D up;
   if (int rc = up.begin(c, ((size_t)c->C + c->L_loc) * (kCamRec + 16 + 1) * 4, 4)) return rc;
   if (u->cam_priors_eta && u->cam_priors_lambda) {
     std::vector<float> rec;
     pack_cam(u->cam_priors_eta, u->cam_priors_lambda, c->C, rec);
-    if (int rc = up.put(c->camp.p, rec.data(), rec.size() * 4)) return rc;
+    if (int rc = up.put(c->arr.camp.p, rec.data(), rec.size() * 4)) return rc;
   }
   if (u->lmk_priors_eta && u->lmk_priors_lambda && c->L_loc) {
     std::vector<float> rec;
     pack_lmk(u->lmk_priors_eta, u->lmk_priors_lambda, c->lmk_begin, c->L_loc, rec);
-    if (int rc = up.put(c->lmkp.p, rec.data(), rec.size() * 4)) return rc;
+    if (int rc = up.put(c->arr.lmkp.p, rec.data(), rec.size() * 4)) return rc;
   }
   if (u->cam_weaken_flag)
-    if (int rc = up.put(c->cwf.p, u->cam_weaken_flag, (size_t)c->C * 4)) return rc;
+    if (int rc = up.put(c->arr.cwf.p, u->cam_weaken_flag, (size_t)c->C * 4)) return rc;
   if (u->lmk_weaken_flag && c->L_loc)
-    if (int rc = up.put(c->lwf.p, u->lmk_weaken_flag + c->lmk_begin, (size_t)c->L_loc * 4)) return rc;
+    if (int rc = up.put(c->arr.lwf.p, u->lmk_weaken_flag + c->lmk_begin, (size_t)c->L_loc * 4)) return rc;
   if (int rc = up.end()) return rc;
   return refresh_beliefs_from_partials(c, false);
 }
@@ -754,21 +750,21 @@ GBP_EXPORT(gbp_timing, c, (gbp_ctx* c, gbp_timing_out* t, int reset), (c, t, res
   if (!c || !t) return GBP_ERR_INVALID;
   drain_sweep_events(c);   // split-phase brackets recorded by gbp_iterate_begin
   resolve_spans(c, true);  // gbp_iterate brackets still in flight
-  t->sweep_ms = c->sweep_ms; t->belief_ms = c->belief_ms; t->total_ms = c->total_ms; t->iterations = c->timed_iters;
-  t->exchange_ms = c->exchange_ms;
+  t->sweep_ms = c->tm.sweep_ms; t->belief_ms = c->tm.belief_ms; t->total_ms = c->tm.total_ms; t->iterations = c->tm.timed_iters;
+  t->exchange_ms = c->tm.exchange_ms;
   t->algorithmic_bytes_per_iter = 1112ull * c->E_loc + 336ull * c->C + 96ull * c->L_loc;
   t->device_bytes_allocated = c->dev_bytes;
-  if (reset) { c->sweep_ms = c->belief_ms = c->total_ms = c->exchange_ms = 0; c->timed_iters = 0; }
+  if (reset) { c->tm.sweep_ms = c->tm.belief_ms = c->tm.total_ms = c->tm.exchange_ms = 0; c->tm.timed_iters = 0; }
   return GBP_OK;
 }
 
 // ---- extras declared below the main program list -------------------------------------------------
 GBP_EXPORT(gbp_set_profiling, c, (gbp_ctx* c, int per_stage_events), (c, per_stage_events)) {
   if (!c) return GBP_ERR_INVALID;
-  c->profile_stages = per_stage_events != 0;
+  c->tm.profile_stages = per_stage_events != 0;
   return GBP_OK;
 }
 
 GBP_EXPORT_T(int, 0, gbp_graph_state, (const gbp_ctx* c), (c)) {
-  return !c ? 0 : (c->persist_ok ? 2 : ((c->graph_exec || c->graph_exec_ev) ? 1 : (c->graph_failed ? -1 : 0)));
+  return !c ? 0 : (c->persist.ok ? 2 : ((c->graph.exec || c->graph.exec_ev) ? 1 : (c->graph.failed ? -1 : 0)));
 }

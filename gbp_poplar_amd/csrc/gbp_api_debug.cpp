@@ -13,7 +13,7 @@ namespace {
 // LMSG as it lies in memory: kLmsgG * 4 = 12 floats per device position (eta 3, Lambda 9)
 int download_lmsg(gbp_ctx* c, std::vector<float>& msg) {
   msg.resize((size_t)c->Ep * kLmsgG * 4);
-  HIPCHK(c, hipMemcpy(msg.data(), c->lmsg.p, msg.size() * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(msg.data(), c->arr.lmsg.p, msg.size() * 4, hipMemcpyDeviceToHost));
   return GBP_OK;
 }
 }  // namespace
@@ -30,7 +30,7 @@ GBP_EXPORT(gbp_debug_get, c, (gbp_ctx* c, int what, float* a, float* b), (c, wha
   auto tri = [](int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; };
   if (what == 0) {
     std::vector<float> f((size_t)c->Ep * kFacG * 4);
-    HIPCHK(c, hipMemcpy(f.data(), c->fac.p, f.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(f.data(), c->arr.fac.p, f.size() * 4, hipMemcpyDeviceToHost));
     for (size_t p = 0; p < c->Ep; ++p) {
       const uint32_t e = c->lay.pos_edge[p];
       if (e == ~0u) continue;
@@ -73,10 +73,10 @@ GBP_EXPORT(gbp_debug_get, c, (gbp_ctx* c, int what, float* a, float* b), (c, wha
   } else if (what == 3 && c->hoist) {
     // hoisted mode: mu of a factor = the per-variable means its last sweep used; dmu is not kept per factor
     std::vector<float> mc((size_t)c->C * 16), ml((size_t)c->L_loc * 8);
-    HIPCHK(c, hipMemcpy(mc.data(), c->hmu_c.p, mc.size() * 4, hipMemcpyDeviceToHost));
-    if (c->L_loc) HIPCHK(c, hipMemcpy(ml.data(), c->hmu_l.p, ml.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(mc.data(), c->arr.hmu_c.p, mc.size() * 4, hipMemcpyDeviceToHost));
+    if (c->L_loc) HIPCHK(c, hipMemcpy(ml.data(), c->arr.hmu_l.p, ml.size() * 4, hipMemcpyDeviceToHost));
     std::vector<int32_t> packed(c->Ep);
-    HIPCHK(c, hipMemcpy(packed.data(), c->fst_packed.p, packed.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(packed.data(), c->arr.fst_packed.p, packed.size() * 4, hipMemcpyDeviceToHost));
     for (size_t p = 0; p < c->Ep; ++p) {
       const uint32_t e = c->lay.pos_edge[p];
       if (e == ~0u) continue;
@@ -87,7 +87,7 @@ GBP_EXPORT(gbp_debug_get, c, (gbp_ctx* c, int what, float* a, float* b), (c, wha
     }
   } else if (what == 3) {
     std::vector<float> f((size_t)c->Ep * kMuG * 4);
-    HIPCHK(c, hipMemcpy(f.data(), c->mu.p, f.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(f.data(), c->arr.mu.p, f.size() * 4, hipMemcpyDeviceToHost));
     for (size_t p = 0; p < c->Ep; ++p) {
       const uint32_t e = c->lay.pos_edge[p];
       if (e == ~0u) continue;
@@ -122,12 +122,12 @@ GBP_EXPORT(gbp_debug_time_sweep, c, (gbp_ctx* c, int ablation, int reps, double*
   };
   one();
   if (!built) return fail(c, GBP_ERR_INVALID, "gbp_debug_time_sweep: ablated sweeps exist in the experiments build only (python -m gbp_poplar_amd.build --experiments)");
-  HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+  HIPCHK(c, hipEventRecord(c->tm.reps_begin, c->stream));
   for (int i = 0; i < reps; ++i) one();
-  HIPCHK(c, hipEventRecord(c->ev2, c->stream));
-  HIPCHK(c, hipEventSynchronize(c->ev2));
+  HIPCHK(c, hipEventRecord(c->tm.reps_end, c->stream));
+  HIPCHK(c, hipEventSynchronize(c->tm.reps_end));
   float ms = 0;
-  HIPCHK(c, hipEventElapsedTime(&ms, c->ev1, c->ev2));
+  HIPCHK(c, hipEventElapsedTime(&ms, c->tm.reps_begin, c->tm.reps_end));
   *avg_us = 1e3 * ms / reps;
   return GBP_OK;
 }
@@ -174,7 +174,7 @@ GBP_EXPORT(gbp_debug_persist_roles, nullptr, (uint32_t n_tiles, uint32_t n_cams,
 }
 GBP_EXPORT(gbp_debug_persist_flow, c, (gbp_ctx* c, int on), (c, on)) {
   if (!c) return GBP_ERR_INVALID;
-  c->persist_flow = on != 0;
+  c->persist.use_flow = on != 0;
   return GBP_OK;
 }
 // Redundant records in the persistent kernel (k_persist_flow<EV, VER = true>): on != 0 — every tagged record of the following launches
@@ -183,9 +183,9 @@ GBP_EXPORT(gbp_debug_persist_flow, c, (gbp_ctx* c, int on), (c, on)) {
 // receives the count since the last call and resets it.  A ctx that does not run in the persistent kernel: GBP_ERR_STATE.
 GBP_EXPORT(gbp_debug_persist_verify, c, (gbp_ctx* c, int on, uint64_t* mismatches), (c, on, mismatches)) {
   if (!c) return GBP_ERR_INVALID;
-  if (!c->flow.lmsg || !c->flow_total4) return fail(c, GBP_ERR_STATE, "gbp_debug_persist_verify: this ctx does not run in the persistent kernel");
+  if (!c->persist.flow.lmsg || !c->persist.flow_total4) return fail(c, GBP_ERR_STATE, "gbp_debug_persist_verify: this ctx does not run in the persistent kernel");
   if (int rc = gbp_sync(c)) return rc;
-  unsigned long long* counter = reinterpret_cast<unsigned long long*>(static_cast<float4*>(c->pflow.p) + 2 * (size_t)c->flow_total4);
+  unsigned long long* counter = reinterpret_cast<unsigned long long*>(static_cast<float4*>(c->persist.pflow.p) + 2 * (size_t)c->persist.flow_total4);
   if (mismatches) {
     unsigned long long v = 0;
     HIPCHK(c, hipMemcpy(&v, counter, 8, hipMemcpyDeviceToHost));
@@ -193,8 +193,8 @@ GBP_EXPORT(gbp_debug_persist_verify, c, (gbp_ctx* c, int on, uint64_t* mismatche
   }
   HIPCHK(c, hipMemsetAsync(counter, 0, 8, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->flow.mirror4 = on ? c->flow_total4 : 0u;
-  c->flow.verify_errors = counter;
+  c->persist.flow.mirror4 = on ? c->persist.flow_total4 : 0u;
+  c->persist.flow.verify_errors = counter;
   return GBP_OK;
 }
 
@@ -292,11 +292,11 @@ GBP_EXPORT(gbp_debug_set_factor_potentials, c, (gbp_ctx* c, const float* eta9E, 
   if (!c || !eta9E || !lam81E) return GBP_ERR_INVALID;
   // (a kCmsgDerived record derives its message from the potential, gbp_kernels.h: the potentials may be replaced only while every
   // record is the zero message — behind the upload or the LINEARISE that follows it, where the tests call this)
-  if (!c->cmsg_zero) return fail(c, GBP_ERR_STATE, "gbp_debug_set_factor_potentials: camera messages are live (call it before the first sweep)");
+  if (!c->arr.cmsg_zero) return fail(c, GBP_ERR_STATE, "gbp_debug_set_factor_potentials: camera messages are live (call it before the first sweep)");
   if (int rc = gbp_sync(c)) return rc;
   auto tri = [](int i, int j) { return i * (i + 1) / 2 + j; };
   std::vector<float> f((size_t)c->Ep * kFacG * 4);
-  HIPCHK(c, hipMemcpy(f.data(), c->fac.p, f.size() * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(f.data(), c->arr.fac.p, f.size() * 4, hipMemcpyDeviceToHost));
   for (size_t p = 0; p < c->Ep; ++p) {
     const uint32_t e = c->lay.pos_edge[p];
     if (e == ~0u) continue;
@@ -306,7 +306,7 @@ GBP_EXPORT(gbp_debug_set_factor_potentials, c, (gbp_ctx* c, const float* eta9E, 
     for (int i = 0; i < 18; ++i) f[tile_off((uint32_t)p, kFacG, 30 + i)] = lam[36 + i];
     for (int i = 0; i < 3; ++i) for (int j = 0; j <= i; ++j) f[tile_off((uint32_t)p, kFacG, 48 + tri(i, j))] = lam[72 + i * 3 + j];
   }
-  HIPCHK(c, hipMemcpy(c->fac.p, f.data(), f.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->arr.fac.p, f.data(), f.size() * 4, hipMemcpyHostToDevice));
   return GBP_OK;
 }
 

@@ -12,24 +12,24 @@ namespace {
 
 // lay.pos_edge on the device: built by the first device-pointer call of a ctx (the one call of these that blocks: a staged copy)
 int need_pos_edge(gbp_ctx* c) {
-  if (c->d_pos_edge.p) return GBP_OK;
-  if (int rc = dev_alloc(c, c->d_pos_edge, (size_t)c->Ep * 4)) return rc;
+  if (c->arr.d_pos_edge.p) return GBP_OK;
+  if (int rc = dev_alloc(c, c->arr.d_pos_edge, (size_t)c->Ep * 4)) return rc;
   H2D up;
   if (int rc = up.begin(c, (size_t)c->Ep * 4, 1)) return rc;
-  if (int rc = up.put(c->d_pos_edge.p, c->lay.pos_edge.data(), (size_t)c->Ep * 4)) return rc;
+  if (int rc = up.put(c->arr.d_pos_edge.p, c->lay.pos_edge.data(), (size_t)c->Ep * 4)) return rc;
   return up.end();
 }
 
 // Launches of the persistent kernel that are still unvalidated are waited for first, as before every other kind of device work
 // (settle: free when none is in flight).  A ctx that left the persistent path after a recovered time-out gets its fresh start.
-// Otherwise the reset gbp_upload makes (persist_reset: barrier words and persist_epoch_base back to zero, behind a stream
+// Otherwise the reset gbp_upload makes (persist_reset: barrier words and persist.epoch_base back to zero, behind a stream
 // synchronisation) is not needed: the two are only ever used as a pair — the kernel waits for epoch_base + its own arrivals on a
-// counter that keeps counting across launches — the tags of the tagged records come from persist_seq, which no upload resets, and
+// counter that keeps counting across launches — the tags of the tagged records come from persist.seq, which no upload resets, and
 // with the log empty and the status word zero there is nothing else persist_reset would change.  Leaving it out is what keeps
 // this call from blocking.
 int settle_for_upload(gbp_ctx* c) {
   if (int rc = settle(c)) return rc;
-  if (c->pstatus_host && (c->persist_ok != c->persist_eligible || *static_cast<volatile unsigned*>(c->pstatus_host) != 0u)) return persist_reset(c);
+  if (c->persist.status.host && (c->persist.ok != c->persist.eligible || *static_cast<volatile unsigned*>(c->persist.status.host) != 0u)) return persist_reset(c);
   return GBP_OK;
 }
 
@@ -50,30 +50,30 @@ namespace api {
 int devio_upload(gbp_ctx* c, const gbp_state_in* in) {
   if (int rc = settle_for_upload(c)) return rc;
   if (int rc = need_pos_edge(c)) return rc;
-  c->active_host.assign(c->Ep, 0);
-  c->active_host_stale = true;
-  for (DevBuf* b : {&c->fac, &c->cmsg, &c->rowp, &c->local, &c->camb, &c->lmkb, &c->hmu_c, &c->hmu_l, &c->clin, &c->camp, &c->lmkp, &c->cscale, &c->cwf, &c->lscale, &c->lwf})
+  c->arr.active_host.assign(c->Ep, 0);
+  c->arr.active_host_stale = true;
+  for (DevBuf* b : {&c->arr.fac, &c->arr.cmsg, &c->arr.rowp, &c->arr.local, &c->arr.camb, &c->arr.lmkb, &c->arr.hmu_c, &c->arr.hmu_l, &c->arr.clin, &c->arr.camp, &c->arr.lmkp, &c->arr.cscale, &c->arr.cwf, &c->arr.lscale, &c->arr.lwf})
     HIPCHK(c, hipMemsetAsync(b->p, 0, b->bytes, c->stream));
-  c->cmsg_zero = true;      // (the fill of CMSG: every record kCmsgZero)
+  c->arr.cmsg_zero = true;      // (the fill of CMSG: every record kCmsgZero)
   UploadDev a{};
-  a.pos_edge = P<uint32_t>(c->d_pos_edge);
+  a.pos_edge = P<uint32_t>(c->arr.d_pos_edge);
   a.damping = in->damping; a.damping_count = in->damping_count; a.active_flag = in->active_flag;
   a.measurements = in->measurements; a.meas_variances = in->meas_variances;
   a.om = in->oldmu ? in->oldmu : in->mu;
-  a.lmsg = P<float4>(c->lmsg); a.fs = factor_state(c); a.fac = P<float4>(c->fac);
-  a.mu = c->hoist ? nullptr : P<float4>(c->mu);
+  a.lmsg = P<float4>(c->arr.lmsg); a.fs = factor_state(c); a.fac = P<float4>(c->arr.fac);
+  a.mu = c->hoist ? nullptr : P<float4>(c->arr.mu);
   a.n = c->Ep;
   launch_upload_dev(a, c->stream);
   HIPCHK(c, hipGetLastError());
   RecSegs t{};
-  seg(t, in->cam_priors_eta, c->camp.p, c->C, 6, kCamRec, 0);
-  seg(t, in->cam_priors_lambda, c->camp.p, c->C, 36, kCamRec, 8);
-  seg(t, in->lmk_priors_eta, c->lmkp.p, c->L, 3, 16, 0);
-  seg(t, in->lmk_priors_lambda, c->lmkp.p, c->L, 9, 16, 4);
-  seg(t, in->cam_scaling, c->cscale.p, c->C, 1, 1, 0);
-  seg(t, in->cam_weaken_flag, c->cwf.p, c->C, 1, 1, 0);
-  seg(t, in->lmk_scaling, c->lscale.p, c->L, 1, 1, 0);
-  seg(t, in->lmk_weaken_flag, c->lwf.p, c->L, 1, 1, 0);
+  seg(t, in->cam_priors_eta, c->arr.camp.p, c->C, 6, kCamRec, 0);
+  seg(t, in->cam_priors_lambda, c->arr.camp.p, c->C, 36, kCamRec, 8);
+  seg(t, in->lmk_priors_eta, c->arr.lmkp.p, c->L, 3, 16, 0);
+  seg(t, in->lmk_priors_lambda, c->arr.lmkp.p, c->L, 9, 16, 4);
+  seg(t, in->cam_scaling, c->arr.cscale.p, c->C, 1, 1, 0);
+  seg(t, in->cam_weaken_flag, c->arr.cwf.p, c->C, 1, 1, 0);
+  seg(t, in->lmk_scaling, c->arr.lscale.p, c->L, 1, 1, 0);
+  seg(t, in->lmk_weaken_flag, c->arr.lwf.p, c->L, 1, 1, 0);
   launch_rec_copy(t, true, c->stream);
   HIPCHK(c, hipGetLastError());
   if (int rc = zero_exchange(c)) return rc;      // (as gbp_upload)
@@ -87,14 +87,14 @@ int devio_read(gbp_ctx* c, gbp_state_out* o) {
   if (int rc = settle(c)) return rc;
   if (o->damping || o->damping_count || o->robust_flag) {
     if (int rc = need_pos_edge(c)) return rc;
-    launch_read_state_dev(P<uint32_t>(c->d_pos_edge), factor_state(c), o->damping, o->damping_count, o->robust_flag, c->Ep, c->stream);
+    launch_read_state_dev(P<uint32_t>(c->arr.d_pos_edge), factor_state(c), o->damping, o->damping_count, o->robust_flag, c->Ep, c->stream);
     HIPCHK(c, hipGetLastError());
   }
   RecSegs t{};
-  seg(t, o->cam_beliefs_eta, c->camb.p, c->C, 6, kCamRec, 0);
-  seg(t, o->cam_beliefs_lambda, c->camb.p, c->C, 36, kCamRec, 8);
-  seg(t, o->lmk_beliefs_eta, c->lmkb.p, c->L, 3, 16, 0);
-  seg(t, o->lmk_beliefs_lambda, c->lmkb.p, c->L, 9, 16, 4);
+  seg(t, o->cam_beliefs_eta, c->arr.camb.p, c->C, 6, kCamRec, 0);
+  seg(t, o->cam_beliefs_lambda, c->arr.camb.p, c->C, 36, kCamRec, 8);
+  seg(t, o->lmk_beliefs_eta, c->arr.lmkb.p, c->L, 3, 16, 0);
+  seg(t, o->lmk_beliefs_lambda, c->arr.lmkb.p, c->L, 9, 16, 4);
   launch_rec_copy(t, false, c->stream);
   HIPCHK(c, hipGetLastError());
   return GBP_OK;
@@ -104,10 +104,10 @@ int devio_read(gbp_ctx* c, gbp_state_out* o) {
 int devio_read_priors(gbp_ctx* c, gbp_priors_out* o) {
   if (int rc = settle(c)) return rc;
   RecSegs t{};
-  seg(t, o->cam_priors_eta, c->camp.p, c->C, 6, kCamRec, 0);
-  seg(t, o->cam_priors_lambda, c->camp.p, c->C, 36, kCamRec, 8);
-  seg(t, o->lmk_priors_eta, c->lmkp.p, c->L, 3, 16, 0);
-  seg(t, o->lmk_priors_lambda, c->lmkp.p, c->L, 9, 16, 4);
+  seg(t, o->cam_priors_eta, c->arr.camp.p, c->C, 6, kCamRec, 0);
+  seg(t, o->cam_priors_lambda, c->arr.camp.p, c->C, 36, kCamRec, 8);
+  seg(t, o->lmk_priors_eta, c->arr.lmkp.p, c->L, 3, 16, 0);
+  seg(t, o->lmk_priors_lambda, c->arr.lmkp.p, c->L, 9, 16, 4);
   launch_rec_copy(t, false, c->stream);
   HIPCHK(c, hipGetLastError());
   return GBP_OK;
@@ -121,23 +121,23 @@ int devio_new_keyframe(gbp_ctx* c, const gbp_kf_update* u) {
   if (int rc = settle(c)) return rc;
   if (u->damping_count || u->active_flag) {
     if (int rc = need_pos_edge(c)) return rc;
-    launch_keyframe_state_dev(P<uint32_t>(c->d_pos_edge), P<int>(c->fst_packed), u->damping_count, u->active_flag, c->Ep, c->stream);
+    launch_keyframe_state_dev(P<uint32_t>(c->arr.d_pos_edge), P<int>(c->arr.fst_packed), u->damping_count, u->active_flag, c->Ep, c->stream);
     HIPCHK(c, hipGetLastError());
-    if (u->active_flag) c->active_host_stale = true;
+    if (u->active_flag) c->arr.active_host_stale = true;
   }
   RecSegs t{};
   if (u->cam_priors_eta && u->cam_priors_lambda) {
-    HIPCHK(c, hipMemsetAsync(c->camp.p, 0, c->camp.bytes, c->stream));      // (the pads of a record: pack_cam writes zeros)
-    seg(t, u->cam_priors_eta, c->camp.p, c->C, 6, kCamRec, 0);
-    seg(t, u->cam_priors_lambda, c->camp.p, c->C, 36, kCamRec, 8);
+    HIPCHK(c, hipMemsetAsync(c->arr.camp.p, 0, c->arr.camp.bytes, c->stream));      // (the pads of a record: pack_cam writes zeros)
+    seg(t, u->cam_priors_eta, c->arr.camp.p, c->C, 6, kCamRec, 0);
+    seg(t, u->cam_priors_lambda, c->arr.camp.p, c->C, 36, kCamRec, 8);
   }
   if (u->lmk_priors_eta && u->lmk_priors_lambda) {
-    HIPCHK(c, hipMemsetAsync(c->lmkp.p, 0, c->lmkp.bytes, c->stream));
-    seg(t, u->lmk_priors_eta, c->lmkp.p, c->L, 3, 16, 0);
-    seg(t, u->lmk_priors_lambda, c->lmkp.p, c->L, 9, 16, 4);
+    HIPCHK(c, hipMemsetAsync(c->arr.lmkp.p, 0, c->arr.lmkp.bytes, c->stream));
+    seg(t, u->lmk_priors_eta, c->arr.lmkp.p, c->L, 3, 16, 0);
+    seg(t, u->lmk_priors_lambda, c->arr.lmkp.p, c->L, 9, 16, 4);
   }
-  seg(t, u->cam_weaken_flag, c->cwf.p, c->C, 1, 1, 0);
-  seg(t, u->lmk_weaken_flag, c->lwf.p, c->L, 1, 1, 0);
+  seg(t, u->cam_weaken_flag, c->arr.cwf.p, c->C, 1, 1, 0);
+  seg(t, u->lmk_weaken_flag, c->arr.lwf.p, c->L, 1, 1, 0);
   launch_rec_copy(t, true, c->stream);
   HIPCHK(c, hipGetLastError());
   return refresh_beliefs_from_partials(c, false);
@@ -149,11 +149,11 @@ int devio_refresh_active_shadow(gbp_ctx* c) {
   D2H down;
   if (int rc = down.begin(c, (size_t)c->Ep * 4, 1)) return rc;
   if (down.up.direct) HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (int rc = down.get(packed.data(), c->fst_packed.p, (size_t)c->Ep * 4)) return rc;
+  if (int rc = down.get(packed.data(), c->arr.fst_packed.p, (size_t)c->Ep * 4)) return rc;
   if (int rc = down.end()) return rc;
-  c->active_host.assign(c->Ep, 0);
-  for (size_t p = 0; p < c->Ep; ++p) c->active_host[p] = ((uint32_t)packed[p] & (kFlagActive | kFlagPad)) == kFlagActive;
-  c->active_host_stale = false;
+  c->arr.active_host.assign(c->Ep, 0);
+  for (size_t p = 0; p < c->Ep; ++p) c->arr.active_host[p] = ((uint32_t)packed[p] & (kFlagActive | kFlagPad)) == kFlagActive;
+  c->arr.active_host_stale = false;
   return GBP_OK;
 }
 

@@ -27,27 +27,24 @@ namespace api {
 // evaluations may be in flight (two result areas).  The health counters are accumulated with atomics in device memory,
 // double-buffered so that no memset launch is needed: k_means zeroes the pair the next evaluation will use.
 static int eval_alloc(gbp_ctx* c) {
-  if (c->eval_host) return GBP_OK;
-  HIPCHK(c, hipHostMalloc(&c->eval_host, sizeof(DeviceEval) * 1025 * 2, hipHostMallocMapped));
-  HIPCHK(c, hipHostGetDevicePointer(&c->eval_host_dev, c->eval_host, 0));
-  HIPCHK(c, hipEventCreateWithFlags(&c->eval_ev[0], hipEventDisableTiming));
-  HIPCHK(c, hipEventCreateWithFlags(&c->eval_ev[1], hipEventDisableTiming));
-  return GBP_OK;
+  if (c->metric.area.host) return GBP_OK;
+  if (int rc = mapped_alloc(c, c->metric.area, sizeof(DeviceEval) * 1025 * 2)) return rc;
+  return event_pair_owned(c, &c->metric.ev[0], &c->metric.ev[1], hipEventDisableTiming);
 }
 
 // k_means + k_eval of the current beliefs into result area `area`, its event recorded behind them
 int eval_enqueue(gbp_ctx* c, int area, DeviceEval* dev_slots) {
-  DeviceEval* slots = dev_slots ? dev_slots : static_cast<DeviceEval*>(c->eval_host_dev) + 1025 * area;
-  unsigned long long* h_cur = P<unsigned long long>(c->health) + 2 * area;
-  unsigned long long* h_next = P<unsigned long long>(c->health) + 2 * (area ^ 1);
-  launch_means(P<float4>(c->camb), P<float4>(c->lmkb), P<float>(c->cam_mu), P<float>(c->lmk_mu), c->C, c->L_loc,
+  DeviceEval* slots = dev_slots ? dev_slots : static_cast<DeviceEval*>(c->metric.area.dev) + 1025 * area;
+  unsigned long long* h_cur = P<unsigned long long>(c->arr.health) + 2 * area;
+  unsigned long long* h_next = P<unsigned long long>(c->arr.health) + 2 * (area ^ 1);
+  launch_means(P<float4>(c->arr.camb), P<float4>(c->arr.lmkb), P<float>(c->arr.cam_mu), P<float>(c->arr.lmk_mu), c->C, c->L_loc,
                h_cur, h_next, /*count_cams=*/c->rank == 0, c->stream);
-  launch_eval(P<uint32_t>(c->row_cam), P<uint32_t>(c->lmk_idx), P<int>(c->fst_packed), P<float4>(c->fac), P<float>(c->cam_mu), P<float>(c->lmk_mu),
-              P<float>(c->dK), c->prm.num_undamped_iters, slots + 1, h_cur, reinterpret_cast<unsigned long long*>(slots), c->n_tiles, c->stream);
+  launch_eval(P<uint32_t>(c->arr.row_cam), P<uint32_t>(c->arr.lmk_idx), P<int>(c->arr.fst_packed), P<float4>(c->arr.fac), P<float>(c->arr.cam_mu), P<float>(c->arr.lmk_mu),
+              P<float>(c->arr.dK), c->prm.num_undamped_iters, slots + 1, h_cur, reinterpret_cast<unsigned long long*>(slots), c->n_tiles, c->stream);
   HIPCHK(c, hipGetLastError());
   if (dev_slots) return GBP_OK;
-  HIPCHK(c, hipEventRecord(c->eval_ev[area], c->stream));
-  c->eval_per_wave[area] = false;
+  HIPCHK(c, hipEventRecord(c->metric.ev[area], c->stream));
+  c->metric.per_wave[area] = false;
   return GBP_OK;
 }
 
@@ -70,30 +67,30 @@ static int out_kind(gbp_ctx* c, const char* fn, const void* out, bool* device) {
 
 // the device twin of one result area of k_eval (first use allocates)
 static int eval_scratch(gbp_ctx* c) {
-  if (c->eval_scratch.p) return GBP_OK;
-  return dev_alloc(c, c->eval_scratch, sizeof(DeviceEval) * 1025);
+  if (c->metric.scratch.p) return GBP_OK;
+  return dev_alloc(c, c->metric.scratch, sizeof(DeviceEval) * 1025);
 }
 
 // One metric of the current beliefs into the caller's device record: k_means + k_eval as eval_begin queues them (the same health area,
 // the parity advanced as one eval_begin / eval_end pair advances it), their partial sums in device memory, the fold behind them.
 static int eval_to_device(gbp_ctx* c, gbp_eval_out* out) {
-  const int area = c->eval_parity & 1;
-  if (int rc = eval_enqueue(c, area, P<DeviceEval>(c->eval_scratch))) return rc;
-  c->eval_parity ^= 1;
-  launch_eval_fold_part(P<DeviceEval>(c->eval_scratch), 0, eval_blocks(c->n_tiles), c->n_tiles, false, 1, out, c->stream);
+  const int area = c->metric.parity & 1;
+  if (int rc = eval_enqueue(c, area, P<DeviceEval>(c->metric.scratch))) return rc;
+  c->metric.parity ^= 1;
+  launch_eval_fold_part(P<DeviceEval>(c->metric.scratch), 0, eval_blocks(c->n_tiles), c->n_tiles, false, 1, out, c->stream);
   HIPCHK(c, hipGetLastError());
   return GBP_OK;
 }
 
 int eval_begin(gbp_ctx* c) {
   if (!c || !c->uploaded) return fail(c, GBP_ERR_STATE, "gbp_eval: upload first");
-  if (c->eval_pending >= 2) return fail(c, GBP_ERR_STATE, "gbp_eval_begin: two evaluations already in flight, call gbp_eval_end first");
+  if (c->metric.pending >= 2) return fail(c, GBP_ERR_STATE, "gbp_eval_begin: two evaluations already in flight, call gbp_eval_end first");
   if (int rc = settle(c)) return rc;
   if (int rc = eval_alloc(c)) return rc;
-  const int area = c->eval_parity & 1;
+  const int area = c->metric.parity & 1;
   if (int rc = eval_enqueue(c, area)) return rc;
-  c->eval_parity ^= 1;
-  c->eval_pending += 1;
+  c->metric.parity ^= 1;
+  c->metric.pending += 1;
   return GBP_OK;
 }
 
@@ -128,28 +125,28 @@ static int sum_eval(gbp_ctx* c, const DeviceEval* part, uint32_t nb, gbp_eval_ou
 
 int eval_end(gbp_ctx* c, gbp_eval_out* o) {
   if (!c || !o) return GBP_ERR_INVALID;
-  if (c->eval_pending < 1) return fail(c, GBP_ERR_STATE, "gbp_eval_end: no evaluation in flight");
+  if (c->metric.pending < 1) return fail(c, GBP_ERR_STATE, "gbp_eval_end: no evaluation in flight");
   std::memset(o, 0, sizeof(*o));
-  const int area = (c->eval_parity + (c->eval_pending == 2 ? 0 : 1)) & 1;   // the OLDEST pending evaluation
-  HIPCHK(c, hipEventSynchronize(c->eval_ev[area]));
-  if (!c->persist_log.empty()) {
+  const int area = (c->metric.parity + (c->metric.pending == 2 ? 0 : 1)) & 1;   // the OLDEST pending evaluation
+  HIPCHK(c, hipEventSynchronize(c->metric.ev[area]));
+  if (!c->persist.log.empty()) {
     // the metric may have come out of a k_persist launch: that launch (the oldest logged one for this area) and everything
     // before it have completed — validate them; after a time-out the recovery has re-queued the metric behind the replay
     unsigned upto = 0;
-    for (const gbp_ctx::Burst& b : c->persist_log)
+    for (const gbp_ctx::Burst& b : c->persist.log)
       if (b.mode == 1 && b.area == area) { upto = b.seq; break; }
-    const bool failed = *static_cast<volatile unsigned*>(c->pstatus_host) != 0u;
+    const bool failed = *static_cast<volatile unsigned*>(c->persist.status.host) != 0u;
     if (failed || upto)
       if (int rc = persist_check(c, upto)) return rc;
-    if (failed) HIPCHK(c, hipEventSynchronize(c->eval_ev[area]));
+    if (failed) HIPCHK(c, hipEventSynchronize(c->metric.ev[area]));
   }
-  c->eval_pending -= 1;
-  return sum_eval(c, static_cast<const DeviceEval*>(c->eval_host) + 1025 * area, eval_blocks(c->n_tiles), o, c->eval_per_wave[area]);
+  c->metric.pending -= 1;
+  return sum_eval(c, static_cast<const DeviceEval*>(c->metric.area.host) + 1025 * area, eval_blocks(c->n_tiles), o, c->metric.per_wave[area]);
 }
 
 int eval(gbp_ctx* c, gbp_eval_out* o) {
   if (!c || !o || !c->uploaded) return fail(c, GBP_ERR_STATE, "gbp_eval: upload first");
-  if (c->eval_pending) return fail(c, GBP_ERR_STATE, "gbp_eval: finish the evaluations in flight (gbp_eval_end) first");
+  if (c->metric.pending) return fail(c, GBP_ERR_STATE, "gbp_eval: finish the evaluations in flight (gbp_eval_end) first");
   bool dev = false;
   if (int rc = out_kind(c, "gbp_eval", o, &dev)) return rc;
   if (dev) {      // not blocking (settle: k_means and k_eval are other device work than the launches it validates)
@@ -169,10 +166,10 @@ namespace {
 // the riding metric's view of the ctx (gbp_kernels.h: EvalRide); valid once ev_alloc has run
 EvalRide eval_ride(gbp_ctx* c) {
   EvalRide e{};
-  e.cam_rec = P<float4>(c->ev_cam); e.lmk_mean = P<float4>(c->ev_lmk); e.part = P<EvalRec>(c->ev_part);
-  e.counter = P<unsigned>(c->ev_ctl);
-  e.health = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->ev_ctl.p) + 8);
-  e.slot_health = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->ev_ctl.p) + 64);
+  e.cam_rec = P<float4>(c->metric.ev_cam); e.lmk_mean = P<float4>(c->metric.ev_lmk); e.part = P<EvalRec>(c->metric.ev_part);
+  e.counter = P<unsigned>(c->metric.ev_ctl);
+  e.health = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->metric.ev_ctl.p) + 8);
+  e.slot_health = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->metric.ev_ctl.p) + 64);
   e.n_tiles = c->n_tiles; e.num_undamped = c->prm.num_undamped_iters;
   return e;
 }
@@ -182,18 +179,18 @@ EvalRide eval_ride(gbp_ctx* c) {
 static PersistEval persist_eval(gbp_ctx* c, int area, bool each) {
   PersistEval ev{};
   ev.on = 1;
-  ev.cam_mu = P<float>(c->cam_mu); ev.lmk_mu = P<float>(c->lmk_mu);
+  ev.cam_mu = P<float>(c->arr.cam_mu); ev.lmk_mu = P<float>(c->arr.lmk_mu);
   ev.num_undamped = c->prm.num_undamped_iters;
   if (each) {
     ev.each = 1;
     ev.stride = c->n_tiles + 1;          // [0] = health copy, then one record per tile wave
-    ev.slots = static_cast<DeviceEval*>(c->series_dev);
+    ev.slots = static_cast<DeviceEval*>(c->persist.series.dev);
   } else {
-    ev.slots = static_cast<DeviceEval*>(c->eval_host_dev) + 1025 * area;      // [0] = health copy, [1 + tile wave] = partial sums
+    ev.slots = static_cast<DeviceEval*>(c->metric.area.dev) + 1025 * area;      // [0] = health copy, [1 + tile wave] = partial sums
   }
-  ev.health = P<unsigned long long>(c->health) + 2 * area;
-  ev.health_next = P<unsigned long long>(c->health) + 2 * (area ^ 1);
-  ev.health_each = P<unsigned long long>(c->health);
+  ev.health = P<unsigned long long>(c->arr.health) + 2 * area;
+  ev.health_next = P<unsigned long long>(c->arr.health) + 2 * (area ^ 1);
+  ev.health_each = P<unsigned long long>(c->arr.health);
   return ev;
 }
 
@@ -204,11 +201,11 @@ static int iterate_eval(gbp_ctx* c, int n) {
   if (!c || !c->uploaded) return fail(c, GBP_ERR_STATE, "gbp_iterate_eval: upload first");
   if (n <= 0) return eval_begin(c);
   bool fused = false;
-  if (c->eval_pending < 2 && n <= kPersistChunk && c->n_tiles <= 1024)
+  if (c->metric.pending < 2 && n <= kPersistChunk && c->n_tiles <= 1024)
     if (int rc = persist_ready(c, &fused)) return rc;
   if (fused) {
     if (int rc = eval_alloc(c)) return rc;
-    const int area = c->eval_parity & 1;
+    const int area = c->metric.parity & 1;
     const PersistEval metric = persist_eval(c, area, false);
     TimedSpan sp(c);
     if (int rc = sp.begin()) return rc;
@@ -226,10 +223,10 @@ static int iterate_eval(gbp_ctx* c, int n) {
     }
     if (lrc == GBP_OK) {
       if (int rc = sp.commit((uint64_t)n)) return rc;
-      HIPCHK(c, hipEventRecord(c->eval_ev[area], c->stream));
-      c->eval_per_wave[area] = true;
-      c->eval_parity ^= 1;
-      c->eval_pending += 1;
+      HIPCHK(c, hipEventRecord(c->metric.ev[area], c->stream));
+      c->metric.per_wave[area] = true;
+      c->metric.parity ^= 1;
+      c->metric.pending += 1;
       return GBP_OK;
     }
     if (lrc != kNotLaunched) return lrc;
@@ -245,41 +242,36 @@ static int iterate_eval(gbp_ctx* c, int n) {
 // k_eval_ride for the piece's last iteration and one k_eval_fold, which reduces every slot to one 56-byte result in host-mapped
 // memory.  Bit-identical to gbp_iterate(1) + gbp_eval per iteration (same operations, same order of the sums).
 static int ev_alloc(gbp_ctx* c) {
-  if (c->ev_depth) return GBP_OK;
+  if (c->metric.ev_depth) return GBP_OK;
   const size_t slot_bytes = (size_t)c->n_tiles * sizeof(EvalRec);
   const uint32_t depth = (uint32_t)std::min<size_t>(256, std::max<size_t>(2, ((size_t)128 << 20) / slot_bytes));      // <= 128 MB of ring
-  if (int rc = dev_alloc(c, c->ev_cam, (size_t)c->C * 3 * 16)) return rc;
-  if (int rc = dev_alloc(c, c->ev_lmk, (size_t)c->L_loc * 16)) return rc;
-  if (int rc = dev_alloc(c, c->ev_part, slot_bytes * depth)) return rc;
-  if (int rc = dev_alloc(c, c->ev_ctl, 64 + (size_t)depth * 16)) return rc;
+  if (int rc = dev_alloc(c, c->metric.ev_cam, (size_t)c->C * 3 * 16)) return rc;
+  if (int rc = dev_alloc(c, c->metric.ev_lmk, (size_t)c->L_loc * 16)) return rc;
+  if (int rc = dev_alloc(c, c->metric.ev_part, slot_bytes * depth)) return rc;
+  if (int rc = dev_alloc(c, c->metric.ev_ctl, 64 + (size_t)depth * 16)) return rc;
   // (dev_alloc zero-fills on the ctx's stream, in front of the first burst that uses the ring: a fill on the NULL stream once raced
   // the first burst's records — a first metric over 3 062 of 200 000 factors — and a device-wide wait stalls every other stream of the process)
-  c->ev_depth = depth;
+  c->metric.ev_depth = depth;
   return GBP_OK;
 }
 // dev: `out` is the caller's device memory — k_eval_fold writes there, nothing waits.  timed = false: the replay of a burst that gbp_timing has counted.
 static int eval_each_ride(gbp_ctx* c, int n, gbp_eval_out* out, bool dev = false, bool timed = true) {
   if (int rc = settle(c)) return rc;
   if (int rc = ev_alloc(c)) return rc;
-  if (!dev && (size_t)n > c->ev_host_cap) {       // one 56-byte result per iteration of the burst, host-mapped
-    if (c->ev_host) { (void)hipHostFree(c->ev_host); c->ev_host = nullptr; c->ev_host_cap = 0; }
-    const size_t cap = std::max<size_t>(1024, (size_t)n);
-    HIPCHK(c, hipHostMalloc(&c->ev_host, sizeof(gbp_eval_out) * cap, hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer(&c->ev_host_dev, c->ev_host, 0));
-    c->ev_host_cap = cap;
-  }
+  if (!dev && sizeof(gbp_eval_out) * (size_t)n > c->metric.ev_results.bytes)       // one 56-byte result per iteration of the burst, host-mapped
+    if (int rc = mapped_alloc(c, c->metric.ev_results, sizeof(gbp_eval_out) * std::max<size_t>(1024, (size_t)n))) return rc;
   static_assert(sizeof(gbp_eval_out) == 56, "k_eval_fold writes gbp_eval_out records");
   SweepArgs a = sweep_args(c);
   a.ev = eval_ride(c);
   TimedSpan sp(c);
   if (timed)
     if (int rc = sp.begin()) return rc;
-  gbp_eval_out* const results = dev ? out : static_cast<gbp_eval_out*>(c->ev_host_dev);
+  gbp_eval_out* const results = dev ? out : static_cast<gbp_eval_out*>(c->metric.ev_results.dev);
   for (int done = 0; done < n;) {         // pieces of at most ev_depth iterations, queued behind each other: no host wait in between
-    const int m = std::min(n - done, (int)c->ev_depth);
-    HIPCHK(c, hipMemsetAsync(c->ev_ctl.p, 0, 64, c->stream));      // iteration counter and health words of this piece
-    if (int rc = c->comm ? iterate_sharded_ev(c, a, m) : iterate_plain(c, a, m, true)) return rc;      // (a sharded ctx: launched directly, both schedules)
-    launch_eval_ride(a.ev, P<uint32_t>(c->row_cam), P<uint32_t>(c->lmk_idx), P<int>(c->fst_packed), P<float4>(c->fac), P<float>(c->dK), c->stream);
+    const int m = std::min(n - done, (int)c->metric.ev_depth);
+    HIPCHK(c, hipMemsetAsync(c->metric.ev_ctl.p, 0, 64, c->stream));      // iteration counter and health words of this piece
+    if (int rc = c->xch.comm ? iterate_sharded_ev(c, a, m) : iterate_plain(c, a, m, true)) return rc;      // (a sharded ctx: launched directly, both schedules)
+    launch_eval_ride(a.ev, P<uint32_t>(c->arr.row_cam), P<uint32_t>(c->arr.lmk_idx), P<int>(c->arr.fst_packed), P<float4>(c->arr.fac), P<float>(c->arr.dK), c->stream);
     launch_eval_fold(a.ev, (uint32_t)m, results + done, c->stream);
     HIPCHK(c, hipGetLastError());
     done += m;
@@ -288,7 +280,7 @@ static int eval_each_ride(gbp_ctx* c, int n, gbp_eval_out* out, bool dev = false
     if (int rc = sp.commit((uint64_t)n)) return rc;
   if (dev) return GBP_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::memcpy(out, c->ev_host, sizeof(gbp_eval_out) * (size_t)n);
+  std::memcpy(out, c->metric.ev_results.host, sizeof(gbp_eval_out) * (size_t)n);
   return GBP_OK;
 }
 
@@ -297,19 +289,19 @@ static int eval_each_ride(gbp_ctx* c, int n, gbp_eval_out* out, bool dev = false
 // out[k] = what gbp_iterate(1) + gbp_eval_global() would have returned.  kNotLaunched: nothing ran, or the launch timed out and the state
 // (priors and flags too) was restored to the start of the burst — the caller runs the passes on the two-kernel path.
 static int series_burst(gbp_ctx* c, int m, unsigned i, unsigned steps2, gbp_eval_out* out) {
-  const int area = c->eval_parity & 1;   // both health areas are zero between evaluations; this launch leaves them so
+  const int area = c->metric.parity & 1;   // both health areas are zero between evaluations; this launch leaves them so
   const PersistEval metric = persist_eval(c, area, true);
   TimedSpan sp(c);
   if (int rc = sp.begin()) return rc;
   if (int rc = launch_persist_burst(c, sweep_args(c), m, &metric, 2, area, i, steps2)) return rc;
   if (int rc = sp.end()) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const bool failed = *static_cast<volatile unsigned*>(c->pstatus_host) != 0u;
+  const bool failed = *static_cast<volatile unsigned*>(c->persist.status.host) != 0u;
   if (int rc = persist_check(c, 0)) return rc;
   if (failed) return kNotLaunched;
   if (int rc = sp.commit((uint64_t)m)) return rc;
   for (int k = 0; k < m; ++k)
-    sum_eval(c, static_cast<const DeviceEval*>(c->series_host) + (size_t)k * metric.stride, eval_blocks(c->n_tiles), out + k, true);
+    sum_eval(c, static_cast<const DeviceEval*>(c->persist.series.host) + (size_t)k * metric.stride, eval_blocks(c->n_tiles), out + k, true);
   return GBP_OK;
 }
 
@@ -319,11 +311,11 @@ static int series_burst(gbp_ctx* c, int m, unsigned i, unsigned steps2, gbp_eval
 // (settle / persist_check) and finds that it timed out restores the snapshot and replays it on the riding path into the same records
 // (persist_recover -> replay_series_dev).  The only host-mapped word involved is the status word of the kernel.
 static int series_burst_dev(gbp_ctx* c, int m, unsigned i, unsigned steps2, gbp_eval_out* out) {
-  if (!c->series_twin.p)
-    if (int rc = dev_alloc(c, c->series_twin, sizeof(DeviceEval) * (size_t)(c->n_tiles + 1) * kSeriesMax)) return rc;
-  const int area = c->eval_parity & 1;
+  if (!c->metric.series_twin.p)
+    if (int rc = dev_alloc(c, c->metric.series_twin, sizeof(DeviceEval) * (size_t)(c->n_tiles + 1) * kSeriesMax)) return rc;
+  const int area = c->metric.parity & 1;
   PersistEval metric = persist_eval(c, area, true);
-  metric.slots = P<DeviceEval>(c->series_twin);
+  metric.slots = P<DeviceEval>(c->metric.series_twin);
   TimedSpan sp(c);
   if (int rc = sp.begin()) return rc;
   if (int rc = launch_persist_burst(c, sweep_args(c), m, &metric, 3, area, i, steps2, out)) return rc;
@@ -371,11 +363,11 @@ static int iterate_passes_eval(gbp_ctx* c, int n, unsigned i0, unsigned steps2, 
     if (dev)
       if (int rc = settle(c)) return rc;
     const int m = weakening_free_run(n - done, i, steps2);
-    bool ride = !c->comm && c->world == 1 && c->hoist && !c->profile_stages && !stream_is_capturing(c);
-    if (c->comm) {      // a ctx with a communicator: the decision and its record (gbp_comm_describe: "metric")
-      ride = metric_rides(c->comm->kind(), c->world, c->hoist, c->profile_stages, stream_is_capturing(c), &c->metric_reason);
-      c->metric_last = ride ? 1 : 2;
-      (ride ? c->metric_riding : c->metric_per_pass) += (uint64_t)m;
+    bool ride = !c->xch.comm && c->world == 1 && c->hoist && !c->tm.profile_stages && !stream_is_capturing(c);
+    if (c->xch.comm) {      // a ctx with a communicator: the decision and its record (gbp_comm_describe: "metric")
+      ride = metric_rides(c->xch.comm->kind(), c->world, c->hoist, c->tm.profile_stages, stream_is_capturing(c), &c->xch.metric_reason);
+      c->xch.metric_last = ride ? 1 : 2;
+      (ride ? c->xch.metric_riding : c->xch.metric_per_pass) += (uint64_t)m;
     }
     if (ride) {
       if (int rc = eval_each_ride(c, m, out + done, dev)) return rc;
@@ -386,7 +378,7 @@ static int iterate_passes_eval(gbp_ctx* c, int n, unsigned i0, unsigned steps2, 
       for (int k = done; k < done + m; ++k) {
         if (int rc = iterate(c, 1)) return rc;
         if (int rc = eval_begin(c)) return rc;
-        if (c->eval_pending == 2) { if (int rc = eval_end(c, out + collected)) return rc; ++collected; }
+        if (c->metric.pending == 2) { if (int rc = eval_end(c, out + collected)) return rc; ++collected; }
       }
       while (collected < done + m) { if (int rc = eval_end(c, out + collected)) return rc; ++collected; }
     }
@@ -398,7 +390,7 @@ static int iterate_passes_eval(gbp_ctx* c, int n, unsigned i0, unsigned steps2, 
 static int iterate_eval_each(gbp_ctx* c, int n, gbp_eval_out* out) {
   if (!c || !c->uploaded) return fail(c, GBP_ERR_STATE, "gbp_iterate_eval_each: upload first");
   if (n < 0 || (n > 0 && !out)) return fail(c, GBP_ERR_INVALID, "gbp_iterate_eval_each: n >= 0 and an array of n results");
-  if (c->eval_pending) return fail(c, GBP_ERR_STATE, "gbp_iterate_eval_each: finish the evaluations in flight (gbp_eval_end) first");
+  if (c->metric.pending) return fail(c, GBP_ERR_STATE, "gbp_iterate_eval_each: finish the evaluations in flight (gbp_eval_end) first");
   bool dev = false;
   if (out)
     if (int rc = out_kind(c, "gbp_iterate_eval_each", out, &dev)) return rc;
@@ -417,12 +409,12 @@ static int ba_loop(gbp_ctx* c, int n, unsigned iter0, unsigned steps, gbp_eval_o
   if (steps >= (1u << 30)) return fail(c, GBP_ERR_INVALID, "gbp_ba_loop: steps < 2^30 (the loop's test is iter < 2 * steps)");
   const unsigned steps2 = 2u * steps;
   if (out) {
-    if (c->eval_pending) return fail(c, GBP_ERR_STATE, "gbp_ba_loop: finish the evaluations in flight (gbp_eval_end) first");
+    if (c->metric.pending) return fail(c, GBP_ERR_STATE, "gbp_ba_loop: finish the evaluations in flight (gbp_eval_end) first");
     bool dev = false;
     if (int rc = out_kind(c, "gbp_ba_loop", out, &dev)) return rc;
     return iterate_passes_eval(c, n, iter0, steps2, out, dev);
   }
-  const bool one_call = !c->comm && c->world == 1 && !c->profile_stages && !stream_is_capturing(c);
+  const bool one_call = !c->xch.comm && c->world == 1 && !c->tm.profile_stages && !stream_is_capturing(c);
   for (int done = 0; done < n;) {
     const unsigned i = iter0 + (unsigned)done;
     if (weakens_before(i, steps2))

@@ -18,50 +18,50 @@ namespace api {
 // (every path that runs sweeps — direct launches, graph captures, the persistent kernel — takes its arguments from here, so from here
 // on the camera messages count as live: what gbp_linearise_factors looks at)
 SweepArgs sweep_args(gbp_ctx* c, bool sweeps) {
-  if (sweeps) c->cmsg_zero = false;
+  if (sweeps) c->arr.cmsg_zero = false;
   SweepArgs a;
-  a.row_cam = P<uint32_t>(c->row_cam); a.lmk_idx = P<uint32_t>(c->lmk_idx); a.fac = P<float4>(c->fac); a.cmsg = P<float4>(c->cmsg);
-  a.cmsg_lit = P<float4>(c->cmsg_lit);
-  a.mu = P<float4>(c->mu); a.lmsg = P<float4>(c->lmsg); a.fst_packed = P<int>(c->fst_packed); a.fst_damp = P<float>(c->fst_damp); a.fst_var = P<float>(c->fst_var); a.camb = P<float4>(c->camb); a.lmkb = P<float4>(c->lmkb);
-  a.rowp = P<float4>(c->rowp);
-  a.cam_mu = P<float4>(c->hmu_c); a.lmk_mu = P<float4>(c->hmu_l); a.cam_lin = P<float4>(c->clin);
+  a.row_cam = P<uint32_t>(c->arr.row_cam); a.lmk_idx = P<uint32_t>(c->arr.lmk_idx); a.fac = P<float4>(c->arr.fac); a.cmsg = P<float4>(c->arr.cmsg);
+  a.cmsg_lit = P<float4>(c->arr.cmsg_lit);
+  a.mu = P<float4>(c->arr.mu); a.lmsg = P<float4>(c->arr.lmsg); a.fst_packed = P<int>(c->arr.fst_packed); a.fst_damp = P<float>(c->arr.fst_damp); a.fst_var = P<float>(c->arr.fst_var); a.camb = P<float4>(c->arr.camb); a.lmkb = P<float4>(c->arr.lmkb);
+  a.rowp = P<float4>(c->arr.rowp);
+  a.cam_mu = P<float4>(c->arr.hmu_c); a.lmk_mu = P<float4>(c->arr.hmu_l); a.cam_lin = P<float4>(c->arr.clin);
   std::memcpy(a.K, c->K, sizeof(a.K));
   a.hp.maxeta_damping = c->prm.maxeta_damping; a.hp.num_undamped_iters = c->prm.num_undamped_iters;
   a.hp.dmu_threshold = c->prm.dmu_threshold; a.hp.min_linear_iters = c->prm.min_linear_iters;
   a.hp.nstds = c->prm.nstds; a.hp.relin_mode = c->prm.relin_mode;
   a.variant = c->prm.reserved[0];      // read by the experiments build only
-  a.tile_perm = c->use_tile_perm ? P<uint32_t>(c->tile_perm) : nullptr;
-  a.seg_live = c->use_seg_live ? P<uint32_t>(c->seg_live) : nullptr;
+  a.tile_perm = c->use_tile_perm ? P<uint32_t>(c->arr.tile_perm) : nullptr;
+  a.seg_live = c->use_seg_live ? P<uint32_t>(c->arr.seg_live) : nullptr;
   a.policy = c->sweep_policy;
   a.ev = EvalRide{};
   return a;
 }
 
 void drop_graph(gbp_ctx* c) {
-  if (c->graph_exec) { (void)hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
-  if (c->graph) { (void)hipGraphDestroy(c->graph); c->graph = nullptr; }
-  if (c->graph_exec_ev) { (void)hipGraphExecDestroy(c->graph_exec_ev); c->graph_exec_ev = nullptr; }
-  if (c->graph_ev) { (void)hipGraphDestroy(c->graph_ev); c->graph_ev = nullptr; }
-  c->graph_iters = 0;
+  if (c->graph.exec) { (void)hipGraphExecDestroy(c->graph.exec); c->graph.exec = nullptr; }
+  if (c->graph.g) { (void)hipGraphDestroy(c->graph.g); c->graph.g = nullptr; }
+  if (c->graph.exec_ev) { (void)hipGraphExecDestroy(c->graph.exec_ev); c->graph.exec_ev = nullptr; }
+  if (c->graph.g_ev) { (void)hipGraphDestroy(c->graph.g_ev); c->graph.g_ev = nullptr; }
+  c->graph.iters = 0;
 }
 
 BeliefArgs belief_args(gbp_ctx* c) {
   BeliefArgs b{};
-  b.rowp = P<float>(c->rowp); b.cam_row_ptr = P<uint32_t>(c->d_cam_row_ptr); b.cam_prior = P<float>(c->camp);
-  b.row_slot = c->lay.row_slot.empty() ? nullptr : P<uint32_t>(c->d_row_slot);
-  b.cam_local = P<float>(c->local); b.gathered = nullptr; b.world = c->world;
-  b.camb = P<float>(c->camb); b.cam_mu = P<float4>(c->hmu_c); b.cam_lin = P<float4>(c->clin); b.n_cams = c->C;
-  b.lmk_prior = P<float4>(c->lmkp); b.lmsg = P<float4>(c->lmsg); b.lmk_ptr = P<uint32_t>(c->d_lmk_ptr);
-  b.lmk_fpos = P<uint32_t>(c->d_lmk_fpos); b.lmk_ix = P<uint32_t>(c->d_lmk_ix);
-  b.lmkb = P<float4>(c->lmkb); b.lmk_mu = P<float4>(c->hmu_l); b.n_lmks = c->L_loc;
+  b.rowp = P<float>(c->arr.rowp); b.cam_row_ptr = P<uint32_t>(c->arr.d_cam_row_ptr); b.cam_prior = P<float>(c->arr.camp);
+  b.row_slot = c->lay.row_slot.empty() ? nullptr : P<uint32_t>(c->arr.d_row_slot);
+  b.cam_local = P<float>(c->arr.local); b.gathered = nullptr; b.world = c->world;
+  b.camb = P<float>(c->arr.camb); b.cam_mu = P<float4>(c->arr.hmu_c); b.cam_lin = P<float4>(c->arr.clin); b.n_cams = c->C;
+  b.lmk_prior = P<float4>(c->arr.lmkp); b.lmsg = P<float4>(c->arr.lmsg); b.lmk_ptr = P<uint32_t>(c->arr.d_lmk_ptr);
+  b.lmk_fpos = P<uint32_t>(c->arr.d_lmk_fpos); b.lmk_ix = P<uint32_t>(c->arr.d_lmk_ix);
+  b.lmkb = P<float4>(c->arr.lmkb); b.lmk_mu = P<float4>(c->arr.hmu_l); b.n_lmks = c->L_loc;
   b.partial_only = 0; b.hoist = c->hoist ? 1 : 0; b.roll = 0;
   b.lmk_blocks = 0; b.lmk_xcd_order = c->prm.tile_order != 1 ? 1 : 0;
   return b;
 }
 
 void weaken_args(gbp_ctx* c, BeliefArgs& b) {
-  b.cam_prior_rw = P<float>(c->camp); b.cam_scale = P<float>(c->cscale); b.cam_wflag = P<uint32_t>(c->cwf);
-  b.lmk_prior_rw = P<float4>(c->lmkp); b.lmk_scale = P<float>(c->lscale); b.lmk_wflag = P<uint32_t>(c->lwf);
+  b.cam_prior_rw = P<float>(c->arr.camp); b.cam_scale = P<float>(c->arr.cscale); b.cam_wflag = P<uint32_t>(c->arr.cwf);
+  b.lmk_prior_rw = P<float4>(c->arr.lmkp); b.lmk_scale = P<float>(c->arr.lscale); b.lmk_wflag = P<uint32_t>(c->arr.lwf);
 }
 
 
@@ -105,10 +105,10 @@ void enqueue_cam_partials(gbp_ctx* c, float* dst, hipStream_t s) {
 // out of capture mode, drops the partial graph and falls back to direct launches for the life of the ctx (results are
 // identical either way).
 static bool ensure_graph(gbp_ctx* c, const SweepArgs& a, bool ev = false) {
-  hipGraph_t& g = ev ? c->graph_ev : c->graph;
-  hipGraphExec_t& x = ev ? c->graph_exec_ev : c->graph_exec;
+  hipGraph_t& g = ev ? c->graph.g_ev : c->graph.g;
+  hipGraphExec_t& x = ev ? c->graph.exec_ev : c->graph.exec;
   if (x) return true;
-  if (c->graph_failed || c->prm.graph_unroll <= 0 || c->stream != c->own_stream) return false;
+  if (c->graph.failed || c->prm.graph_unroll <= 0 || c->stream != c->own_stream) return false;
   hipError_t e = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
   if (e == hipSuccess) {
     for (int i = 0; i < c->prm.graph_unroll; ++i) enqueue_iteration(c, a, ev);
@@ -118,10 +118,10 @@ static bool ensure_graph(gbp_ctx* c, const SweepArgs& a, bool ev = false) {
   if (e != hipSuccess) {
     (void)hipGetLastError();
     drop_graph(c);
-    c->graph_failed = true;
+    c->graph.failed = true;
     return false;
   }
-  c->graph_iters = c->prm.graph_unroll;
+  c->graph.iters = c->prm.graph_unroll;
   return true;
 }
 
@@ -130,12 +130,12 @@ static bool ensure_graph(gbp_ctx* c, const SweepArgs& a, bool ev = false) {
 // counter in device memory, so they replay from a graph of their own)
 int iterate_plain(gbp_ctx* c, const SweepArgs& a, int n, bool ev) {
   int left = n;
-  bool use_graph = (c->stream == c->own_stream) && c->prm.graph_unroll > 0 && n >= c->prm.graph_unroll && !c->graph_failed;
-  if (use_graph && !(ev ? c->graph_exec_ev : c->graph_exec)) use_graph = ensure_graph(c, a, ev);
+  bool use_graph = (c->stream == c->own_stream) && c->prm.graph_unroll > 0 && n >= c->prm.graph_unroll && !c->graph.failed;
+  if (use_graph && !(ev ? c->graph.exec_ev : c->graph.exec)) use_graph = ensure_graph(c, a, ev);
   if (use_graph) {
-    while (left >= c->graph_iters) {
-      HIPCHK(c, hipGraphLaunch(ev ? c->graph_exec_ev : c->graph_exec, c->stream));
-      left -= c->graph_iters;
+    while (left >= c->graph.iters) {
+      HIPCHK(c, hipGraphLaunch(ev ? c->graph.exec_ev : c->graph.exec, c->stream));
+      left -= c->graph.iters;
     }
   }
   for (; left > 0; --left) enqueue_iteration(c, a, ev);
@@ -199,7 +199,7 @@ int iterate_passes(gbp_ctx* c, int n, unsigned i0, unsigned steps2) {
 int iterate(gbp_ctx* c, int n) {
   if (!c || !c->uploaded) return fail(c, GBP_ERR_STATE, "gbp_iterate: upload first");
   if (n <= 0) return GBP_OK;
-  if (c->comm) {
+  if (c->xch.comm) {
     if (int rc = settle(c)) return rc;
     return iterate_sharded(c, n);
   }
@@ -215,7 +215,7 @@ int iterate(gbp_ctx* c, int n) {
     c->beliefs_valid = true;
     return GBP_OK;
   }
-  if (c->profile_stages) {
+  if (c->tm.profile_stages) {
     // Per-stage timing: all n iterations are queued back to back with a hipEvent before / between / after the
     // two kernels, and read after ONE synchronisation, so a bracket holds the kernel (plus the ~1 us
     // dependent-launch gap), not the idle-queue start-up latency a per-iteration sync would add.
@@ -244,7 +244,7 @@ int iterate(gbp_ctx* c, int n) {
       float a_ms = 0, b_ms = 0;
       HIPCHK(c, hipEventElapsedTime(&a_ms, ev[2 * i], ev[2 * i + 1]));
       HIPCHK(c, hipEventElapsedTime(&b_ms, ev[2 * i + 1], ev[2 * i + 2]));
-      c->sweep_ms += a_ms; c->belief_ms += b_ms;
+      c->tm.sweep_ms += a_ms; c->tm.belief_ms += b_ms;
     }
     HIPCHK(c, hipGetLastError());
     return sp.commit((uint64_t)n);
@@ -268,7 +268,7 @@ GBP_EXPORT(gbp_weaken_priors, c, (gbp_ctx* c), (c)) { return weaken_priors(c); }
 GBP_EXPORT(gbp_refresh_begin, c, (gbp_ctx* c), (c)) {
   if (!c || !c->uploaded) return fail(c, GBP_ERR_STATE, "upload first");
   if (int rc = settle(c)) return rc;
-  float4* dst = exch(c) ? static_cast<float4*>(c->send_dev) : P<float4>(c->local);
+  float4* dst = exch(c) ? static_cast<float4*>(c->xch.send_dev) : P<float4>(c->arr.local);
   if (!dst) return fail(c, GBP_ERR_STATE, "exchange buffers not set");
   enqueue_cam_partials(c, reinterpret_cast<float*>(dst));
   HIPCHK(c, hipGetLastError());
@@ -286,11 +286,11 @@ GBP_EXPORT(gbp_refresh_end, c, (gbp_ctx* c), (c)) {
 GBP_EXPORT(gbp_linearise_factors, c, (gbp_ctx* c), (c)) {
   if (!c || !c->uploaded) return fail(c, GBP_ERR_STATE, "upload first");
   if (int rc = settle(c)) return rc;
-  if (!c->cmsg_zero && !c->cmsg_lit.p) {
+  if (!c->arr.cmsg_zero && !c->arr.cmsg_lit.p) {
     // LINEARISE under live messages: k_linearise rewrites the potentials the kCmsgDerived records derive their Lambda from, so it
     // first makes those records literal (gbp_kernels.h: CMSG) — in a side array that only such a call pays for.  A captured graph
     // holds the sweep's arguments without it: dropped, the next burst captures again.
-    if (int rc = dev_alloc(c, c->cmsg_lit, (size_t)c->Ep * kCmsgLitG * 16)) return rc;
+    if (int rc = dev_alloc(c, c->arr.cmsg_lit, (size_t)c->Ep * kCmsgLitG * 16)) return rc;
     drop_graph(c);
   }
   launch_linearise(sweep_args(c, /*sweeps=*/false), c->n_tiles, c->stream);
@@ -301,10 +301,10 @@ GBP_EXPORT(gbp_linearise_factors, c, (gbp_ctx* c), (c)) {
 // LINEARISE_PROG (ba.cpp:890-893): prog_ub, then RelineariseFactorVertex on every factor.
 GBP_EXPORT(gbp_linearise, c, (gbp_ctx* c), (c)) {
   if (!c || !c->uploaded) return fail(c, GBP_ERR_STATE, "gbp_linearise: upload first");
-  if (c->world > 1 && !c->comm)
+  if (c->world > 1 && !c->xch.comm)
     return fail(c, GBP_ERR_STATE, "sharded ctx without a communicator: gbp_comm_init first, or use refresh_begin / exchange / refresh_end / linearise_factors");
   int rc = gbp_refresh_begin(c);
-  if (rc == GBP_OK && c->comm) rc = exchange_now(c);
+  if (rc == GBP_OK && c->xch.comm) rc = exchange_now(c);
   if (rc == GBP_OK) rc = gbp_refresh_end(c);
   if (rc == GBP_OK) rc = gbp_linearise_factors(c);
   return rc;
@@ -313,17 +313,13 @@ GBP_EXPORT(gbp_linearise, c, (gbp_ctx* c), (c)) {
 GBP_EXPORT(gbp_iterate_begin, c, (gbp_ctx* c), (c)) {
   if (!c || !c->uploaded) return fail(c, GBP_ERR_STATE, "upload first");
   if (int rc = settle(c)) return rc;
-  float4* dst = exch(c) ? static_cast<float4*>(c->send_dev) : P<float4>(c->local);
+  float4* dst = exch(c) ? static_cast<float4*>(c->xch.send_dev) : P<float4>(c->arr.local);
   if (!dst) return fail(c, GBP_ERR_STATE, "exchange buffers not set");
-  if (c->profile_stages) {  // bracket the sweep launch; the pair is read (and timed_iters counted) by gbp_timing
-    if (c->pending_sweep_ev.size() >= 256) drain_sweep_events(c);   // bounded: long profiled runs never pile up events
+  if (c->tm.profile_stages) {  // bracket the sweep launch; the pair is read (and timed_iters counted) by gbp_timing
+    if (c->tm.pending_sweep_ev.size() >= 256) drain_sweep_events(c);   // bounded: long profiled runs never pile up events
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(c, hipEventCreate(&e0));
-    if (hipError_t e_ = hipEventCreate(&e1); e_ != hipSuccess) {
-      (void)hipEventDestroy(e0);
-      return fail(c, GBP_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e_));
-    }
-    c->pending_sweep_ev.emplace_back(e0, e1);
+    if (int rc = event_pair(c, &e0, &e1)) return rc;
+    c->tm.pending_sweep_ev.push_back({e0, e1});
     HIPCHK(c, hipEventRecord(e0, c->stream));
     launch_sweep(sweep_args(c), c->n_tiles, c->hoist, c->stream);
     HIPCHK(c, hipEventRecord(e1, c->stream));
@@ -362,9 +358,9 @@ GBP_EXPORT(gbp_iterate_end, c, (gbp_ctx* c), (c)) {
 GBP_EXPORT(gbp_prepare, c, (gbp_ctx* c), (c)) {
   if (!c || !c->uploaded) return fail(c, GBP_ERR_STATE, "gbp_prepare: upload first");
   if (int rc = settle(c)) return rc;
-  if (c->comm || c->world > 1) return GBP_OK;               // sharded iterations run from direct launches by default
-  if (c->persist_ok) return GBP_OK;                         // multi-iteration bursts run inside k_persist: nothing to capture
-  if (ensure_graph(c, sweep_args(c))) (void)hipGraphUpload(c->graph_exec, c->stream);
+  if (c->xch.comm || c->world > 1) return GBP_OK;               // sharded iterations run from direct launches by default
+  if (c->persist.ok) return GBP_OK;                         // multi-iteration bursts run inside k_persist: nothing to capture
+  if (ensure_graph(c, sweep_args(c))) (void)hipGraphUpload(c->graph.exec, c->stream);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return GBP_OK;
 }

@@ -30,7 +30,7 @@ namespace gbp {
 namespace api {
 
 void persist_forget(gbp_ctx* c) {
-  if (!c->persist_eligible) return;
+  if (!c->persist.eligible) return;
   // its launches have ended before its memory goes away; the "last launcher" words are only ever compared
   (void)hipStreamSynchronize(c->stream);
   std::lock_guard<std::mutex> lock(g_persist_mu);
@@ -40,23 +40,19 @@ void persist_forget(gbp_ctx* c) {
 // gbp_upload: whatever the launches in flight did is overwritten by the upload; a ctx that left the persistent path after a
 // recovered time-out gets it back
 int persist_reset(gbp_ctx* c) {
-  if (!c->pstatus_host) return GBP_OK;
-  c->persist_log.clear();
-  HIPCHK(c, hipMemsetAsync(c->psync.p, 0, kPersistSyncWords * sizeof(unsigned), c->stream));
+  if (!c->persist.status.host) return GBP_OK;
+  c->persist.log.clear();
+  HIPCHK(c, hipMemsetAsync(c->persist.psync.p, 0, kPersistSyncWords * sizeof(unsigned), c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  *static_cast<volatile unsigned*>(c->pstatus_host) = 0u;
-  c->persist_epoch_base = 0;
-  c->persist_ok = c->persist_eligible;
+  *static_cast<volatile unsigned*>(c->persist.status.host) = 0u;
+  c->persist.epoch_base = 0;
+  c->persist.ok = c->persist.eligible;
   return GBP_OK;
 }
 
 // The persistent kernel for this ctx, or nothing (not eligible / not co-resident: the ctx stays on the two-kernel path, with the
 // reason in gbp_last_error where there is one).  Returns an error only when a HIP call failed.
 int persist_setup(gbp_ctx* c, const gbp_params* prm, bool sharded) {
-  int rc = GBP_OK;
-  auto CK = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && rc == GBP_OK) { create_error() = std::string(what) + ": " + hipGetErrorString(e); rc = GBP_ERR_HIP; }
-  };
   const char* pe = prm ? nullptr : std::getenv("GBP_PERSIST");     // measurements through the CLIs (they pass no params): -1 / 0 / 1 like gbp_params.persistent
   const int mode = pe ? std::atoi(pe) : c->prm.persistent;
   const char* pc = prm ? nullptr : std::getenv("GBP_PERSIST_COOP");
@@ -70,119 +66,101 @@ int persist_setup(gbp_ctx* c, const gbp_params* prm, bool sharded) {
   // (k_persist sweeps tile w on wave w and its camera role adds rows cam_row_ptr[c] .. cam_row_ptr[c + 1] where camera-major order
   // puts them: a graph with a tile permutation or with rows placed by landmark class never runs in it, whatever the size
   // thresholds of the three features say)
-  if (mode >= 0 && !sharded && c->hoist && !c->use_tile_perm && c->lay.row_slot.empty() && nb <= (mode > 0 ? 1u << 30 : auto_limit)) {
-    const int resident = persist_max_resident_blocks();
-    if (resident > 0 && nb <= (uint32_t)resident) {
-      rc = dev_alloc(c, c->psync, kPersistSyncWords * sizeof(unsigned));
-      if (rc == GBP_OK) {
-        CK(hipHostMalloc(&c->pstatus_host, 64, hipHostMallocMapped), "hipHostMalloc");
-        if (rc == GBP_OK) {
-          std::memset(c->pstatus_host, 0, 64);
-          CK(hipHostGetDevicePointer(&c->pstatus_dev, c->pstatus_host, 0), "hipHostGetDevicePointer");
-        }
-      } else {
-        create_error() = c->err;
-      }
-      if (rc == GBP_OK) {
-        // Co-residency.  Plain launch (default): the occupancy query says the workgroups fit; a probe (the placement + three
-        // barriers, no work) checks that THIS device's dispatcher keeps them resident together — under the process-wide lock
-        // and behind the device's last k_persist launch, so that it does not compete with one; what another PROCESS does to
-        // the GPU later is caught by the bounded barrier wait and undone by persist_recover.  Cooperative launch (persist_coop
-        // = 1): the runtime refuses a grid that cannot be resident at once and the driver never runs two cooperative grids
-        // side by side, whichever process they belong to — measured on MI355X: two concurrent `ba fr1xyz` then take turns
-        // (44 ms each instead of 22), and every launch costs 30-60 us more (profiles/r04_persist_launch.md), which is why
-        // it is the option and not the default.  A failing probe leaves the ctx on the two-kernel path and says so in
-        // gbp_last_error.
-        int dev = 0, coop_attr = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&coop_attr, hipDeviceAttributeCooperativeLaunch, dev);
-        std::lock_guard<std::mutex> lock(g_persist_mu);
-        if (g_persist_event[dev & 15] && g_persist_last_ctx[dev & 15]) (void)hipStreamWaitEvent(c->stream, g_persist_event[dev & 15], 0);
-        bool ok = false;
-        const auto t_probe = std::chrono::steady_clock::now();
-        if (coop_mode > 0 && coop_attr) {
-          ok = persist_probe(c->n_tiles, c->C, c->L_loc, P<unsigned>(c->psync), static_cast<unsigned*>(c->pstatus_dev),
-                             static_cast<volatile unsigned*>(c->pstatus_host), true, c->stream);
-          c->persist_coop = ok;
-          if (!ok) c->err = "k_persist: the cooperative launch was refused or its barriers timed out";
-        }
-        if (coop_mode > 0 && !coop_attr) c->err = "k_persist: this device does not offer cooperative launches";
-        if (coop_mode <= 0) {
-          ok = persist_probe(c->n_tiles, c->C, c->L_loc, P<unsigned>(c->psync), static_cast<unsigned*>(c->pstatus_dev),
-                             static_cast<volatile unsigned*>(c->pstatus_host), false, c->stream);
-          if (!ok) c->err = "k_persist: the workgroups of this graph are not co-resident under the spread placement on this device (probe timed out)";
-        }
-        c->probe_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_probe).count();
-        if (!ok) c->err += "; iterations run on the two-kernel path";
-        c->persist_ok = c->persist_eligible = ok;
-        if (ok) CK(hipMemsetAsync(c->psync.p, 0, kPersistSyncWords * sizeof(unsigned), c->stream), "hipMemsetAsync");   // counter back to 0 after the probe
-        else (void)hipGetLastError();
-      }
-      if (rc == GBP_OK && c->persist_ok) {
-        // snapshot arena: one slot for every array a k_persist launch mutates
-        // (+ the priors and the weaken flags: a launch of gbp_ba_loop weakens priors itself)
-        DevBuf* segs[] = {&c->lmsg, &c->fst_packed, &c->fst_damp, &c->cmsg, &c->fac, &c->rowp, &c->camb, &c->lmkb, &c->hmu_c, &c->hmu_l, &c->clin, &c->local,
-                          &c->camp, &c->lmkp, &c->cwf, &c->lwf};
-        static_assert(sizeof(segs) / sizeof(segs[0]) <= (size_t)kMaxCopySegs, "k_copy_segments takes kMaxCopySegs segments");
-        size_t total = 0;
-        for (DevBuf* b : segs) total += (b->bytes + 15) / 16 * 16;
-        rc = dev_alloc(c, c->psnap, total);
-        if (rc == GBP_OK) {
-          size_t off = 0;
-          int i = 0;
-          for (DevBuf* b : segs) {
-            void* slot = static_cast<char*>(c->psnap.p) + off;
-            c->snap_save.src[i] = b->p; c->snap_save.dst[i] = slot; c->snap_save.n4[i] = (b->bytes + 15) / 16;      // (hipMalloc granules are larger)
-            c->snap_restore.src[i] = slot; c->snap_restore.dst[i] = b->p; c->snap_restore.n4[i] = (b->bytes + 15) / 16;
-            off += (b->bytes + 15) / 16 * 16;
-            ++i;
-          }
-          c->snap_save.n = c->snap_restore.n = i;
-        } else {
-          create_error() = c->err;
-        }
-      }
-      if (rc == GBP_OK && c->persist_ok) {
-        // tagged shadows of the arrays that cross waves inside a launch (k_persist_flow): two halves each
-        const size_t Ep = (size_t)c->n_tiles * 64, C_ = c->C, L_ = c->L_loc;
-        const size_t n4[10] = {2 * Ep * 4, 2 * (Ep / 16) * kFlowRow4, 2 * C_ * kFlowCam4, 2 * C_ * 2, 2 * C_ * kFlowClin4, 2 * L_ * kFlowLmk4, 2 * L_,
-                               2 * C_ * 4, 2 * L_, (size_t)kSeriesMax};      // (the last: [kSeriesMax][2] 64-bit health words = kSeriesMax float4)
-        size_t total = 0;
-        for (size_t n : n4) total += n;
-#ifdef GBP_BUILD_TEST_HOOKS
-        // gbp_debug_persist_verify: room for the redundant copy of every record + the mismatch counter (the product allocates neither)
-        rc = dev_alloc(c, c->pflow, 2 * total * 16 + 64);
-        c->flow_total4 = (uint32_t)total;
-#else
-        rc = dev_alloc(c, c->pflow, total * 16);
-#endif
-        if (rc == GBP_OK) {
-          float4* q = static_cast<float4*>(c->pflow.p);
-          float4** dst[9] = {&c->flow.lmsg, &c->flow.rowp, &c->flow.camb, &c->flow.cmu, &c->flow.clin, &c->flow.lmkb, &c->flow.lmu, &c->flow.emc, &c->flow.eml};
-          for (int i = 0; i < 9; ++i) { *dst[i] = q; q += n4[i]; }
-          c->flow.health_iter = reinterpret_cast<unsigned long long*>(q);
-          // the host-mapped slots of gbp_iterate_eval_each / gbp_ba_loop: here, not inside the first timed burst (pinning 5 MB takes
-          // ~0.5 ms, a twentieth of a default `ba fr1xyz` run).  gbp_create fails without them: every ctx that can reach the
-          // persistent path has them (series_burst relies on it)
-          if (!c->series_host) {
-            CK(hipHostMalloc(&c->series_host, sizeof(DeviceEval) * (size_t)(c->n_tiles + 1) * kSeriesMax, hipHostMallocMapped), "hipHostMalloc");
-            if (rc == GBP_OK) CK(hipHostGetDevicePointer(&c->series_dev, c->series_host, 0), "hipHostGetDevicePointer");
-          }
-#ifdef GBP_BUILD_TEST_HOOKS
-          const char* pf = prm ? nullptr : std::getenv("GBP_PERSIST_FLOW");      // (the barrier kernel exists in the test-hooks build only)
-          if (pf && std::atoi(pf) == 0) c->persist_flow = false;
-#endif
-        } else {
-          create_error() = c->err;
-        }
-      }
+  if (mode < 0 || sharded || !c->hoist || c->use_tile_perm || !c->lay.row_slot.empty() || nb > (mode > 0 ? 1u << 30 : auto_limit)) return GBP_OK;
+  const int resident = persist_max_resident_blocks();
+  if (resident <= 0 || nb > (uint32_t)resident) return GBP_OK;
+  if (int rc = dev_alloc(c, c->persist.psync, kPersistSyncWords * sizeof(unsigned))) return rc;
+  if (int rc = mapped_alloc(c, c->persist.status, 64)) return rc;
+  std::memset(c->persist.status.host, 0, 64);
+  {
+    // Co-residency.  Plain launch (default): the occupancy query says the workgroups fit; a probe (the placement + three
+    // barriers, no work) checks that THIS device's dispatcher keeps them resident together — under the process-wide lock
+    // and behind the device's last k_persist launch, so that it does not compete with one; what another PROCESS does to
+    // the GPU later is caught by the bounded barrier wait and undone by persist_recover.  Cooperative launch (persist_coop
+    // = 1): the runtime refuses a grid that cannot be resident at once and the driver never runs two cooperative grids
+    // side by side, whichever process they belong to — measured on MI355X: two concurrent `ba fr1xyz` then take turns
+    // (44 ms each instead of 22), and every launch costs 30-60 us more (profiles/r04_persist_launch.md), which is why
+    // it is the option and not the default.  A failing probe leaves the ctx on the two-kernel path and says so in
+    // gbp_last_error.
+    int dev = 0, coop_attr = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&coop_attr, hipDeviceAttributeCooperativeLaunch, dev);
+    std::lock_guard<std::mutex> lock(g_persist_mu);
+    if (g_persist_event[dev & 15] && g_persist_last_ctx[dev & 15]) (void)hipStreamWaitEvent(c->stream, g_persist_event[dev & 15], 0);
+    bool ok = false;
+    const auto t_probe = std::chrono::steady_clock::now();
+    if (coop_mode > 0 && coop_attr) {
+      ok = persist_probe(c->n_tiles, c->C, c->L_loc, P<unsigned>(c->persist.psync), static_cast<unsigned*>(c->persist.status.dev),
+                         static_cast<volatile unsigned*>(c->persist.status.host), true, c->stream);
+      c->persist.coop = ok;
+      if (!ok) c->err = "k_persist: the cooperative launch was refused or its barriers timed out";
     }
+    if (coop_mode > 0 && !coop_attr) c->err = "k_persist: this device does not offer cooperative launches";
+    if (coop_mode <= 0) {
+      ok = persist_probe(c->n_tiles, c->C, c->L_loc, P<unsigned>(c->persist.psync), static_cast<unsigned*>(c->persist.status.dev),
+                         static_cast<volatile unsigned*>(c->persist.status.host), false, c->stream);
+      if (!ok) c->err = "k_persist: the workgroups of this graph are not co-resident under the spread placement on this device (probe timed out)";
+    }
+    c->persist.probe_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_probe).count();
+    if (!ok) c->err += "; iterations run on the two-kernel path";
+    c->persist.ok = c->persist.eligible = ok;
+    if (!ok) {
+      (void)hipGetLastError();
+      return GBP_OK;
+    }
+    HIPCHK(c, hipMemsetAsync(c->persist.psync.p, 0, kPersistSyncWords * sizeof(unsigned), c->stream));   // counter back to 0 after the probe
   }
-  return rc;
+  {
+    // snapshot arena: one slot for every array a k_persist launch mutates
+    // (+ the priors and the weaken flags: a launch of gbp_ba_loop weakens priors itself)
+    DevBuf* segs[] = {&c->arr.lmsg, &c->arr.fst_packed, &c->arr.fst_damp, &c->arr.cmsg, &c->arr.fac, &c->arr.rowp, &c->arr.camb, &c->arr.lmkb, &c->arr.hmu_c, &c->arr.hmu_l, &c->arr.clin, &c->arr.local,
+                      &c->arr.camp, &c->arr.lmkp, &c->arr.cwf, &c->arr.lwf};
+    static_assert(sizeof(segs) / sizeof(segs[0]) <= (size_t)kMaxCopySegs, "k_copy_segments takes kMaxCopySegs segments");
+    size_t total = 0;
+    for (DevBuf* b : segs) total += (b->bytes + 15) / 16 * 16;
+    if (int rc = dev_alloc(c, c->persist.psnap, total)) return rc;
+    size_t off = 0;
+    int i = 0;
+    for (DevBuf* b : segs) {
+      void* slot = static_cast<char*>(c->persist.psnap.p) + off;
+      c->persist.snap_save.src[i] = b->p; c->persist.snap_save.dst[i] = slot; c->persist.snap_save.n4[i] = (b->bytes + 15) / 16;      // (hipMalloc granules are larger)
+      c->persist.snap_restore.src[i] = slot; c->persist.snap_restore.dst[i] = b->p; c->persist.snap_restore.n4[i] = (b->bytes + 15) / 16;
+      off += (b->bytes + 15) / 16 * 16;
+      ++i;
+    }
+    c->persist.snap_save.n = c->persist.snap_restore.n = i;
+  }
+  // tagged shadows of the arrays that cross waves inside a launch (k_persist_flow): two halves each
+  const size_t Ep = (size_t)c->n_tiles * 64, C_ = c->C, L_ = c->L_loc;
+  const size_t n4[10] = {2 * Ep * 4, 2 * (Ep / 16) * kFlowRow4, 2 * C_ * kFlowCam4, 2 * C_ * 2, 2 * C_ * kFlowClin4, 2 * L_ * kFlowLmk4, 2 * L_,
+                         2 * C_ * 4, 2 * L_, (size_t)kSeriesMax};      // (the last: [kSeriesMax][2] 64-bit health words = kSeriesMax float4)
+  size_t total = 0;
+  for (size_t n : n4) total += n;
+#ifdef GBP_BUILD_TEST_HOOKS
+  // gbp_debug_persist_verify: room for the redundant copy of every record + the mismatch counter (the product allocates neither)
+  const int flow_rc = dev_alloc(c, c->persist.pflow, 2 * total * 16 + 64);
+  c->persist.flow_total4 = (uint32_t)total;
+#else
+  const int flow_rc = dev_alloc(c, c->persist.pflow, total * 16);
+#endif
+  if (flow_rc) return flow_rc;
+  float4* q = static_cast<float4*>(c->persist.pflow.p);
+  float4** dst[9] = {&c->persist.flow.lmsg, &c->persist.flow.rowp, &c->persist.flow.camb, &c->persist.flow.cmu, &c->persist.flow.clin, &c->persist.flow.lmkb, &c->persist.flow.lmu, &c->persist.flow.emc, &c->persist.flow.eml};
+  for (int i = 0; i < 9; ++i) { *dst[i] = q; q += n4[i]; }
+  c->persist.flow.health_iter = reinterpret_cast<unsigned long long*>(q);
+  // the host-mapped slots of gbp_iterate_eval_each / gbp_ba_loop: here, not inside the first timed burst (pinning 5 MB takes
+  // ~0.5 ms, a twentieth of a default `ba fr1xyz` run).  gbp_create fails without them: every ctx that can reach the
+  // persistent path has them (series_burst relies on it)
+  if (int rc = mapped_alloc(c, c->persist.series, sizeof(DeviceEval) * (size_t)(c->n_tiles + 1) * kSeriesMax)) return rc;
+#ifdef GBP_BUILD_TEST_HOOKS
+  const char* pf = prm ? nullptr : std::getenv("GBP_PERSIST_FLOW");      // (the barrier kernel exists in the test-hooks build only)
+  if (pf && std::atoi(pf) == 0) c->persist.use_flow = false;
+#endif
+  return GBP_OK;
 }
 
 int settle(gbp_ctx* c) {
-  if (c->persist_log.empty()) return GBP_OK;
+  if (c->persist.log.empty()) return GBP_OK;
   // unvalidated k_persist launches and a caller who has begun capturing the stream: synchronising would invalidate their capture
   if (stream_is_capturing(c))
     return fail(c, GBP_ERR_STATE, "bursts of the persistent kernel are still in flight on this stream: call gbp_sync before beginning a stream capture");
@@ -190,25 +168,25 @@ int settle(gbp_ctx* c) {
   return persist_check(c, 0);
 }
 
-// A k_persist launch gave up at a barrier (*pstatus_host = its number): undo it and everything queued behind it, replay
+// A k_persist launch gave up at a barrier (*pstatus.host = its number): undo it and everything queued behind it, replay
 // on the two-kernel path.  The snapshot kernel of every later launch saw the abort word and left the arena alone, so the
 // arena holds the state the first failed launch started from.
 static int persist_recover(gbp_ctx* c) {
   HIPCHK(c, hipStreamSynchronize(c->stream));        // the failed launch and the no-op launches behind it have ended
-  const unsigned first = *static_cast<volatile unsigned*>(c->pstatus_host);
+  const unsigned first = *static_cast<volatile unsigned*>(c->persist.status.host);
   std::vector<gbp_ctx::Burst> redo;
-  for (const gbp_ctx::Burst& b : c->persist_log)
+  for (const gbp_ctx::Burst& b : c->persist.log)
     if (b.seq >= first) redo.push_back(b);
-  c->persist_log.clear();
-  launch_copy_segments(c->snap_restore, nullptr, c->stream);
+  c->persist.log.clear();
+  launch_copy_segments(c->persist.snap_restore, nullptr, c->stream);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemsetAsync(c->psync.p, 0, kPersistSyncWords * sizeof(unsigned), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->health.p, 0, 32, c->stream));       // both areas are zero between evaluations
+  HIPCHK(c, hipMemsetAsync(c->persist.psync.p, 0, kPersistSyncWords * sizeof(unsigned), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->arr.health.p, 0, 32, c->stream));       // both areas are zero between evaluations
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  *static_cast<volatile unsigned*>(c->pstatus_host) = 0u;
-  c->persist_epoch_base = 0;
-  c->persist_ok = false;                              // until the next gbp_upload
-  c->persist_recoveries += 1;
+  *static_cast<volatile unsigned*>(c->persist.status.host) = 0u;
+  c->persist.epoch_base = 0;
+  c->persist.ok = false;                              // until the next gbp_upload
+  c->persist.recoveries += 1;
   const SweepArgs a = sweep_args(c);
   long iters = 0;
   for (const gbp_ctx::Burst& b : redo) {
@@ -236,11 +214,11 @@ static int persist_recover(gbp_ctx* c) {
 
 // The stream has been synchronised, or an event recorded behind launch `upto` has completed (0 = everything queued has).
 int persist_check(gbp_ctx* c, unsigned upto) {
-  if (!c->pstatus_host || c->persist_log.empty()) return GBP_OK;
-  if (*static_cast<volatile unsigned*>(c->pstatus_host) != 0u) return persist_recover(c);
-  if (upto == 0) c->persist_log.clear();
+  if (!c->persist.status.host || c->persist.log.empty()) return GBP_OK;
+  if (*static_cast<volatile unsigned*>(c->persist.status.host) != 0u) return persist_recover(c);
+  if (upto == 0) c->persist.log.clear();
   else
-    while (!c->persist_log.empty() && c->persist_log.front().seq <= upto) c->persist_log.erase(c->persist_log.begin());
+    while (!c->persist.log.empty() && c->persist.log.front().seq <= upto) c->persist.log.erase(c->persist.log.begin());
   return GBP_OK;
 }
 
@@ -255,11 +233,11 @@ bool stream_is_capturing(gbp_ctx* c) {
 // barrier targets are launch arguments computed by the host, a replayed graph would wait for arrivals long past.
 int persist_ready(gbp_ctx* c, bool* yes) {
   *yes = false;
-  if (!c->persist_ok || c->comm || c->world != 1 || c->profile_stages) return GBP_OK;
+  if (!c->persist.ok || c->xch.comm || c->world != 1 || c->tm.profile_stages) return GBP_OK;
   if (stream_is_capturing(c)) return GBP_OK;
-  if (c->persist_log.size() >= kPersistLogMax)
+  if (c->persist.log.size() >= kPersistLogMax)
     if (int rc = settle(c)) return rc;
-  *yes = c->persist_ok;
+  *yes = c->persist.ok;
   return GBP_OK;
 }
 
@@ -277,14 +255,14 @@ int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, int n, const PersistEva
   }
   A.n_tiles = c->n_tiles;
   A.n_iters = n;
-  A.sync = P<unsigned>(c->psync);
-  A.status = static_cast<unsigned*>(c->pstatus_dev);
-  A.epoch_base = c->persist_epoch_base;
-  A.seq = c->persist_seq + 1;
+  A.sync = P<unsigned>(c->persist.psync);
+  A.status = static_cast<unsigned*>(c->persist.status.dev);
+  A.epoch_base = c->persist.epoch_base;
+  A.seq = c->persist.seq + 1;
   if (ev) A.ev = *ev;
-  const bool flow = c->persist_flow && c->flow.lmsg != nullptr;      // hand-offs through tagged records (k_persist_flow)
+  const bool flow = c->persist.use_flow && c->persist.flow.lmsg != nullptr;      // hand-offs through tagged records (k_persist_flow)
   if (flow) {
-    A.f = c->flow;
+    A.f = c->persist.flow;
     A.f.tag0 = (A.seq & 0x7ffffu) << 13;      // + iteration (<= kPersistChunk) + 1: never the tag of a record an earlier launch left behind
   }
   {
@@ -298,14 +276,14 @@ int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, int n, const PersistEva
     if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     if (g_persist_last_ctx[dev & 15] && (g_persist_last_ctx[dev & 15] != c || g_persist_last_stream[dev & 15] != c->stream))
       HIPCHK(c, hipStreamWaitEvent(c->stream, e, 0));
-    launch_copy_segments(c->snap_save, P<unsigned>(c->psync) + 32, c->stream);       // skipped on the device once the abort word is set (5-7 us per launch)
+    launch_copy_segments(c->persist.snap_save, P<unsigned>(c->persist.psync) + 32, c->stream);       // skipped on the device once the abort word is set (5-7 us per launch)
     HIPCHK(c, hipGetLastError());
-    const hipError_t le = launch_persist(A, c->persist_coop, c->stream);
+    const hipError_t le = launch_persist(A, c->persist.coop, c->stream);
     if (le != hipSuccess) {
       (void)hipGetLastError();
-      if (!c->persist_coop) return fail(c, GBP_ERR_HIP, std::string("k_persist launch: ") + hipGetErrorString(le));
+      if (!c->persist.coop) return fail(c, GBP_ERR_HIP, std::string("k_persist launch: ") + hipGetErrorString(le));
       // the runtime refused the cooperative grid: nothing ran, nothing is lost — this ctx continues on the two-kernel path
-      c->persist_ok = c->persist_eligible = false;
+      c->persist.ok = c->persist.eligible = false;
       c->warn = std::string("warning: the cooperative launch of the persistent kernel was refused (") + hipGetErrorString(le) +
                 "); iterations run on the two-kernel path";
       c->err = c->warn;
@@ -318,10 +296,10 @@ int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, int n, const PersistEva
   const unsigned nb = persist_grid(c->n_tiles, c->C, c->L_loc, ev != nullptr && ev->each != 0).nb;      // the grid launch_persist used
   // arrivals of this launch (n <= kPersistChunk; the counter wraps, grid_sync compares wrap-safe): two hand-offs per iteration — with
   // tagged records none, and ONE barrier at the end of a launch that carries the metric
-  c->persist_epoch_base += flow ? (ev ? nb : 0u) : nb * (unsigned)(2 * n - 1 + (ev ? 1 : 0));
-  c->persist_seq += 1;
-  c->persist_log.push_back(gbp_ctx::Burst{c->persist_seq, n, mode, area, w_first, w_steps2, out_dev});
-  c->persist_launches += 1;
+  c->persist.epoch_base += flow ? (ev ? nb : 0u) : nb * (unsigned)(2 * n - 1 + (ev ? 1 : 0));
+  c->persist.seq += 1;
+  c->persist.log.push_back(gbp_ctx::Burst{c->persist.seq, n, mode, area, w_first, w_steps2, out_dev});
+  c->persist.launches += 1;
   return GBP_OK;
 }
 

@@ -44,10 +44,19 @@ struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
 };
+// pinned host memory that the device reads and writes through `dev` (hipHostMallocMapped)
+struct MappedBuf {
+  void* host = nullptr;
+  void* dev = nullptr;
+  size_t bytes = 0;
+};
 }  // namespace api
 }  // namespace gbp
 
 struct gbp_ctx {
+  using DevBuf = gbp::api::DevBuf;
+  using MappedBuf = gbp::api::MappedBuf;
+  // ---- the problem, the shard, the sizes of the device order, the stream: set by gbp_create (gbp_api_ctx.cpp), read by every unit ----
   uint32_t C = 0, L = 0, E = 0;       // global sizes
   uint32_t lmk_begin = 0, lmk_end = 0, L_loc = 0, E_loc = 0;
   int rank = 0, world = 1;
@@ -55,114 +64,132 @@ struct gbp_ctx {
   gbp_params prm;
   gbp::Layout lay;                         // device order (host side): position <-> file edge, rows, slots, tile order
   uint32_t Ep = 0, n_tiles = 0, n_rows = 0;
-  // device memory
-  using DevBuf = gbp::api::DevBuf;
-  std::vector<DevBuf*> all;
-  DevBuf fst_packed, fst_damp, fst_var;      // [Ep] the per-factor state planes (gbp_kernels.h)
-  DevBuf row_cam, lmk_idx, fac, cmsg, mu, lmsg, camb, camp, lmkb, lmkp, rowp, local, d_cam_row_ptr, d_row_slot, d_lmk_ptr, cwf, lwf,
-      cscale, lscale, cam_mu, lmk_mu, dK, evalp, hmu_c, hmu_l, clin, d_lmk_fpos, d_lmk_ix, health, tile_perm;
-  // host -> device copies of small graphs go through this pinned, device-mapped buffer and a copy kernel (gbp_api_ctx.cpp: H2D)
-  void* stage_host = nullptr;
-  void* stage_dev = nullptr;
-  size_t stage_cap = 0;
-  size_t stage_hint = 0;               // what gbp_upload will stage: the buffer is pinned once, at that size (gbp_create)
-  DevBuf cmsg_lit;                     // CMSG_LIT (gbp_kernels.h): allocated by the first gbp_linearise that finds camera messages live
-  bool cmsg_zero = true;               // no sweep has been set up since the zero fill of the last upload: every CMSG record is kCmsgZero
-  DevBuf idx_arena;                    // the index arrays of the device order (row_cam, lmk_idx, lmk_fpos, lmk_ix, the row / landmark pointers, row_slot, K, tile_perm: views into it)
-  DevBuf st_a, st_b;                   // [Ep] scratch of the per-factor state set kernel
-  std::vector<uint8_t> active_host;    // [Ep] host shadow of the active flags (hoist guard of gbp_new_keyframe)
-  // device-resident caller arrays (gbp_api_devio.cpp)
   int device = 0;                      // the GPU this ctx lives on (current device of gbp_create)
-  DevBuf d_pos_edge;                   // [Ep] lay.pos_edge on the device; allocated by the first call that passes device pointers
-  bool active_host_stale = false;      // a device-pointer call changed the active flags: the shadow is read back before its next use
   bool use_tile_perm = false;
-  DevBuf seg_live;                     // [n_tiles] which segments (four positions) of a tile hold a factor (view into idx_arena; SweepArgs.seg_live)
   bool use_seg_live = false;
   uint32_t sweep_policy = 0;           // kPol* bits of SweepArgs.policy for this graph's shape (sweep_policy_for)
   bool hoist = true;  // per-variable belief means (k_sweep<true>); false = literal per-factor mu/oldmu tensors
-  void* send_dev = nullptr;
-  void* recv_dev = nullptr;
-  // library-owned exchange (gbp_comm_init*): communicator, buffers, a second stream so the all-gather overlaps the
-  // rank-local landmark half of the belief update (fork / join through two events: capturable into the hipGraph)
-  gbp::Comm* comm = nullptr;
-  DevBuf xrecv;                        // [world][C][44] gathered camera partials; this rank writes its own slot (in-place all-gather)
-  hipStream_t comm_stream = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  int comm_warm = 0;                   // sharded iterations run directly so far (RCCL must have run before a capture)
-  bool comm_single_stream = false;     // all-gather on the main stream, no second queue (default for world <= 2)
-  const char* comm_selected_by = "caller";   // gbp_comm_describe: who chose the transport — "caller", "rule" (transport 0) or "measurement" (5)
-  std::string comm_measured;           // transport 5: the JSON list of what gbp_comm_init timed, one entry per candidate ("" for the others)
-  // gbp_comm_describe's "metric" member: passes with the metric since gbp_comm_init, by path (gbp_transport.hpp: metric_rides)
-  int metric_last = 0;                 // 0 none yet, 1 the last burst rode in the sharded iteration, 2 it ran the per-pass loop
-  uint64_t metric_riding = 0, metric_per_pass = 0;
-  const char* metric_reason = "";      // why the last per-pass burst did not ride (static text)
   hipStream_t own_stream = nullptr, stream = nullptr;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t graph_exec = nullptr;
-  int graph_iters = 0;
-  bool graph_failed = false;           // a capture / instantiation failed once: direct launches from then on
-  // the same for iterations that carry the metric (k_sweep<EV> + k_beliefs<EV>: gbp_iterate_eval_each beyond k_persist)
-  hipGraph_t graph_ev = nullptr;
-  hipGraphExec_t graph_exec_ev = nullptr;
-  DevBuf ev_cam, ev_lmk, ev_part, ev_ctl;   // metric records of the belief owners, ring of per-tile partial sums, counter + health words
-  uint32_t ev_depth = 0;               // slots of the ring = iterations per piece of a burst
-  void* ev_host = nullptr;             // pinned + device-mapped: one gbp_eval_out per iteration of a burst (k_eval_fold)
-  size_t ev_host_cap = 0;
-  void* ev_host_dev = nullptr;
-  bool sharded_graph = false;          // gbp_params.graph_unroll > 0 was asked for explicitly (see iterate_sharded)
   bool uploaded = false, beliefs_valid = false;
   bool lmk_half_done = false;          // gbp_iterate_local already refreshed the landmark beliefs of this iteration
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
-  // gbp_iterate does not block the host: each call is bracketed by an event pair that is read later (gbp_timing, or
-  // when the ring is full), so a caller that evaluates the metric every iteration pays ONE host synchronisation per
-  // iteration (inside gbp_eval), not two
-  struct Span { hipEvent_t a, b; };
-  std::vector<Span> spans;             // recorded, not yet read
-  std::vector<Span> span_pool;         // reusable event pairs
-  void* eval_host = nullptr;           // pinned + device-mapped: k_eval writes the metric partials + health counters here
-  void* eval_host_dev = nullptr;
-  void* series_host = nullptr;         // gbp_iterate_eval_each: [kSeriesMax metrics][1 + workgroups] slots, same kind of memory
-  void* series_dev = nullptr;
-  // the metric into gbp_eval_out records on the GPU (gbp_eval / gbp_ba_loop / gbp_iterate_eval_each with a device `out`): the same
-  // records in DEVICE memory, folded by k_eval_fold_part; allocated by the first call that needs them
-  DevBuf eval_scratch;                 // [1025] one result area of k_eval
-  DevBuf series_twin;                  // [kSeriesMax][n_tiles + 1] the series slots of the persistent kernel
-  int eval_parity = 0, eval_pending = 0;
-  bool eval_per_wave[2] = {false, false};   // result area written by k_persist (one record per tile wave) or by k_eval (one per workgroup)
-  hipEvent_t eval_ev[2] = {nullptr, nullptr};
-  bool profile_stages = false;
-  // k_persist (small graphs): n iterations in one launch
-  bool persist_ok = false;             // bursts run inside k_persist (eligible, co-resident, no time-out since the last upload)
-  bool persist_eligible = false;       // what persist_ok returns to at the next gbp_upload after a recovered time-out
-  bool persist_coop = false;           // launched with hipLaunchCooperativeKernel (co-residency guaranteed by the runtime / driver)
-  // A launch whose barrier timed out (workgroups not co-resident: e.g. another process holds CUs) is UNDONE and replayed on the
-  // two-kernel path: every launch is preceded by a snapshot of the arrays it mutates (one copy kernel, skipped once the abort
-  // word is set), later launches of the ctx return at once, and the host — at the next point where it synchronises anyway —
-  // restores the snapshot and replays the logged launches from the first failed one on.
+  // ---- what the ctx owns on the HIP side (gbp_api_ctx.cpp): each kind is registered in one place and released by gbp_destroy, in
+  // this order: events, device memory (dev_alloc), pinned memory (mapped_alloc), the two streams last ----
+  std::vector<hipEvent_t*> events;     // the named events (event_create / event_pair_owned); pairs in flight live in their containers (tm.spans, tm.pending_*)
+  std::vector<DevBuf*> all;
+  std::vector<MappedBuf*> mapped;
+  uint64_t dev_bytes = 0;
+  // ---- the per-factor and per-variable device arrays: allocated by gbp_create (gbp_api_ctx.cpp), streamed by every launch ----
+  struct Arrays {
+    DevBuf fst_packed, fst_damp, fst_var;      // [Ep] the per-factor state planes (gbp_kernels.h)
+    DevBuf row_cam, lmk_idx, fac, cmsg, mu, lmsg, camb, camp, lmkb, lmkp, rowp, local, d_cam_row_ptr, d_row_slot, d_lmk_ptr, cwf, lwf,
+        cscale, lscale, cam_mu, lmk_mu, dK, hmu_c, hmu_l, clin, d_lmk_fpos, d_lmk_ix, health, tile_perm;
+    DevBuf cmsg_lit;                     // CMSG_LIT (gbp_kernels.h): allocated by the first gbp_linearise that finds camera messages live
+    bool cmsg_zero = true;               // no sweep has been set up since the zero fill of the last upload: every CMSG record is kCmsgZero
+    DevBuf idx_arena;                    // the index arrays of the device order (row_cam, lmk_idx, lmk_fpos, lmk_ix, the row / landmark pointers, row_slot, K, tile_perm: views into it)
+    DevBuf st_a, st_b;                   // [Ep] scratch of the per-factor state set kernel
+    std::vector<uint8_t> active_host;    // [Ep] host shadow of the active flags (hoist guard of gbp_new_keyframe)
+    // device-resident caller arrays (gbp_api_devio.cpp)
+    DevBuf d_pos_edge;                   // [Ep] lay.pos_edge on the device; allocated by the first call that passes device pointers
+    bool active_host_stale = false;      // a device-pointer call changed the active flags: the shadow is read back before its next use
+    DevBuf seg_live;                     // [n_tiles] which segments (four positions) of a tile hold a factor (view into idx_arena; SweepArgs.seg_live)
+  } arr;
+  // ---- staging (gbp_api_ctx.cpp: H2D, D2H) ----
+  struct Stage {
+    // host -> device copies of small graphs go through this pinned, device-mapped buffer and a copy kernel (gbp_api_ctx.cpp: H2D)
+    MappedBuf buf;
+    size_t hint = 0;                     // what gbp_upload will stage: the buffer is pinned once, at that size (gbp_create)
+  } stage;
+  // ---- the captured iterations (gbp_api_launch.cpp; a sharded ctx: captured by gbp_api_comm.cpp) ----
+  struct Graphs {
+    hipGraph_t g = nullptr;
+    hipGraphExec_t exec = nullptr;
+    int iters = 0;
+    bool failed = false;                 // a capture / instantiation failed once: direct launches from then on
+    // the same for iterations that carry the metric (k_sweep<EV> + k_beliefs<EV>: gbp_iterate_eval_each beyond k_persist)
+    hipGraph_t g_ev = nullptr;
+    hipGraphExec_t exec_ev = nullptr;
+    bool sharded = false;                // gbp_params.graph_unroll > 0 was asked for explicitly (see iterate_sharded)
+  } graph;
+  // ---- the metric (gbp_api_eval.cpp) ----
+  struct Metric {
+    DevBuf ev_cam, ev_lmk, ev_part, ev_ctl;   // metric records of the belief owners, ring of per-tile partial sums, counter + health words
+    uint32_t ev_depth = 0;               // slots of the ring = iterations per piece of a burst
+    MappedBuf ev_results;                // pinned + device-mapped: one gbp_eval_out per iteration of a burst (k_eval_fold)
+    MappedBuf area;                      // pinned + device-mapped: k_eval writes the metric partials + health counters here
+    // the metric into gbp_eval_out records on the GPU (gbp_eval / gbp_ba_loop / gbp_iterate_eval_each with a device `out`): the same
+    // records in DEVICE memory, folded by k_eval_fold_part; allocated by the first call that needs them
+    DevBuf scratch;                      // [1025] one result area of k_eval
+    DevBuf series_twin;                  // [kSeriesMax][n_tiles + 1] the series slots of the persistent kernel
+    int parity = 0, pending = 0;
+    bool per_wave[2] = {false, false};   // result area written by k_persist (one record per tile wave) or by k_eval (one per workgroup)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+  } metric;
+  // ---- the persistent kernel (gbp_api_persist.cpp) ----
   // mode 0 = gbp_iterate, 1 = gbp_iterate_eval (metric in eval area `area`), 2 = eval_each / gbp_ba_loop with metrics (blocking),
   // 3 = the same with the results going to the caller's device records `out` (not blocking: the recovery replays passes and metrics);
   // w_steps2 != 0: the launch weakens priors itself (gbp_ba_loop: loop index of its first iteration, twice the --steps)
   struct Burst { unsigned seq; int n; int mode; int area; unsigned w_first = 0, w_steps2 = 0; void* out = nullptr; };
-  DevBuf pflow;                        // tagged shadows of k_persist_flow (PersistFlow), one allocation
-  gbp::PersistFlow flow{};                  // the tagged shadows of k_persist_flow
-  uint32_t flow_total4 = 0;            // test-hooks builds: float4 of the shadows (the redundant copies of gbp_debug_persist_verify follow them)
-  bool persist_flow = true;            // test-hooks build: gbp_debug_persist_flow(ctx, 0) / GBP_PERSIST_FLOW=0 run the barrier kernel of rounds 3-4 instead
-  std::vector<Burst> persist_log;      // launched, completion not yet validated
-  unsigned persist_seq = 0;
-  DevBuf psnap;                        // snapshot arena
-  gbp::CopySegs snap_save{}, snap_restore{};
+  struct Persist {
+    // k_persist (small graphs): n iterations in one launch
+    bool ok = false;                     // bursts run inside k_persist (eligible, co-resident, no time-out since the last upload)
+    bool eligible = false;               // what `ok` returns to at the next gbp_upload after a recovered time-out
+    bool coop = false;                   // launched with hipLaunchCooperativeKernel (co-residency guaranteed by the runtime / driver)
+    // A launch whose barrier timed out (workgroups not co-resident: e.g. another process holds CUs) is UNDONE and replayed on the
+    // two-kernel path: every launch is preceded by a snapshot of the arrays it mutates (one copy kernel, skipped once the abort
+    // word is set), later launches of the ctx return at once, and the host — at the next point where it synchronises anyway —
+    // restores the snapshot and replays the logged launches from the first failed one on.
+    DevBuf pflow;                        // tagged shadows of k_persist_flow (PersistFlow), one allocation
+    gbp::PersistFlow flow{};                  // the tagged shadows of k_persist_flow
+    uint32_t flow_total4 = 0;            // test-hooks builds: float4 of the shadows (the redundant copies of gbp_debug_persist_verify follow them)
+    bool use_flow = true;                // test-hooks build: gbp_debug_persist_flow(ctx, 0) / GBP_PERSIST_FLOW=0 run the barrier kernel of rounds 3-4 instead
+    std::vector<Burst> log;              // launched, completion not yet validated
+    unsigned seq = 0;
+    DevBuf psnap;                        // snapshot arena
+    gbp::CopySegs snap_save{}, snap_restore{};
+    uint64_t recoveries = 0;
+    double probe_ms = 0;                 // gbp_create: what the co-residency probe took (the first kernel launch of the process: code-object load included)
+    DevBuf psync;                        // barrier words
+    MappedBuf status;                    // pinned + device-mapped: raised by the kernel if a barrier gave up
+    uint64_t launches = 0;
+    unsigned epoch_base = 0;             // arrivals the barrier counter has seen so far (it keeps counting across launches)
+    MappedBuf series;                    // gbp_iterate_eval_each: [kSeriesMax metrics][1 + workgroups] slots, same kind of memory (read by gbp_api_eval.cpp)
+  } persist;
+  // ---- the exchange of a sharded ctx (gbp_api_comm.cpp) ----
+  struct Exchange {
+    void* send_dev = nullptr;
+    void* recv_dev = nullptr;
+    // library-owned exchange (gbp_comm_init*): communicator, buffers, a second stream so the all-gather overlaps the
+    // rank-local landmark half of the belief update (fork / join through two events: capturable into the hipGraph)
+    gbp::Comm* comm = nullptr;
+    DevBuf xrecv;                        // [world][C][44] gathered camera partials; this rank writes its own slot (in-place all-gather)
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    int warm = 0;                        // sharded iterations run directly so far (RCCL must have run before a capture)
+    bool single_stream = false;          // all-gather on the main stream, no second queue (default for world <= 2)
+    const char* selected_by = "caller";  // gbp_comm_describe: who chose the transport — "caller", "rule" (transport 0) or "measurement" (5)
+    std::string measured;                // transport 5: the JSON list of what gbp_comm_init timed, one entry per candidate ("" for the others)
+    // gbp_comm_describe's "metric" member: passes with the metric since gbp_comm_init, by path (gbp_transport.hpp: metric_rides)
+    int metric_last = 0;                 // 0 none yet, 1 the last burst rode in the sharded iteration, 2 it ran the per-pass loop
+    uint64_t metric_riding = 0, metric_per_pass = 0;
+    const char* metric_reason = "";      // why the last per-pass burst did not ride (static text)
+  } xch;
+  // ---- timing and profiling (the brackets: gbp_api_ctx.cpp; recorded by the units that launch) ----
+  struct Span { hipEvent_t a, b; };
+  struct Timing {
+    hipEvent_t reps_begin = nullptr, reps_end = nullptr;   // bracket of a run of repeated launches that the call itself waits for (gbp_comm_probe, gbp_debug_time_sweep)
+    // gbp_iterate does not block the host: each call is bracketed by an event pair that is read later (gbp_timing, or
+    // when the ring is full), so a caller that evaluates the metric every iteration pays ONE host synchronisation per
+    // iteration (inside gbp_eval), not two
+    std::vector<Span> spans;             // recorded, not yet read
+    std::vector<Span> span_pool;         // reusable event pairs
+    bool profile_stages = false;
+    std::vector<Span> pending_sweep_ev;  // split-phase profiling: brackets not yet read
+    double sweep_ms = 0, belief_ms = 0, total_ms = 0, exchange_ms = 0;
+    std::vector<Span> pending_exch_ev;   // profiling: brackets of partials + all-gather
+    uint64_t timed_iters = 0;
+  } tm;
+  // ---- texts (every unit: fail(), gbp_last_error) ----
   std::string warn;                    // text of the last recovered incident (also left in `err`, the call returns GBP_OK)
-  uint64_t persist_recoveries = 0;
-  double probe_ms = 0;                 // gbp_create: what the co-residency probe took (the first kernel launch of the process: code-object load included)
-  DevBuf psync;                        // barrier words
-  void* pstatus_host = nullptr;        // pinned + device-mapped: raised by the kernel if a barrier gave up
-  void* pstatus_dev = nullptr;
-  uint64_t persist_launches = 0;
-  unsigned persist_epoch_base = 0;     // arrivals the barrier counter has seen so far (it keeps counting across launches)
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending_sweep_ev;  // split-phase profiling: brackets not yet read
-  double sweep_ms = 0, belief_ms = 0, total_ms = 0, exchange_ms = 0;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending_exch_ev;     // profiling: brackets of partials + all-gather
-  uint64_t timed_iters = 0, dev_bytes = 0;
   std::string err;
 };
 
@@ -188,9 +215,17 @@ namespace api {
 // ---- gbp_api_ctx.cpp --------------------------------------------------------------------------------------------------------
 std::string& create_error();                                 // thread-local text of the last failed gbp_create / ctx-less call
 int dev_alloc(gbp_ctx* c, DevBuf& b, size_t bytes);         // zero-filled device memory owned by the ctx (fill ordered on c->stream)
+// Pinned, device-mapped host memory owned by the ctx, at least `bytes` of it (not filled).  A buffer that is too small is freed and
+// pinned again at the new size — its contents are lost, and the caller has made sure that nothing on the device still uses it.
+int mapped_alloc(gbp_ctx* c, MappedBuf& b, size_t bytes);
+// Events owned by the ctx.  event_create / event_pair_owned: *e is a member of the ctx, destroyed with it.  event_pair: both events or
+// none, handed to the caller's container (spans, span_pool, pending_*), which gbp_destroy walks as well.
+int event_create(gbp_ctx* c, hipEvent_t* e, unsigned flags);
+int event_pair(gbp_ctx* c, hipEvent_t* a, hipEvent_t* b, unsigned flags = hipEventDefault);
+int event_pair_owned(gbp_ctx* c, hipEvent_t* a, hipEvent_t* b, unsigned flags);
 template <class T> inline T* P(DevBuf& b) { return static_cast<T*>(b.p); }
 // does this ctx combine camera partials through exchange buffers (sharded, or a 1-rank communicator)?
-inline bool exch(const gbp_ctx* c) { return c->world > 1 || c->comm != nullptr; }
+inline bool exch(const gbp_ctx* c) { return c->world > 1 || c->xch.comm != nullptr; }
 // The host -> device copies of ONE call (gbp_create, gbp_upload, gbp_new_keyframe).  The first small and the first medium-sized
 // hipMemcpy of a process cost 11 - 15 ms and 7 - 9 ms on this stack (set-up of two copy paths inside the runtime, profiles/exp_first_copy.hip)
 // — more than the 1 500 iterations of a `ba fr1xyz` run.  A call that moves at most kStageMax bytes therefore stages its pieces in one
@@ -208,6 +243,9 @@ struct H2D {
   int stage(const void* src, size_t bytes, const void** dev);  // staged only (!direct): the bytes where a kernel of the caller's reads them
   int end();
   int flush();
+  // room for `bytes` (padded to whole float4s) in the staging buffer, at *off, and one copy segment queued: out of it to dst_dev, or
+  // (dst_dev == NULL) into it from src_dev.  Launches the queued segments first when kMaxCopySegs of them wait.
+  int queue(size_t bytes, void* dst_dev, const void* src_dev, size_t* off);
 };
 // ... and the device -> host copies of one call (gbp_read, gbp_read_priors), the same way round: get() queues, end() returns with every
 // destination filled (the first device -> host hipMemcpy of a process pays the same set-up when no host -> device one came before it)
@@ -221,15 +259,15 @@ struct D2H {
 };
 // timing brackets of the iterate calls (read later: gbp_timing, or when the ring is full)
 int resolve_spans(gbp_ctx* c, bool wait);
-// The bracket of one iterate call.  begin() records its start event; end() its end event, handing the pair to c->spans; commit(n)
+// The bracket of one iterate call.  begin() records its start event; end() its end event, handing the pair to c->tm.spans; commit(n)
 // ends it (unless end() already has), counts n timed iterations and marks the beliefs valid.  A span that was never ended (an
-// error return) gives its events back to c->span_pool.
+// error return) gives its events back to c->tm.span_pool.
 class TimedSpan {
  public:
   explicit TimedSpan(gbp_ctx* c) : c_(c) {}
   TimedSpan(const TimedSpan&) = delete;
   TimedSpan& operator=(const TimedSpan&) = delete;
-  ~TimedSpan() { if (open_) c_->span_pool.push_back(sp_); }
+  ~TimedSpan() { if (open_) c_->tm.span_pool.push_back(sp_); }
   int begin();
   int end();
   int commit(uint64_t n);
@@ -239,8 +277,6 @@ class TimedSpan {
   bool open_ = false;
 };
 void drain_sweep_events(gbp_ctx* c);
-// a pair of timing events for per-stage profiling: created (or fails with the ctx's error text)
-int event_pair(gbp_ctx* c, hipEvent_t* a, hipEvent_t* b);
 // The construction knobs of the device order and the cache policy of the sweep: the defaults are the product.  Only the
 // test-hooks build can change them (gbp_debug_layout_options / gbp_debug_force_sweep_policy: measurements and tests).
 extern LayoutOptions g_layout_options;
@@ -248,7 +284,7 @@ extern int g_force_sweep_policy;
 extern int g_force_seg_skip;      // -1: by shape; 0 / 1: never / always skip the all-pad segments in the sweep (gbp_debug_force_seg_skip)
 
 // Per-factor scalar state lives in three planes indexed by device position (gbp_kernels.h)
-inline FactorState factor_state(gbp_ctx* c) { return FactorState{P<int>(c->fst_packed), P<float>(c->fst_damp), P<float>(c->fst_var)}; }
+inline FactorState factor_state(gbp_ctx* c) { return FactorState{P<int>(c->arr.fst_packed), P<float>(c->arr.fst_damp), P<float>(c->arr.fst_var)}; }
 inline size_t tile_off(uint32_t p, int G, int f) {  // float offset of float f of position p in a G-group tiled array
   return (((size_t)(p >> 6) * G + (f >> 2)) * 64 + (p & 63)) * 4 + (f & 3);
 }
@@ -269,7 +305,7 @@ inline int weakening_free_run(int n, unsigned i, unsigned steps2) {
 // passes from loop index i that ONE launch of the persistent kernel takes, at most cap of the n left: a weakening inside the launch
 // needs the tagged-record kernel; the barrier kernel (test-hooks build) takes the passes up to the next weakening
 inline int persist_burst(const gbp_ctx* c, int n, unsigned i, unsigned steps2, int cap) {
-  const int m = c->persist_flow && c->flow.lmsg != nullptr ? n : weakening_free_run(n, i, steps2);
+  const int m = c->persist.use_flow && c->persist.flow.lmsg != nullptr ? n : weakening_free_run(n, i, steps2);
   return m < cap ? m : cap;
 }
 // camera beliefs from stored partials (single GPU: the local sums; sharded: recv_dev) + landmark beliefs re-summed.  roll = true
@@ -328,7 +364,7 @@ int devio_upload(gbp_ctx* c, const gbp_state_in* in);
 int devio_read(gbp_ctx* c, gbp_state_out* out);
 int devio_read_priors(gbp_ctx* c, gbp_priors_out* out);
 int devio_new_keyframe(gbp_ctx* c, const gbp_kf_update* upd);
-int devio_refresh_active_shadow(gbp_ctx* c);   // c->active_host from the device (after a device-pointer call changed the flags)
+int devio_refresh_active_shadow(gbp_ctx* c);   // c->arr.active_host from the device (after a device-pointer call changed the flags)
 
 // ---- gbp_api_comm.cpp -------------------------------------------------------------------------------------------------------
 int exchange_now(gbp_ctx* c, hipStream_t s = nullptr);      // plain all-gather of the camera partials on the ctx's stream (or on s)
