@@ -14,7 +14,9 @@ OBJDIR  := $(PKG)/_obj/make
 # (the rule of gbp_poplar_amd/build.py: every csrc/*.cpp that is not the main of a CLI)
 HOST_SRCS := $(filter-out %_main.cpp,$(notdir $(wildcard $(CSRC)/*.cpp)))
 OBJS    := $(OBJDIR)/gbp_kernels.o $(HOST_SRCS:%.cpp=$(OBJDIR)/%.o)
-HDRS    := $(wildcard $(CSRC)/*.h $(CSRC)/*.hpp $(CSRC)/hooks/* $(CSRC)/experiments/* include/*.h)
+# every file under csrc/ that is not itself a compiled translation unit (a csrc/*.cpp, gbp_kernels.hip): headers, the kernel units,
+# hooks and experiments that gbp_kernels.hip #includes, the export map
+HDRS    := $(filter-out $(CSRC)/gbp_kernels.hip $(wildcard $(CSRC)/*.cpp),$(wildcard $(CSRC)/*.* $(CSRC)/*/*)) $(wildcard include/*.h)
 
 all: $(LIB) $(PKG)/bin/ba $(PKG)/bin/slam $(PKG)/bin/bal_convert
 

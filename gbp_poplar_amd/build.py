@@ -11,8 +11,9 @@ hipcc cross-compiles for gfx950 without a GPU.  -ffp-contract=off: results are c
 bit-for-bit with the CPU oracle, so no FMA contraction on either side.
 
 Every translation unit is compiled to an object of its own (gbp_poplar_amd/_obj/<variant>/, in parallel, only when it or a
-header changed) and the objects are linked: the device code (gbp_kernels.hip, ~25 s) is not recompiled for an edit of the host
-side of the C-ABI, whose translation units are plain C++ (no device pass).
+header changed) and the objects are linked: the device code (gbp_kernels.hip = the units of csrc/kernels/ as ONE translation unit,
+~25 s) is not recompiled for an edit of the host side of the C-ABI, whose translation units are plain C++ (no device pass).  The
+objects of all the variants asked for are compiled in one pool.
 """
 import concurrent.futures
 import os
@@ -53,10 +54,11 @@ def _stale(target, deps):
 
 
 def _headers():
+    """Every file under csrc/ that is not itself a compiled translation unit (a csrc/*.cpp, gbp_kernels.hip): the headers, the
+    kernel units, hooks and experiments that gbp_kernels.hip #includes, the export map.  (The Makefile states the same rule.)"""
     inc = os.path.join(HERE, "..", "include")
-    hdr = [os.path.join(d, f) for d, _, fs in os.walk(CSRC) for f in fs if f.endswith((".h", ".hpp"))]
-    hdr += [os.path.join(d, f) for d in (os.path.join(CSRC, "hooks"), os.path.join(CSRC, "experiments")) if os.path.isdir(d)
-            for f in os.listdir(d)]          # device sources #included by gbp_kernels.hip
+    hdr = [os.path.join(d, f) for d, _, fs in os.walk(CSRC) for f in fs
+           if not (d == CSRC and (f.endswith(".cpp") or f in DEVICE_SRCS))]
     return hdr + [os.path.join(inc, f) for f in os.listdir(inc)] + [os.path.abspath(__file__)]
 
 
@@ -77,7 +79,16 @@ def _compile(src, obj, defines, verbose):
     subprocess.check_call(cmd)
 
 
-def _build_lib(target, variant, defines, force, verbose):
+# variant (= its directory under _obj/) -> the library, the defines of its objects
+VARIANTS = {
+    "product": (LIB, []),
+    "test": (TEST_LIB, ["-DGBP_BUILD_TEST_HOOKS"]),
+    "exp": (EXP_LIB, ["-DGBP_BUILD_EXPERIMENTS", "-DGBP_BUILD_TEST_HOOKS"]),
+}
+
+
+def _stale_objects(variant, force):
+    """(every object of the variant's library, [(source, object)] of those that have to be compiled)"""
     odir = os.path.join(OBJ, variant)
     os.makedirs(odir, exist_ok=True)
     hdr = _headers()
@@ -87,26 +98,41 @@ def _build_lib(target, variant, defines, force, verbose):
         objs.append(obj)
         if force or _stale(obj, hdr + [os.path.join(CSRC, s)]):
             todo.append((s, obj))
-    if todo:
-        workers = min(len(todo), 16, os.cpu_count() or 1)
-        with concurrent.futures.ThreadPoolExecutor(workers) as ex:
-            for f in [ex.submit(_compile, s, o, defines, verbose) for s, o in todo]:
+    return objs, todo
+
+
+def _link(target, objs, verbose):
+    cmd = [hipcc(), "-shared", "-o", target, "--offload-arch=" + ARCH] + objs + \
+          ["-ldl", "-pthread", "-Wl,--version-script=" + os.path.join(CSRC, "gbp_exports.map")]      # (-pthread: the host helpers' reader threads, for a libc that still keeps them in libpthread)
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+
+
+def _build_libs(variants, force, verbose):
+    """The stale objects of ALL the variants in one pool (a variant's device translation unit takes as long as the rest of it
+    together, so three variants one after the other leave most cores idle), each library linked once its own objects are there."""
+    plan = {v: _stale_objects(v, force) for v in variants}
+    todo = [(s, o, v) for v in variants for s, o in plan[v][1]]
+    todo.sort(key=lambda t: t[0] not in DEVICE_SRCS)          # the long compiles first
+    with concurrent.futures.ThreadPoolExecutor(min(len(todo), 16) or 1) as ex:
+        done = {v: [] for v in variants}
+        for s, o, v in todo:
+            done[v].append(ex.submit(_compile, s, o, VARIANTS[v][1], verbose))
+        for v in variants:
+            for f in done[v]:
                 f.result()
-    if todo or force or _stale(target, objs):
-        cmd = [hipcc(), "-shared", "-o", target, "--offload-arch=" + ARCH] + objs + \
-              ["-ldl", "-pthread", "-Wl,--version-script=" + os.path.join(CSRC, "gbp_exports.map")]      # (-pthread: the host helpers' reader threads, for a libc that still keeps them in libpthread)
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
-    return target
+            target, objs = VARIANTS[v][0], plan[v][0]
+            if done[v] or force or _stale(target, objs):
+                _link(target, objs, verbose)
 
 
-def build(force=False, verbose=False, test_hooks=True):
-    _build_lib(LIB, "product", [], force, verbose)
-    if test_hooks:
-        _build_lib(TEST_LIB, "test", ["-DGBP_BUILD_TEST_HOOKS"], force, verbose)
-    if os.path.exists(EXP_LIB):          # keep an existing measurement build in step with the sources (never created here)
-        build_experiments(force, verbose)
+def build(force=False, verbose=False, test_hooks=True, variants=None):
+    """variants: the libraries to build (names of VARIANTS); by default the product, the test-hooks build unless test_hooks is
+    false, and the experiments build where one exists (kept in step with the sources, never created by default)."""
+    if variants is None:
+        variants = ["product"] + (["test"] if test_hooks else []) + (["exp"] if os.path.exists(EXP_LIB) else [])
+    _build_libs(list(variants), force, verbose)
     os.makedirs(BIN, exist_ok=True)
     inc = os.path.join(HERE, "..", "include")
     cli_deps = [os.path.join(CSRC, f) for f in ("cli_common.hpp", "gbp_transport.hpp", "gbp_metric_gather.hpp")] + [os.path.join(inc, f) for f in os.listdir(inc)] + [LIB]
@@ -126,10 +152,12 @@ def build(force=False, verbose=False, test_hooks=True):
 def build_experiments(force=False, verbose=False):
     """The measurement build: the product sources + test hooks + the ablated / experimental kernel instantiations.
     Loaded only by profiles/*.py (GBP_LIB)."""
-    return _build_lib(EXP_LIB, "exp", ["-DGBP_BUILD_EXPERIMENTS", "-DGBP_BUILD_TEST_HOOKS"], force, verbose)
+    _build_libs(["exp"], force, verbose)
+    return EXP_LIB
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, verbose=True))
-    if "--experiments" in sys.argv:
-        print(build_experiments(force="--force" in sys.argv, verbose=True))
+    exp = "--experiments" in sys.argv
+    print(build(force="--force" in sys.argv, verbose=True, variants=["product", "test", "exp"] if exp else None))
+    if exp:
+        print(EXP_LIB)

@@ -1,5 +1,5 @@
 // experiments/gbp_lab_kernels.hip — the LABORATORY: mapping experiments and timing ablations that DESIGN.md's mapping decision
-// and profiles/HISTORY.md quote.  Included by gbp_kernels.hip (inside namespace gbp, behind the product kernels) ONLY when the
+// and profiles/HISTORY.md quote.  Included by gbp_kernels.hip (behind the product kernels) ONLY when the
 // library is built with -DGBP_BUILD_EXPERIMENTS (`python -m gbp_poplar_amd.build --experiments` -> libgbp_mi355x_exp.so, loaded
 // by profiles/*.py and tests/test_gpu_experiments.py); neither the product nor the test-hooks library contains a line of it.
 //   k_sweep_lab<LAB>   a COPY of the product sweep's shell (sweep_tile) with timing ablations — results are garbage:
@@ -12,7 +12,16 @@
 //   k_sweep_coop16     the north star's sub-wave mapping: 16 lanes per factor, blocks in LDS (bit-identical to k_sweep)
 //   k_inv6_coop        16 lanes per 6x6 inverse (gbp_debug_math op 9)
 // plus the environment overrides of the persistent kernel's placement (GBP_PERSIST_SPREAD).
+#pragma once
+#include "../kernels/gbp_tile.hpp"
+#include "../kernels/gbp_vertex.hpp"
+#include "../kernels/gbp_persist_support.hpp"      // XwBuf (the write-through row sums of ablation 256)
+#include "../kernels/gbp_sweep.hip"     // sweep_tile, k_sweep, kWpb
+
 #include <cstdlib>
+
+namespace gbp {
+using namespace gbpdev;
 
 // ---- timing ablations: the product sweep's shell with pieces switched off ----
 template <int LAB>
@@ -572,3 +581,5 @@ int lab_persist_spread(int spread) {
   static const int env_spread = std::getenv("GBP_PERSIST_SPREAD") ? std::atoi(std::getenv("GBP_PERSIST_SPREAD")) : 0;
   return env_spread ? env_spread : spread;
 }
+
+}  // namespace gbp

@@ -100,7 +100,7 @@ GBP_EXPORT(gbp_debug_get, c, (gbp_ctx* c, int what, float* a, float* b), (c, wha
   return GBP_OK;
 }
 
-// Timing experiment: average duration (us) of `reps` launches of an ablated k_sweep (see gbp_kernels.hip).
+// Timing experiment: average duration (us) of `reps` launches of an ablated k_sweep (see experiments/gbp_lab_kernels.hip).
 // The ctx state is garbage afterwards; upload again before using it.
 GBP_EXPORT(gbp_debug_time_sweep, c, (gbp_ctx* c, int ablation, int reps, double* avg_us), (c, ablation, reps, avg_us)) {
   if (!c || !avg_us || reps <= 0 || !c->uploaded) return GBP_ERR_INVALID;

@@ -1,7 +1,7 @@
 // gbp_api_devio.cpp — the four programs that move state, for a caller whose arrays live on the ctx's GPU (include/gbp_mi355x.h,
 // "Device-resident arrays"): gbp_upload / gbp_read / gbp_read_priors / gbp_new_keyframe land here when their struct holds device
 // pointers (gbp_api_ctx.cpp: struct_kind).  Same targets and same bits as the host-pointer forms, which stage through pinned memory:
-// here kernels read and write the caller's file-order arrays directly (gbp_kernels.hip, "device-resident caller arrays"), everything
+// here kernels read and write the caller's file-order arrays directly (kernels/gbp_state_io.hip, "device-resident caller arrays"), everything
 // is queued on the ctx's stream and nothing waits for it.
 #include "gbp_ctx.hpp"
 

@@ -24,7 +24,7 @@ constexpr int kFacG = 14;
 // it (the camera belief is built from ROWP), and only its eta depends on older history (it is damped): the Lambda part of an active
 // factor's message is Lambda_cc - (Lambda_cl Bi) Lambda_lc (gbp_codelets.cpp:592-637), a function of the potential the factor holds
 // anyway and of the 3x3 inverse Bi it was computed from; the same fp32 operations on the same operands give the same bits, so the
-// record keeps Bi and the sweep re-derives the 21 lower-triangle entries it needs (cam_msg_lambda in gbp_kernels.hip):
+// record keeps Bi and the sweep re-derives the 21 lower-triangle entries it needs (cam_msg_lambda in kernels/gbp_vertex.hpp):
 //   [0..5] eta  [6..14] Bi (row-major)  [15] format word
 // Format (a float, so that the zero fill of gbp_upload IS format 0):
 //   kCmsgZero     the message is zero: what the fill leaves and what an inactive or pad factor writes
@@ -306,7 +306,7 @@ struct DeviceEval {  // per-block partials, summed on the host in block order
 };
 
 // ---- the launchers ------------------------------------------------------------------------------
-// Every function declared from here on (and persist_grid above) is defined exactly once per link: by gbp_kernels.hip, or — the CPU
+// Every function declared from here on (and persist_grid above) is defined exactly once per link: by gbp_kernels.hip (in the kernel unit of kernels/ that holds its kernel), or — the CPU
 // sanitizer build of the host code — by tests/sanitize/kernel_stubs.cpp, which fails to link when one is missing or declared otherwise.
 void launch_sweep(const SweepArgs& a, uint32_t n_tiles, bool hoist, hipStream_t s, bool ev = false);
 void launch_linearise(const SweepArgs& a, uint32_t n_tiles, hipStream_t s);
@@ -350,7 +350,7 @@ void launch_state_set(int* fst_packed, const int* new_count, const uint32_t* ctl
 // slots of its FAC tile (the rest of FAC is zeroed by the caller)
 struct FactorState { int* packed; float* damp; float* var; };      // FST_PACKED, FST_DAMP, FST_VAR
 void launch_upload_scatter(float4* lmsg, const FactorState& fs, float4* fac, const float4* st, const float* var, uint32_t n, hipStream_t s);
-// ---- device-resident caller arrays (gbp_api_devio.cpp; the kernels: "device-resident caller arrays" in gbp_kernels.hip) ----
+// ---- device-resident caller arrays (gbp_api_devio.cpp; the kernels: "device-resident caller arrays" in kernels/gbp_state_io.hip) ----
 // gbp_upload from device pointers: the caller's file-order arrays (NULL = zeros, as in gbp_state_in) -> the records k_upload_scatter writes
 struct UploadDev {
   const uint32_t* pos_edge;        // [n] file index of the factor at device position p, ~0u = pad

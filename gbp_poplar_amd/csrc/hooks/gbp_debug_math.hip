@@ -1,6 +1,13 @@
 // hooks/gbp_debug_math.hip — TEST HOOK (include/gbp_mi355x_debug.h: gbp_debug_math): the device math layer of
-// gbp_device_math.hpp on caller-supplied vectors.  Included by gbp_kernels.hip inside namespace gbp when the library is built
+// gbp_device_math.hpp on caller-supplied vectors.  Included by gbp_kernels.hip when the library is built
 // with -DGBP_BUILD_TEST_HOOKS (libgbp_mi355x_test.so); the product library does not contain it.
+#pragma once
+#include "../kernels/gbp_vertex.hpp"      // belief_means
+#include "gbp_debug_vertex.hip"           // debug_vertex_widths, launch_debug_vertex: the vertex ops are reached through this hook
+
+namespace gbp {
+using namespace gbpdev;
+
 #ifdef GBP_BUILD_EXPERIMENTS
 void lab_launch_inv6_coop(const float* in, float* out, int n, hipStream_t s);
 #endif
@@ -138,3 +145,5 @@ void launch_debug_math(int op, const float* in, float* out, int n, hipStream_t s
 #endif
   hipLaunchKernelGGL(k_debug_math, dim3((n + 63) / 64), dim3(64), 0, s, op, in, out, n, in_w, out_w);
 }
+
+}  // namespace gbp

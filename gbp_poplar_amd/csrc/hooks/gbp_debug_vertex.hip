@@ -1,6 +1,6 @@
 // hooks/gbp_debug_vertex.hip — TEST HOOK (include/gbp_mi355x_debug.h: gbp_debug_vertex): the PRODUCT's vertex layer — relin_core and
-// factor_update of gbp_kernels.hip, the code every sweep kernel runs per lane — on caller-supplied factors, one lane per case, in the
-// reference's tensor names and layouts.  Included by gbp_kernels.hip inside namespace gbp when the library is built with
+// factor_update of kernels/gbp_vertex.hpp, the code every sweep kernel runs per lane — on caller-supplied factors, one lane per case, in the
+// reference's tensor names and layouts.  Included by gbp_kernels.hip when the library is built with
 // -DGBP_BUILD_TEST_HOOKS (libgbp_mi355x_test.so); the product library does not contain it.
 //
 // A case is one factor's complete vertex input; the lane packs it into the FAC[56] / literal camera message [28] / LMSG[16] / CAMB[44] / LMKB[16] records
@@ -20,6 +20,13 @@
 //   factor eta 9, lambda 81 | cam message eta 6, lambda 36 (all 36 entries: what goes into the row sums) | lmk message eta 3, lambda 9
 //   | mu 9 (op 2: the hoisted means; that mode keeps no per-factor mu) | dmu | damping | damping_count (int) | robust_flag (uint)
 //   op 0 writes the potential and the robust flag, zeros elsewhere.
+#pragma once
+#include "../kernels/gbp_tile.hpp"
+#include "../kernels/gbp_vertex.hpp"
+
+namespace gbp {
+using namespace gbpdev;
+
 constexpr int kVtxIn = 229, kVtxOut = 157;
 
 template <int OP>
@@ -214,3 +221,5 @@ static void launch_debug_vertex(int op, const float* in, float* out, int n, hipS
   else if (op == 1) hipLaunchKernelGGL(k_debug_vertex<1>, grid, block, 0, s, in, out, n);
   else hipLaunchKernelGGL(k_debug_vertex<2>, grid, block, 0, s, in, out, n);
 }
+
+}  // namespace gbp

@@ -1,6 +1,6 @@
 // hooks/gbp_flow_torture.hip — TEST HOOK (include/gbp_mi355x_debug.h: gbp_debug_flow_torture): the detector under the one
 // hardware property k_persist_flow relies on that no architecture manual promises — "a 16-byte aligned store of one lane is not
-// observed torn by a wave on another XCD" (gbp_kernels.h: PersistFlow).  Included by gbp_kernels.hip inside namespace gbp when the
+// observed torn by a wave on another XCD" (gbp_kernels.h: PersistFlow).  Included by gbp_kernels.hip when the
 // library is built with -DGBP_BUILD_TEST_HOOKS; the product library does not contain it.
 //
 // The same instructions as the product (XwBuf::st4 / ld4: 128-bit buffer stores / loads with sc1), the same protocol (tagged records,
@@ -14,6 +14,12 @@
 // CONTROL (inject != 0): every 64th record of a lane's round is stored the way a tearing memory system would show it — its tag word
 // first (a 4-byte store), the full record a little later — so that a consumer can meet the awaited tag over the previous payload:
 // the detector must then REPORT torn records (tests/test_gpu_parity.py asserts > 0), which shows that it can.
+#pragma once
+#include "../kernels/gbp_persist_support.hpp"      // XwBuf
+
+namespace gbp {
+using namespace gbpdev;
+
 GBP_DEV unsigned torture_word(unsigned tag, unsigned idx, unsigned c) {
   unsigned x = tag * 0x9E3779B1u ^ (idx + 0x7F4A7C15u) * 0x85EBCA6Bu ^ (c + 1u) * 0xC2B2AE35u;
   x ^= x >> 15; x *= 0x2C1B3C6Du; x ^= x >> 12;
@@ -98,3 +104,5 @@ bool launch_flow_torture(float4* buf, unsigned long long* out, int blocks, int K
   else return false;
   return true;
 }
+
+}  // namespace gbp

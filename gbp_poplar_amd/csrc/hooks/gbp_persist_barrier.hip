@@ -1,9 +1,17 @@
 // gbp_persist_barrier.hip — k_persist<EV>: the persistent kernel of rounds 3-4, two counter barriers per iteration.
 //
 // Not part of the product since round 5 (k_persist_flow replaced it: hand-offs through tagged records).  Kept in the TEST-HOOKS build
-// (included by gbp_kernels.hip under GBP_BUILD_TEST_HOOKS, at the place it used to stand: it uses the helpers above it) as the
+// (included by kernels/gbp_persist.hip under GBP_BUILD_TEST_HOOKS: launch_persist names it) as the
 // reference the parity tests compare the new kernel with and for A/B measurements (gbp_debug_persist_flow(ctx, 0),
 // profiles/time_bursts.py flow=0).
+#pragma once
+#include "../kernels/gbp_tile.hpp"
+#include "../kernels/gbp_vertex.hpp"
+#include "../kernels/gbp_metric_math.hpp"
+#include "../kernels/gbp_persist_support.hpp"
+
+namespace gbp {
+using namespace gbpdev;
 
 // EV: does the launch carry the metric (A.ev.on)?  A launch without it runs an instantiation that holds none of the metric's
 // code or registers (plain bursts 14.3 -> 14.0 us per iteration on fr1xyz).
@@ -121,7 +129,7 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
       eval_wave_record(slots + 1 + w, lane, packed, A.ev.num_undamped, s_norm, s_half);
     }
     // each: this half counts from zero again when its turn comes (two hand-offs from now); one metric: the area goes back to zero like
-    // every other user of the health words leaves it (k_eval in gbp_kernels.hip)
+    // every other user of the health words leaves it (k_eval in kernels/gbp_metric.hip)
     if (bid == 0 && threadIdx.x == 0) health_handoff(slots, health_of(k));
   };
   auto metric_means = [&](uint32_t k, float (&cmv)[6], float (&lmu)[3]) {
@@ -276,7 +284,7 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       if (cam_live && cam_wave) X_camb.st1(v * (uint32_t)kCamRec + cj, sh[wib][cj]);
     } else if (lmk_wave) {
-      float4 acc = lmk_quad_dense(lmk_prior4, q4);      // the sums run on the dense image of the messages (lmsg_load in gbp_kernels.hip)
+      float4 acc = lmk_quad_dense(lmk_prior4, q4);      // the sums run on the dense image of the messages (lmsg_load in kernels/gbp_tile.hpp)
       {  // both batches of loads are issued before the first add (one memory round trip for up to 30 slots: the
          // wave has 512 registers per lane to itself); the adds stay in slot order
         float4 m[15], m2[15];
@@ -376,3 +384,5 @@ __global__ __launch_bounds__(256) void k_persist(const PersistArgs A) {
 
   if (has_tile) tile_regs_store(a, tile, lane, fac, fac_dirty, lm);
 }
+
+}  // namespace gbp

@@ -1,4 +1,4 @@
-"""The device's VERTEX layer — relin_core and factor_update of csrc/gbp_kernels.hip, the per-lane code of every sweep kernel —
+"""The device's VERTEX layer — relin_core and factor_update of csrc/kernels/gbp_vertex.hpp, the per-lane code of every sweep kernel —
 against the vertex cases of tests/vertex_cases.py, one lane per case through the test hook gbp_debug_vertex:
 
   * == the restatement (oracle_gbp.c, trig mode 1: the device's convention) on the FULL generated set, ops 0 / 1 / 2, bit for bit;

@@ -1,4 +1,4 @@
-"""The hand-placed DPP adds of the camera row sums (row16_sums_store, gbp_kernels.hip) sit in inline asm, which hipcc's hazard
+"""The hand-placed DPP adds of the camera row sums (row16_sums_store, csrc/kernels/gbp_tile.hpp) sit in inline asm, which hipcc's hazard
 recogniser does not look into: on gfx9-class hardware a DPP operand must have been written at least two instructions (wait
 states) before the DPP instruction reads it — nothing interlocks, the lanes would read stale registers.  The kernel source
 arranges that by construction (blocks of six behind an s_nop, operands produced before their block); this test holds the
