@@ -16,7 +16,10 @@
 #include "../../include/gbp_mi355x_multi.h"       // --ipus N: one forked rank per GPU
 #include "gbp_transport.hpp"                      // --transport: the names of gbp_comm_init's transport numbers
 #include "gbp_metric_gather.hpp"                  // --ipus N: the cross-rank sum of a burst's metric records
+#include "../../include/gbp_mi355x_post.h"        // --cov_file: means and marginal covariances of the beliefs (libgbp_mi355x_post.so)
 #include "../../include/gbp_mi355x_compat.h"      // MetricPipe: the metric in two halves (gbp_iterate_eval / gbp_eval_end), so that printing overlaps the next iterations
+
+#include <hip/hip_runtime_api.h>                  // --cov_file: the device arrays the readout works on (nothing else here touches HIP)
 
 #include <condition_variable>
 #include <deque>
@@ -101,6 +104,7 @@ struct Options {
   int eval_every = 1;
   int transport = (int)gbp::Transport::Auto;   // --transport (gbp_transport.hpp): what gbp_comm_init is given
   std::string out_file;         // --out_file: write the refined problem (belief means) in the input's format
+  std::string cov_file;         // --cov_file: write every variable's mean and marginal covariance (gbp_post_moments)
   bool force_sharded = false;   // --force_sharded: run the multi-rank code path (fork, shard ctx, communicator) with one rank
 };
 
@@ -129,7 +133,9 @@ inline void usage(bool slam) {
                "  --transport arg (=auto)        exchange between ranks: auto | rccl | host | p2p | p2p-slices | measured (host, p2p, p2p-slices: ranks may\n"
                "                                 share a GPU; host is also spelled host-staged; measured: time every transport the ranks\n"
                "                                 can form, keep the fastest)\n"
-               "  --out_file arg                 write the refined cameras / landmarks (belief means) in the input's format\n";
+               "  --out_file arg                 write the refined cameras / landmarks (belief means) in the input's format\n"
+               "  --cov_file arg                 write every camera's / landmark's mean and marginal covariance: line 1 `C L`, then per camera\n"
+               "                                 6 + 36 values, per landmark 3 + 9 values (covariances row-major)\n";
 }
 
 // returns 0 = run, 1 = exit with code 0 (help), 2 = exit with code 1 (error)
@@ -172,6 +178,7 @@ inline int parse(int argc, char** argv, bool slam, Options& o) {
       else if (k == "eval_every") o.eval_every = std::max(1, std::stoi(v));
       else if (k == "force_sharded") o.force_sharded = B(v);
       else if (k == "out_file") o.out_file = v;
+      else if (k == "cov_file") o.cov_file = v;
       else if (k == "transport") {
         using T = gbp::Transport;
         o.transport = v == "rccl" ? (int)T::Rccl : (v == "host" || v == "host-staged") ? (int)T::HostStaged : v == "p2p" ? (int)T::P2p : v == "p2p-slices" ? (int)T::P2pSlices :
@@ -308,26 +315,17 @@ struct RankCtx {
   gbp_shard shard{0, 1, 0, 0};
 };
 
-// The result area of a forked run with --out_file: cam_beliefs_eta [6C], cam_beliefs_lambda [36C], lmk_beliefs_eta [3L], lmk_beliefs_lambda [9L]
+// The result area of a forked run with --out_file / --cov_file: cam_beliefs_eta [6C], cam_beliefs_lambda [36C], lmk_beliefs_eta [3L], lmk_beliefs_lambda [9L]
 inline size_t result_floats(uint32_t C, uint32_t L) { return 42 * (size_t)C + 12 * (size_t)L; }
+
+inline bool wants_result(const Options& o) { return !o.out_file.empty() || !o.cov_file.empty(); }
 
 constexpr int kLeaveNow = 2;      // write_solution: this rank failed where the others still wait for it — it leaves without meeting them again
 
-// --out_file of a forked run.  Every rank reads its beliefs into the SHARED arrays: gbp_read on a sharded ctx writes the landmarks of the
-// rank's own range at their global indices, so the ranks fill disjoint bytes; the cameras, replicated and bit-identical, are rank 0's.
-// ONE barrier (the region's: release / acquire on its shared words, whatever the transport) lies between every rank's writes and rank 0's
-// reads.  A rank whose read or barrier fails writes nothing and does not reach another barrier: the file never holds arrays that some
-// rank has not filled.
-inline int write_solution_ranks(const Options& o, const Problem& P, gbp_ctx* ctx, const RankCtx& rk) {
+// --out_file: the belief means in the format of the input, observations unchanged
+inline int write_out_file(const Options& o, const Problem& P, const float* cbe, const float* cbl, const float* lbe, const float* lbl) {
+  if (o.out_file.empty()) return 0;
   const uint32_t C = P.bal.n_cams, L = P.bal.n_lmks;
-  if (!rk.result) { std::cerr << "rank " << rk.rank << ": no shared result area for --out_file\n"; return kLeaveNow; }
-  float *cbe = rk.result, *cbl = cbe + 6 * (size_t)C, *lbe = cbl + 36 * (size_t)C, *lbl = lbe + 3 * (size_t)L;
-  gbp_state_out out{};
-  out.lmk_beliefs_eta = lbe; out.lmk_beliefs_lambda = lbl;
-  if (rk.rank == 0) { out.cam_beliefs_eta = cbe; out.cam_beliefs_lambda = cbl; }
-  if (gbp_read(ctx, &out) != GBP_OK) { std::cerr << "rank " << rk.rank << ": gbp_read failed: " << gbp_last_error(ctx) << "\n"; return kLeaveNow; }
-  if (gbp_comm_barrier(ctx) != GBP_OK) { std::cerr << "rank " << rk.rank << ": gbp_comm_barrier failed: " << gbp_last_error(ctx) << "\n"; return kLeaveNow; }
-  if (rk.rank != 0) return 0;
   std::vector<double> cams(6 * (size_t)C), pts(3 * (size_t)L);
   gbp_belief_means(C, L, cbe, cbl, lbe, lbl, cams.data(), pts.data());
   gbp_bal res = P.bal;
@@ -337,23 +335,79 @@ inline int write_solution_ranks(const Options& o, const Problem& P, gbp_ctx* ctx
   return 0;
 }
 
-// --out_file: the solution (belief means) in the format of the input, observations unchanged.  A forked run (--ipus N, --force_sharded):
+// --cov_file: mean and marginal covariance of every variable from the beliefs in host arrays (a forked run's gathered ones alike), through
+// the readout library on the current device.  Line 1 `C L`, then per camera 6 + 36 values, per landmark 3 + 9 values, %.9g.  Nothing on stdout.
+inline int write_cov_file(const Options& o, const Problem& P, const float* cbe, const float* cbl, const float* lbe, const float* lbl) {
+  if (o.cov_file.empty()) return 0;
+  const uint32_t C = P.bal.n_cams, L = P.bal.n_lmks;
+  const size_t n_in = result_floats(C, L), n = 2 * n_in;
+  struct Dev {
+    float* p = nullptr;
+    ~Dev() { if (p) (void)hipFree(p); }
+  } dev;
+  std::vector<float> host(n_in);
+  auto hip_ok = [](hipError_t e, const char* what) {
+    if (e != hipSuccess) std::cerr << "--cov_file: " << what << " failed: " << hipGetErrorString(e) << "\n";
+    return e == hipSuccess;
+  };
+  if (!hip_ok(hipMalloc(reinterpret_cast<void**>(&dev.p), n * sizeof(float)), "hipMalloc")) return 1;
+  float *d_cbe = dev.p, *d_cbl = d_cbe + 6 * (size_t)C, *d_lbe = d_cbl + 36 * (size_t)C, *d_lbl = d_lbe + 3 * (size_t)L;
+  float *d_cm = dev.p + n_in, *d_cc = d_cm + 6 * (size_t)C, *d_lm = d_cc + 36 * (size_t)C, *d_lc = d_lm + 3 * (size_t)L;
+  const struct { float* d; const float* h; size_t count; } in[4] = {{d_cbe, cbe, 6 * (size_t)C}, {d_cbl, cbl, 36 * (size_t)C}, {d_lbe, lbe, 3 * (size_t)L}, {d_lbl, lbl, 9 * (size_t)L}};
+  for (const auto& a : in)
+    if (a.count && !hip_ok(hipMemcpy(a.d, a.h, a.count * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy")) return 1;
+  // (the default stream: the blocking copies before and behind the launch are ordered with it)
+  if (gbp_post_moments(nullptr, C, L, d_cbe, d_cbl, d_lbe, d_lbl, d_cm, d_cc, d_lm, d_lc, nullptr, nullptr) != GBP_OK) {
+    std::cerr << "--cov_file: " << gbp_post_last_error() << "\n";
+    return 1;
+  }
+  if (n_in && !hip_ok(hipMemcpy(host.data(), d_cm, n_in * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy")) return 1;
+  FILE* f = std::fopen(o.cov_file.c_str(), "w");
+  if (!f) { std::cerr << "ERROR: unable to write " << o.cov_file << "\n"; return 1; }
+  std::fprintf(f, "%u %u\n", C, L);
+  const float *cm = host.data(), *cc = cm + 6 * (size_t)C, *lm = cc + 36 * (size_t)C, *lc = lm + 3 * (size_t)L;
+  auto line = [f](const float* mean, const float* cov, int w) {
+    for (int i = 0; i < w; ++i) std::fprintf(f, "%.9g ", mean[i]);
+    for (int i = 0; i < w * w; ++i) std::fprintf(f, i + 1 < w * w ? "%.9g " : "%.9g\n", cov[i]);
+  };
+  for (uint32_t c = 0; c < C; ++c) line(cm + 6 * (size_t)c, cc + 36 * (size_t)c, 6);
+  for (uint32_t l = 0; l < L; ++l) line(lm + 3 * (size_t)l, lc + 9 * (size_t)l, 3);
+  const bool bad = std::ferror(f) != 0;
+  if (std::fclose(f) != 0 || bad) { std::cerr << "ERROR: unable to write " << o.cov_file << "\n"; return 1; }
+  return 0;
+}
+
+// --out_file / --cov_file of a forked run.  Every rank reads its beliefs into the SHARED arrays: gbp_read on a sharded ctx writes the landmarks of the
+// rank's own range at their global indices, so the ranks fill disjoint bytes; the cameras, replicated and bit-identical, are rank 0's.
+// ONE barrier (the region's: release / acquire on its shared words, whatever the transport) lies between every rank's writes and rank 0's
+// reads.  A rank whose read or barrier fails writes nothing and does not reach another barrier: the file never holds arrays that some
+// rank has not filled.
+inline int write_solution_ranks(const Options& o, const Problem& P, gbp_ctx* ctx, const RankCtx& rk) {
+  const uint32_t C = P.bal.n_cams, L = P.bal.n_lmks;
+  if (!rk.result) { std::cerr << "rank " << rk.rank << ": no shared result area for --out_file / --cov_file\n"; return kLeaveNow; }
+  float *cbe = rk.result, *cbl = cbe + 6 * (size_t)C, *lbe = cbl + 36 * (size_t)C, *lbl = lbe + 3 * (size_t)L;
+  gbp_state_out out{};
+  out.lmk_beliefs_eta = lbe; out.lmk_beliefs_lambda = lbl;
+  if (rk.rank == 0) { out.cam_beliefs_eta = cbe; out.cam_beliefs_lambda = cbl; }
+  if (gbp_read(ctx, &out) != GBP_OK) { std::cerr << "rank " << rk.rank << ": gbp_read failed: " << gbp_last_error(ctx) << "\n"; return kLeaveNow; }
+  if (gbp_comm_barrier(ctx) != GBP_OK) { std::cerr << "rank " << rk.rank << ": gbp_comm_barrier failed: " << gbp_last_error(ctx) << "\n"; return kLeaveNow; }
+  if (rk.rank != 0) return 0;
+  if (const int rc = write_out_file(o, P, cbe, cbl, lbe, lbl)) return rc;
+  return write_cov_file(o, P, cbe, cbl, lbe, lbl);
+}
+
+// --out_file / --cov_file: the solution from the beliefs the run ends with.  A forked run (--ipus N, --force_sharded):
 // write_solution_ranks.
 inline int write_solution(const Options& o, const Problem& P, gbp_ctx* ctx, const RankCtx& rk) {
-  if (o.out_file.empty()) return 0;
+  if (!wants_result(o)) return 0;
   if (rk.region) return write_solution_ranks(o, P, ctx, rk);
   const uint32_t C = P.bal.n_cams, L = P.bal.n_lmks;
   std::vector<float> cbe(6 * (size_t)C), cbl(36 * (size_t)C), lbe(3 * (size_t)L), lbl(9 * (size_t)L);
   gbp_state_out out{};
   out.cam_beliefs_eta = cbe.data(); out.cam_beliefs_lambda = cbl.data(); out.lmk_beliefs_eta = lbe.data(); out.lmk_beliefs_lambda = lbl.data();
   if (gbp_read(ctx, &out) != GBP_OK) { std::cerr << "gbp_read failed: " << gbp_last_error(ctx) << "\n"; return 1; }
-  std::vector<double> cams(6 * (size_t)C), pts(3 * (size_t)L);
-  gbp_belief_means(C, L, cbe.data(), cbl.data(), lbe.data(), lbl.data(), cams.data(), pts.data());
-  gbp_bal res = P.bal;
-  res.cameras = cams.data(); res.points = pts.data();
-  if (gbp_bal_write(o.out_file.c_str(), &res) != GBP_OK) { std::cerr << "ERROR: unable to write " << o.out_file << "\n"; return 1; }
-  std::cout << "Refined problem written to " << o.out_file << "\n";
-  return 0;
+  if (const int rc = write_out_file(o, P, cbe.data(), cbl.data(), lbe.data(), lbl.data())) return rc;
+  return write_cov_file(o, P, cbe.data(), cbl.data(), lbe.data(), lbl.data());
 }
 
 // A single-process run brings the HIP runtime up (120 - 240 ms: the first call that needs it) on a second thread WHILE the main thread

@@ -22,6 +22,16 @@ namespace gbpdev {
 // (measured per site with the executed-instruction counters, profiles/r04_alu_diet.md).
 #define GBP_SLP_FENCE(x) asm("" : "+v"(x))
 
+// "Does any lane of the wave see p": the builtin in a HIP translation unit.  The routines below are also compiled as plain C++
+// for the host (post/post_math.hpp: the solution readout's host twin, where one call is one "lane"); there the wave is that one
+// call, and the two device intrinsics the routines use are spelled out.
+#if defined(__HIP__)
+#define GBP_ANY_LANE(p) (__builtin_amdgcn_ballot_w64(p) != 0ull)
+#else
+#define GBP_ANY_LANE(p) (p)
+inline uint32_t __float_as_uint(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
+#endif
+
 // packed lower-triangle index, i >= j
 GBP_DEV constexpr int tri(int i, int j) { return i * (i + 1) / 2 + j; }
 GBP_DEV constexpr int trisym(int i, int j) { return i >= j ? tri(i, j) : tri(j, i); }
@@ -57,7 +67,7 @@ GBP_DEV void div_shared(const float (&v)[N], float m, float (&q)[N]) {
   const bool redo = least < 2u * (__float_as_uint(thr) + 2u) - 1u;
   // (the slow path behind a WAVE-UNIFORM test, so that it is a branch no wavefront takes instead of nine divisions the
   // compiler might if-convert into every lane's instruction stream)
-  if (__builtin_amdgcn_ballot_w64(redo) != 0ull) {
+  if (GBP_ANY_LANE(redo)) {
     if (redo) {
       GBP_UNROLL
       for (int i = 0; i < N; ++i) q[i] = v[i] / m;

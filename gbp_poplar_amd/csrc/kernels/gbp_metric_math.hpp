@@ -1,6 +1,7 @@
 // kernels/gbp_metric_math.hpp — the metric math: fp64 pivot solves of the beliefs, the reprojection residual of a factor, the
 // order of the metric's sums and the records they leave.  Device helpers only; used by the metric kernels and by every kernel the
-// metric rides in (k_sweep<EV>, k_beliefs*_ev, k_persist_flow<EV>).
+// metric rides in (k_sweep<EV>, k_beliefs*_ev, k_persist_flow<EV>).  The per-lane arithmetic in front of "THE ORDER OF THE METRIC'S
+// SUMS" is also what the solution readout is made of (post/post_math.hpp), which compiles it for the host as well.
 #pragma once
 #include "../gbp_kernels.h"
 #include "../gbp_device_math.hpp"
@@ -105,8 +106,10 @@ GBP_DEV void eval_cam_rot(const float (&cm)[6], float (&R)[9]) {
     }
   }
 }
+// the residual itself, z - pi(mean): what the metric sums (eval_residual) and what the solution readout hands out per observation
+// (post/post_math.hpp)
 template <class KF>     // Kd[i]: the pin-hole matrix from a device pointer (k_eval) or from the kernel arguments
-GBP_DEV void eval_residual(const float (&R)[9], const float (&t)[3], const float (&lmu)[3], float z0, float z1, KF&& Kd, double& s_norm, double& s_half) {
+GBP_DEV void eval_reproj_residual(const float (&R)[9], const float (&t)[3], const float (&lmu)[3], float z0, float z1, KF&& Kd, float& r0, float& r1) {
   float pcf[3], pr[2];
   GBP_UNROLL
   for (int i = 0; i < 3; ++i) pcf[i] = (R[i * 3] * lmu[0] + R[i * 3 + 1] * lmu[1]) + R[i * 3 + 2] * lmu[2];
@@ -114,7 +117,13 @@ GBP_DEV void eval_residual(const float (&R)[9], const float (&t)[3], const float
   for (int i = 0; i < 3; ++i) pcf[i] += t[i];
   GBP_UNROLL
   for (int i = 0; i < 2; ++i) pr[i] = ((Kd[i * 3] * pcf[0] + Kd[i * 3 + 1] * pcf[1]) + Kd[i * 3 + 2] * pcf[2]) / pcf[2];
-  const float r0 = z0 - pr[0], r1 = z1 - pr[1];
+  r0 = z0 - pr[0];
+  r1 = z1 - pr[1];
+}
+template <class KF>
+GBP_DEV void eval_residual(const float (&R)[9], const float (&t)[3], const float (&lmu)[3], float z0, float z1, KF&& Kd, double& s_norm, double& s_half) {
+  float r0, r1;
+  eval_reproj_residual(R, t, lmu, z0, z1, Kd, r0, r1);
   s_norm += (double)sqrtf(r0 * r0 + r1 * r1);
   s_half += (double)(float)(0.5 * (double)(r0 * r0 + r1 * r1));
 }
@@ -124,6 +133,7 @@ GBP_DEV void eval_factor(const float (&cm)[6], const float (&lmu)[3], float z0, 
   const float t[3] = {cm[0], cm[1], cm[2]};
   eval_residual(R, t, lmu, z0, z1, Kd, s_norm, s_half);
 }
+#if defined(__HIP__)      // below: wave-level code (what is above is per-lane arithmetic that post/post_math.hpp also compiles for the host)
 // THE ORDER OF THE METRIC'S SUMS (every path produces exactly these fp64 additions):
 //   w_t  = the 64 lane values of tile t (0 + the factor's term) reduced by the shuffle tree below;
 //   B_b  = ((w_4b + w_4b+1) + w_4b+2) + w_4b+3      the 256 factor positions of sweep workgroup b;
@@ -207,5 +217,7 @@ GBP_DEV void health_handoff(DeviceEval* slots, unsigned long long* h) {
   __hip_atomic_store(&h[0], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __hip_atomic_store(&h[1], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+
+#endif  // __HIP__
 
 }  // namespace gbp

@@ -184,7 +184,7 @@ int main(int argc, char** argv) {
   cli::phases().mark("file_parse_s");             // the file, the priors, the scalings
   if (P.bal.n_cams < 2) { std::cerr << "slam needs at least two keyframes\n"; return 1; }
   const int world = cli::round_up_pow2(std::max(1, o.gpus));   // slam.cpp:422-425 / ba.cpp:617-621
-  const size_t result_count = o.out_file.empty() ? 0 : cli::result_floats(P.bal.n_cams, P.bal.n_lmks);      // --out_file: the ranks' shared belief arrays
+  const size_t result_count = cli::wants_result(o) ? cli::result_floats(P.bal.n_cams, P.bal.n_lmks) : 0;      // --out_file / --cov_file: the ranks' shared belief arrays
   const int rc = cli::run_ranks(world, P.bal.n_cams, o.force_sharded, result_count, [&](cli::RankCtx& rk) { return run(o, P, rk); });
   // Everything is written and flushed, the ctx is destroyed: leave WITHOUT running the HIP runtime's exit handlers (70 - 90 ms during
   // which the user's prompt does not come back: a fifth of a `ba fr1xyz` run; the driver reclaims the process's resources either way)

@@ -168,6 +168,20 @@ class ShardedGbp:
                                ("damping", "damping_count", "robust_flag"))
         return out
 
+    def solution(self, measurements=None, active_flag=None, gather=True):
+        """GbpEngine.solution() of the sharded run: means, marginal covariances and status words of every variable — and, with
+        `measurements` (the whole graph's, [2E]), the residual and reprojection covariance of every edge — from read(gather).
+        gather=True (collective: every rank calls it): the complete solution on every rank; gather=False: this rank's view, entries of
+        other ranks' landmarks and of their factors are meaningless.  numpy arrays; blocks."""
+        from . import post
+        out = post.moments(self.read(gather=gather))
+        if measurements is not None:
+            p = self.e.problem
+            n_e = int(p.n_edges)
+            ids = [np.ctypeslib.as_array(a, shape=(n_e,)) if n_e else np.zeros(0, np.uint32) for a in (p.cam_id, p.lmk_id)]
+            out.update(post.residuals(ids[0], ids[1], [p.K[i] for i in range(9)], out, measurements, active_flag, covs=out))
+        return out
+
     def read_priors(self, gather=False):
         """as read(): the local view, or with gather=True the landmark priors of every range from its owner"""
         out = self.e.read_priors()

@@ -32,6 +32,8 @@ class GbpEngine:
         if rc != 0:
             raise GbpError("gbp_create: %s (status %d)" % (self.lib.gbp_last_error(None).decode(), rc))
         self.h = h
+        self._stream = None          # the caller's stream the ctx runs on (set_stream); None: a stream of the ctx's own
+        self._edge_ids = None        # cam_id / lmk_id on the GPU (solution())
         self._device = self._current_device(only_if_initialised=True)      # the GPU the ctx lives on: the current device of gbp_create
 
     def close(self):
@@ -171,6 +173,45 @@ class GbpEngine:
             s = cabi.fill_struct(cabi.GbpKfUpdate(), upd, keep)
         self._chk(self.lib.gbp_new_keyframe(self.h, C.byref(s)), "gbp_new_keyframe")
 
+    # ---- the solution: what a user wants from a finished run (gbp_poplar_amd/post.py, include/gbp_mi355x_post.h) ----
+    def solution(self, measurements=None, active_flag=None, device=False):
+        """The beliefs as means, marginal covariances and status words per variable — post.moments(read(device=True)) — and, with
+        `measurements` [2E] (and `active_flag` [E], default: every edge active; numpy arrays or tensors on the engine's GPU), the
+        reprojection residual and its covariance per edge — post.residuals over the graph's cam_id / lmk_id and K.  Returns one dict:
+        cam_mean, cam_cov, lmk_mean, lmk_cov, cam_status, lmk_status (+ residual, reproj_cov); see post.py for shapes and meaning.
+        Everything is computed on the GPU from the device-resident read.  Where the ctx runs on the caller's stream (set_stream), the
+        read and the readout are queued there and nothing waits; where it runs on a stream of its own, THIS CALL BLOCKS: it calls
+        sync() between the read and the readout, which is launched on torch's current stream.  device=False (default): numpy
+        arrays, which blocks in either case; device=True: tensors on the engine's GPU, valid for work queued behind the call."""
+        import torch
+        from . import post
+        beliefs = self.read(device=True)
+        if self._stream is None:
+            self.sync()
+        dev = self.device()
+        with torch.cuda.device(dev):
+            stream = self._stream if self._stream is not None else torch.cuda.current_stream().cuda_stream
+            out = post.moments(beliefs, stream=stream)
+            if measurements is not None:
+                if self._edge_ids is None:
+                    ids = [np.ctypeslib.as_array(p, shape=(self.E,)) if self.E else np.zeros(0, np.uint32) for p in (self.problem.cam_id, self.problem.lmk_id)]
+                    self._edge_ids = [torch.from_numpy(a.view(np.int32).copy()).to(dev) for a in ids]
+
+                def on_gpu(a, ints):
+                    if a is None or cabi.is_device_tensor(a):
+                        return a
+                    a = np.ascontiguousarray(a, dtype=np.uint32 if ints else np.float32).reshape(-1)
+                    t = torch.from_numpy(a.view(np.int32) if ints else a).to(dev)
+                    if self._stream is not None:      # (staged on torch's current stream, read on the ctx's)
+                        torch.cuda.current_stream().synchronize()
+                    return t
+                out.update(post.residuals(self._edge_ids[0], self._edge_ids[1], [self.problem.K[i] for i in range(9)], out,
+                                          on_gpu(measurements, False), on_gpu(active_flag, True), covs=out, stream=stream))
+        if device:
+            return out
+        torch.cuda.synchronize(dev)
+        return {k: (v.cpu().numpy().view(np.uint32) if k.endswith("status") else v.cpu().numpy()) for k, v in out.items()}
+
     # The metric in device memory.  eval / iterate_eval_each / ba_loop with device=True (or out= a contiguous torch.int64 tensor on the
     # engine's GPU, [7] for eval, [n, 7] for the loops) make the library write its gbp_eval_out records there: the call does not wait, the
     # records are valid for work queued behind it on the ctx's stream (set_stream) or after sync(), and the tensor must stay allocated
@@ -252,6 +293,7 @@ class GbpEngine:
     # ---- split-phase (sharded) ----
     def set_stream(self, stream_handle):
         self._chk(self.lib.gbp_set_stream(self.h, C.c_void_p(stream_handle)), "gbp_set_stream")
+        self._stream = int(stream_handle) if stream_handle else None      # (NULL / 0: back on the ctx's own stream)
 
     def set_exchange_buffers(self, send_ptr, recv_ptr):
         self._chk(self.lib.gbp_set_exchange_buffers(self.h, C.c_void_p(send_ptr), C.c_void_p(recv_ptr)),

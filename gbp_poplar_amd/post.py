@@ -1,0 +1,176 @@
+"""Solution readout — Python face of libgbp_mi355x_post.so (include/gbp_mi355x_post.h): means, marginal covariances and a status word
+per variable from the beliefs gbp_read returns (moments), reprojection residuals and their covariance per observation (residuals).
+
+Both take torch tensors on the GPU — read in place, results in fresh tensors on the same GPU, nothing waits: the work is queued on
+`stream` (a raw stream handle; default: torch's current stream) and the results are valid for what is queued behind it there.  Both
+also take numpy arrays: those are staged through device tensors and the call blocks until the numpy results are there.  The library is
+a loader of its own beside _lib.py: it has no ctx and is not part of the program list.  There is no CPU path: the kernels are HIP."""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _cabi as cabi
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(HERE, "libgbp_mi355x_post.so")
+GBP_POST_ABI_VERSION = 1
+STATUS_NONFINITE, STATUS_NONPD = 1, 2      # status bits: an output of the variable is not finite / Lambda fails the LDL^T pivot test
+_lib = None
+
+_vp = C.c_void_p
+# every symbol include/gbp_mi355x_post.h declares (array pointers are device addresses: passed as void*)
+_SIGS = {
+    "gbp_post_abi_version": (C.c_int, []),
+    "gbp_post_last_error": (C.c_char_p, []),
+    "gbp_post_moments": (C.c_int, [_vp, C.c_uint32, C.c_uint32] + [_vp] * 10),
+    "gbp_post_residuals": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, C.POINTER(C.c_float)] + [_vp] * 8),
+}
+
+
+def symbols():
+    return sorted(_SIGS)
+
+
+def load():
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise RuntimeError("native library %s is missing — build it with `python -m gbp_poplar_amd.build` "
+                           "(hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
+    if os.environ.get("GBP_NO_TORCH") != "1":      # one HIP runtime per process: torch's first (see _lib.load)
+        try:
+            import torch
+            torch.cuda.is_available()
+        except ImportError:
+            pass
+    lib = C.CDLL(LIB_PATH)
+    lib.gbp_post_abi_version.restype = C.c_int
+    lib.gbp_post_abi_version.argtypes = []
+    if lib.gbp_post_abi_version() != GBP_POST_ABI_VERSION:
+        raise RuntimeError("%s has ABI version %d, these bindings were written for %d — rebuild (python -m gbp_poplar_amd.build)"
+                           % (LIB_PATH, lib.gbp_post_abi_version(), GBP_POST_ABI_VERSION))
+    for name, (res, args) in _SIGS.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _lib = lib
+    return lib
+
+
+class PostError(RuntimeError):
+    pass
+
+
+def _chk(rc, what):
+    if rc != 0:
+        raise PostError("%s: %s (status %d)" % (what, load().gbp_post_last_error().decode(), rc))
+
+
+_BELIEFS = (("cam_beliefs_eta", 6), ("cam_beliefs_lambda", 36), ("lmk_beliefs_eta", 3), ("lmk_beliefs_lambda", 9))
+_F32, _U32 = ("torch.float32",), ("torch.int32", "torch.uint32")
+
+
+def _device_of(arrays):
+    dev = {a.device for a in arrays if cabi.is_device_tensor(a)}
+    if len(dev) != 1:
+        raise TypeError("expected torch tensors on ONE GPU, got %s" % (sorted(map(str, dev)) or "none"))
+    return dev.pop()
+
+
+def _tensor(name, a, dtypes, count, device):
+    """`a` as the library reads it: a contiguous tensor of one of `dtypes` with `count` elements on `device` (nothing is converted)"""
+    if not cabi.is_device_tensor(a):
+        raise TypeError("%s: a host array beside device tensors — one call takes host arrays or device tensors, not both" % name)
+    if a.device != device:
+        raise TypeError("%s is on %s, the other arrays on %s" % (name, a.device, device))
+    if str(a.dtype) not in dtypes:
+        raise TypeError("%s: dtype %s, expected %s (no silent conversion of device tensors)" % (name, a.dtype, dtypes[0]))
+    if not a.is_contiguous():
+        raise TypeError("%s is not contiguous (no silent copy of device tensors)" % name)
+    if a.numel() != count:
+        raise TypeError("%s has %d elements, expected %d" % (name, a.numel(), count))
+    return a
+
+
+def _ptr(t):
+    return _vp(t.data_ptr()) if t is not None and t.numel() else _vp()
+
+
+def _stream_handle(stream):
+    import torch
+    if stream is None:
+        return torch.cuda.current_stream().cuda_stream
+    return int(getattr(stream, "cuda_stream", stream))
+
+
+def _to_device(a, ints=False):
+    """a numpy array (or None) -> a flat tensor on the current GPU: float32, or the uint32 bits as int32"""
+    import torch
+    if a is None:
+        return None
+    if not torch.cuda.is_available():
+        raise PostError("no HIP device: the solution readout runs on the GPU (there is no CPU path)")
+    a = np.ascontiguousarray(a, dtype=np.uint32 if ints else np.float32).reshape(-1)
+    return torch.from_numpy(a.view(np.int32) if ints else a).to("cuda")
+
+
+def _to_host(out):
+    """the numpy form of a result (blocks until every stream of the GPU has finished); status words as uint32"""
+    import torch
+    torch.cuda.synchronize()
+    return {k: (v.cpu().numpy().view(np.uint32) if k.endswith("status") else v.cpu().numpy()) for k, v in out.items()}
+
+
+def moments(beliefs, stream=None):
+    """beliefs: the four belief arrays of read() (cam_beliefs_eta [6C], cam_beliefs_lambda [36C], lmk_beliefs_eta [3L],
+    lmk_beliefs_lambda [9L]; other members are ignored).  Returns cam_mean [6C], cam_cov [36C], lmk_mean [3L], lmk_cov [9L] (float32; the
+    covariances row-major, the general inverse: not symmetrised), cam_status [C], lmk_status [L] (int32; STATUS_NONFINITE | STATUS_NONPD).
+    Device tensors in: device tensors out, not blocking.  numpy in: numpy out, blocking."""
+    import torch
+    b = {k: beliefs[k] for k, _ in _BELIEFS}
+    if not any(cabi.is_device_tensor(a) for a in b.values()):
+        return _to_host(moments({k: _to_device(v) for k, v in b.items()}, stream))
+    dev = _device_of(b.values())
+    n_c, n_l = b["cam_beliefs_eta"].numel() // 6, b["lmk_beliefs_eta"].numel() // 3
+    t = {k: _tensor(k, b[k], _F32, w * (n_c if k.startswith("cam") else n_l), dev) for k, w in _BELIEFS}
+    out = {"cam_mean": torch.empty(6 * n_c, dtype=torch.float32, device=dev), "cam_cov": torch.empty(36 * n_c, dtype=torch.float32, device=dev),
+           "lmk_mean": torch.empty(3 * n_l, dtype=torch.float32, device=dev), "lmk_cov": torch.empty(9 * n_l, dtype=torch.float32, device=dev),
+           "cam_status": torch.empty(n_c, dtype=torch.int32, device=dev), "lmk_status": torch.empty(n_l, dtype=torch.int32, device=dev)}
+    with torch.cuda.device(dev):
+        _chk(load().gbp_post_moments(_vp(_stream_handle(stream)), n_c, n_l, *[_ptr(t[k]) for k, _ in _BELIEFS],
+                                     *[_ptr(out[k]) for k in ("cam_mean", "cam_cov", "lmk_mean", "lmk_cov", "cam_status", "lmk_status")]),
+             "gbp_post_moments")
+    return out
+
+
+def residuals(cam_id, lmk_id, K, means, measurements, active_flag=None, covs=None, stream=None):
+    """One result per edge, in file order.  cam_id, lmk_id [E] (int32 / uint32), K: the nine pin-hole entries (host), means: cam_mean
+    [6C] and lmk_mean [3L], measurements [2E], active_flag [E] or None (= all active), covs: cam_cov [36C] and lmk_cov [9L] or None.
+    Returns residual [2E] = z - pi(mean) and, with covs, reproj_cov [3E] = (S00, S01, S11) of J_c cov_c J_c^T + J_l cov_l J_l^T (the
+    camera-landmark cross term is neglected); inactive edges hold zeros.  Device tensors in: device tensors out, not blocking.  numpy
+    in: numpy out, blocking."""
+    import torch
+    arrays = {"cam_id": cam_id, "lmk_id": lmk_id, "cam_mean": means["cam_mean"], "lmk_mean": means["lmk_mean"], "measurements": measurements,
+              "active_flag": active_flag, "cam_cov": None if covs is None else covs["cam_cov"], "lmk_cov": None if covs is None else covs["lmk_cov"]}
+    ints = ("cam_id", "lmk_id", "active_flag")
+    if not any(cabi.is_device_tensor(a) for a in arrays.values()):
+        d = {k: _to_device(v, k in ints) for k, v in arrays.items()}
+        return _to_host(residuals(d["cam_id"], d["lmk_id"], K, d, d["measurements"], d["active_flag"], None if covs is None else d, stream))
+    present = [a for a in arrays.values() if a is not None]
+    dev = _device_of(present)
+    n_e = arrays["cam_id"].numel()
+    n_c, n_l = arrays["cam_mean"].numel() // 6, arrays["lmk_mean"].numel() // 3
+    counts = {"cam_id": n_e, "lmk_id": n_e, "cam_mean": 6 * n_c, "lmk_mean": 3 * n_l, "measurements": 2 * n_e, "active_flag": n_e,
+              "cam_cov": 36 * n_c, "lmk_cov": 9 * n_l}
+    t = {k: None if a is None else _tensor(k, a, _U32 if k in ints else _F32, counts[k], dev) for k, a in arrays.items()}
+    out = {"residual": torch.empty(2 * n_e, dtype=torch.float32, device=dev)}
+    if covs is not None:
+        out["reproj_cov"] = torch.empty(3 * n_e, dtype=torch.float32, device=dev)
+    k9 = (C.c_float * 9)(*[float(x) for x in np.asarray(K, dtype=np.float64).reshape(9)])
+    with torch.cuda.device(dev):
+        _chk(load().gbp_post_residuals(_vp(_stream_handle(stream)), n_c, n_l, n_e, _ptr(t["cam_id"]), _ptr(t["lmk_id"]), k9, _ptr(t["cam_mean"]),
+                                       _ptr(t["lmk_mean"]), _ptr(t["measurements"]), _ptr(t["active_flag"]), _ptr(t["cam_cov"]), _ptr(t["lmk_cov"]),
+                                       _ptr(out["residual"]), _ptr(out.get("reproj_cov"))), "gbp_post_residuals")
+    return out
