@@ -1,6 +1,6 @@
 # Top-level build for C/C++ users (the Python entry point __graft_entry__.build() does the same).
-#   make            libgbp_mi355x.so (HIP kernels + C-ABI + host helpers, gfx950), libgbp_mi355x_post.so (the solution readout)
-#                   and bin/ba, bin/slam, bin/bal_convert
+#   make            libgbp_mi355x.so (HIP kernels + C-ABI + host helpers, gfx950), libgbp_mi355x_post.so (the solution readout),
+#                   libgbp_mi355x_seed.so (landmark / keyframe seeding) and bin/ba, bin/slam, bin/bal_convert
 #   make oracle     the CPU oracle (test infrastructure)
 #   make test       CPU test suite
 HIPCC   ?= hipcc
@@ -11,9 +11,11 @@ CSRC    := $(PKG)/csrc
 LIB     := $(PKG)/libgbp_mi355x.so
 POST    := $(PKG)/post
 POST_LIB := $(PKG)/libgbp_mi355x_post.so
+SEED    := $(PKG)/seed
+SEED_LIB := $(PKG)/libgbp_mi355x_seed.so
 HIPFLAGS := -O3 -std=c++17 -fPIC -ffp-contract=off -fvisibility=hidden -Wall -Wno-unused-function
 OBJDIR  := $(PKG)/_obj/make
-# the ROCm tree of $(HIPCC): its headers for the plain C++ translation units, its runtime for the CLIs (--cov_file hands device arrays to the readout)
+# the ROCm tree of $(HIPCC): its headers for the plain C++ translation units, its runtime for the CLIs (--cov_file and --lmk_init hand device arrays to the readout and the seeding)
 ROCM    := $(patsubst %/,%,$(dir $(shell readlink -f $$(which $(HIPCC)))))/..
 # device code: host + gfx950 pass; the C-ABI (gbp_api_*.cpp, see gbp_ctx.hpp), the device order, the transports, the host helpers: plain C++
 # (the rule of gbp_poplar_amd/build.py: every csrc/*.cpp that is not the main of a CLI)
@@ -23,7 +25,7 @@ OBJS    := $(OBJDIR)/gbp_kernels.o $(HOST_SRCS:%.cpp=$(OBJDIR)/%.o)
 # hooks and experiments that gbp_kernels.hip #includes, the export map
 HDRS    := $(filter-out $(CSRC)/gbp_kernels.hip $(wildcard $(CSRC)/*.cpp),$(wildcard $(CSRC)/*.* $(CSRC)/*/*)) $(wildcard include/*.h)
 
-all: $(LIB) $(POST_LIB) $(PKG)/bin/ba $(PKG)/bin/slam $(PKG)/bin/bal_convert
+all: $(LIB) $(POST_LIB) $(SEED_LIB) $(PKG)/bin/ba $(PKG)/bin/slam $(PKG)/bin/bal_convert
 
 $(OBJDIR)/gbp_kernels.o: $(CSRC)/gbp_kernels.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
@@ -44,9 +46,17 @@ $(OBJDIR)/gbp_post.o: $(POST)/gbp_post.hip $(wildcard $(POST)/*.hpp) $(HDRS)
 $(POST_LIB): $(OBJDIR)/gbp_post.o $(POST)/gbp_post_exports.map
 	$(HIPCC) -shared -o $@ --offload-arch=$(ARCH) $< -Wl,--version-script=$(POST)/gbp_post_exports.map
 
-$(PKG)/bin/%: $(CSRC)/%_main.cpp $(CSRC)/cli_common.hpp $(CSRC)/gbp_transport.hpp $(CSRC)/gbp_metric_gather.hpp include/gbp_mi355x.h include/gbp_mi355x_multi.h include/gbp_mi355x_compat.h include/gbp_mi355x_post.h $(LIB) $(POST_LIB)
+# landmark / keyframe seeding (include/gbp_mi355x_seed.h): built the way the readout is
+$(OBJDIR)/gbp_seed.o: $(SEED)/gbp_seed.hip $(wildcard $(SEED)/*.hpp) $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) -c -o $@ $(HIPFLAGS) --offload-arch=$(ARCH) -x hip $<
+
+$(SEED_LIB): $(OBJDIR)/gbp_seed.o $(SEED)/gbp_seed_exports.map
+	$(HIPCC) -shared -o $@ --offload-arch=$(ARCH) $< -Wl,--version-script=$(SEED)/gbp_seed_exports.map
+
+$(PKG)/bin/%: $(CSRC)/%_main.cpp $(CSRC)/cli_common.hpp $(CSRC)/gbp_transport.hpp $(CSRC)/gbp_metric_gather.hpp include/gbp_mi355x.h include/gbp_mi355x_multi.h include/gbp_mi355x_compat.h include/gbp_mi355x_post.h include/gbp_mi355x_seed.h $(LIB) $(POST_LIB) $(SEED_LIB)
 	@mkdir -p $(PKG)/bin
-	$(CXX) -o $@ -O2 -std=c++17 -ffp-contract=off -pthread -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include $< -L$(PKG) -lgbp_mi355x -lgbp_mi355x_post \
+	$(CXX) -o $@ -O2 -std=c++17 -ffp-contract=off -pthread -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include $< -L$(PKG) -lgbp_mi355x -lgbp_mi355x_post -lgbp_mi355x_seed \
 		-L$(ROCM)/lib -lamdhip64 -Wl,-rpath,$(ROCM)/lib '-Wl,-rpath,$$ORIGIN/..'
 
 oracle:
@@ -57,7 +67,7 @@ test: all oracle
 	python -m pytest tests -x -q -m "not gpu"
 
 clean:
-	rm -rf $(OBJDIR) $(LIB) $(POST_LIB) $(PKG)/bin/ba $(PKG)/bin/slam $(PKG)/bin/bal_convert
+	rm -rf $(OBJDIR) $(LIB) $(POST_LIB) $(SEED_LIB) $(PKG)/bin/ba $(PKG)/bin/slam $(PKG)/bin/bal_convert
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle test clean

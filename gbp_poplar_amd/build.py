@@ -4,6 +4,7 @@
                                              gbp_poplar_amd/libgbp_mi355x_test.so  the same sources + the test hooks of
                                                                                    include/gbp_mi355x_debug.h (tests/ only)
                                              gbp_poplar_amd/libgbp_mi355x_post.so  the solution readout (post/, include/gbp_mi355x_post.h)
+                                             gbp_poplar_amd/libgbp_mi355x_seed.so  landmark / keyframe seeding (seed/, include/gbp_mi355x_seed.h)
     python -m gbp_poplar_amd.build --experiments
                                           -> gbp_poplar_amd/libgbp_mi355x_exp.so   + csrc/experiments/: timing ablations / mapping
                                                                                    experiments (profiles/*.py only)
@@ -30,6 +31,8 @@ TEST_LIB = os.path.join(HERE, "libgbp_mi355x_test.so")  # + gbp_debug_* (include
 EXP_LIB = os.path.join(HERE, "libgbp_mi355x_exp.so")    # + timing ablations and mapping experiments (profiles/*.py only)
 POST = os.path.join(HERE, "post")                       # the solution readout: a library of its own (one HIP translation unit, its own export map)
 POST_LIB = os.path.join(HERE, "libgbp_mi355x_post.so")
+SEED = os.path.join(HERE, "seed")                       # landmark / keyframe seeding: a library of its own, built the way the readout is
+SEED_LIB = os.path.join(HERE, "libgbp_mi355x_seed.so")
 BIN = os.path.join(HERE, "bin")
 ARCH = "gfx950"
 # -fvisibility=hidden: the library exports the gbp_* functions of include/*.h (GBP_API) and nothing else
@@ -126,6 +129,20 @@ def _build_post(force, verbose):
         subprocess.check_call(cmd)
 
 
+def _build_seed(force, verbose):
+    """libgbp_mi355x_seed.so: seed/gbp_seed.hip with the flags of the product, linked with seed/gbp_seed_exports.map"""
+    odir = os.path.join(OBJ, "seed")
+    os.makedirs(odir, exist_ok=True)
+    src, obj = os.path.join(SEED, "gbp_seed.hip"), os.path.join(odir, "gbp_seed.o")
+    if force or _stale(obj, _headers() + [os.path.join(SEED, f) for f in os.listdir(SEED)]):
+        _compile(src, obj, [], verbose)
+    if force or _stale(SEED_LIB, [obj]):
+        cmd = [hipcc(), "-shared", "-o", SEED_LIB, "--offload-arch=" + ARCH, obj, "-Wl,--version-script=" + os.path.join(SEED, "gbp_seed_exports.map")]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+
+
 def _build_libs(variants, force, verbose):
     """The stale objects of ALL the variants in one pool (a variant's device translation unit takes as long as the rest of it
     together, so three variants one after the other leave most cores idle), each library linked once its own objects are there."""
@@ -149,21 +166,23 @@ def build(force=False, verbose=False, test_hooks=True, variants=None):
     false, and the experiments build where one exists (kept in step with the sources, never created by default)."""
     if variants is None:
         variants = ["product"] + (["test"] if test_hooks else []) + (["exp"] if os.path.exists(EXP_LIB) else [])
-    with concurrent.futures.ThreadPoolExecutor(1) as ex:      # (beside the variants: its device pass is the long part)
+    with concurrent.futures.ThreadPoolExecutor(2) as ex:      # (beside the variants: their device passes are the long part)
         post = ex.submit(_build_post, force, verbose)
+        seed = ex.submit(_build_seed, force, verbose)
         _build_libs(list(variants), force, verbose)
         post.result()
+        seed.result()
     os.makedirs(BIN, exist_ok=True)
     inc = os.path.join(HERE, "..", "include")
-    cli_deps = [os.path.join(CSRC, f) for f in ("cli_common.hpp", "gbp_transport.hpp", "gbp_metric_gather.hpp")] + [os.path.join(inc, f) for f in os.listdir(inc)] + [LIB, POST_LIB]
+    cli_deps = [os.path.join(CSRC, f) for f in ("cli_common.hpp", "gbp_transport.hpp", "gbp_metric_gather.hpp")] + [os.path.join(inc, f) for f in os.listdir(inc)] + [LIB, POST_LIB, SEED_LIB]
     for name, src in CLI_SRCS.items():
         path = os.path.join(CSRC, src)
         exe = os.path.join(BIN, name)
         if os.path.exists(path) and (force or _stale(exe, cli_deps + [path])):
             # the CLIs are plain C++ on top of the C-ABI: host compiler, linked against the in-tree library
-            # (ba / slam: + the readout library, and the HIP runtime for the device arrays --cov_file hands it)
+            # (ba / slam: + the readout and seeding libraries, and the HIP runtime for the device arrays --cov_file / --lmk_init hand them)
             rocm = os.path.dirname(os.path.dirname(os.path.realpath(hipcc())))
-            post = [] if name == "bal_convert" else ["-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), "-lgbp_mi355x_post",
+            post = [] if name == "bal_convert" else ["-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), "-lgbp_mi355x_post", "-lgbp_mi355x_seed",
                                                      "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath," + os.path.join(rocm, "lib")]
             cmd = [shutil.which("g++") or "g++", "-o", exe, "-O2", "-std=c++17", "-ffp-contract=off", "-pthread", path,
                    "-L" + HERE, "-lgbp_mi355x"] + post + ["-Wl,-rpath,$ORIGIN/.."]

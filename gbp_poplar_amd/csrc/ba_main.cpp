@@ -17,6 +17,8 @@ static int run(const cli::Options& o, cli::Problem& P, cli::RankCtx& rk) {
 
   gbp_ctx* ctx = nullptr;
   if (const int rc = cli::create_rank_ctx(o, P, rk, &ctx)) return rc;
+  cli::Seeder seeder;
+  if (o.triangulate && seeder.start(o, P)) { gbp_destroy(ctx); return 1; }
   std::cout << "Running program to stream initial data to GPU\n";
   const gbp_state_in in = cli::state_in(P);
   CLI_CHECK(ctx, gbp_upload(ctx, &in));

@@ -10,13 +10,16 @@
 //     HIP), landmark-sharded, camera partial sums all-gathered once per iteration by RCCL over xGMI
 //     (ba.cpp:414-417,617-649 spread one Poplar graph over N x 1216 tiles); `--camspertile` is accepted and ignored;
 //   * `--seed S` makes the initialisation-noise flags reproducible (the reference seeds from the clock,
-//     dataio.cpp:334,349,406); `--eval_every K` thins the per-iteration read-back + metric (default 1).
+//     dataio.cpp:334,349,406); `--eval_every K` thins the per-iteration read-back + metric (default 1);
+//   * `--lmk_init triangulate` takes the landmarks' prior means and strengths from the observations and the camera prior means
+//     (libgbp_mi355x_seed.so) instead of the file's `points` section, which is then not used at all.
 #pragma once
 #include "../../include/gbp_mi355x.h"
 #include "../../include/gbp_mi355x_multi.h"       // --ipus N: one forked rank per GPU
 #include "gbp_transport.hpp"                      // --transport: the names of gbp_comm_init's transport numbers
 #include "gbp_metric_gather.hpp"                  // --ipus N: the cross-rank sum of a burst's metric records
 #include "../../include/gbp_mi355x_post.h"        // --cov_file: means and marginal covariances of the beliefs (libgbp_mi355x_post.so)
+#include "../../include/gbp_mi355x_seed.h"        // --lmk_init triangulate: landmark priors from observations (libgbp_mi355x_seed.so)
 #include "../../include/gbp_mi355x_compat.h"      // MetricPipe: the metric in two halves (gbp_iterate_eval / gbp_eval_end), so that printing overlaps the next iterations
 
 #include <hip/hip_runtime_api.h>                  // --cov_file: the device arrays the readout works on (nothing else here touches HIP)
@@ -105,6 +108,7 @@ struct Options {
   int transport = (int)gbp::Transport::Auto;   // --transport (gbp_transport.hpp): what gbp_comm_init is given
   std::string out_file;         // --out_file: write the refined problem (belief means) in the input's format
   std::string cov_file;         // --cov_file: write every variable's mean and marginal covariance (gbp_post_moments)
+  bool triangulate = false;     // --lmk_init triangulate (default: file)
   bool force_sharded = false;   // --force_sharded: run the multi-rank code path (fork, shard ctx, communicator) with one rank
 };
 
@@ -133,6 +137,8 @@ inline void usage(bool slam) {
                "  --transport arg (=auto)        exchange between ranks: auto | rccl | host | p2p | p2p-slices | measured (host, p2p, p2p-slices: ranks may\n"
                "                                 share a GPU; host is also spelled host-staged; measured: time every transport the ranks\n"
                "                                 can form, keep the fastest)\n"
+               "  --lmk_init arg (=file)         landmark prior means and strengths: file (the file's points) | triangulate (from the\n"
+               "                                 observations and the camera prior means; the file's points are not used; one GPU)\n"
                "  --out_file arg                 write the refined cameras / landmarks (belief means) in the input's format\n"
                "  --cov_file arg                 write every camera's / landmark's mean and marginal covariance: line 1 `C L`, then per camera\n"
                "                                 6 + 36 values, per landmark 3 + 9 values (covariances row-major)\n";
@@ -177,6 +183,10 @@ inline int parse(int argc, char** argv, bool slam, Options& o) {
       else if (k == "seed") o.seed = std::stoull(v);
       else if (k == "eval_every") o.eval_every = std::max(1, std::stoi(v));
       else if (k == "force_sharded") o.force_sharded = B(v);
+      else if (k == "lmk_init") {
+        if (v != "file" && v != "triangulate") { std::cerr << "--lmk_init: expected file or triangulate\n"; return 2; }
+        o.triangulate = v == "triangulate";
+      }
       else if (k == "out_file") o.out_file = v;
       else if (k == "cov_file") o.cov_file = v;
       else if (k == "transport") {
@@ -191,6 +201,8 @@ inline int parse(int argc, char** argv, bool slam, Options& o) {
     return 2;
   }
   if (o.bal_file.empty()) { std::cerr << "the option '--bal_file' is required but missing\n"; return 2; }
+  if (o.triangulate && o.av_depth_on) { std::cerr << "--lmk_init triangulate and --avdepth_on both place the landmarks: choose one\n"; return 2; }
+  if (o.triangulate && (o.gpus > 1 || o.force_sharded)) { std::cerr << "--lmk_init triangulate runs on one GPU\n"; return 2; }
   return 0;
 }
 
@@ -247,7 +259,7 @@ inline int load_problem(const Options& o, Problem& P) {
     std::cout << "\nAdding Gaussian noise with std: " << o.transnoise << "m to the keyframe translaton intialisations\n";
   if (o.rotnoise != 0.f)
     std::cout << "Adding Gaussian noise with std: " << o.rotnoise << " to the keyframe rotation intialisations\n";
-  const bool lmk_noise = o.lmktrans_noise != 0.f && !o.av_depth_on;
+  const bool lmk_noise = o.lmktrans_noise != 0.f && !o.av_depth_on && !o.triangulate;      // (triangulate: the file's points are not used, noised or not)
   if (lmk_noise)
     std::cout << "Adding Gaussian noise with std: " << o.lmktrans_noise << "m to the landmark intialisations\n";
   gbp_init_add_noise(C, L, o.transnoise, o.rotnoise, lmk_noise ? o.lmktrans_noise : 0.f, seed, P.cam_mean.data(), P.lmk_mean.data());
@@ -304,6 +316,107 @@ inline void print_verbose(const Readback& r) {  // ba.cpp:1030-1051
   std::cout << '\n';
   std::fflush(stdout);
 }
+
+// ---- --lmk_init triangulate: the landmark priors from the observations (include/gbp_mi355x_seed.h) ----------------------
+// The device arrays of the seeding calls, allocated once.  Everything goes through the default stream with blocking copies, as
+// write_cov_file does.  start(): every landmark from ALL its observations at the camera prior means — the landmark priors of the
+// upload, and the points the camera priors' strengths are taken at (gbp_set_prior_lambda's "file" points: the file's are not used).
+// keyframe(): slam's per-keyframe step — the new camera's prior eta (gbp_seed_keyframe in place of gbp_slam_initialise_new_kf, the
+// same bits), then the landmarks this keyframe activated from every now-active observation, at the belief means of the cameras so
+// far and the new camera's pose guess; every other prior passes through.
+struct Seeder {
+  uint32_t C = 0, L = 0, E = 0;
+  std::vector<uint32_t> lmk_start, lmk_edges, status, select;
+  std::vector<float> cam_mean;
+  std::vector<double> cams64, pts64;
+  gbp_seed_options opts{};
+  char* base = nullptr;
+  uint32_t *d_cam_id = nullptr, *d_start = nullptr, *d_edges = nullptr, *d_active = nullptr, *d_select = nullptr, *d_status = nullptr;
+  float *d_meas = nullptr, *d_cam_mean = nullptr, *d_lmk_mean = nullptr, *d_lpe = nullptr, *d_lpl = nullptr;
+  float *d_cbe = nullptr, *d_cbl = nullptr, *d_cpl = nullptr, *d_cpe = nullptr, *d_guess = nullptr;
+  void* d_ws = nullptr;
+  ~Seeder() { if (base) (void)hipFree(base); }
+  static bool ok(hipError_t e, const char* what) {
+    if (e != hipSuccess) std::cerr << "--lmk_init triangulate: " << what << " failed: " << hipGetErrorString(e) << "\n";
+    return e == hipSuccess;
+  }
+  static bool seed_ok(int rc) {
+    if (rc != GBP_OK) std::cerr << "--lmk_init triangulate: " << gbp_seed_last_error() << "\n";
+    return rc == GBP_OK;
+  }
+  template <class T> bool up(T* d, const T* h, size_t n) { return n == 0 || ok(hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy"); }
+  template <class T> bool down(T* h, const T* d, size_t n) { return n == 0 || ok(hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost), "hipMemcpy"); }
+
+  int init(const Options& o, const Problem& P) {
+    C = P.bal.n_cams; L = P.bal.n_lmks; E = P.bal.n_edges;
+    gbp_seed_default_options(&opts);
+    opts.reproj_meas_var = o.reproj_meas_var;
+    lmk_start.resize((size_t)L + 1); lmk_edges.resize(E); status.resize(L); select.resize(L);
+    if (!seed_ok(gbp_seed_index(L, E, P.lmk_id.data(), lmk_start.data(), lmk_edges.data()))) return 1;
+    size_t at = 0;
+    const auto take = [&at](size_t bytes) { const size_t here = at; at += (bytes + 255) & ~(size_t)255; return here; };
+    const size_t o_ws = take(gbp_seed_workspace_bytes(C)), o_cam_id = take(4 * (size_t)E), o_start = take(4 * ((size_t)L + 1)), o_edges = take(4 * (size_t)E),
+                 o_active = take(4 * (size_t)E), o_select = take(4 * (size_t)L), o_status = take(4 * (size_t)L), o_meas = take(8 * (size_t)E),
+                 o_cam_mean = take(24 * (size_t)C), o_lmk_mean = take(12 * (size_t)L), o_lpe = take(12 * (size_t)L), o_lpl = take(36 * (size_t)L),
+                 o_cbe = take(24 * (size_t)C), o_cbl = take(144 * (size_t)C), o_cpl = take(144 * (size_t)C), o_cpe = take(24 * (size_t)C), o_guess = take(24);
+    if (!ok(hipMalloc(reinterpret_cast<void**>(&base), at), "hipMalloc")) return 1;
+    d_ws = base + o_ws;
+    const auto u32 = [this](size_t off) { return reinterpret_cast<uint32_t*>(base + off); };
+    const auto f32 = [this](size_t off) { return reinterpret_cast<float*>(base + off); };
+    d_cam_id = u32(o_cam_id); d_start = u32(o_start); d_edges = u32(o_edges); d_active = u32(o_active); d_select = u32(o_select); d_status = u32(o_status);
+    d_meas = f32(o_meas); d_cam_mean = f32(o_cam_mean); d_lmk_mean = f32(o_lmk_mean); d_lpe = f32(o_lpe); d_lpl = f32(o_lpl);
+    d_cbe = f32(o_cbe); d_cbl = f32(o_cbl); d_cpl = f32(o_cpl); d_cpe = f32(o_cpe); d_guess = f32(o_guess);
+    return up(d_cam_id, P.cam_id.data(), E) && up(d_start, lmk_start.data(), (size_t)L + 1) && up(d_edges, lmk_edges.data(), E) &&
+                   up(d_meas, P.meas.data(), 2 * (size_t)E) ? 0 : 1;
+  }
+
+  // the landmarks `sel` (NULL: all) from the observations `active` (NULL: all) at the camera means `cams`, into P's landmark priors
+  int landmarks(Problem& P, const float* cams, const uint32_t* active, const uint32_t* sel) {
+    if (!up(d_cam_mean, cams, 6 * (size_t)C) || (active && !up(d_active, active, E)) || (sel && !up(d_select, sel, L)) ||
+        !up(d_lmk_mean, P.lmk_mean.data(), 3 * (size_t)L) || !up(d_lpe, P.lpe.data(), 3 * (size_t)L) || !up(d_lpl, P.lpl.data(), 9 * (size_t)L))
+      return 1;
+    if (!seed_ok(gbp_seed_landmarks(nullptr, C, L, E, d_cam_id, d_start, d_edges, P.K.data(), d_cam_mean, d_meas, active ? d_active : nullptr,
+                                    sel ? d_select : nullptr, &opts, d_ws, d_lmk_mean, d_lpe, d_lpl, d_status, nullptr)))
+      return 1;
+    return down(P.lmk_mean.data(), d_lmk_mean, 3 * (size_t)L) && down(P.lpe.data(), d_lpe, 3 * (size_t)L) && down(P.lpl.data(), d_lpl, 9 * (size_t)L) &&
+                   down(status.data(), d_status, L) ? 0 : 1;
+  }
+
+  int start(const Options& o, Problem& P) {
+    if (init(o, P)) return 1;
+    std::fill(P.lmk_mean.begin(), P.lmk_mean.end(), 0.f);      // a landmark nobody observes: zero mean, zero prior (as the file rule gives it)
+    std::fill(P.lpe.begin(), P.lpe.end(), 0.f);
+    std::fill(P.lpl.begin(), P.lpl.end(), 0.f);
+    if (landmarks(P, P.cam_mean.data(), nullptr, nullptr)) return 1;
+    size_t n_tri = 0, n_placed = 0, n_none = 0;
+    for (uint32_t l = 0; l < L; ++l) {
+      if (status[l] & GBP_SEED_NO_VIEW) ++n_none;
+      else if (status[l] & (GBP_SEED_ONE_VIEW | GBP_SEED_LOW_PARALLAX | GBP_SEED_NONFINITE)) ++n_placed;
+      else ++n_tri;
+    }
+    std::cout << "Triangulating the landmarks from their observations: " << n_tri << " triangulated, " << n_placed
+              << " placed on the ray of their first observation, " << n_none << " without an observation\n";
+    // the camera priors by today's rule, their strengths taken at the seeded points; the landmark priors stay the seeded ones
+    std::vector<float> lpe(P.lpe.size()), lpl(P.lpl.size());
+    gbp_set_prior_lambda(&P.prob, o.reproj_meas_var, P.cam_file.data(), P.lmk_mean.data(), P.cam_mean.data(), P.lmk_mean.data(), P.cpe.data(),
+                         P.cpl.data(), lpe.data(), lpl.data());
+    gbp_prior_scalings(C, L, P.cpl.data(), o.steps, o.prior_std_weaker_factor, o.first_cam_prior_std, P.cscale.data(), P.lscale.data());
+    return 0;
+  }
+
+  // slam: P.cpe / P.cpl / P.lpe / P.lpl hold gbp_read_priors' arrays, rb the beliefs, P.active / P.lwf the flags gbp_slam_update_flags left
+  int keyframe(Problem& P, uint32_t data_counter, const float* cbe, const float* cbl, const float* lbe, const float* lbl) {
+    if (!up(d_cbe, cbe, 6 * (size_t)C) || !up(d_cbl, cbl, 36 * (size_t)C) || !up(d_cpl, P.cpl.data(), 36 * (size_t)C) || !up(d_cpe, P.cpe.data(), 6 * (size_t)C))
+      return 1;
+    if (!seed_ok(gbp_seed_keyframe(nullptr, C, data_counter, data_counter + 1, d_cbe, d_cbl, d_cpl, d_cpe, d_guess))) return 1;
+    cams64.resize(6 * (size_t)C); pts64.resize(3 * (size_t)L); cam_mean.resize(6 * (size_t)C);
+    gbp_belief_means(C, L, cbe, cbl, lbe, lbl, cams64.data(), pts64.data());
+    for (size_t i = 0; i < cam_mean.size(); ++i) cam_mean[i] = (float)cams64[i];
+    if (!down(P.cpe.data(), d_cpe, 6 * (size_t)C) || !down(cam_mean.data() + 6 * ((size_t)data_counter + 1), d_guess, 6)) return 1;
+    for (uint32_t l = 0; l < L; ++l) select[l] = P.lwf[l] != 0u;      // what this keyframe activated (gbp_slam_update_flags)
+    return landmarks(P, cam_mean.data(), P.active.data(), select.data());
+  }
+};
 
 // ---- one process per GPU (`--ipus N` / `--gpus N`) -------------------------------------------------------------------
 struct RankCtx {

@@ -19,6 +19,8 @@ static int run(const cli::Options& o, cli::Problem& P, cli::RankCtx& rk) {
 
   gbp_ctx* ctx = nullptr;
   if (const int rc = cli::create_rank_ctx(o, P, rk, &ctx)) return rc;
+  cli::Seeder seeder;
+  if (o.triangulate && seeder.start(o, P)) { gbp_destroy(ctx); return 1; }
   const gbp_state_in in = cli::state_in(P);
   CLI_CHECK(ctx, gbp_upload(ctx, &in));
   cli::phases().mark("upload_s");
@@ -72,7 +74,11 @@ static int run(const cli::Options& o, cli::Problem& P, cli::RankCtx& rk) {
       else banner();
       CLI_CHECK(ctx, gbp_read_priors(ctx, &po));
       CLI_CHECK(ctx, gbp_read(ctx, &rb.out));
-      gbp_slam_initialise_new_kf(data_counter, rb.cbe.data(), rb.cbl.data(), P.cpl.data(), P.cpe.data());
+      if (o.triangulate) {
+        if (seeder.keyframe(P, data_counter, rb.cbe.data(), rb.cbl.data(), rb.lbe.data(), rb.lbl.data())) { gbp_destroy(ctx); return 1; }
+      } else {
+        gbp_slam_initialise_new_kf(data_counter, rb.cbe.data(), rb.cbl.data(), P.cpl.data(), P.cpe.data());
+      }
       std::fill(P.count.begin(), P.count.end(), -15);           // literal, slam.cpp:1039-1041
       gbp_kf_update up{};
       up.damping_count = P.count.data();

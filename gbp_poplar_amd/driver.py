@@ -39,8 +39,24 @@ def k_matrix(bal):
     return np.array([bal["fx"], 0.0, bal["cx"], 0.0, bal["fy"], bal["cy"], 0.0, 0.0, 1.0], dtype=np.float32)
 
 
-def build_inputs(bal, opts, host, slam=False):
-    """Everything WRITE_PROG uploads, as a dict of numpy arrays (ba.cpp:494-604, slam.cpp:575-595)."""
+LMK_INIT = ("file", "triangulate")
+
+
+def _seed_options(opts):
+    from . import seed
+    return seed.default_options(reproj_meas_var=opts.reproj_meas_var)
+
+
+def build_inputs(bal, opts, host, slam=False, lmk_init="file"):
+    """Everything WRITE_PROG uploads, as a dict of numpy arrays (ba.cpp:494-604, slam.cpp:575-595).
+
+    lmk_init = "triangulate": the landmarks' prior means and strengths come from the observations and the (possibly noised) camera
+    prior means (seed.landmarks over ALL observations; runs on the GPU), not from the file's points, which are not used at all: the
+    camera priors are computed as ever, their strengths taken at the seeded points.  extra["lmk_index"] then holds seed.index()."""
+    if lmk_init not in LMK_INIT:
+        raise ValueError("lmk_init: expected one of %s, got %r" % (LMK_INIT, lmk_init))
+    if lmk_init == "triangulate" and getattr(opts, "avdepth_on", False):
+        raise ValueError('lmk_init="triangulate" and avdepth_on both place the landmarks: choose one')
     C, L, E = int(bal["n_cams"]), int(bal["n_lmks"]), int(bal["n_edges"])
     K = k_matrix(bal)
     cam_file = np.asarray(bal["cameras"], dtype=np.float64).astype(np.float32)   # ba.cpp:523-528
@@ -52,8 +68,19 @@ def build_inputs(bal, opts, host, slam=False):
                                                  0.0 if opts.avdepth_on else opts.ltn, seed)
     if getattr(opts, "avdepth_on", False):                                       # ba.cpp:546-548
         lmk_mean = host.init_av_depth(bal["cam_id"], bal["lmk_id"], C, L, cam_mean, lmk_mean)
-    cpe, cpl, lpe, lpl = host.set_prior_lambda(bal["cam_id"], bal["lmk_id"], C, L, K, opts.reproj_meas_var,
-                                               cam_file, lmk_file, cam_mean, lmk_mean)
+    measurements = np.asarray(bal["observations"], dtype=np.float64).astype(np.float32)
+    extra = {}
+    if lmk_init == "triangulate":
+        from . import seed
+        extra["lmk_index"] = seed.index(bal["lmk_id"], L)
+        s = seed.landmarks(bal["cam_id"], *extra["lmk_index"], K, cam_mean, measurements, options=_seed_options(opts))
+        lmk_mean = s["lmk_mean"]
+        cpe, cpl, _, _ = host.set_prior_lambda(bal["cam_id"], bal["lmk_id"], C, L, K, opts.reproj_meas_var,
+                                               cam_file, lmk_mean, cam_mean, lmk_mean)
+        lpe, lpl = s["lmk_priors_eta"], s["lmk_priors_lambda"]
+    else:
+        cpe, cpl, lpe, lpl = host.set_prior_lambda(bal["cam_id"], bal["lmk_id"], C, L, K, opts.reproj_meas_var,
+                                                   cam_file, lmk_file, cam_mean, lmk_mean)
     cs, ls = host.prior_scalings(C, L, cpl, opts.steps, opts.prior_std_weaker_factor, opts.first_cam_prior_std)
     steps = int(opts.steps)
     state = {
@@ -62,10 +89,9 @@ def build_inputs(bal, opts, host, slam=False):
         # mu / oldmu are zero in the reference (ba.cpp:582-583): left out = NULL = zeros in the C-ABI
         "cam_scaling": cs, "lmk_scaling": ls,
         "cam_priors_eta": cpe, "cam_priors_lambda": cpl, "lmk_priors_eta": lpe, "lmk_priors_lambda": lpl,
-        "measurements": np.asarray(bal["observations"], dtype=np.float64).astype(np.float32),
+        "measurements": measurements,
         "meas_variances": np.full(E, opts.reproj_meas_var, np.float32),
     }
-    extra = {}
     if not slam:                                                             # ba.cpp:588-590
         state["active_flag"] = np.ones(E, np.uint32)
         state["cam_weaken_flag"] = np.full(C, steps, np.uint32)
@@ -132,8 +158,14 @@ def run_ba(engine, state, opts, n_iters=None, eval_every=1, log=None):
     return traj
 
 
-def run_slam(engine, host, bal, state, extra, opts, iters_between_kfs=None, max_iters=None, eval_every=1, log=None):
-    """slam.cpp:1013-1103."""
+def run_slam(engine, host, bal, state, extra, opts, iters_between_kfs=None, max_iters=None, eval_every=1, log=None, lmk_init="file"):
+    """slam.cpp:1013-1103.
+
+    lmk_init = "triangulate", at every keyframe: the new camera's prior eta comes from seed.keyframe (the bits of
+    slam_initialise_new_kf), and the landmarks this keyframe activated are seeded from every now-active observation, at the belief
+    means of the cameras so far and the new camera's pose guess; every other prior passes through."""
+    if lmk_init not in LMK_INIT:
+        raise ValueError("lmk_init: expected one of %s, got %r" % (LMK_INIT, lmk_init))
     C, L, E = int(bal["n_cams"]), int(bal["n_lmks"]), int(bal["n_edges"])
     ibk = opts.iters_between_kfs if iters_between_kfs is None else iters_between_kfs
     steps = int(opts.steps)
@@ -161,8 +193,21 @@ def run_slam(engine, host, bal, state, extra, opts, iters_between_kfs=None, max_
                                            active, lwf, cwf, laf)
             pri = engine.read_priors()
             bel = engine.read()
-            host.slam_initialise_new_kf(data_counter, bel["cam_beliefs_eta"], bel["cam_beliefs_lambda"],
-                                        pri["cam_priors_lambda"], pri["cam_priors_eta"])
+            if lmk_init == "triangulate":
+                from . import seed
+                pri["cam_priors_eta"], guess = seed.keyframe(data_counter, data_counter + 1, bel["cam_beliefs_eta"], bel["cam_beliefs_lambda"],
+                                                             pri["cam_priors_lambda"], pri["cam_priors_eta"])
+                cam_mean = host.belief_means(C, L, bel["cam_beliefs_eta"], bel["cam_beliefs_lambda"], bel["lmk_beliefs_eta"],
+                                             bel["lmk_beliefs_lambda"])[0].astype(np.float32)
+                cam_mean[6 * (data_counter + 1):6 * (data_counter + 2)] = guess
+                start, edges = extra["lmk_index"] if "lmk_index" in extra else seed.index(bal["lmk_id"], L)
+                s = seed.landmarks(bal["cam_id"], start, edges, k_matrix(bal), cam_mean, state["measurements"], active_flag=active,
+                                   select=(lwf != 0).astype(np.uint32), options=_seed_options(opts),
+                                   out={"lmk_priors_eta": pri["lmk_priors_eta"], "lmk_priors_lambda": pri["lmk_priors_lambda"]})
+                pri["lmk_priors_eta"], pri["lmk_priors_lambda"] = s["lmk_priors_eta"], s["lmk_priors_lambda"]
+            else:
+                host.slam_initialise_new_kf(data_counter, bel["cam_beliefs_eta"], bel["cam_beliefs_lambda"],
+                                            pri["cam_priors_lambda"], pri["cam_priors_eta"])
             engine.new_keyframe({"damping_count": np.full(E, -15, np.int32),   # literal -15, slam.cpp:1040
                                  "cam_priors_eta": pri["cam_priors_eta"], "cam_priors_lambda": pri["cam_priors_lambda"],
                                  "lmk_priors_eta": pri["lmk_priors_eta"], "lmk_priors_lambda": pri["lmk_priors_lambda"],

@@ -11,6 +11,7 @@ import os
 import numpy as np
 
 from . import _cabi as cabi
+from . import _devarrays as arr
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libgbp_mi355x_post.so")
@@ -69,51 +70,13 @@ def _chk(rc, what):
 
 
 _BELIEFS = (("cam_beliefs_eta", 6), ("cam_beliefs_lambda", 36), ("lmk_beliefs_eta", 3), ("lmk_beliefs_lambda", 9))
-_F32, _U32 = ("torch.float32",), ("torch.int32", "torch.uint32")
-
-
-def _device_of(arrays):
-    dev = {a.device for a in arrays if cabi.is_device_tensor(a)}
-    if len(dev) != 1:
-        raise TypeError("expected torch tensors on ONE GPU, got %s" % (sorted(map(str, dev)) or "none"))
-    return dev.pop()
-
-
-def _tensor(name, a, dtypes, count, device):
-    """`a` as the library reads it: a contiguous tensor of one of `dtypes` with `count` elements on `device` (nothing is converted)"""
-    if not cabi.is_device_tensor(a):
-        raise TypeError("%s: a host array beside device tensors — one call takes host arrays or device tensors, not both" % name)
-    if a.device != device:
-        raise TypeError("%s is on %s, the other arrays on %s" % (name, a.device, device))
-    if str(a.dtype) not in dtypes:
-        raise TypeError("%s: dtype %s, expected %s (no silent conversion of device tensors)" % (name, a.dtype, dtypes[0]))
-    if not a.is_contiguous():
-        raise TypeError("%s is not contiguous (no silent copy of device tensors)" % name)
-    if a.numel() != count:
-        raise TypeError("%s has %d elements, expected %d" % (name, a.numel(), count))
-    return a
-
-
-def _ptr(t):
-    return _vp(t.data_ptr()) if t is not None and t.numel() else _vp()
-
-
-def _stream_handle(stream):
-    import torch
-    if stream is None:
-        return torch.cuda.current_stream().cuda_stream
-    return int(getattr(stream, "cuda_stream", stream))
+_F32, _U32 = arr.F32, arr.U32
+_device_of, _tensor, _ptr, _stream_handle = arr.device_of, arr.tensor, arr.ptr, arr.stream_handle      # shared with seed.py
 
 
 def _to_device(a, ints=False):
     """a numpy array (or None) -> a flat tensor on the current GPU: float32, or the uint32 bits as int32"""
-    import torch
-    if a is None:
-        return None
-    if not torch.cuda.is_available():
-        raise PostError("no HIP device: the solution readout runs on the GPU (there is no CPU path)")
-    a = np.ascontiguousarray(a, dtype=np.uint32 if ints else np.float32).reshape(-1)
-    return torch.from_numpy(a.view(np.int32) if ints else a).to("cuda")
+    return arr.to_device(a, ints, PostError, "the solution readout")
 
 
 def _to_host(out):
