@@ -9,10 +9,9 @@ ARCH    ?= gfx950
 PKG     := gbp_poplar_amd
 CSRC    := $(PKG)/csrc
 LIB     := $(PKG)/libgbp_mi355x.so
-POST    := $(PKG)/post
-POST_LIB := $(PKG)/libgbp_mi355x_post.so
-SEED    := $(PKG)/seed
-SEED_LIB := $(PKG)/libgbp_mi355x_seed.so
+# the libraries without a ctx (post: the solution readout, seed: landmark / keyframe seeding): directory $(PKG)/<name>, one rule below
+SATELLITES := post seed
+SAT_LIBS := $(SATELLITES:%=$(PKG)/libgbp_mi355x_%.so)
 HIPFLAGS := -O3 -std=c++17 -fPIC -ffp-contract=off -fvisibility=hidden -Wall -Wno-unused-function
 OBJDIR  := $(PKG)/_obj/make
 # the ROCm tree of $(HIPCC): its headers for the plain C++ translation units, its runtime for the CLIs (--cov_file and --lmk_init hand device arrays to the readout and the seeding)
@@ -25,7 +24,7 @@ OBJS    := $(OBJDIR)/gbp_kernels.o $(HOST_SRCS:%.cpp=$(OBJDIR)/%.o)
 # hooks and experiments that gbp_kernels.hip #includes, the export map
 HDRS    := $(filter-out $(CSRC)/gbp_kernels.hip $(wildcard $(CSRC)/*.cpp),$(wildcard $(CSRC)/*.* $(CSRC)/*/*)) $(wildcard include/*.h)
 
-all: $(LIB) $(POST_LIB) $(SEED_LIB) $(PKG)/bin/ba $(PKG)/bin/slam $(PKG)/bin/bal_convert
+all: $(LIB) $(SAT_LIBS) $(PKG)/bin/ba $(PKG)/bin/slam $(PKG)/bin/bal_convert
 
 $(OBJDIR)/gbp_kernels.o: $(CSRC)/gbp_kernels.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
@@ -38,23 +37,19 @@ $(OBJDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
 $(LIB): $(OBJS)
 	$(HIPCC) -shared -o $@ --offload-arch=$(ARCH) $(OBJS) -ldl -pthread -Wl,--version-script=$(CSRC)/gbp_exports.map
 
-# the solution readout (include/gbp_mi355x_post.h): one HIP translation unit, the product's flags, an export map of its own
-$(OBJDIR)/gbp_post.o: $(POST)/gbp_post.hip $(wildcard $(POST)/*.hpp) $(HDRS)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) -c -o $@ $(HIPFLAGS) --offload-arch=$(ARCH) -x hip $<
+# a ctx-less library (include/gbp_mi355x_<name>.h): one HIP translation unit, the product's flags, an export map of its own;
+# $(PKG)/stateless/ is what they share
+define SATELLITE_RULES
+$(OBJDIR)/gbp_$(1).o: $(PKG)/$(1)/gbp_$(1).hip $$(wildcard $(PKG)/$(1)/*.hpp $(PKG)/stateless/*.hpp) $$(HDRS)
+	@mkdir -p $$(OBJDIR)
+	$$(HIPCC) -c -o $$@ $$(HIPFLAGS) --offload-arch=$$(ARCH) -x hip $$<
 
-$(POST_LIB): $(OBJDIR)/gbp_post.o $(POST)/gbp_post_exports.map
-	$(HIPCC) -shared -o $@ --offload-arch=$(ARCH) $< -Wl,--version-script=$(POST)/gbp_post_exports.map
+$(PKG)/libgbp_mi355x_$(1).so: $(OBJDIR)/gbp_$(1).o $(PKG)/$(1)/gbp_$(1)_exports.map
+	$$(HIPCC) -shared -o $$@ --offload-arch=$$(ARCH) $$< -Wl,--version-script=$(PKG)/$(1)/gbp_$(1)_exports.map
+endef
+$(foreach s,$(SATELLITES),$(eval $(call SATELLITE_RULES,$(s))))
 
-# landmark / keyframe seeding (include/gbp_mi355x_seed.h): built the way the readout is
-$(OBJDIR)/gbp_seed.o: $(SEED)/gbp_seed.hip $(wildcard $(SEED)/*.hpp) $(HDRS)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) -c -o $@ $(HIPFLAGS) --offload-arch=$(ARCH) -x hip $<
-
-$(SEED_LIB): $(OBJDIR)/gbp_seed.o $(SEED)/gbp_seed_exports.map
-	$(HIPCC) -shared -o $@ --offload-arch=$(ARCH) $< -Wl,--version-script=$(SEED)/gbp_seed_exports.map
-
-$(PKG)/bin/%: $(CSRC)/%_main.cpp $(CSRC)/cli_common.hpp $(CSRC)/gbp_transport.hpp $(CSRC)/gbp_metric_gather.hpp include/gbp_mi355x.h include/gbp_mi355x_multi.h include/gbp_mi355x_compat.h include/gbp_mi355x_post.h include/gbp_mi355x_seed.h $(LIB) $(POST_LIB) $(SEED_LIB)
+$(PKG)/bin/%: $(CSRC)/%_main.cpp $(CSRC)/cli_common.hpp $(CSRC)/gbp_transport.hpp $(CSRC)/gbp_metric_gather.hpp include/gbp_mi355x.h include/gbp_mi355x_multi.h include/gbp_mi355x_compat.h include/gbp_mi355x_post.h include/gbp_mi355x_seed.h $(LIB) $(SAT_LIBS)
 	@mkdir -p $(PKG)/bin
 	$(CXX) -o $@ -O2 -std=c++17 -ffp-contract=off -pthread -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include $< -L$(PKG) -lgbp_mi355x -lgbp_mi355x_post -lgbp_mi355x_seed \
 		-L$(ROCM)/lib -lamdhip64 -Wl,-rpath,$(ROCM)/lib '-Wl,-rpath,$$ORIGIN/..'
@@ -67,7 +62,7 @@ test: all oracle
 	python -m pytest tests -x -q -m "not gpu"
 
 clean:
-	rm -rf $(OBJDIR) $(LIB) $(POST_LIB) $(SEED_LIB) $(PKG)/bin/ba $(PKG)/bin/slam $(PKG)/bin/bal_convert
+	rm -rf $(OBJDIR) $(LIB) $(SAT_LIBS) $(PKG)/bin/ba $(PKG)/bin/slam $(PKG)/bin/bal_convert
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle test clean

@@ -1,5 +1,6 @@
 """What the ctx-less libraries' bindings (post.py, seed.py) share: checking the device tensors a call reads in place, their addresses, the
-stream handle, and the staging of numpy arrays through the current GPU.  Nothing here converts or copies a device tensor."""
+stream handle, the return-code check, and the host round trip of a call that is given numpy arrays (staged through the current GPU).
+Nothing here converts or copies a device tensor."""
 import ctypes as C
 
 import numpy as np
@@ -52,3 +53,31 @@ def to_device(a, ints, error, what):
         raise error("no HIP device: %s runs on the GPU (there is no CPU path)" % what)
     a = np.ascontiguousarray(a, dtype=np.uint32 if ints else np.float32).reshape(-1)
     return torch.from_numpy(a.view(np.int32) if ints else a).to("cuda")
+
+
+def check(rc, what, last_error, error):
+    """a library's return code: error("<what>: <the library's text of the failure> (status <rc>)") unless it is GBP_OK"""
+    if rc != 0:
+        raise error("%s: %s (status %d)" % (what, last_error().decode(), rc))
+
+
+def k9(K):
+    """the nine pin-hole entries as the float [9] the libraries take (host)"""
+    return (C.c_float * 9)(*[float(x) for x in np.asarray(K, dtype=np.float64).reshape(9)])
+
+
+def on_host(arrays):
+    """does a call take the host round trip: none of its arrays (name -> array or None) is a device tensor"""
+    return not any(cabi.is_device_tensor(a) for a in arrays.values())
+
+
+def round_trip(arrays, ints, device_form, uints, error, what):
+    """The numpy face of a call: stage `arrays` (those named in `ints` as uint32 bits; error, what: see to_device), run
+    device_form(staged), wait until every stream of the GPU has finished, and hand its results (a dict or a tuple of tensors) back as
+    numpy, the ones named in `uints` as uint32."""
+    import torch
+    res = device_form({k: to_device(v, k in ints, error, what) for k, v in arrays.items()})
+    torch.cuda.synchronize()
+    if isinstance(res, dict):
+        return {k: (v.cpu().numpy().view(np.uint32) if k in uints else v.cpu().numpy()) for k, v in res.items()}
+    return tuple(v.cpu().numpy() for v in res)

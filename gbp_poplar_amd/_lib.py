@@ -4,6 +4,7 @@ import ctypes as C
 import os
 
 from . import _cabi as cabi
+from ._loader import load_library
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # GBP_LIB: measurement scripts under profiles/ point this at the experiments build (build.py --experiments)
@@ -11,9 +12,7 @@ LIB_PATH = os.environ.get("GBP_LIB") or os.path.join(HERE, "libgbp_mi355x.so")
 # the product sources + the gbp_debug_* hooks of include/gbp_mi355x_debug.h; loaded by tests that look at internal state
 TEST_LIB_PATH = os.environ.get("GBP_LIB") or os.path.join(HERE, "libgbp_mi355x_test.so")
 EXP_LIB_PATH = os.path.join(HERE, "libgbp_mi355x_exp.so")    # build.py --experiments: + ablations / mapping experiments
-_lib = None
-_test_lib = None
-_exp_lib = None
+_loaded = {}      # False / True / "exp" -> the library
 
 # every symbol include/gbp_mi355x.h, gbp_mi355x_multi.h and gbp_mi355x_compat.h declare (tests/test_cabi_symbols.py parses the headers and checks this list)
 _SIGS = {
@@ -121,47 +120,10 @@ def debug_symbols():
 
 
 def load(hooks=False):
-    """The product library (hooks=False) or the test-hooks build of the same sources (hooks=True)."""
-    global _lib, _test_lib, _exp_lib
-    if hooks == "exp":               # the experiments build (mapping experiments: tests/test_gpu_experiments.py, profiles/)
-        if _exp_lib is not None:
-            return _exp_lib
-    elif hooks and _test_lib is not None:
-        return _test_lib
-    elif not hooks and _lib is not None:
-        return _lib
-    path = EXP_LIB_PATH if hooks == "exp" else (TEST_LIB_PATH if hooks else LIB_PATH)
-    if not os.path.exists(path):
-        raise RuntimeError(
-            "native library %s is missing — build it with `python -m gbp_poplar_amd.build` "
-            "(hipcc, gfx950). There is no CPU fallback." % path)
-    # One HIP runtime per process: PyTorch-ROCm bundles its own libamdhip64.so.7 and dlopens it by path, so
-    # if this library (linked against /opt/rocm's copy) initialised the GPU first, a later `import torch`
-    # would bring up a second runtime that finds "No HIP GPUs".  Loading torch's runtime first makes our
-    # DT_NEEDED libamdhip64.so.7 resolve to the copy already in the process.  (The C++ CLIs never load torch.)
-    if os.environ.get("GBP_NO_TORCH") != "1":
-        try:
-            import torch
-            torch.cuda.is_available()
-        except ImportError:
-            pass
-    lib = C.CDLL(path)
-    lib.gbp_abi_version.restype = C.c_int        # first: a stale .so gets the rebuild message, not an AttributeError for a new symbol
-    lib.gbp_abi_version.argtypes = []
-    if lib.gbp_abi_version() != cabi.GBP_ABI_VERSION:
-        raise RuntimeError("%s has ABI version %d, these bindings were written for %d — rebuild (python -m gbp_poplar_amd.build)"
-                           % (path, lib.gbp_abi_version(), cabi.GBP_ABI_VERSION))
-    sigs = dict(_SIGS)
-    if hooks:
-        sigs.update(_DEBUG_SIGS)
-    for name, (res, args) in sigs.items():
-        fn = getattr(lib, name)          # AttributeError if the .so does not export a declared symbol
-        fn.restype = res
-        fn.argtypes = args
-    if hooks == "exp":
-        _exp_lib = lib
-    elif hooks:
-        _test_lib = lib
-    else:
-        _lib = lib
-    return lib
+    """The product library (hooks=False), the test-hooks build of the same sources (hooks=True) or the experiments build
+    (hooks="exp": mapping experiments, tests/test_gpu_experiments.py and profiles/); each loaded once."""
+    key = "exp" if hooks == "exp" else bool(hooks)
+    if key not in _loaded:
+        path = {"exp": EXP_LIB_PATH, True: TEST_LIB_PATH, False: LIB_PATH}[key]
+        _loaded[key] = load_library(path, "gbp_abi_version", cabi.GBP_ABI_VERSION, dict(_SIGS, **(_DEBUG_SIGS if hooks else {})))
+    return _loaded[key]

@@ -15,7 +15,8 @@ bit-for-bit with the CPU oracle, so no FMA contraction on either side.
 Every translation unit is compiled to an object of its own (gbp_poplar_amd/_obj/<variant>/, in parallel, only when it or a
 header changed) and the objects are linked: the device code (gbp_kernels.hip = the units of csrc/kernels/ as ONE translation unit,
 ~25 s) is not recompiled for an edit of the host side of the C-ABI, whose translation units are plain C++ (no device pass).  The
-objects of all the variants asked for are compiled in one pool.
+objects of all the variants asked for, and those of the ctx-less libraries (SATELLITES: a table entry each, one recipe), are
+compiled in one pool.
 """
 import concurrent.futures
 import os
@@ -29,10 +30,15 @@ OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libgbp_mi355x.so")
 TEST_LIB = os.path.join(HERE, "libgbp_mi355x_test.so")  # + gbp_debug_* (include/gbp_mi355x_debug.h): what tests/ load for stage-level checks
 EXP_LIB = os.path.join(HERE, "libgbp_mi355x_exp.so")    # + timing ablations and mapping experiments (profiles/*.py only)
-POST = os.path.join(HERE, "post")                       # the solution readout: a library of its own (one HIP translation unit, its own export map)
-POST_LIB = os.path.join(HERE, "libgbp_mi355x_post.so")
-SEED = os.path.join(HERE, "seed")                       # landmark / keyframe seeding: a library of its own, built the way the readout is
-SEED_LIB = os.path.join(HERE, "libgbp_mi355x_seed.so")
+POST_LIB = os.path.join(HERE, "libgbp_mi355x_post.so")  # the solution readout
+SEED_LIB = os.path.join(HERE, "libgbp_mi355x_seed.so")  # landmark / keyframe seeding
+# The libraries without a ctx, each one HIP translation unit with the product's flags and an export map of its own:
+# name (= its directory under _obj/) -> (source directory, source, export map, library).  stateless/ is what they share.
+STATELESS = os.path.join(HERE, "stateless")
+SATELLITES = {
+    "post": (os.path.join(HERE, "post"), "gbp_post.hip", "gbp_post_exports.map", POST_LIB),
+    "seed": (os.path.join(HERE, "seed"), "gbp_seed.hip", "gbp_seed_exports.map", SEED_LIB),
+}
 BIN = os.path.join(HERE, "bin")
 ARCH = "gfx950"
 # -fvisibility=hidden: the library exports the gbp_* functions of include/*.h (GBP_API) and nothing else
@@ -79,7 +85,7 @@ def _compile(src, obj, defines, verbose):
         cmd += ["--offload-arch=" + ARCH, "-x", "hip"]
     else:
         cmd += ["-x", "c++", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc()))), "include")]
-    cmd.append(os.path.join(CSRC, src))
+    cmd.append(src)
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
@@ -93,85 +99,66 @@ VARIANTS = {
 }
 
 
-def _stale_objects(variant, force):
-    """(every object of the variant's library, [(source, object)] of those that have to be compiled)"""
-    odir = os.path.join(OBJ, variant)
+def _stale_objects(name, srcs, deps, force):
+    """(every object of library `name` (under _obj/<name>/), [(source, object)] of those that have to be compiled): an object is
+    stale against its own source and `deps`"""
+    odir = os.path.join(OBJ, name)
     os.makedirs(odir, exist_ok=True)
-    hdr = _headers()
     objs, todo = [], []
-    for s in LIB_SRCS:
-        obj = os.path.join(odir, os.path.splitext(s)[0] + ".o")
+    for s in srcs:
+        obj = os.path.join(odir, os.path.splitext(os.path.basename(s))[0] + ".o")
         objs.append(obj)
-        if force or _stale(obj, hdr + [os.path.join(CSRC, s)]):
+        if force or _stale(obj, deps + [s]):
             todo.append((s, obj))
     return objs, todo
 
 
-def _link(target, objs, verbose):
-    cmd = [hipcc(), "-shared", "-o", target, "--offload-arch=" + ARCH] + objs + \
-          ["-ldl", "-pthread", "-Wl,--version-script=" + os.path.join(CSRC, "gbp_exports.map")]      # (-pthread: the host helpers' reader threads, for a libc that still keeps them in libpthread)
+def _link(target, objs, export_map, extra, verbose):
+    cmd = [hipcc(), "-shared", "-o", target, "--offload-arch=" + ARCH] + objs + extra + ["-Wl,--version-script=" + export_map]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
 
 
-def _build_post(force, verbose):
-    """libgbp_mi355x_post.so: post/gbp_post.hip with the flags of the product, linked with post/gbp_post_exports.map"""
-    odir = os.path.join(OBJ, "post")
-    os.makedirs(odir, exist_ok=True)
-    src, obj = os.path.join(POST, "gbp_post.hip"), os.path.join(odir, "gbp_post.o")
-    if force or _stale(obj, _headers() + [os.path.join(POST, f) for f in os.listdir(POST)]):
-        _compile(src, obj, [], verbose)
-    if force or _stale(POST_LIB, [obj]):
-        cmd = [hipcc(), "-shared", "-o", POST_LIB, "--offload-arch=" + ARCH, obj, "-Wl,--version-script=" + os.path.join(POST, "gbp_post_exports.map")]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
+def _recipes(variants, satellites):
+    """library -> (name, sources, what its objects depend on beside their source, defines, export map, extra link flags)"""
+    hdr = _headers()
+    out = {}
+    for v in variants:      # (-pthread: the host helpers' reader threads, for a libc that still keeps them in libpthread)
+        lib, defines = VARIANTS[v]
+        out[lib] = (v, [os.path.join(CSRC, s) for s in LIB_SRCS], hdr, defines, os.path.join(CSRC, "gbp_exports.map"), ["-ldl", "-pthread"])
+    for n in satellites:    # stale against its own directory, stateless/ and the core's headers; the map only links
+        src_dir, src, export_map, lib = SATELLITES[n]
+        own = [os.path.join(d, f) for d in (src_dir, STATELESS) for f in os.listdir(d) if f != export_map]
+        out[lib] = (n, [os.path.join(src_dir, src)], hdr + own, [], os.path.join(src_dir, export_map), [])
+    return out
 
 
-def _build_seed(force, verbose):
-    """libgbp_mi355x_seed.so: seed/gbp_seed.hip with the flags of the product, linked with seed/gbp_seed_exports.map"""
-    odir = os.path.join(OBJ, "seed")
-    os.makedirs(odir, exist_ok=True)
-    src, obj = os.path.join(SEED, "gbp_seed.hip"), os.path.join(odir, "gbp_seed.o")
-    if force or _stale(obj, _headers() + [os.path.join(SEED, f) for f in os.listdir(SEED)]):
-        _compile(src, obj, [], verbose)
-    if force or _stale(SEED_LIB, [obj]):
-        cmd = [hipcc(), "-shared", "-o", SEED_LIB, "--offload-arch=" + ARCH, obj, "-Wl,--version-script=" + os.path.join(SEED, "gbp_seed_exports.map")]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
-
-
-def _build_libs(variants, force, verbose):
-    """The stale objects of ALL the variants in one pool (a variant's device translation unit takes as long as the rest of it
+def _build_libs(variants, force, verbose, satellites=()):
+    """The stale objects of ALL the libraries in one pool (a variant's device translation unit takes as long as the rest of it
     together, so three variants one after the other leave most cores idle), each library linked once its own objects are there."""
-    plan = {v: _stale_objects(v, force) for v in variants}
-    todo = [(s, o, v) for v in variants for s, o in plan[v][1]]
-    todo.sort(key=lambda t: t[0] not in DEVICE_SRCS)          # the long compiles first
+    recipes = _recipes(variants, satellites)
+    plan = {lib: _stale_objects(r[0], r[1], r[2], force) for lib, r in recipes.items()}
+    todo = [(s, o, lib) for lib in plan for s, o in plan[lib][1]]
+    todo.sort(key=lambda t: (os.path.basename(t[0]) not in DEVICE_SRCS, not t[0].endswith(".hip")))          # the long compiles first
     with concurrent.futures.ThreadPoolExecutor(min(len(todo), 16) or 1) as ex:
-        done = {v: [] for v in variants}
-        for s, o, v in todo:
-            done[v].append(ex.submit(_compile, s, o, VARIANTS[v][1], verbose))
-        for v in variants:
-            for f in done[v]:
+        done = {lib: [] for lib in plan}
+        for s, o, lib in todo:
+            done[lib].append(ex.submit(_compile, s, o, recipes[lib][3], verbose))
+        for lib, (_, _, _, _, export_map, extra) in recipes.items():
+            for f in done[lib]:
                 f.result()
-            target, objs = VARIANTS[v][0], plan[v][0]
-            if done[v] or force or _stale(target, objs):
-                _link(target, objs, verbose)
+            if done[lib] or force or _stale(lib, plan[lib][0] + [export_map]):
+                _link(lib, plan[lib][0], export_map, extra, verbose)
 
 
 def build(force=False, verbose=False, test_hooks=True, variants=None):
     """variants: the libraries to build (names of VARIANTS); by default the product, the test-hooks build unless test_hooks is
-    false, and the experiments build where one exists (kept in step with the sources, never created by default)."""
+    false, and the experiments build where one exists (kept in step with the sources, never created by default).  The ctx-less
+    libraries (SATELLITES) are always built."""
     if variants is None:
         variants = ["product"] + (["test"] if test_hooks else []) + (["exp"] if os.path.exists(EXP_LIB) else [])
-    with concurrent.futures.ThreadPoolExecutor(2) as ex:      # (beside the variants: their device passes are the long part)
-        post = ex.submit(_build_post, force, verbose)
-        seed = ex.submit(_build_seed, force, verbose)
-        _build_libs(list(variants), force, verbose)
-        post.result()
-        seed.result()
+    _build_libs(list(variants), force, verbose, list(SATELLITES))
     os.makedirs(BIN, exist_ok=True)
     inc = os.path.join(HERE, "..", "include")
     cli_deps = [os.path.join(CSRC, f) for f in ("cli_common.hpp", "gbp_transport.hpp", "gbp_metric_gather.hpp")] + [os.path.join(inc, f) for f in os.listdir(inc)] + [LIB, POST_LIB, SEED_LIB]

@@ -4,14 +4,12 @@ per variable from the beliefs gbp_read returns (moments), reprojection residuals
 Both take torch tensors on the GPU — read in place, results in fresh tensors on the same GPU, nothing waits: the work is queued on
 `stream` (a raw stream handle; default: torch's current stream) and the results are valid for what is queued behind it there.  Both
 also take numpy arrays: those are staged through device tensors and the call blocks until the numpy results are there.  The library is
-a loader of its own beside _lib.py: it has no ctx and is not part of the program list.  There is no CPU path: the kernels are HIP."""
+loaded beside _lib.py's (the same _loader): it has no ctx and is not part of the program list.  There is no CPU path: the kernels are HIP."""
 import ctypes as C
 import os
 
-import numpy as np
-
-from . import _cabi as cabi
 from . import _devarrays as arr
+from ._loader import load_library
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libgbp_mi355x_post.so")
@@ -35,29 +33,9 @@ def symbols():
 
 def load():
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError("native library %s is missing — build it with `python -m gbp_poplar_amd.build` "
-                           "(hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
-    if os.environ.get("GBP_NO_TORCH") != "1":      # one HIP runtime per process: torch's first (see _lib.load)
-        try:
-            import torch
-            torch.cuda.is_available()
-        except ImportError:
-            pass
-    lib = C.CDLL(LIB_PATH)
-    lib.gbp_post_abi_version.restype = C.c_int
-    lib.gbp_post_abi_version.argtypes = []
-    if lib.gbp_post_abi_version() != GBP_POST_ABI_VERSION:
-        raise RuntimeError("%s has ABI version %d, these bindings were written for %d — rebuild (python -m gbp_poplar_amd.build)"
-                           % (LIB_PATH, lib.gbp_post_abi_version(), GBP_POST_ABI_VERSION))
-    for name, (res, args) in _SIGS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = load_library(LIB_PATH, "gbp_post_abi_version", GBP_POST_ABI_VERSION, _SIGS)
+    return _lib
 
 
 class PostError(RuntimeError):
@@ -65,25 +43,14 @@ class PostError(RuntimeError):
 
 
 def _chk(rc, what):
-    if rc != 0:
-        raise PostError("%s: %s (status %d)" % (what, load().gbp_post_last_error().decode(), rc))
+    arr.check(rc, what, load().gbp_post_last_error, PostError)
 
 
 _BELIEFS = (("cam_beliefs_eta", 6), ("cam_beliefs_lambda", 36), ("lmk_beliefs_eta", 3), ("lmk_beliefs_lambda", 9))
 _F32, _U32 = arr.F32, arr.U32
-_device_of, _tensor, _ptr, _stream_handle = arr.device_of, arr.tensor, arr.ptr, arr.stream_handle      # shared with seed.py
-
-
-def _to_device(a, ints=False):
-    """a numpy array (or None) -> a flat tensor on the current GPU: float32, or the uint32 bits as int32"""
-    return arr.to_device(a, ints, PostError, "the solution readout")
-
-
-def _to_host(out):
-    """the numpy form of a result (blocks until every stream of the GPU has finished); status words as uint32"""
-    import torch
-    torch.cuda.synchronize()
-    return {k: (v.cpu().numpy().view(np.uint32) if k.endswith("status") else v.cpu().numpy()) for k, v in out.items()}
+_device_of, _tensor, _ptr, _stream_handle = arr.device_of, arr.tensor, arr.ptr, arr.stream_handle
+_STATUS = ("cam_status", "lmk_status")      # as numpy: uint32
+_WHAT = "the solution readout"              # (what has no CPU path, in the error for numpy arrays without a GPU)
 
 
 def moments(beliefs, stream=None):
@@ -93,8 +60,8 @@ def moments(beliefs, stream=None):
     Device tensors in: device tensors out, not blocking.  numpy in: numpy out, blocking."""
     import torch
     b = {k: beliefs[k] for k, _ in _BELIEFS}
-    if not any(cabi.is_device_tensor(a) for a in b.values()):
-        return _to_host(moments({k: _to_device(v) for k, v in b.items()}, stream))
+    if arr.on_host(b):
+        return arr.round_trip(b, (), lambda d: moments(d, stream), _STATUS, PostError, _WHAT)
     dev = _device_of(b.values())
     n_c, n_l = b["cam_beliefs_eta"].numel() // 6, b["lmk_beliefs_eta"].numel() // 3
     t = {k: _tensor(k, b[k], _F32, w * (n_c if k.startswith("cam") else n_l), dev) for k, w in _BELIEFS}
@@ -118,9 +85,9 @@ def residuals(cam_id, lmk_id, K, means, measurements, active_flag=None, covs=Non
     arrays = {"cam_id": cam_id, "lmk_id": lmk_id, "cam_mean": means["cam_mean"], "lmk_mean": means["lmk_mean"], "measurements": measurements,
               "active_flag": active_flag, "cam_cov": None if covs is None else covs["cam_cov"], "lmk_cov": None if covs is None else covs["lmk_cov"]}
     ints = ("cam_id", "lmk_id", "active_flag")
-    if not any(cabi.is_device_tensor(a) for a in arrays.values()):
-        d = {k: _to_device(v, k in ints) for k, v in arrays.items()}
-        return _to_host(residuals(d["cam_id"], d["lmk_id"], K, d, d["measurements"], d["active_flag"], None if covs is None else d, stream))
+    if arr.on_host(arrays):
+        return arr.round_trip(arrays, ints, lambda d: residuals(d["cam_id"], d["lmk_id"], K, d, d["measurements"], d["active_flag"],
+                                                                None if covs is None else d, stream), _STATUS, PostError, _WHAT)
     present = [a for a in arrays.values() if a is not None]
     dev = _device_of(present)
     n_e = arrays["cam_id"].numel()
@@ -131,9 +98,8 @@ def residuals(cam_id, lmk_id, K, means, measurements, active_flag=None, covs=Non
     out = {"residual": torch.empty(2 * n_e, dtype=torch.float32, device=dev)}
     if covs is not None:
         out["reproj_cov"] = torch.empty(3 * n_e, dtype=torch.float32, device=dev)
-    k9 = (C.c_float * 9)(*[float(x) for x in np.asarray(K, dtype=np.float64).reshape(9)])
     with torch.cuda.device(dev):
-        _chk(load().gbp_post_residuals(_vp(_stream_handle(stream)), n_c, n_l, n_e, _ptr(t["cam_id"]), _ptr(t["lmk_id"]), k9, _ptr(t["cam_mean"]),
+        _chk(load().gbp_post_residuals(_vp(_stream_handle(stream)), n_c, n_l, n_e, _ptr(t["cam_id"]), _ptr(t["lmk_id"]), arr.k9(K), _ptr(t["cam_mean"]),
                                        _ptr(t["lmk_mean"]), _ptr(t["measurements"]), _ptr(t["active_flag"]), _ptr(t["cam_cov"]), _ptr(t["lmk_cov"]),
                                        _ptr(out["residual"]), _ptr(out.get("reproj_cov"))), "gbp_post_residuals")
     return out

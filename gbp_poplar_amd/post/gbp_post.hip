@@ -1,7 +1,8 @@
 // post/gbp_post.hip — libgbp_mi355x_post.so (include/gbp_mi355x_post.h): the two readout kernels and the exports that launch them.
 // The arithmetic is post_math.hpp's (shared with the host twin the tests compile); here are the mapping, the memory accesses and
 // the argument checks.  Not on the iteration path: one launch per call, on the caller's stream, nothing allocated, nothing waited for.
-#include "post_export.hpp"
+#include "../../include/gbp_mi355x_post.h"
+#include "../stateless/stateless_export.hpp"
 #include "post_math.hpp"
 
 namespace gbp {
@@ -106,24 +107,17 @@ __global__ __launch_bounds__(256) void k_post_residuals(uint32_t n_cams, uint32_
   }
 }
 
-static int launched(const char* what) {
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(GBP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(err));
-  return GBP_OK;
-}
-static int null_arg(const char* fn, const char* arg) { return fail(GBP_ERR_INVALID, std::string(fn) + ": " + arg + " is NULL"); }
-constexpr uint64_t kMaxLanes = 0xffffff00ull;      // one lane per item, 32-bit lane index
-
 }  // namespace post
 }  // namespace gbp
 
 using namespace gbp::post;
+using namespace gbp::stateless;
 
-GBP_POST_EXPORT_T(int, 0, gbp_post_abi_version, (void), ()) { return GBP_POST_ABI_VERSION; }
+GBP_STATELESS_EXPORT_T(int, 0, gbp_post_abi_version, (void), ()) { return GBP_POST_ABI_VERSION; }
 
-GBP_POST_EXPORT_T(const char*, "", gbp_post_last_error, (void), ()) { return last_error().c_str(); }
+GBP_STATELESS_EXPORT_T(const char*, "", gbp_post_last_error, (void), ()) { return last_error().c_str(); }
 
-GBP_POST_EXPORT(gbp_post_moments,
+GBP_STATELESS_EXPORT(gbp_post_moments,
                 (void* hip_stream, uint32_t n_cams, uint32_t n_lmks, const float* cam_eta, const float* cam_lambda, const float* lmk_eta,
                  const float* lmk_lambda, float* cam_mean, float* cam_cov, float* lmk_mean, float* lmk_cov, uint32_t* cam_status,
                  uint32_t* lmk_status),
@@ -135,7 +129,7 @@ GBP_POST_EXPORT(gbp_post_moments,
   if (n_lmks && !lmk_eta) return null_arg(fn, "lmk_eta");
   if (n_lmks && !lmk_lambda) return null_arg(fn, "lmk_lambda");
   const uint64_t n = (uint64_t)n_cams + n_lmks;
-  if (n > kMaxLanes) return fail(GBP_ERR_INVALID, std::string(fn) + ": n_cams + n_lmks is too large");
+  if (n > kMaxLanes) return bad_arg(fn, "n_cams + n_lmks is too large");
   last_error().clear();
   if (n == 0) return GBP_OK;
   hipLaunchKernelGGL(k_post_moments, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), n_cams, n_lmks,
@@ -143,7 +137,7 @@ GBP_POST_EXPORT(gbp_post_moments,
   return launched(fn);
 }
 
-GBP_POST_EXPORT(gbp_post_residuals,
+GBP_STATELESS_EXPORT(gbp_post_residuals,
                 (void* hip_stream, uint32_t n_cams, uint32_t n_lmks, uint32_t n_edges, const uint32_t* cam_id, const uint32_t* lmk_id,
                  const float K[9], const float* cam_mean, const float* lmk_mean, const float* measurements, const uint32_t* active_flag,
                  const float* cam_cov, const float* lmk_cov, float* residual, float* reproj_cov),
@@ -151,8 +145,8 @@ GBP_POST_EXPORT(gbp_post_residuals,
                  residual, reproj_cov)) {
   const char* fn = "gbp_post_residuals";
   if (!K) return null_arg(fn, "K");
-  if (reproj_cov && !cam_cov) return fail(GBP_ERR_INVALID, std::string(fn) + ": reproj_cov needs cam_cov, which is NULL");
-  if (reproj_cov && !lmk_cov) return fail(GBP_ERR_INVALID, std::string(fn) + ": reproj_cov needs lmk_cov, which is NULL");
+  if (reproj_cov && !cam_cov) return bad_arg(fn, "reproj_cov needs cam_cov, which is NULL");
+  if (reproj_cov && !lmk_cov) return bad_arg(fn, "reproj_cov needs lmk_cov, which is NULL");
   if (n_edges) {
     if (!cam_id) return null_arg(fn, "cam_id");
     if (!lmk_id) return null_arg(fn, "lmk_id");
@@ -160,10 +154,10 @@ GBP_POST_EXPORT(gbp_post_residuals,
     if (!lmk_mean) return null_arg(fn, "lmk_mean");
     if (!measurements) return null_arg(fn, "measurements");
     if (!residual) return null_arg(fn, "residual");
-    if (n_cams == 0) return fail(GBP_ERR_INVALID, std::string(fn) + ": n_cams is 0 with n_edges > 0");
-    if (n_lmks == 0) return fail(GBP_ERR_INVALID, std::string(fn) + ": n_lmks is 0 with n_edges > 0");
+    if (n_cams == 0) return bad_arg(fn, "n_cams is 0 with n_edges > 0");
+    if (n_lmks == 0) return bad_arg(fn, "n_lmks is 0 with n_edges > 0");
   }
-  if ((uint64_t)n_edges > kMaxLanes) return fail(GBP_ERR_INVALID, std::string(fn) + ": n_edges is too large");
+  if ((uint64_t)n_edges > kMaxLanes) return bad_arg(fn, "n_edges is too large");
   last_error().clear();
   if (n_edges == 0) return GBP_OK;
   K9 k;

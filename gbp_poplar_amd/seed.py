@@ -4,16 +4,17 @@ keyframe from the previous camera's belief (keyframe).
 
 landmarks and keyframe take torch tensors on the GPU — read in place, results in fresh tensors on the same GPU or written into the
 tensors passed as `out`, nothing waits: the work is queued on `stream` (a raw stream handle; default: torch's current stream).  Both
-also take numpy arrays: those are staged through device tensors and the call blocks until the numpy results are there.  The library is a
-loader of its own beside _lib.py and post.py: it has no ctx.  There is no CPU path: the kernels are HIP."""
+also take numpy arrays: those are staged through device tensors and the call blocks until the numpy results are there.  The library is
+loaded beside _lib.py's and post.py's (the same _loader): it has no ctx.  There is no CPU path: the kernels are HIP."""
 import ctypes as C
 import os
 
 import numpy as np
 
 from . import _cabi as cabi
+from . import _devarrays as arr
 from ._devarrays import F32 as _F32, U32 as _U32, device_of as _device_of, ptr as _ptr, stream_handle as _stream_handle, tensor as _tensor
-from ._devarrays import to_device
+from ._loader import load_library
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libgbp_mi355x_seed.so")
@@ -51,29 +52,9 @@ def symbols():
 
 def load():
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError("native library %s is missing — build it with `python -m gbp_poplar_amd.build` "
-                           "(hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
-    if os.environ.get("GBP_NO_TORCH") != "1":      # one HIP runtime per process: torch's first (see _lib.load)
-        try:
-            import torch
-            torch.cuda.is_available()
-        except ImportError:
-            pass
-    lib = C.CDLL(LIB_PATH)
-    lib.gbp_seed_abi_version.restype = C.c_int
-    lib.gbp_seed_abi_version.argtypes = []
-    if lib.gbp_seed_abi_version() != GBP_SEED_ABI_VERSION:
-        raise RuntimeError("%s has ABI version %d, these bindings were written for %d — rebuild (python -m gbp_poplar_amd.build)"
-                           % (LIB_PATH, lib.gbp_seed_abi_version(), GBP_SEED_ABI_VERSION))
-    for name, (res, args) in _SIGS.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = load_library(LIB_PATH, "gbp_seed_abi_version", GBP_SEED_ABI_VERSION, _SIGS)
+    return _lib
 
 
 class SeedError(RuntimeError):
@@ -81,12 +62,10 @@ class SeedError(RuntimeError):
 
 
 def _chk(rc, what):
-    if rc != 0:
-        raise SeedError("%s: %s (status %d)" % (what, load().gbp_seed_last_error().decode(), rc))
+    arr.check(rc, what, load().gbp_seed_last_error, SeedError)
 
 
-def _to_device(a, ints=False):
-    return to_device(a, ints, SeedError, "the seeding")
+_WHAT = "the seeding"      # (what has no CPU path, in the error for numpy arrays without a GPU)
 
 
 def default_options(**changes):
@@ -128,6 +107,7 @@ def workspace_bytes(n_cams):
 
 _OUT = (("lmk_mean", 3, "float"), ("lmk_priors_eta", 3, "float"), ("lmk_priors_lambda", 9, "float"), ("status", 1, "int"), ("n_views", 1, "int"))
 _INTS = ("cam_id", "lmk_start", "lmk_edges", "active_flag", "select")
+_UINTS = ("status", "n_views")      # the integer outputs: uint32 as numpy
 
 
 def landmarks(cam_id, lmk_start, lmk_edges, K, cam_mean, measurements, active_flag=None, select=None, options=None, out=None, workspace=None,
@@ -146,14 +126,11 @@ def landmarks(cam_id, lmk_start, lmk_edges, K, cam_mean, measurements, active_fl
     unknown = set(out) - {k for k, _, _ in _OUT}
     if unknown:
         raise TypeError("out: unknown arrays %s" % sorted(unknown))
-    if not any(cabi.is_device_tensor(a) for a in list(arrays.values()) + list(out.values())):
+    if arr.on_host(dict(arrays, **out)):      # (the two sets of names are disjoint)
         check_index(lmk_start, lmk_edges)
-        d = {k: _to_device(v, k in _INTS) for k, v in arrays.items()}
-        o = {k: _to_device(v, k in ("status", "n_views")) for k, v in out.items()}
-        res = landmarks(d["cam_id"], d["lmk_start"], d["lmk_edges"], K, d["cam_mean"], d["measurements"], d["active_flag"], d["select"], options, o,
-                        None, stream)
-        torch.cuda.synchronize()
-        return {k: (v.cpu().numpy().view(np.uint32) if k in ("status", "n_views") else v.cpu().numpy()) for k, v in res.items()}
+        return arr.round_trip(dict(arrays, **out), _INTS + _UINTS, lambda d: landmarks(
+            d["cam_id"], d["lmk_start"], d["lmk_edges"], K, d["cam_mean"], d["measurements"], d["active_flag"], d["select"], options,
+            {k: d[k] for k in out}, None, stream), _UINTS, SeedError, _WHAT)
     dev = _device_of([a for a in list(arrays.values()) + list(out.values()) if a is not None])
     n_e, n_l, n_c = arrays["cam_id"].numel(), arrays["lmk_start"].numel() - 1, arrays["cam_mean"].numel() // 6
     if n_l < 0:
@@ -174,9 +151,8 @@ def landmarks(cam_id, lmk_start, lmk_edges, K, cam_mean, measurements, active_fl
     opts = options if options is not None else default_options()
     if not isinstance(opts, Options):
         raise TypeError("options: expected a seed.Options (seed.default_options(...))")
-    k9 = (C.c_float * 9)(*[float(x) for x in np.asarray(K, dtype=np.float64).reshape(9)])
     with torch.cuda.device(dev):
-        _chk(load().gbp_seed_landmarks(_vp(_stream_handle(stream)), n_c, n_l, n_e, _ptr(t["cam_id"]), _ptr(t["lmk_start"]), _ptr(t["lmk_edges"]), k9,
+        _chk(load().gbp_seed_landmarks(_vp(_stream_handle(stream)), n_c, n_l, n_e, _ptr(t["cam_id"]), _ptr(t["lmk_start"]), _ptr(t["lmk_edges"]), arr.k9(K),
                                        _ptr(t["cam_mean"]), _ptr(t["measurements"]), _ptr(t["active_flag"]), _ptr(t["select"]), C.byref(opts),
                                        _ptr(workspace), *[_ptr(res[k]) for k, _, _ in _OUT]), "gbp_seed_landmarks")
     return res
@@ -189,11 +165,9 @@ def keyframe(src, dst, cam_beliefs_eta, cam_beliefs_lambda, cam_priors_lambda, c
     import torch
     arrays = {"cam_beliefs_eta": cam_beliefs_eta, "cam_beliefs_lambda": cam_beliefs_lambda, "cam_priors_lambda": cam_priors_lambda,
               "cam_priors_eta": cam_priors_eta}
-    if not any(cabi.is_device_tensor(a) for a in arrays.values()):
-        d = {k: _to_device(v) for k, v in arrays.items()}
-        eta, mean = keyframe(src, dst, d["cam_beliefs_eta"], d["cam_beliefs_lambda"], d["cam_priors_lambda"], d["cam_priors_eta"], stream)
-        torch.cuda.synchronize()
-        return eta.cpu().numpy(), mean.cpu().numpy()
+    if arr.on_host(arrays):
+        return arr.round_trip(arrays, (), lambda d: keyframe(src, dst, d["cam_beliefs_eta"], d["cam_beliefs_lambda"], d["cam_priors_lambda"],
+                                                             d["cam_priors_eta"], stream), (), SeedError, _WHAT)
     dev = _device_of(arrays.values())
     n_c = arrays["cam_beliefs_eta"].numel() // 6
     t = {k: _tensor(k, a, _F32, (36 if k.endswith("lambda") else 6) * n_c, dev) for k, a in arrays.items()}

@@ -2,7 +2,8 @@
 // The arithmetic is seed_math.hpp's (shared with the host twin the tests compile); here are the mapping, the memory accesses and the
 // argument checks.  Not on the iteration path: one call per start / per keyframe, on the caller's stream, nothing allocated, nothing
 // waited for.
-#include "seed_export.hpp"
+#include "../../include/gbp_mi355x_seed.h"
+#include "../stateless/stateless_export.hpp"
 #include "seed_math.hpp"
 
 #include <cmath>
@@ -70,15 +71,6 @@ __global__ __launch_bounds__(64) void k_seed_keyframe(uint32_t src, uint32_t dst
   }
 }
 
-static int launched(const char* what) {
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(GBP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(err));
-  return GBP_OK;
-}
-static int null_arg(const char* fn, const char* arg) { return fail(GBP_ERR_INVALID, std::string(fn) + ": " + arg + " is NULL"); }
-static int bad_arg(const char* fn, const std::string& what) { return fail(GBP_ERR_INVALID, std::string(fn) + ": " + what); }
-constexpr uint64_t kMaxLanes = 0xffffff00ull;      // one lane per item, 32-bit lane index
-
 static void defaults(gbp_seed_options& o) {
   o.min_parallax = 5e-3f;
   o.fallback_depth = 1.f;
@@ -90,19 +82,20 @@ static void defaults(gbp_seed_options& o) {
 }  // namespace gbp
 
 using namespace gbp::seed;
+using namespace gbp::stateless;
 
-GBP_SEED_EXPORT_T(int, 0, gbp_seed_abi_version, (void), ()) { return GBP_SEED_ABI_VERSION; }
+GBP_STATELESS_EXPORT_T(int, 0, gbp_seed_abi_version, (void), ()) { return GBP_SEED_ABI_VERSION; }
 
-GBP_SEED_EXPORT_T(const char*, "", gbp_seed_last_error, (void), ()) { return last_error().c_str(); }
+GBP_STATELESS_EXPORT_T(const char*, "", gbp_seed_last_error, (void), ()) { return last_error().c_str(); }
 
-GBP_SEED_EXPORT(gbp_seed_default_options, (gbp_seed_options* opts), (opts)) {
+GBP_STATELESS_EXPORT(gbp_seed_default_options, (gbp_seed_options* opts), (opts)) {
   if (!opts) return null_arg("gbp_seed_default_options", "opts");
   defaults(*opts);
   last_error().clear();
   return GBP_OK;
 }
 
-GBP_SEED_EXPORT(gbp_seed_index, (uint32_t n_lmks, uint32_t n_edges, const uint32_t* lmk_id, uint32_t* lmk_start, uint32_t* lmk_edges),
+GBP_STATELESS_EXPORT(gbp_seed_index, (uint32_t n_lmks, uint32_t n_edges, const uint32_t* lmk_id, uint32_t* lmk_start, uint32_t* lmk_edges),
                 (n_lmks, n_edges, lmk_id, lmk_start, lmk_edges)) {
   const char* fn = "gbp_seed_index";
   if (!lmk_start) return null_arg(fn, "lmk_start");
@@ -120,7 +113,7 @@ GBP_SEED_EXPORT(gbp_seed_index, (uint32_t n_lmks, uint32_t n_edges, const uint32
   return GBP_OK;
 }
 
-GBP_SEED_EXPORT(gbp_seed_check_index, (uint32_t n_lmks, uint32_t n_edges, const uint32_t* lmk_start, const uint32_t* lmk_edges),
+GBP_STATELESS_EXPORT(gbp_seed_check_index, (uint32_t n_lmks, uint32_t n_edges, const uint32_t* lmk_start, const uint32_t* lmk_edges),
                 (n_lmks, n_edges, lmk_start, lmk_edges)) {
   const char* fn = "gbp_seed_check_index";
   if (!lmk_start) return null_arg(fn, "lmk_start");
@@ -136,9 +129,9 @@ GBP_SEED_EXPORT(gbp_seed_check_index, (uint32_t n_lmks, uint32_t n_edges, const 
   return GBP_OK;
 }
 
-GBP_SEED_EXPORT_T(size_t, 0, gbp_seed_workspace_bytes, (uint32_t n_cams), (n_cams)) { return sizeof(CamRec) * (size_t)n_cams; }
+GBP_STATELESS_EXPORT_T(size_t, 0, gbp_seed_workspace_bytes, (uint32_t n_cams), (n_cams)) { return sizeof(CamRec) * (size_t)n_cams; }
 
-GBP_SEED_EXPORT(gbp_seed_landmarks,
+GBP_STATELESS_EXPORT(gbp_seed_landmarks,
                 (void* hip_stream, uint32_t n_cams, uint32_t n_lmks, uint32_t n_edges, const uint32_t* cam_id, const uint32_t* lmk_start,
                  const uint32_t* lmk_edges, const float K[9], const float* cam_mean, const float* measurements, const uint32_t* active_flag,
                  const uint32_t* select, const gbp_seed_options* opts, void* workspace, float* lmk_mean, float* lmk_priors_eta,
@@ -190,7 +183,7 @@ GBP_SEED_EXPORT(gbp_seed_landmarks,
   return launched(fn);
 }
 
-GBP_SEED_EXPORT(gbp_seed_keyframe,
+GBP_STATELESS_EXPORT(gbp_seed_keyframe,
                 (void* hip_stream, uint32_t n_cams, uint32_t src, uint32_t dst, const float* cam_beliefs_eta, const float* cam_beliefs_lambda,
                  const float* cam_priors_lambda, float* cam_priors_eta, float* cam_mean_out),
                 (hip_stream, n_cams, src, dst, cam_beliefs_eta, cam_beliefs_lambda, cam_priors_lambda, cam_priors_eta, cam_mean_out)) {

@@ -2,11 +2,10 @@
 a stand-alone program: compiled here, run as a process, never loaded into python), its file format, the hand-made belief blocks, the
 oracle's beliefs of a sequence, and the float64 side of the residual / reprojection-covariance checks."""
 import os
-import subprocess
 
 import numpy as np
 
-from tests import ref64
+from tests import host_twin, ref64
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAIN = os.path.join(ROOT, "tests", "sanitize", "post_math_main.cpp")
@@ -15,44 +14,24 @@ OUTPUTS = (("cam_mean", 6, np.float32), ("cam_cov", 36, np.float32), ("lmk_mean"
            ("cam_status", 1, np.uint32), ("lmk_status", 1, np.uint32))
 
 
-def _rocm_include():
-    import shutil
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    return os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "include")
-
-
 def compile_host(exe, sanitize):
-    """the host twin: g++, no FMA contraction (the device is built with -ffp-contract=off too); sanitize: ASan + UBSan"""
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g"] if sanitize else []
-    subprocess.check_call(["g++", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I" + _rocm_include(), "-O1", "-ffp-contract=off", "-Wall",
-                           "-Wno-unknown-pragmas", "-Wno-unused-function"] + san + [MAIN, "-o", exe], cwd=ROOT)
-    return exe
+    return host_twin.compile_host(MAIN, exe, sanitize)
 
 
 def run_host(exe, tmp, beliefs, cam_id=(), lmk_id=(), K=None, measurements=(), active_flag=None, want_cov=True, trig="libm"):
     """-> dict of the eight outputs of the program (flat arrays) for the beliefs (dict of the four arrays) and the edges.
     trig: "libm" (the host's sinf / cosf in the residual's rotation: what gbp_eval_host calls) or "device" (the GPU math library's
-    algorithm, bit for bit: the twin of the kernels; see the program)"""
+    algorithm, bit for bit: the twin of the kernels; see tests/sanitize/device_trig_twin.hpp)"""
     b = [np.ascontiguousarray(beliefs[k], np.float32).ravel() for k in BELIEFS]
     C, L = b[0].size // 6, b[2].size // 3
     cam_id, lmk_id = np.ascontiguousarray(cam_id, np.uint32), np.ascontiguousarray(lmk_id, np.uint32)
     E = cam_id.size
     act = np.ones(E, np.uint32) if active_flag is None else np.ascontiguousarray(active_flag, np.uint32)
     K = np.zeros(9, np.float32) if K is None else np.ascontiguousarray(K, np.float32).ravel()
-    fin, fout = os.path.join(str(tmp), "post_in.bin"), os.path.join(str(tmp), "post_out.bin")
-    with open(fin, "wb") as f:
-        for a in [np.array([C, L, E, int(want_cov)], np.uint32)] + b + [cam_id, lmk_id, K, np.ascontiguousarray(measurements, np.float32).ravel(), act]:
-            f.write(a.tobytes())
-    p = subprocess.run([exe, fin, fout, trig], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
-    assert p.returncode == 0 and "post_math: ok" in p.stdout, (p.returncode, p.stdout[-300:], p.stderr[-3000:])
-    raw = open(fout, "rb").read()
-    out, at = {}, 0
-    for name, w, dt in OUTPUTS + (("residual", 2, np.float32), ("reproj_cov", 3, np.float32)):
-        n = w * (E if name in ("residual", "reproj_cov") else C if name.startswith("cam") else L)
-        out[name] = np.frombuffer(raw, dt, n, at).copy()
-        at += 4 * n
-    assert at == len(raw)
-    return out
+    parts = [np.array([C, L, E, int(want_cov)], np.uint32)] + b + [cam_id, lmk_id, K, np.ascontiguousarray(measurements, np.float32).ravel(), act]
+    outputs = [(name, dt, w * (C if name.startswith("cam") else L)) for name, w, dt in OUTPUTS] + \
+              [("residual", np.float32, 2 * E), ("reproj_cov", np.float32, 3 * E)]
+    return host_twin.run(exe, tmp, "post", parts, outputs, trig)
 
 
 def hand_made(width):

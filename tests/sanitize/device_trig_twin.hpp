@@ -1,6 +1,10 @@
-// The GPU math library's sinf / cosf for |x| < 2^17, restated in IEEE operations (tests/sanitize/post_math_main.cpp tells how it was
-// read from the compiler's output for gfx950 and keeps the first copy; tests/test_seed_cpu.py holds the two equal).  The one operation
-// of eval_cam_rot IEEE 754 does not pin: with g_device_trig set, twin_sinf / twin_cosf give the device's bits, otherwise the host libm's.
+// The GPU math library's sinf / cosf for |x| < 2^17, restated in IEEE operations: the only copy, for both host twins
+// (post_math_main.cpp, seed_math_main.cpp).  sinf / cosf are the one operation of eval_cam_rot that IEEE 754 does not pin: the host's
+// libm and the GPU's math library both return a float within an ulp or so of the true value, not always the same one (measured: cosf one
+// ulp apart for two of six test cameras).  Without g_device_trig, twin_sinf / twin_cosf are the host libm's — what gbp_eval_host calls,
+// so the CPU tests compare like with like.  With it they evaluate the GPU library's own algorithm — a three-term Cody-Waite reduction
+// by pi/2 and two short polynomials, every multiply-add fused, as the gfx950 code object of the kernels does it (read from the
+// compiler's output for sinf / cosf) — in IEEE operations that give the same bits on any host: the twin the GPU tests compare with.
 // Include it behind <cmath> and the HIP headers, then `#define sinf twin_sinf` / `#define cosf twin_cosf` around the arithmetic header.
 #pragma once
 #include <cmath>
@@ -29,7 +33,7 @@ static void device_sincos_reduced(float ax, int& n, float& s, float& c) {
 }
 static float twin_sinf(float x) {
   const float ax = std::fabs(x);
-  if (!g_device_trig || !(ax < 131072.0f)) return sinf(x);
+  if (!g_device_trig || !(ax < 131072.0f)) return sinf(x);      // (beyond 2^17 the library reduces with a table of 2/pi: no rotation vector gets there)
   int n;
   float s, c;
   device_sincos_reduced(ax, n, s, c);

@@ -8,83 +8,32 @@
 // OUT: float cam_mean [6C], cam_cov [36C], lmk_mean [3L], lmk_cov [9L]; uint32 cam_status [C], lmk_status [L];
 //     float residual [2E], reproj_cov [3E] (zeros without want_cov) — the residuals at the means and covariances just computed,
 //     as gbp_post_residuals computes them from the output of gbp_post_moments.
-// libm | device (default libm): whose sinf / cosf the rotation of the residual (eval_cam_rot) takes.  They are the one operation of
-// the chain that IEEE 754 does not pin: the host's libm and the GPU's math library both return a float within an ulp or so of the true
-// value, not always the same one (measured: cosf one ulp apart for two of six test cameras).  "libm" is what gbp_eval_host calls, so
-// the CPU tests compare like with like; "device" evaluates the GPU library's own algorithm for |x| < 2^17 — a three-term Cody-Waite
-// reduction by pi/2 and two short polynomials, every multiply-add fused, as the gfx950 code object of the kernels does it (read from
-// the compiler's output for sinf / cosf) — in IEEE operations that give the same bits on any host: the twin the GPU tests compare with.
+// libm | device (default libm): whose sinf / cosf the rotation of the residual (eval_cam_rot) takes: the one operation of the chain
+// IEEE 754 does not pin.  device = the twin of the GPU math library's algorithm in tests/sanitize/device_trig_twin.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdio>
-#include <cstring>
 #include <vector>
 
-static bool g_device_trig = false;
-static uint32_t bits_of(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
-static float float_of(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
-static float f64(uint64_t u) { double d; std::memcpy(&d, &u, 8); return (float)d; }      // (the constants: doubles that are exact floats)
-// r = |x| - n pi/2 with n = rint(|x| 2/pi); sin and cos of r by their polynomials
-static void device_sincos_reduced(float ax, int& n, float& s, float& c) {
-  const float fn = std::rint(ax * f64(0x3FE45F3060000000ull));
-  float r = std::fmaf(fn, f64(0xBFF921FB40000000ull), ax);
-  r = std::fmaf(fn, f64(0xBE74442D00000000ull), r);
-  r = std::fmaf(fn, f64(0xBCF8469880000000ull), r);
-  n = (int)fn;
-  const float t = r * r;
-  float a = std::fmaf(t, f64(0xBF29833040000000ull), f64(0x3F81103880000000ull));
-  a = std::fmaf(t, a, f64(0xBFC55553A0000000ull));
-  s = std::fmaf(r, t * a, r);
-  float b = std::fmaf(t, f64(0x3EFAEA6680000000ull), f64(0xBF56C9E760000000ull));
-  b = std::fmaf(t, b, f64(0x3FA5557EE0000000ull));
-  b = std::fmaf(t, b, f64(0xBFE0000080000000ull));
-  c = std::fmaf(t, b, 1.0f);
-}
-static float twin_sinf(float x) {
-  const float ax = std::fabs(x);
-  if (!g_device_trig || !(ax < 131072.0f)) return sinf(x);      // (beyond 2^17 the library reduces with a table of 2/pi: no rotation vector gets there)
-  int n;
-  float s, c;
-  device_sincos_reduced(ax, n, s, c);
-  return float_of(bits_of((n & 1) ? c : s) ^ (((uint32_t)n << 30) & 0x80000000u) ^ (bits_of(ax) ^ bits_of(x)));
-}
-static float twin_cosf(float x) {
-  const float ax = std::fabs(x);
-  if (!g_device_trig || !(ax < 131072.0f)) return cosf(x);
-  int n;
-  float s, c;
-  device_sincos_reduced(ax, n, s, c);
-  return float_of(bits_of((n & 1) ? -s : c) ^ (((uint32_t)n << 30) & 0x80000000u));
-}
+#include "device_trig_twin.hpp"
+#include "host_twin_io.hpp"
 #define sinf twin_sinf      // (behind <cmath> and the HIP headers, in front of the arithmetic: only eval_cam_rot calls them)
 #define cosf twin_cosf
 #include "../../gbp_poplar_amd/post/post_math.hpp"
 #undef sinf
 #undef cosf
 
-template <class T> static bool get(FILE* f, std::vector<T>& v, size_t n) {
-  v.resize(n);
-  return n == 0 || std::fread(v.data(), sizeof(T), n, f) == n;
-}
-template <class T> static bool put(FILE* f, const std::vector<T>& v) { return v.empty() || std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size(); }
-
 int main(int argc, char** argv) {
-  if (argc != 3 && argc != 4) { std::fprintf(stderr, "usage: %s IN OUT [libm|device]\n", argv[0]); return 2; }
-  if (argc == 4) {
-    if (std::strcmp(argv[3], "device") != 0 && std::strcmp(argv[3], "libm") != 0) { std::fprintf(stderr, "unknown trig mode %s\n", argv[3]); return 2; }
-    g_device_trig = std::strcmp(argv[3], "device") == 0;
-  }
-  FILE* in = std::fopen(argv[1], "rb");
-  if (!in) { std::fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
+  FILE* in = twin_open(argc, argv);
+  if (!in) return 2;
   std::vector<uint32_t> dims, cam_id, lmk_id, active;
   std::vector<float> ce, cl, le, ll, K, z;
   bool ok = get(in, dims, 4);
   const size_t C = ok ? dims[0] : 0, L = ok ? dims[1] : 0, E = ok ? dims[2] : 0;
   ok = ok && get(in, ce, 6 * C) && get(in, cl, 36 * C) && get(in, le, 3 * L) && get(in, ll, 9 * L) && get(in, cam_id, E) && get(in, lmk_id, E) &&
        get(in, K, 9) && get(in, z, 2 * E) && get(in, active, E);
-  std::fclose(in);
-  if (!ok) { std::fprintf(stderr, "%s is truncated\n", argv[1]); return 2; }
+  if (!twin_read(in, ok, argv)) return 2;
   const bool want_cov = dims[3] != 0;
 
   std::vector<float> cm(6 * C), cc(36 * C), lm(3 * L), lc(9 * L), res(2 * E, 0.f), rc(3 * E, 0.f);
@@ -119,10 +68,8 @@ int main(int argc, char** argv) {
       for (int i = 0; i < 3; ++i) rc[3 * e + i] = s[i];
     }
   }
-  FILE* out = std::fopen(argv[2], "wb");
-  if (!out) { std::fprintf(stderr, "cannot write %s\n", argv[2]); return 2; }
+  FILE* out = twin_create(argv);
+  if (!out) return 2;
   ok = put(out, cm) && put(out, cc) && put(out, lm) && put(out, lc) && put(out, cs) && put(out, ls) && put(out, res) && put(out, rc);
-  if (std::fclose(out) != 0 || !ok) { std::fprintf(stderr, "cannot write %s\n", argv[2]); return 2; }
-  std::printf("post_math: ok\n");
-  return 0;
+  return twin_done(out, ok, argv, "post_math");
 }

@@ -13,30 +13,19 @@
 
 #include <cmath>
 #include <cstdio>
-#include <cstring>
 #include <vector>
 
 #include "device_trig_twin.hpp"
+#include "host_twin_io.hpp"
 #define sinf twin_sinf      // (behind <cmath> and the HIP headers, in front of the arithmetic: only eval_cam_rot calls them)
 #define cosf twin_cosf
 #include "../../gbp_poplar_amd/seed/seed_math.hpp"
 #undef sinf
 #undef cosf
 
-template <class T> static bool get(FILE* f, std::vector<T>& v, size_t n) {
-  v.resize(n);
-  return n == 0 || std::fread(v.data(), sizeof(T), n, f) == n;
-}
-template <class T> static bool put(FILE* f, const std::vector<T>& v) { return v.empty() || std::fwrite(v.data(), sizeof(T), v.size(), f) == v.size(); }
-
 int main(int argc, char** argv) {
-  if (argc != 3 && argc != 4) { std::fprintf(stderr, "usage: %s IN OUT [libm|device]\n", argv[0]); return 2; }
-  if (argc == 4) {
-    if (std::strcmp(argv[3], "device") != 0 && std::strcmp(argv[3], "libm") != 0) { std::fprintf(stderr, "unknown trig mode %s\n", argv[3]); return 2; }
-    g_device_trig = std::strcmp(argv[3], "device") == 0;
-  }
-  FILE* in = std::fopen(argv[1], "rb");
-  if (!in) { std::fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
+  FILE* in = twin_open(argc, argv);
+  if (!in) return 2;
   std::vector<uint32_t> dims, iters, cam_id, lmk_start, lmk_edges, active, select, status, n_views;
   std::vector<float> fopts, cam_mean, K, z, mean, eta, lambda;
   bool ok = get(in, dims, 4);
@@ -44,8 +33,7 @@ int main(int argc, char** argv) {
   ok = ok && get(in, fopts, 3) && get(in, iters, 1) && get(in, cam_mean, 6 * C) && get(in, cam_id, E) && get(in, lmk_start, L + 1) &&
        get(in, lmk_edges, E) && get(in, K, 9) && get(in, z, 2 * E) && get(in, active, E) && get(in, select, L) && get(in, mean, 3 * L) &&
        get(in, eta, 3 * L) && get(in, lambda, 9 * L) && get(in, status, L) && get(in, n_views, L);
-  std::fclose(in);
-  if (!ok) { std::fprintf(stderr, "%s is truncated\n", argv[1]); return 2; }
+  if (!twin_read(in, ok, argv)) return 2;
   const bool has_select = dims[3] != 0;
 
   using namespace gbp::seed;
@@ -74,10 +62,8 @@ int main(int argc, char** argv) {
     for (int i = 0; i < 3; ++i) { mean[3 * l + i] = s.mean[i]; eta[3 * l + i] = s.eta[i]; }
     for (int i = 0; i < 9; ++i) lambda[9 * l + i] = (i % 4 == 0) ? s.lam : 0.f;
   }
-  FILE* out = std::fopen(argv[2], "wb");
-  if (!out) { std::fprintf(stderr, "cannot write %s\n", argv[2]); return 2; }
+  FILE* out = twin_create(argv);
+  if (!out) return 2;
   ok = put(out, mean) && put(out, eta) && put(out, lambda) && put(out, status) && put(out, n_views);
-  if (std::fclose(out) != 0 || !ok) { std::fprintf(stderr, "cannot write %s\n", argv[2]); return 2; }
-  std::printf("seed_math: ok\n");
-  return 0;
+  return twin_done(out, ok, argv, "seed_math");
 }

@@ -10,9 +10,10 @@ tests allow the code under test 8 x that (the project's convention), per measure
     lam      max over landmarks of |lam - lam64| / lam64
 """
 import os
-import subprocess
 
 import numpy as np
+
+from tests import host_twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAIN = os.path.join(ROOT, "tests", "sanitize", "seed_math_main.cpp")
@@ -23,18 +24,8 @@ OUTPUTS = (("lmk_mean", 3, np.float32), ("lmk_priors_eta", 3, np.float32), ("lmk
            ("n_views", 1, np.uint32))
 
 
-def _rocm_include():
-    import shutil
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    return os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "include")
-
-
 def compile_host(exe, sanitize):
-    """the host twin: g++, no FMA contraction (the device is built with -ffp-contract=off too); sanitize: ASan + UBSan"""
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g"] if sanitize else []
-    subprocess.check_call(["g++", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I" + _rocm_include(), "-O1", "-ffp-contract=off", "-Wall",
-                           "-Wno-unknown-pragmas", "-Wno-unused-function"] + san + [MAIN, "-o", exe], cwd=ROOT)
-    return exe
+    return host_twin.compile_host(MAIN, exe, sanitize)
 
 
 def index_numpy(lmk_id, n_lmks):
@@ -62,24 +53,12 @@ def run_host(exe, tmp, graph, opts=None, select=None, before=None, trig="libm"):
     act = np.ones(E, np.uint32) if graph.get("active_flag") is None else np.ascontiguousarray(graph["active_flag"], np.uint32)
     sel = np.ones(L, np.uint32) if select is None else np.ascontiguousarray(select, np.uint32)
     before = initial_outputs(L) if before is None else before
-    fin, fout = os.path.join(str(tmp), "seed_in.bin"), os.path.join(str(tmp), "seed_out.bin")
     parts = [np.array([C, L, E, int(select is not None)], np.uint32),
              np.array([o["min_parallax"], o["fallback_depth"], o["reproj_meas_var"]], np.float32), np.array([o["refine_iters"]], np.uint32),
              np.ascontiguousarray(graph["cam_mean"], np.float32).ravel(), cam_id, np.ascontiguousarray(graph["lmk_start"], np.uint32),
              np.ascontiguousarray(graph["lmk_edges"], np.uint32), np.ascontiguousarray(graph["K"], np.float32).ravel(),
              np.ascontiguousarray(graph["measurements"], np.float32).ravel(), act, sel] + [before[k] for k, _, _ in OUTPUTS]
-    with open(fin, "wb") as f:
-        for a in parts:
-            f.write(a.tobytes())
-    p = subprocess.run([exe, fin, fout, trig], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert p.returncode == 0 and "seed_math: ok" in p.stdout, (p.returncode, p.stdout[-300:], p.stderr[-3000:])
-    raw = open(fout, "rb").read()
-    out, at = {}, 0
-    for name, w, dt in OUTPUTS:
-        out[name] = np.frombuffer(raw, dt, w * L, at).copy()
-        at += 4 * w * L
-    assert at == len(raw)
-    return out
+    return host_twin.run(exe, tmp, "seed", parts, [(name, dt, w * L) for name, w, dt in OUTPUTS], trig, timeout=300)
 
 
 # ---- the definition, in numpy, in one dtype ----

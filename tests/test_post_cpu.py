@@ -23,17 +23,13 @@
    answer GBP_ERR_INVALID and name the argument before anything touches HIP.
 """
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import post_support as ps
+from tests import stateless_cabi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-POST = os.path.join(ROOT, "gbp_poplar_amd", "post")
 COV_BOUND = 2.0 ** -21
 COND_LIMIT = 1e6
 MAX_EXCLUDED = 0.01
@@ -161,40 +157,16 @@ def test_residuals_reproduce_the_metrics_per_factor_terms(name, runs):
 
 
 # ---- the C-ABI ----
-def _declared():
-    src = open(os.path.join(ROOT, "include", "gbp_mi355x_post.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"^\s*(?:GBP_API\s+)?(?:const\s+char\s*\*|int|void|size_t)\s+(gbp_\w+)\s*\(", src, flags=re.M)))
+EXPORTS = ["gbp_post_abi_version", "gbp_post_last_error", "gbp_post_moments", "gbp_post_residuals"]
 
 
 def test_library_exports_the_header_and_nothing_else():
     from gbp_poplar_amd import post
-    names = _declared()
-    assert names == ["gbp_post_abi_version", "gbp_post_last_error", "gbp_post_moments", "gbp_post_residuals"] == post.symbols()
-    out = subprocess.run(["nm", "-D", "--defined-only", post.LIB_PATH], stdout=subprocess.PIPE, text=True, check=True).stdout
-    assert {l.split()[-1] for l in out.splitlines() if l.strip()} == set(names)
-    assert post.load().gbp_post_abi_version() == post.GBP_POST_ABI_VERSION == 1
+    stateless_cabi.check_exports(post, "gbp_mi355x_post.h", EXPORTS, 1)
 
 
 def test_every_export_is_defined_through_the_guard_macro():
-    defined, stray = {}, []
-    for f in sorted(os.listdir(POST)):
-        if not f.endswith((".cpp", ".hip", ".hpp")):
-            continue
-        src = re.sub(r"//[^\n]*", "", open(os.path.join(POST, f)).read())
-        for m in re.finditer(r"^GBP_POST_EXPORT(?:_T)?\(\s*(?:[^,()]+,\s*[^,]+,\s*)?(gbp_\w+)\s*,", src, flags=re.M):
-            defined.setdefault(m.group(1), []).append(f)
-        if 'extern "C"' in src and f != "post_export.hpp":
-            stray.append(f)
-        stray += ["%s: %s" % (f, m.group(1)) for m in re.finditer(r"^(?:int|void|size_t|const char\s*\*)\s+(gbp_\w+)\s*\(", src, flags=re.M)]
-    assert not stray, stray
-    assert set(defined) == set(_declared()) and all(len(v) == 1 for v in defined.values()), defined
-    macro = open(os.path.join(POST, "post_export.hpp")).read()
-    assert macro.count("catch (...)") >= 2 and "guarded(#name" in macro
-    # nothing of the readout is defined inside csrc/ (whose every *.cpp goes into the core library)
-    for dirpath, _, files in os.walk(os.path.join(ROOT, "gbp_poplar_amd", "csrc")):
-        for f in files:
-            assert "gbp_post_" not in open(os.path.join(dirpath, f)).read() or f == "cli_common.hpp", f
+    stateless_cabi.check_guard("post", "gbp_mi355x_post.h", EXPORTS)
 
 
 P = C.c_void_p(64)      # any non-NULL address: a call that fails its argument checks touches neither the array nor HIP

@@ -25,10 +25,10 @@ import numpy as np
 import pytest
 
 from tests import seed_support as ss
+from tests import stateless_cabi
 from tests.conftest import seq_path
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEED = os.path.join(ROOT, "gbp_poplar_amd", "seed")
 FACTOR = 8.0
 
 
@@ -221,40 +221,14 @@ EXPORTS = ["gbp_seed_abi_version", "gbp_seed_check_index", "gbp_seed_default_opt
            "gbp_seed_last_error", "gbp_seed_workspace_bytes"]
 
 
-def _declared():
-    src = open(os.path.join(ROOT, "include", "gbp_mi355x_seed.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"^\s*(?:GBP_API\s+)?(?:const\s+char\s*\*|int|void|size_t)\s+(gbp_\w+)\s*\(", src, flags=re.M)))
-
-
 def test_library_exports_the_header_and_nothing_else():
     from gbp_poplar_amd import seed
-    assert _declared() == EXPORTS == seed.symbols()
-    out = subprocess.run(["nm", "-D", "--defined-only", seed.LIB_PATH], stdout=subprocess.PIPE, text=True, check=True).stdout
-    assert {l.split()[-1] for l in out.splitlines() if l.strip()} == set(EXPORTS)
-    assert seed.load().gbp_seed_abi_version() == seed.GBP_SEED_ABI_VERSION == 1
+    stateless_cabi.check_exports(seed, "gbp_mi355x_seed.h", EXPORTS, 1)
     assert seed.workspace_bytes(1000) == 64000
 
 
 def test_every_export_is_defined_through_the_guard_macro():
-    defined, stray = {}, []
-    for f in sorted(os.listdir(SEED)):
-        if not f.endswith((".cpp", ".hip", ".hpp")):
-            continue
-        src = re.sub(r"//[^\n]*", "", open(os.path.join(SEED, f)).read())
-        for m in re.finditer(r"^GBP_SEED_EXPORT(?:_T)?\(\s*(?:[^,()]+,\s*[^,]+,\s*)?(gbp_\w+)\s*,", src, flags=re.M):
-            defined.setdefault(m.group(1), []).append(f)
-        if 'extern "C"' in src and f != "seed_export.hpp":
-            stray.append(f)
-        stray += ["%s: %s" % (f, m.group(1)) for m in re.finditer(r"^(?:int|void|size_t|const char\s*\*)\s+(gbp_\w+)\s*\(", src, flags=re.M)]
-    assert not stray, stray
-    assert set(defined) == set(EXPORTS) and all(len(v) == 1 for v in defined.values()), defined
-    macro = open(os.path.join(SEED, "seed_export.hpp")).read()
-    assert macro.count("catch (...)") >= 2 and "guarded(#name" in macro
-    # nothing of the seeding is defined inside csrc/ (whose every *.cpp goes into the core library)
-    for dirpath, _, files in os.walk(os.path.join(ROOT, "gbp_poplar_amd", "csrc")):
-        for f in files:
-            assert "gbp_seed_" not in open(os.path.join(dirpath, f)).read() or f == "cli_common.hpp", f
+    stateless_cabi.check_guard("seed", "gbp_mi355x_seed.h", EXPORTS)
 
 
 def test_default_options_are_the_headers():
@@ -325,13 +299,17 @@ def test_empty_problems_are_legal_without_a_device():
     assert lib.gbp_seed_index(0, 0, None, np.zeros(1, np.uint32).ctypes.data_as(C.POINTER(C.c_uint32)), None) == 0
 
 
-def test_the_trig_twin_is_the_readout_programs():
-    """tests/sanitize/device_trig_twin.hpp restates what post_math_main.cpp holds inline: the same code, comments aside"""
-    def code(path):
-        """from the switch to the end of twin_cosf, without comments, white space squeezed"""
-        src = re.sub(r"[ \t]*//[^\n]*", "", open(os.path.join(ROOT, "tests", "sanitize", path)).read()) + "#define sinf"
-        return re.sub(r"\s+", " ", src[src.index("static bool g_device_trig"):src.index("#define sinf")]).strip()
-    assert code("device_trig_twin.hpp") == code("post_math_main.cpp") and "twin_cosf" in code("device_trig_twin.hpp")
+def test_both_host_twins_take_their_trig_from_the_one_twin_header():
+    """tests/sanitize/device_trig_twin.hpp holds the only copy of the device's sinf / cosf: both mains include it, put it in front of
+    their arithmetic header by the two defines, and define none of it themselves"""
+    for main, math in (("post_math_main.cpp", "post/post_math.hpp"), ("seed_math_main.cpp", "seed/seed_math.hpp")):
+        src = re.sub(r"[ \t]*//[^\n]*", "", open(os.path.join(ROOT, "tests", "sanitize", main)).read())
+        assert re.search(r'#include "device_trig_twin\.hpp"\n(?:#include [^\n]*\n)*#define sinf twin_sinf\n#define cosf twin_cosf\n'
+                         r'#include "\.\./\.\./gbp_poplar_amd/%s"\n#undef sinf\n#undef cosf\n' % re.escape(math), src), main
+        for name in ("twin_sinf", "twin_cosf", "device_sincos_reduced"):
+            assert not re.search(r"\b%s\s*\([^;{]*\)\s*\{" % name, src), (main, name)
+    twin = open(os.path.join(ROOT, "tests", "sanitize", "device_trig_twin.hpp")).read()
+    assert all(re.search(r"\b%s\s*\([^;{]*\)\s*\{" % name, twin) for name in ("twin_sinf", "twin_cosf", "device_sincos_reduced"))
 
 
 def test_numpy_arrays_without_a_device_raise_a_seed_error(monkeypatch):
