@@ -29,7 +29,7 @@ int need_pos_edge(gbp_ctx* c) {
 // this call from blocking.
 int settle_for_upload(gbp_ctx* c) {
   if (int rc = settle(c)) return rc;
-  if (c->persist.status.host && (c->persist.ok != c->persist.eligible || *static_cast<volatile unsigned*>(c->persist.status.host) != 0u)) return persist_reset(c);
+  if (c->persist.status.host && (c->persist.ok != c->persist.eligible || persist_failed_seq(c) != 0u)) return persist_reset(c);
   return GBP_OK;
 }
 

@@ -48,6 +48,14 @@ int eval_enqueue(gbp_ctx* c, int area, DeviceEval* dev_slots) {
   return GBP_OK;
 }
 
+// The two result areas (and their health words) take turns.  next_area: the one the next metric goes to; claim_area, once that metric
+// is queued: the turn passes on, and (in_flight) the metric waits for a gbp_eval_end.
+static int next_area(const gbp_ctx* c) { return c->metric.parity & 1; }
+static void claim_area(gbp_ctx* c, bool in_flight) {
+  c->metric.parity ^= 1;
+  if (in_flight) c->metric.pending += 1;
+}
+
 // Is `out` of fn memory of the ctx's GPU?  Called after the argument and state checks of the call.  Host memory (unregistered, pinned,
 // host-registered): *device = false, today's path.  GBP_ERR_INVALID naming `out`: another GPU's memory, managed memory, a landmark-sharded
 // ctx (struct_kind), a device address that is not 8-byte aligned; GBP_ERR_STATE: the caller is capturing the ctx's stream.
@@ -74,9 +82,9 @@ static int eval_scratch(gbp_ctx* c) {
 // One metric of the current beliefs into the caller's device record: k_means + k_eval as eval_begin queues them (the same health area,
 // the parity advanced as one eval_begin / eval_end pair advances it), their partial sums in device memory, the fold behind them.
 static int eval_to_device(gbp_ctx* c, gbp_eval_out* out) {
-  const int area = c->metric.parity & 1;
+  const int area = next_area(c);
   if (int rc = eval_enqueue(c, area, P<DeviceEval>(c->metric.scratch))) return rc;
-  c->metric.parity ^= 1;
+  claim_area(c, /*in_flight=*/false);
   launch_eval_fold_part(P<DeviceEval>(c->metric.scratch), 0, eval_blocks(c->n_tiles), c->n_tiles, false, 1, out, c->stream);
   HIPCHK(c, hipGetLastError());
   return GBP_OK;
@@ -87,10 +95,9 @@ int eval_begin(gbp_ctx* c) {
   if (c->metric.pending >= 2) return fail(c, GBP_ERR_STATE, "gbp_eval_begin: two evaluations already in flight, call gbp_eval_end first");
   if (int rc = settle(c)) return rc;
   if (int rc = eval_alloc(c)) return rc;
-  const int area = c->metric.parity & 1;
+  const int area = next_area(c);
   if (int rc = eval_enqueue(c, area)) return rc;
-  c->metric.parity ^= 1;
-  c->metric.pending += 1;
+  claim_area(c, /*in_flight=*/true);
   return GBP_OK;
 }
 
@@ -133,9 +140,9 @@ int eval_end(gbp_ctx* c, gbp_eval_out* o) {
     // the metric may have come out of a k_persist launch: that launch (the oldest logged one for this area) and everything
     // before it have completed — validate them; after a time-out the recovery has re-queued the metric behind the replay
     unsigned upto = 0;
-    for (const gbp_ctx::Burst& b : c->persist.log)
-      if (b.mode == 1 && b.area == area) { upto = b.seq; break; }
-    const bool failed = *static_cast<volatile unsigned*>(c->persist.status.host) != 0u;
+    for (const Burst& b : c->persist.log)
+      if (b.kind == BurstKind::MetricAtEnd && b.area == area) { upto = b.seq; break; }
+    const bool failed = persist_failed_seq(c) != 0u;
     if (failed || upto)
       if (int rc = persist_check(c, upto)) return rc;
     if (failed) HIPCHK(c, hipEventSynchronize(c->metric.ev[area]));
@@ -205,31 +212,34 @@ static int iterate_eval(gbp_ctx* c, int n) {
     if (int rc = persist_ready(c, &fused)) return rc;
   if (fused) {
     if (int rc = eval_alloc(c)) return rc;
-    const int area = c->metric.parity & 1;
+    const int area = next_area(c);
     const PersistEval metric = persist_eval(c, area, false);
     TimedSpan sp(c);
     if (int rc = sp.begin()) return rc;
     // A long burst with ONE metric at its end: all but the last iteration in the launch that carries no metric code at all (the
     // instantiation with the metric runs every iteration ~0.5 us slower: 59 us per 100 iterations on fr1xyz against ~10 us for
     // one more launch), the last iteration and the metric in a launch of their own.
-    int head = n >= 16 ? n - 1 : 0;
-    int lrc = head ? launch_persist_burst(c, sweep_args(c), head, nullptr, 0, 0) : GBP_OK;
-    if (lrc == kNotLaunched) head = 0;      // nothing ran: everything on the two-kernel path below
-    if (lrc == GBP_OK) lrc = launch_persist_burst(c, sweep_args(c), n - head, &metric, 1, area);
-    if (lrc == kNotLaunched && head) {      // the head ran, the ctx then left the persistent path: the last iteration and the metric on the two-kernel path
-      if (int rc = sp.commit((uint64_t)head)) return rc;
-      if (int rc = iterate(c, n - head)) return rc;
-      return eval_begin(c);
+    Burst head, tail;
+    head.n = n >= 16 ? n - 1 : 0;
+    tail.kind = BurstKind::MetricAtEnd; tail.n = n - head.n; tail.area = area;
+    BurstOutcome ran = BurstOutcome::Ran;
+    if (head.n)
+      if (int rc = launch_persist_burst(c, sweep_args(c), head, nullptr, &ran)) return rc;
+    if (ran == BurstOutcome::Ran) {      // (the head NotRun: nothing ran, everything on the two-kernel path below)
+      if (int rc = launch_persist_burst(c, sweep_args(c), tail, &metric, &ran)) return rc;
+      if (ran == BurstOutcome::Ran) {
+        if (int rc = sp.commit((uint64_t)n)) return rc;
+        HIPCHK(c, hipEventRecord(c->metric.ev[area], c->stream));
+        c->metric.per_wave[area] = true;
+        claim_area(c, /*in_flight=*/true);
+        return GBP_OK;
+      }
+      if (head.n) {      // the head ran, the ctx then left the persistent path: the last iteration and the metric on the two-kernel path
+        if (int rc = sp.commit((uint64_t)head.n)) return rc;
+        if (int rc = iterate(c, tail.n)) return rc;
+        return eval_begin(c);
+      }
     }
-    if (lrc == GBP_OK) {
-      if (int rc = sp.commit((uint64_t)n)) return rc;
-      HIPCHK(c, hipEventRecord(c->metric.ev[area], c->stream));
-      c->metric.per_wave[area] = true;
-      c->metric.parity ^= 1;
-      c->metric.pending += 1;
-      return GBP_OK;
-    }
-    if (lrc != kNotLaunched) return lrc;
   }
   if (int rc = iterate(c, n)) return rc;
   return eval_begin(c);
@@ -286,21 +296,23 @@ static int eval_each_ride(gbp_ctx* c, int n, gbp_eval_out* out, bool dev = false
 
 // m <= kSeriesMax passes from loop index i in ONE launch of the persistent kernel with the metric after every one of them (blocking):
 // the metric of pass k rides in the sweep phase of pass k + 1 (both only read the beliefs), its partial sums go to host-mapped memory,
-// out[k] = what gbp_iterate(1) + gbp_eval_global() would have returned.  kNotLaunched: nothing ran, or the launch timed out and the state
-// (priors and flags too) was restored to the start of the burst — the caller runs the passes on the two-kernel path.
-static int series_burst(gbp_ctx* c, int m, unsigned i, unsigned steps2, gbp_eval_out* out) {
-  const int area = c->metric.parity & 1;   // both health areas are zero between evaluations; this launch leaves them so
-  const PersistEval metric = persist_eval(c, area, true);
+// out[k] = what gbp_iterate(1) + gbp_eval_global() would have returned.  *outcome = NotRun: nothing ran; TimedOut: the launch timed out and
+// the state (priors and flags too) was restored to the start of the burst — either way the caller runs the passes on the two-kernel path.
+static int series_burst(gbp_ctx* c, const Piece& p, unsigned steps2, gbp_eval_out* out, BurstOutcome* outcome) {
+  Burst b = burst_of(BurstKind::SeriesHost, p, steps2);
+  b.area = next_area(c);      // both health areas are zero between evaluations; this launch leaves them so
+  const PersistEval metric = persist_eval(c, b.area, true);
   TimedSpan sp(c);
   if (int rc = sp.begin()) return rc;
-  if (int rc = launch_persist_burst(c, sweep_args(c), m, &metric, 2, area, i, steps2)) return rc;
+  if (int rc = launch_persist_burst(c, sweep_args(c), b, &metric, outcome)) return rc;
+  if (*outcome != BurstOutcome::Ran) return GBP_OK;
   if (int rc = sp.end()) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const bool failed = *static_cast<volatile unsigned*>(c->persist.status.host) != 0u;
+  const bool failed = persist_failed_seq(c) != 0u;
   if (int rc = persist_check(c, 0)) return rc;
-  if (failed) return kNotLaunched;
-  if (int rc = sp.commit((uint64_t)m)) return rc;
-  for (int k = 0; k < m; ++k)
+  if (failed) { *outcome = BurstOutcome::TimedOut; return GBP_OK; }
+  if (int rc = sp.commit((uint64_t)p.m)) return rc;
+  for (int k = 0; k < p.m; ++k)
     sum_eval(c, static_cast<const DeviceEval*>(c->persist.series.host) + (size_t)k * metric.stride, eval_blocks(c->n_tiles), out + k, true);
   return GBP_OK;
 }
@@ -309,19 +321,21 @@ static int series_burst(gbp_ctx* c, int m, unsigned i, unsigned steps2, gbp_eval
 // slots, one workgroup of k_eval_fold_part per pass folds them into out[k] behind the launch (and in front of the next launch, which
 // reuses the twin), and the launch stays in the log of unvalidated launches with what a replay needs — whoever validates it later
 // (settle / persist_check) and finds that it timed out restores the snapshot and replays it on the riding path into the same records
-// (persist_recover -> replay_series_dev).  The only host-mapped word involved is the status word of the kernel.
-static int series_burst_dev(gbp_ctx* c, int m, unsigned i, unsigned steps2, gbp_eval_out* out) {
+// (persist_recover: BurstKind::SeriesDevice).  The only host-mapped word involved is the status word of the kernel.
+static int series_burst_dev(gbp_ctx* c, const Piece& p, unsigned steps2, gbp_eval_out* out, BurstOutcome* outcome) {
   if (!c->metric.series_twin.p)
     if (int rc = dev_alloc(c, c->metric.series_twin, sizeof(DeviceEval) * (size_t)(c->n_tiles + 1) * kSeriesMax)) return rc;
-  const int area = c->metric.parity & 1;
-  PersistEval metric = persist_eval(c, area, true);
+  Burst b = burst_of(BurstKind::SeriesDevice, p, steps2);
+  b.area = next_area(c); b.out = out;
+  PersistEval metric = persist_eval(c, b.area, true);
   metric.slots = P<DeviceEval>(c->metric.series_twin);
   TimedSpan sp(c);
   if (int rc = sp.begin()) return rc;
-  if (int rc = launch_persist_burst(c, sweep_args(c), m, &metric, 3, area, i, steps2, out)) return rc;
-  launch_eval_fold_part(metric.slots, metric.stride, eval_blocks(c->n_tiles), c->n_tiles, true, (uint32_t)m, out, c->stream);
+  if (int rc = launch_persist_burst(c, sweep_args(c), b, &metric, outcome)) return rc;
+  if (*outcome != BurstOutcome::Ran) return GBP_OK;
+  launch_eval_fold_part(metric.slots, metric.stride, eval_blocks(c->n_tiles), c->n_tiles, true, (uint32_t)p.m, out, c->stream);
   HIPCHK(c, hipGetLastError());
-  return sp.commit((uint64_t)m);
+  return sp.commit((uint64_t)p.m);
 }
 
 // per_factor_mu = 1, per-stage timing, a ctx with a communicator whose metric does not ride: the loop the riding path replaces, with device records — per pass
@@ -335,19 +349,23 @@ static int eval_each_plain_dev(gbp_ctx* c, int m, gbp_eval_out* out) {
   return GBP_OK;
 }
 
+}  // namespace
+
 // The driver of passes WITH the metric after every one of them (gbp_iterate_eval_each: i0 = steps2 = 0; gbp_ba_loop), blocking:
 // passes i0 .. i0 + n - 1 of the reference's loop (ba.cpp:1001-1028), WEAKEN_PRIORS in front of pass i iff weakens_before(i, steps2),
-// GBP_PROG, the metric.  On a graph that runs in the persistent kernel the passes are launches of at most kSeriesMax (persist_burst):
+// GBP_PROG, the metric.  On a graph that runs in the persistent kernel the passes are launches of at most kSeriesMax (PassWalk):
 // k_persist_flow applies WeakenPriorVertex itself in front of its later passes, only a weakening in front of a launch's first pass is
 // a launch of its own.  Everywhere else — and after a recovered time-out — each run of passes up to the next weakening carries the
 // metric in its sweeps (eval_each_ride; a ctx with a communicator: where metric_rides says so, gbp_transport.hpp), or is the loop it
 // replaces, two metrics in flight.
 // dev: out[] is memory of the ctx's GPU and nothing here blocks — launches of the persistent kernel queue behind the unvalidated ones
 // as gbp_iterate's do (persist_ready), the other paths wait for those first (settle) as every other kind of device work does.
-static int iterate_passes_eval(gbp_ctx* c, int n, unsigned i0, unsigned steps2, gbp_eval_out* out, bool dev = false) {
-  for (int done = 0; done < n;) {
-    const unsigned i = i0 + (unsigned)done;
-    if (weakens_before(i, steps2))
+// replay: persist_recover, for a SeriesDevice launch that timed out — the state is the one the launch started from, the weakening in
+// front of its first pass included; the ctx has left the persistent path and rides (it ran there: hoisted, one GPU, no communicator),
+// whatever the caller has set since; gbp_timing has counted the passes.
+int gbp::api::iterate_passes_eval(gbp_ctx* c, int n, unsigned i0, unsigned steps2, gbp_eval_out* out, bool dev, bool replay) {
+  for (PassWalk w(n, i0, steps2, /*front_done=*/replay); !w.done();) {
+    if (w.weakens())
       if (int rc = weaken_priors(c)) return rc;
     if (!dev)
       if (int rc = settle(c)) return rc;
@@ -355,34 +373,33 @@ static int iterate_passes_eval(gbp_ctx* c, int n, unsigned i0, unsigned steps2, 
     if (eval_blocks(c->n_tiles) == (c->n_tiles + 3) / 4)
       if (int rc = persist_ready(c, &fused)) return rc;
     if (fused) {
-      const int m = persist_burst(c, n - done, i, steps2, (int)kSeriesMax);
-      const int rc = dev ? series_burst_dev(c, m, i, steps2, out + done) : series_burst(c, m, i, steps2, out + done);
-      if (rc == GBP_OK) { done += m; continue; }
-      if (rc != kNotLaunched) return rc;
+      const Piece p = w.peek((int)kSeriesMax, persist_tagged(c));
+      BurstOutcome ran;
+      if (int rc = dev ? series_burst_dev(c, p, steps2, out + p.at, &ran) : series_burst(c, p, steps2, out + p.at, &ran)) return rc;
+      if (ran == BurstOutcome::Ran) { w.take(p); continue; }
     }
     if (dev)
       if (int rc = settle(c)) return rc;
-    const int m = weakening_free_run(n - done, i, steps2);
-    bool ride = !c->xch.comm && c->world == 1 && c->hoist && !c->tm.profile_stages && !stream_is_capturing(c);
+    const Piece p = w.next(kNoCap, /*weaken_inside=*/false);
+    bool ride = replay || (c->hoist && plain_single_gpu(c));
     if (c->xch.comm) {      // a ctx with a communicator: the decision and its record (gbp_comm_describe: "metric")
       ride = metric_rides(c->xch.comm->kind(), c->world, c->hoist, c->tm.profile_stages, stream_is_capturing(c), &c->xch.metric_reason);
       c->xch.metric_last = ride ? 1 : 2;
-      (ride ? c->xch.metric_riding : c->xch.metric_per_pass) += (uint64_t)m;
+      (ride ? c->xch.metric_riding : c->xch.metric_per_pass) += (uint64_t)p.m;
     }
     if (ride) {
-      if (int rc = eval_each_ride(c, m, out + done, dev)) return rc;
+      if (int rc = eval_each_ride(c, p.m, out + p.at, dev, /*timed=*/!replay)) return rc;
     } else if (dev) {
-      if (int rc = eval_each_plain_dev(c, m, out + done)) return rc;
+      if (int rc = eval_each_plain_dev(c, p.m, out + p.at)) return rc;
     } else {
-      int collected = done;
-      for (int k = done; k < done + m; ++k) {
+      int collected = p.at;
+      for (int k = 0; k < p.m; ++k) {
         if (int rc = iterate(c, 1)) return rc;
         if (int rc = eval_begin(c)) return rc;
         if (c->metric.pending == 2) { if (int rc = eval_end(c, out + collected)) return rc; ++collected; }
       }
-      while (collected < done + m) { if (int rc = eval_end(c, out + collected)) return rc; ++collected; }
+      while (collected < p.at + p.m) { if (int rc = eval_end(c, out + collected)) return rc; ++collected; }
     }
-    done += m;
   }
   return GBP_OK;
 }
@@ -400,8 +417,8 @@ static int iterate_eval_each(gbp_ctx* c, int n, gbp_eval_out* out) {
 }
 
 // n passes of the body of the reference's iteration loop (ba.cpp:1001-1028) from loop index iter0.  Without the metric (out == NULL)
-// not blocking, like gbp_iterate: one iterate_passes call per piece of at most kPersistChunk passes, the weakening in front of a piece
-// a launch of its own, every later one riding in a launch of the persistent kernel or in the belief update of the iteration before it.
+// not blocking, like gbp_iterate: ONE iterate_passes call — the weakening in front of a launch of the persistent kernel a launch of its
+// own, every other one riding in such a launch or in the belief update of the iteration before it.
 // A sharded ctx, per-stage timing and a caller's capture keep gbp_iterate's own paths: one call per run of passes up to the next weakening.
 static int ba_loop(gbp_ctx* c, int n, unsigned iter0, unsigned steps, gbp_eval_out* out) {
   if (!c || !c->uploaded) return fail(c, GBP_ERR_STATE, "gbp_ba_loop: upload first");
@@ -414,32 +431,11 @@ static int ba_loop(gbp_ctx* c, int n, unsigned iter0, unsigned steps, gbp_eval_o
     if (int rc = out_kind(c, "gbp_ba_loop", out, &dev)) return rc;
     return iterate_passes_eval(c, n, iter0, steps2, out, dev);
   }
-  const bool one_call = !c->xch.comm && c->world == 1 && !c->tm.profile_stages && !stream_is_capturing(c);
-  for (int done = 0; done < n;) {
-    const unsigned i = iter0 + (unsigned)done;
-    if (weakens_before(i, steps2))
+  if (plain_single_gpu(c)) return n ? iterate_passes(c, n, iter0, steps2) : GBP_OK;
+  for (PassWalk w(n, iter0, steps2); !w.done();) {
+    if (w.weakens())
       if (int rc = weaken_priors(c)) return rc;
-    const int m = one_call ? std::min(n - done, kPersistChunk) : weakening_free_run(n - done, i, steps2);
-    if (int rc = one_call ? iterate_passes(c, m, i, steps2) : iterate(c, m)) return rc;
-    done += m;
-  }
-  return GBP_OK;
-}
-
-}  // namespace
-
-// persist_recover: launch b (mode 3) is undone, the state is the one it started from — the weakening in front of its first pass
-// included, which was a launch of its own.  Its passes on the riding path into the records it was given: what iterate_passes_eval
-// queues for a ctx that is not on the persistent path (a ctx that was runs hoisted, on one GPU, without a communicator).
-int gbp::api::replay_series_dev(gbp_ctx* c, const gbp_ctx::Burst& b) {
-  gbp_eval_out* out = static_cast<gbp_eval_out*>(b.out);
-  for (int done = 0; done < b.n;) {
-    const unsigned i = b.w_first + (unsigned)done;
-    if (done > 0 && weakens_before(i, b.w_steps2))
-      if (int rc = weaken_priors(c)) return rc;
-    const int m = weakening_free_run(b.n - done, i, b.w_steps2);
-    if (int rc = eval_each_ride(c, m, out + done, true, false)) return rc;
-    done += m;
+    if (int rc = iterate(c, w.next(kNoCap, /*weaken_inside=*/false).m)) return rc;
   }
   return GBP_OK;
 }

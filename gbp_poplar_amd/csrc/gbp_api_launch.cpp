@@ -147,25 +147,27 @@ int iterate_plain(gbp_ctx* c, const SweepArgs& a, int n, bool ev) {
 // front of pass i0 (if any) already done by the caller: a weakening in front of a later pass rides in the belief update of the
 // iteration before it (enqueue_iteration: weaken_after), the runs between them replay from the hipGraph.
 int iterate_weaken_plain(gbp_ctx* c, const SweepArgs& a, int n, unsigned i0, unsigned steps2) {
-  for (int k = 0; k < n;) {
-    const int run = weakening_free_run(n - k, i0 + (unsigned)k, steps2);
-    const bool weaken_after = k + run < n;      // the run's last iteration takes the weakened priors in its belief update
-    if (int rc = iterate_plain(c, a, run - (weaken_after ? 1 : 0))) return rc;
+  for (PassWalk w(n, i0, steps2, /*front_done=*/true); !w.done();) {
+    const Piece p = w.next(kNoCap, /*weaken_inside=*/false);
+    const bool weaken_after = !w.done();      // the run's last iteration takes the weakened priors in its belief update
+    if (int rc = iterate_plain(c, a, p.m - (weaken_after ? 1 : 0))) return rc;
     if (weaken_after) {
       enqueue_iteration(c, a, false, true);
       HIPCHK(c, hipGetLastError());
     }
-    k += run;
   }
   return GBP_OK;
 }
 
 // The driver of passes WITHOUT the metric (gbp_iterate: steps2 = 0; gbp_ba_loop without the metric): passes i0 .. i0 + n - 1 of the
-// reference's loop on a single-GPU ctx, the weakening in front of pass i0 (if any) already done by the caller; not blocking.  Small
-// graphs run them inside the persistent kernel, in launches of at most kPersistChunk passes (a launch cannot be pre-empted) that apply
-// the weakenings in front of their later passes themselves; everything else — and the rest of the passes once the ctx has left the
-// persistent path — runs on the two-kernel path (iterate_weaken_plain).
+// reference's loop on a single-GPU ctx; not blocking.  Small graphs run them inside the persistent kernel, in launches of at most
+// kPersistChunk passes (a launch cannot be pre-empted) that apply the weakenings in front of their later passes themselves — only a
+// weakening in front of a launch's first pass is a launch of its own; everything else — and the rest of the passes once the ctx has
+// left the persistent path — runs on the two-kernel path (iterate_weaken_plain).
 int iterate_passes(gbp_ctx* c, int n, unsigned i0, unsigned steps2) {
+  PassWalk w(n, i0, steps2);
+  if (w.weakens())
+    if (int rc = weaken_priors(c)) return rc;
   bool persist = false;
   if (n >= 2)                          // a single iteration is as fast from two launches (measured)
     if (int rc = persist_ready(c, &persist)) return rc;
@@ -174,22 +176,21 @@ int iterate_passes(gbp_ctx* c, int n, unsigned i0, unsigned steps2) {
   const SweepArgs a = sweep_args(c);
   TimedSpan sp(c);
   if (int rc = sp.begin()) return rc;
-  int done = 0;
-  while (persist && done < n) {
-    const int m = persist_burst(c, n - done, i0 + (unsigned)done, steps2, kPersistChunk);
-    const int rc = launch_persist_burst(c, a, m, nullptr, 0, 0, i0 + (unsigned)done, steps2);
-    if (rc == kNotLaunched) break;
-    if (rc != GBP_OK) return rc;
-    done += m;
-    if (done < n) {
-      if (weakens_before(i0 + (unsigned)done, steps2))
-        if (int rc2 = weaken_priors(c)) return rc2;
-      if (int rc2 = persist_ready(c, &persist)) return rc2;
+  while (persist && !w.done()) {
+    const Piece p = w.peek(kPersistChunk, persist_tagged(c));
+    BurstOutcome ran;
+    if (int rc = launch_persist_burst(c, a, burst_of(BurstKind::Plain, p, steps2), nullptr, &ran)) return rc;
+    if (ran != BurstOutcome::Ran) break;
+    w.take(p);
+    if (!w.done()) {
+      if (w.weakens())
+        if (int rc = weaken_priors(c)) return rc;
+      if (int rc = persist_ready(c, &persist)) return rc;
     }
   }
-  if (done < n) {       // (settle: free unless the ctx has just left the persistent path with launches in flight)
+  if (!w.done()) {      // (settle: free unless the ctx has just left the persistent path with launches in flight)
     if (int rc = settle(c)) return rc;
-    if (int rc = iterate_weaken_plain(c, a, n - done, i0 + (unsigned)done, steps2)) return rc;
+    if (int rc = iterate_weaken_plain(c, a, w.left(), w.index(), steps2)) return rc;
   }
   HIPCHK(c, hipGetLastError());
   return sp.commit((uint64_t)n);

@@ -44,7 +44,7 @@ int persist_reset(gbp_ctx* c) {
   c->persist.log.clear();
   HIPCHK(c, hipMemsetAsync(c->persist.psync.p, 0, kPersistSyncWords * sizeof(unsigned), c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  *static_cast<volatile unsigned*>(c->persist.status.host) = 0u;
+  persist_status_word(c) = 0u;
   c->persist.epoch_base = 0;
   c->persist.ok = c->persist.eligible;
   return GBP_OK;
@@ -173,7 +173,7 @@ int settle(gbp_ctx* c) {
 // arena holds the state the first failed launch started from.
 static int persist_recover(gbp_ctx* c) {
   HIPCHK(c, hipStreamSynchronize(c->stream));        // the failed launch and the no-op launches behind it have ended
-  const unsigned first = *static_cast<volatile unsigned*>(c->persist.status.host);
+  const unsigned first = persist_failed_seq(c);
   std::vector<gbp_ctx::Burst> redo;
   for (const gbp_ctx::Burst& b : c->persist.log)
     if (b.seq >= first) redo.push_back(b);
@@ -183,24 +183,27 @@ static int persist_recover(gbp_ctx* c) {
   HIPCHK(c, hipMemsetAsync(c->persist.psync.p, 0, kPersistSyncWords * sizeof(unsigned), c->stream));
   HIPCHK(c, hipMemsetAsync(c->arr.health.p, 0, 32, c->stream));       // both areas are zero between evaluations
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  *static_cast<volatile unsigned*>(c->persist.status.host) = 0u;
+  persist_status_word(c) = 0u;
   c->persist.epoch_base = 0;
   c->persist.ok = false;                              // until the next gbp_upload
-  c->persist.recoveries += 1;
+  // What the replay of a launch is.  The state is the one the launch started from, the weakening in front of its first pass
+  // included (a launch of its own): front_done.
   const SweepArgs a = sweep_args(c);
   long iters = 0;
-  for (const gbp_ctx::Burst& b : redo) {
-    if (b.mode == 2) continue;                        // gbp_iterate_eval_each is blocking: it replays its own burst
-    if (b.mode == 3) {                                // ... with device records it is not: passes, weakenings and metrics replayed here
-      if (int rc = replay_series_dev(c, b)) return rc;
-      iters += b.n;
-      continue;
+  for (const Burst& b : redo) {
+    switch (b.kind) {
+      case BurstKind::SeriesHost: continue;           // nothing: the blocking caller replays its own burst (series_burst: TimedOut)
+      case BurstKind::Plain:                          // its passes, the weakenings riding in the belief updates before them
+      case BurstKind::MetricAtEnd:                    // the same, and k_means + k_eval into its result area
+        if (int rc = iterate_weaken_plain(c, a, b.n, b.first, b.steps2)) return rc;
+        if (b.kind == BurstKind::MetricAtEnd)
+          if (int rc = eval_enqueue(c, b.area)) return rc;
+        break;
+      case BurstKind::SeriesDevice:                   // its passes through the driver that launched it, the metric riding into the caller's records
+        if (int rc = iterate_passes_eval(c, b.n, b.first, b.steps2, static_cast<gbp_eval_out*>(b.out), /*dev=*/true, /*replay=*/true)) return rc;
+        break;
     }
-    if (b.w_steps2) { if (int rc = iterate_weaken_plain(c, a, b.n, b.w_first, b.w_steps2)) return rc; }
-    else if (int rc = iterate_plain(c, a, b.n)) return rc;
     iters += b.n;
-    if (b.mode == 1)
-      if (int rc = eval_enqueue(c, b.area)) return rc;
   }
   // the replay has completed when this returns: the callers (gbp_sync, gbp_read*, gbp_new_keyframe, gbp_set_stream, the debug
   // accessors) go on to blocking copies on the NULL stream, which a non-blocking stream does not order against
@@ -215,7 +218,7 @@ static int persist_recover(gbp_ctx* c) {
 // The stream has been synchronised, or an event recorded behind launch `upto` has completed (0 = everything queued has).
 int persist_check(gbp_ctx* c, unsigned upto) {
   if (!c->persist.status.host || c->persist.log.empty()) return GBP_OK;
-  if (*static_cast<volatile unsigned*>(c->persist.status.host) != 0u) return persist_recover(c);
+  if (persist_failed_seq(c) != 0u) return persist_recover(c);
   if (upto == 0) c->persist.log.clear();
   else
     while (!c->persist.log.empty() && c->persist.log.front().seq <= upto) c->persist.log.erase(c->persist.log.begin());
@@ -233,24 +236,25 @@ bool stream_is_capturing(gbp_ctx* c) {
 // barrier targets are launch arguments computed by the host, a replayed graph would wait for arrivals long past.
 int persist_ready(gbp_ctx* c, bool* yes) {
   *yes = false;
-  if (!c->persist.ok || c->xch.comm || c->world != 1 || c->tm.profile_stages) return GBP_OK;
-  if (stream_is_capturing(c)) return GBP_OK;
+  if (!c->persist.ok || !plain_single_gpu(c)) return GBP_OK;
   if (c->persist.log.size() >= kPersistLogMax)
     if (int rc = settle(c)) return rc;
   *yes = c->persist.ok;
   return GBP_OK;
 }
 
-// n iterations inside ONE k_persist launch (+ the metric phases when `ev` is given).  The barrier counter keeps counting
-// across the launches of a ctx (no memset per launch): the host tracks how many arrivals it has seen.
-int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, int n, const PersistEval* ev, int mode, int area,
-                         uint32_t w_first, uint32_t w_steps2, void* out_dev) {
+// b.n iterations inside ONE k_persist launch (+ the metric phases when `ev` is given).  The barrier counter keeps counting
+// across the launches of a ctx (no memset per launch): the host tracks how many arrivals it has seen.  *outcome = Ran, or NotRun (with
+// GBP_OK): the runtime refused the launch and the ctx has left the persistent path.
+int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, const Burst& b, const PersistEval* ev, BurstOutcome* outcome) {
+  *outcome = BurstOutcome::NotRun;
+  const int n = b.n;
   PersistArgs A{};
   A.s = a;
   A.b = belief_args(c);
   A.b.roll = 1;
-  if (w_steps2) {      // WEAKEN_PRIORS inside the launch (gbp_ba_loop)
-    A.w_first = w_first; A.w_steps2 = w_steps2;
+  if (b.steps2) {      // WEAKEN_PRIORS inside the launch (gbp_ba_loop)
+    A.w_first = b.first; A.w_steps2 = b.steps2;
     weaken_args(c, A.b);
   }
   A.n_tiles = c->n_tiles;
@@ -260,7 +264,7 @@ int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, int n, const PersistEva
   A.epoch_base = c->persist.epoch_base;
   A.seq = c->persist.seq + 1;
   if (ev) A.ev = *ev;
-  const bool flow = c->persist.use_flow && c->persist.flow.lmsg != nullptr;      // hand-offs through tagged records (k_persist_flow)
+  const bool flow = persist_tagged(c);      // hand-offs through tagged records (k_persist_flow)
   if (flow) {
     A.f = c->persist.flow;
     A.f.tag0 = (A.seq & 0x7ffffu) << 13;      // + iteration (<= kPersistChunk) + 1: never the tag of a record an earlier launch left behind
@@ -287,7 +291,7 @@ int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, int n, const PersistEva
       c->warn = std::string("warning: the cooperative launch of the persistent kernel was refused (") + hipGetErrorString(le) +
                 "); iterations run on the two-kernel path";
       c->err = c->warn;
-      return kNotLaunched;
+      return GBP_OK;
     }
     HIPCHK(c, hipEventRecord(e, c->stream));
     g_persist_last_ctx[dev & 15] = c;
@@ -298,8 +302,9 @@ int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, int n, const PersistEva
   // tagged records none, and ONE barrier at the end of a launch that carries the metric
   c->persist.epoch_base += flow ? (ev ? nb : 0u) : nb * (unsigned)(2 * n - 1 + (ev ? 1 : 0));
   c->persist.seq += 1;
-  c->persist.log.push_back(gbp_ctx::Burst{c->persist.seq, n, mode, area, w_first, w_steps2, out_dev});
-  c->persist.launches += 1;
+  c->persist.log.push_back(b);
+  c->persist.log.back().seq = c->persist.seq;
+  *outcome = BurstOutcome::Ran;
   return GBP_OK;
 }
 

@@ -6,9 +6,11 @@
 //   gbp_api_launch.cpp   what a program launches: LINEARISE, GBP_PROG (hipGraph replay / direct launches), WEAKEN_PRIORS, the
 //                        split-phase iteration, and iterate_passes — the driver of passes without the metric (gbp_iterate,
 //                        gbp_ba_loop without the metric)                                       (ba.cpp:863-865,890-905)
-//   gbp_api_persist.cpp  the persistent kernel's launches: co-residency probe, snapshot, log of unvalidated launches, recovery
+//   gbp_api_persist.cpp  the persistent kernel's launches: co-residency probe, snapshot, log of unvalidated launches (one typed
+//                        Burst each), recovery — the replay of every BurstKind
 //   gbp_api_eval.cpp     the metric on the device (util.cpp:74-144): gbp_eval*, gbp_iterate_eval, and iterate_passes_eval — the
 //                        driver of passes with the metric after each (gbp_iterate_eval_each, gbp_ba_loop)  (ba.cpp:1001-1053)
+//   gbp_loop_plan.hpp    where those drivers cut the reference's loop into pieces and where its weakenings fall (PassWalk): pure, no HIP
 //   gbp_api_comm.cpp     sharded ctx: communicator glue, the sharded iteration, gbp_eval_global  (ba.cpp:414-417,617-649)
 //   gbp_api_devio.cpp    WRITE, READ, READ_PRIORS, NEW_KEYFRAME for callers whose arrays live on the ctx's GPU (device pointers)
 //   gbp_api_debug.cpp    the test hooks of include/gbp_mi355x_debug.h (test-hooks builds only)
@@ -27,6 +29,7 @@
 #include "gbp_export.hpp"
 #include "gbp_kernels.h"
 #include "gbp_layout.hpp"
+#include "gbp_loop_plan.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -125,10 +128,21 @@ struct gbp_ctx {
     hipEvent_t ev[2] = {nullptr, nullptr};
   } metric;
   // ---- the persistent kernel (gbp_api_persist.cpp) ----
-  // mode 0 = gbp_iterate, 1 = gbp_iterate_eval (metric in eval area `area`), 2 = eval_each / gbp_ba_loop with metrics (blocking),
-  // 3 = the same with the results going to the caller's device records `out` (not blocking: the recovery replays passes and metrics);
-  // w_steps2 != 0: the launch weakens priors itself (gbp_ba_loop: loop index of its first iteration, twice the --steps)
-  struct Burst { unsigned seq; int n; int mode; int area; unsigned w_first = 0, w_steps2 = 0; void* out = nullptr; };
+  enum class BurstKind {
+    Plain,         // gbp_iterate, gbp_ba_loop without the metric
+    MetricAtEnd,   // gbp_iterate_eval (metric in eval area `area`)
+    SeriesHost,    // eval_each / gbp_ba_loop with metrics (blocking)
+    SeriesDevice,  // the same with the results going to the caller's device records `out` (not blocking: the recovery replays passes and metrics)
+  };
+  // One launch of the persistent kernel: what launch_persist_burst is asked for, and — with seq filled in — its entry in the log
+  struct Burst {
+    BurstKind kind = BurstKind::Plain;
+    int n = 0;                           // passes
+    int area = 0;                        // the metric's result / health area (every kind but Plain)
+    unsigned first = 0, steps2 = 0;      // steps2 != 0: the launch weakens priors itself (gbp_ba_loop: loop index of its first pass, twice the --steps)
+    void* out = nullptr;                 // SeriesDevice: the caller's records
+    unsigned seq = 0;                    // its number among the launches of the ctx (launch_persist_burst)
+  };
   struct Persist {
     // k_persist (small graphs): n iterations in one launch
     bool ok = false;                     // bursts run inside k_persist (eligible, co-resident, no time-out since the last upload)
@@ -146,11 +160,9 @@ struct gbp_ctx {
     unsigned seq = 0;
     DevBuf psnap;                        // snapshot arena
     gbp::CopySegs snap_save{}, snap_restore{};
-    uint64_t recoveries = 0;
     double probe_ms = 0;                 // gbp_create: what the co-residency probe took (the first kernel launch of the process: code-object load included)
     DevBuf psync;                        // barrier words
-    MappedBuf status;                    // pinned + device-mapped: raised by the kernel if a barrier gave up
-    uint64_t launches = 0;
+    MappedBuf status;                    // pinned + device-mapped: raised by the kernel if a barrier gave up (read: persist_failed_seq)
     unsigned epoch_base = 0;             // arrivals the barrier counter has seen so far (it keeps counting across launches)
     MappedBuf series;                    // gbp_iterate_eval_each: [kSeriesMax metrics][1 + workgroups] slots, same kind of memory (read by gbp_api_eval.cpp)
   } persist;
@@ -195,6 +207,8 @@ struct gbp_ctx {
 
 namespace gbp {
 namespace api {
+using Burst = gbp_ctx::Burst;
+using BurstKind = gbp_ctx::BurstKind;
 
 // ---- errors -----------------------------------------------------------------------------------------------------------------
 // (fail(), guarded() and the GBP_EXPORT macros: gbp_export.hpp)
@@ -294,34 +308,33 @@ SweepArgs sweep_args(gbp_ctx* c, bool sweeps = true);      // sweeps = false: fo
 BeliefArgs belief_args(gbp_ctx* c);
 void weaken_args(gbp_ctx* c, BeliefArgs& b);                  // the prior arrays WeakenPriorVertex writes (b.weaken is the caller's)
 void drop_graph(gbp_ctx* c);
-// The reference's loop (ba.cpp:1001-1008) runs WEAKEN_PRIORS in front of pass i iff (i + 1) % 2 == 0 and i < 2 * steps (= steps2).
-inline bool weakens_before(unsigned i, unsigned steps2) { return ((i + 1u) % 2u == 0u) && i < steps2; }
-// passes from loop index i up to (not including) the next weakening after it, at most n
-inline int weakening_free_run(int n, unsigned i, unsigned steps2) {
-  int m = 1;
-  while (m < n && !weakens_before(i + (unsigned)m, steps2)) ++m;
-  return m;
-}
-// passes from loop index i that ONE launch of the persistent kernel takes, at most cap of the n left: a weakening inside the launch
-// needs the tagged-record kernel; the barrier kernel (test-hooks build) takes the passes up to the next weakening
-inline int persist_burst(const gbp_ctx* c, int n, unsigned i, unsigned steps2, int cap) {
-  const int m = c->persist.use_flow && c->persist.flow.lmsg != nullptr ? n : weakening_free_run(n, i, steps2);
-  return m < cap ? m : cap;
-}
+// (where the reference's loop weakens and how the drivers below cut it into pieces: gbp_loop_plan.hpp)
 // camera beliefs from stored partials (single GPU: the local sums; sharded: recv_dev) + landmark beliefs re-summed.  roll = true
 // at the end of an iteration, false for prior-only refreshes (WEAKEN_PRIORS, NEW_KEYFRAME, LINEARISE).
 int refresh_beliefs_from_partials(gbp_ctx* c, bool roll, bool do_lmk = true, bool weaken = false);
 void enqueue_iteration(gbp_ctx* c, const SweepArgs& a, bool ev = false, bool weaken_after = false);
 void enqueue_cam_partials(gbp_ctx* c, float* dst, hipStream_t s = nullptr);
 int iterate_plain(gbp_ctx* c, const SweepArgs& a, int n, bool ev = false);                      // hipGraph replays + remainder
-int iterate_weaken_plain(gbp_ctx* c, const SweepArgs& a, int n, unsigned i0, unsigned steps2);  // the same with the loop's weakenings riding
-int iterate_passes(gbp_ctx* c, int n, unsigned i0, unsigned steps2);  // the driver of passes without the metric (single GPU)
+int iterate_weaken_plain(gbp_ctx* c, const SweepArgs& a, int n, unsigned i0, unsigned steps2);  // the same with the loop's weakenings riding (the one in front of pass i0: the caller's)
+int iterate_passes(gbp_ctx* c, int n, unsigned i0, unsigned steps2);  // the driver of passes without the metric (single GPU), weakenings included
 int iterate(gbp_ctx* c, int n);                              // GBP_PROG x n: persistent kernel / hipGraph / sharded
 int weaken_priors(gbp_ctx* c);                               // WEAKEN_PRIORS
 
 // ---- gbp_api_persist.cpp ----------------------------------------------------------------------------------------------------
 constexpr int kPersistChunk = 4096;      // iterations per k_persist launch (a launch cannot be pre-empted: ~60 ms at 15 us each)
-constexpr int kNotLaunched = 1;          // launch_persist_burst: nothing ran, the ctx has left the persistent path
+// What became of a burst, beside the status code of the call (GBP_OK with every one of them)
+enum class BurstOutcome {
+  Ran,
+  NotRun,      // launch_persist_burst: nothing ran, the ctx has left the persistent path
+  TimedOut,    // series_burst (blocking): the launch ran, timed out, and the state was restored to the start of the burst
+};
+// the status word the kernel raises (host-mapped; valid once persist_setup has allocated it): the number of the first launch of this
+// ctx that gave up at a wait, 0 while none has
+inline volatile unsigned& persist_status_word(const gbp_ctx* c) { return *static_cast<volatile unsigned*>(c->persist.status.host); }
+inline unsigned persist_failed_seq(const gbp_ctx* c) { return persist_status_word(c); }
+// do this ctx's bursts hand off through tagged records (k_persist_flow, which also weakens in front of its later passes: PassWalk's
+// weaken_inside)?  Not the barrier kernel of the test-hooks build.
+inline bool persist_tagged(const gbp_ctx* c) { return c->persist.use_flow && c->persist.flow.lmsg != nullptr; }
 int persist_setup(gbp_ctx* c, const gbp_params* prm, bool sharded);   // gbp_create: probe, snapshot arena, tagged shadows (or none: not eligible)
 void persist_forget(gbp_ctx* c);                            // gbp_destroy: its launches have ended, nobody waits for this ctx again
 int persist_reset(gbp_ctx* c);                              // gbp_upload: a fresh start for the persistent path
@@ -330,16 +343,23 @@ int persist_reset(gbp_ctx* c);                              // gbp_upload: a fre
 int settle(gbp_ctx* c);
 int persist_check(gbp_ctx* c, unsigned upto);               // the stream has been synchronised / an event behind launch `upto` completed
 bool stream_is_capturing(gbp_ctx* c);
+// One GPU, no communicator, no per-stage profiling, the ctx's stream not being captured right now (asked on every call): the ctx whose
+// passes the drivers of this library plan themselves (iterate_passes, the riding metric, the persistent kernel)
+inline bool plain_single_gpu(gbp_ctx* c) { return !c->xch.comm && c->world == 1 && !c->tm.profile_stages && !stream_is_capturing(c); }
 int persist_ready(gbp_ctx* c, bool* yes);                   // may the next burst run inside the persistent kernel?
-int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, int n, const PersistEval* ev, int mode, int area,
-                         uint32_t w_first = 0, uint32_t w_steps2 = 0, void* out_dev = nullptr);
+// the launch that runs piece p of a loop with weakenings under steps2 (area and out: the caller's)
+inline Burst burst_of(BurstKind kind, const Piece& p, unsigned steps2) { Burst b; b.kind = kind; b.n = p.m; b.first = p.first; b.steps2 = steps2; return b; }
+// b.n passes in ONE launch of the persistent kernel (+ the metric phases `ev`, for every kind but Plain); logged as b with its seq
+int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, const gbp_ctx::Burst& b, const PersistEval* ev, BurstOutcome* outcome);
 
 // ---- gbp_api_eval.cpp -------------------------------------------------------------------------------------------------------
 // k_means + k_eval of the current beliefs with the health words of area `area`, into that result area (host-mapped, its event recorded
 // behind them) or into dev_slots (device memory, [1025]: no event)
 int eval_enqueue(gbp_ctx* c, int area, DeviceEval* dev_slots = nullptr);
-// recovery of a timed-out launch of mode 3 (persist_recover): its passes on the two-kernel path, the metric riding, into the same device records
-int replay_series_dev(gbp_ctx* c, const gbp_ctx::Burst& b);
+// The driver of passes with the metric after each (gbp_iterate_eval_each, gbp_ba_loop): passes i0 .. i0 + n - 1 of the reference's loop,
+// out[k] = the metric after pass i0 + k.  dev: out is memory of the ctx's GPU, nothing blocks.  replay: the recovery of a timed-out
+// SeriesDevice launch (persist_recover) runs its passes through the same driver, off the persistent path, into the same records.
+int iterate_passes_eval(gbp_ctx* c, int n, unsigned i0, unsigned steps2, gbp_eval_out* out, bool dev = false, bool replay = false);
 int eval_begin(gbp_ctx* c);
 int eval_end(gbp_ctx* c, gbp_eval_out* o);
 int eval(gbp_ctx* c, gbp_eval_out* o);
