@@ -61,6 +61,12 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
     lmk_i = a.lmk_idx[p];
     tile_regs_load(a, tile, lane, stage, [&](uint32_t i4) { return a.lmsg[i4]; }, fac, cm, lm);
   }
+  // A pad position names camera pos_cam (its row's, or camera 0 in a row of pads only) and landmark 0 without being a factor of either:
+  // no owner waits for it, so an owner is not held back until the pad lane has read a record.  A landmark group without a factor (waits
+  // for nothing) or a camera ahead of an all-pad tile then overwrites the half the pad lane polls, and the lane would wait for a tag
+  // that is gone until the time-out.  A pad is never active: factor_update and the metric read none of these records for it, so a pad
+  // lane takes whatever its loads return and waits for nothing.
+  const bool pad_lane = has_tile && ((uint32_t)__float_as_int(lm[13]) & kFlagPad) != 0u;
   float K[9];
   GBP_UNROLL
   for (int i = 0; i < 9; ++i) K[i] = a.K[i];
@@ -166,12 +172,12 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
   auto metric_of = [&](uint32_t kk, int packed, float4 (&c)[4], float4 l0) -> bool {
     const unsigned tg = F.tag0 + kk + 1u;
     const uint32_t ec = ((kk & 1u) * nC + cam_i) * 4u, el = (kk & 1u) * nL + lmk_i;
-    if (!__all(flow_is(c[0], tg) && flow_is(c[1], tg) && flow_is(c[2], tg) && flow_is(c[3], tg) && flow_is(l0, tg))) {
+    if (!__all(pad_lane || (flow_is(c[0], tg) && flow_is(c[1], tg) && flow_is(c[2], tg) && flow_is(c[3], tg) && flow_is(l0, tg)))) {
       if (!flow_wait([&]() {
             GBP_UNROLL
             for (int g = 0; g < 4; ++g) c[g] = S_emc.ld4(ec + (uint32_t)g);
             l0 = S_eml.ld4(el);
-            return flow_is(c[0], tg) && flow_is(c[1], tg) && flow_is(c[2], tg) && flow_is(c[3], tg) && flow_is(l0, tg);
+            return pad_lane || (flow_is(c[0], tg) && flow_is(c[1], tg) && flow_is(c[2], tg) && flow_is(c[3], tg) && flow_is(l0, tg));
           }, A.sync, A.status, A.seq)) return false;
     }
     const float R[9] = {c[0].x, c[0].y, c[0].z, c[1].x, c[1].y, c[1].z, c[2].x, c[2].y, c[2].z};
@@ -202,7 +208,7 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
       float4 c4[kFlowCam4], m4[2], q7[kFlowClin4], l5[kFlowLmk4], u4;
       const uint32_t cb0 = (h_in * nC + cam_i), lb0 = (h_in * nL + lmk_i);
       // probe: the records the two owners store last (the camera's belief behind its mean and CAM_LIN, the landmark's squared mean changes)
-      if (!flow_wait([&]() { return flow_is(S_camb.ld4(cb0 * kFlowCam4), t_in) && flow_is(S_lmkb.ld4(lb0 * kFlowLmk4 + 4u), t_in); },
+      if (!flow_wait([&]() { return pad_lane || (flow_is(S_camb.ld4(cb0 * kFlowCam4), t_in) && flow_is(S_lmkb.ld4(lb0 * kFlowLmk4 + 4u), t_in)); },
                      A.sync, A.status, A.seq)) return;
       if (!flow_wait([&]() {
             bool ok = true;
@@ -221,7 +227,7 @@ __global__ __launch_bounds__(256) void k_persist_flow(const PersistArgs A) {
             for (int g = 0; g < (int)kFlowClin4; ++g) ok = ok && flow_is(q7[g], t_in);
             GBP_UNROLL
             for (int g = 0; g < (int)kFlowLmk4; ++g) ok = ok && flow_is(l5[g], t_in);
-            return ok && flow_is(u4, t_in);
+            return pad_lane || (ok && flow_is(u4, t_in));
           }, A.sync, A.status, A.seq)) return;
       float cb[44], lb[16], mu[12];
       {

@@ -1585,6 +1585,58 @@ def test_health_counters_with_metric_calls_of_every_kind_interleaved(flow, oracl
     assert eb[-1]["n_nonfinite"] > 0 and eb[-1]["n_nonpd"] > 0
 
 
+def test_pad_lanes_do_not_wait_for_a_factorless_first_landmark_group():
+    """Found by the seeded slice of the soak (tests/test_gpu_fuzz.py, SLAM seed 60099): a pad position names landmark 0 without being
+    one of its factors.  Where landmarks 0 .. 15 — one wave's group in k_persist_flow — have no factor at all, their owner waits for
+    nobody, runs iterations ahead and overwrites the half of its tagged records a pad lane still polled for the older tag: the tile wave
+    waited 1.5 s for a tag that was gone, the launch timed out and the ctx left the persistent path (launch 7 and launch 3 of two runs of
+    that seed: a race the tile usually won).  Pad lanes wait for nothing now.  Here: such a graph, 120 launches of every kind on the
+    tagged-record kernel, none may time out, and the state equals the two-kernel path's bit for bit."""
+    from gbp_poplar_amd import _cabi, driver, hostlib
+    from gbp_poplar_amd.engine import GbpEngine
+    from tests import fuzz_support as fz
+    rng = np.random.default_rng(60099)
+    bal = fz.random_problem(rng, size="tiny")
+    bal["lmk_id"] = bal["lmk_id"] + np.uint32(16)          # landmarks 0 .. 15: no factor
+    bal["n_lmks"] += 16
+    bal["points"] = np.concatenate([rng.uniform(-1, 1, 48), bal["points"]])
+    deg = np.bincount(bal["cam_id"], minlength=bal["n_cams"])
+    assert (deg % 16 != 0).any()                           # pad positions exist
+    opts = driver.Options()
+    opts.undamped_start = 2
+    K, state, _ = driver.build_inputs(bal, opts, hostlib)
+    steps = int(opts.steps)
+    kw = dict(dmu_threshold=0.02, min_linear_iters=3, num_undamped_iters=2)
+    a = GbpEngine(bal["cam_id"], bal["lmk_id"], bal["n_cams"], bal["n_lmks"], K, hooks=True, params=_cabi.GbpParams.defaults(persistent=1, **kw))
+    b = GbpEngine(bal["cam_id"], bal["lmk_id"], bal["n_cams"], bal["n_lmks"], K, hooks=True, params=_cabi.GbpParams.defaults(persistent=-1, **kw))
+    assert a.graph_state() == 2
+    for e in (a, b):
+        e.upload(state)
+        e.linearise()
+    it, evs = 0, []
+    for launch in range(120):
+        n = 2 + launch % 3
+        if launch % 3 == 0:
+            a.iterate(n) if it >= 2 * steps else a.ba_loop(n, it, steps, metrics=False)
+        elif launch % 3 == 1:
+            evs = a.ba_loop(n, it, steps)
+        else:
+            a.ba_loop(n, it, steps, metrics=False)
+        for i in range(it, it + n):
+            if (i + 1) % 2 == 0 and i < 2 * steps:
+                b.weaken_priors()
+            b.iterate(1)
+        it += n
+        if launch % 3 == 1:
+            eb = b.eval()
+            assert all(evs[-1][k] == eb[k] or (evs[-1][k] != evs[-1][k] and eb[k] != eb[k]) for k in eb), (launch, evs[-1], eb)
+    a.sync()
+    assert a.graph_state() == 2 and "timed out" not in a.last_error(), a.last_error()
+    sa, sb = fz.snapshot(a), fz.snapshot(b)
+    for k in sb:
+        assert np.array_equal(sa[k], sb[k], equal_nan=True), k
+
+
 # ---- BASELINE.json's full size (S1: 1 000 cams x 100 000 lmks x 1 000 000 factors) ---------------------------------
 
 @pytest.fixture(scope="module")
