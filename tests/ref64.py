@@ -268,3 +268,104 @@ def metric_terms(beliefs, bal, K, measurements, active, rotation_transposed=Fals
         sq = np.sum(r * r, axis=1)
         norm[act], half[act] = np.sqrt(sq), 0.5 * sq
     return norm, half
+
+
+# ---- the variable side: beliefs as sums, the health predicates (tests/test_wide_state_cpu.py, tests/test_gpu_wide_state.py) ------
+def lower_mirrored(lam, width):
+    """(N, width, width) float64 matrices from their LOWER triangles alone, mirrored: how inv6x6 reads a camera's Lambda (the upper
+    triangle of a camera message is not stored by the engines, and that of a camera belief is not read by the sweeps)"""
+    A = _f64(lam, -1, width, width)
+    return np.tril(A) + np.swapaxes(np.tril(A, -1), 1, 2)
+
+
+def belief_sums(bal, priors, messages, active):
+    """Every variable's belief as the plain float64 sum of its prior and the messages of its ACTIVE factors, and beside each sum the sum
+    of the absolute values of the same terms (the scale a relative error is measured on).  priors: the four *_priors_* tensors as
+    read_priors() returns them; messages: cam_eta [6E], cam_lambda [36E], lmk_eta [3E], lmk_lambda [9E] in file order.  Of a camera's
+    Lambdas (prior and messages) only the lower triangle is read and mirrored (lower_mirrored): compare the sum with the lower triangle
+    of a camera belief.
+    Returns {"cam_eta": (sum (C, 6), scale (C, 6)), "cam_lambda": ((C, 36), (C, 36)), "lmk_eta": ..., "lmk_lambda": ...}."""
+    C, L = int(bal["n_cams"]), int(bal["n_lmks"])
+    cam_id, lmk_id = np.asarray(bal["cam_id"], np.int64), np.asarray(bal["lmk_id"], np.int64)
+    E = cam_id.size
+    act = np.asarray(active).reshape(-1) == 1
+    cl = lower_mirrored(messages["cam_lambda"], 6)
+    terms = {"cam_eta": (cam_id, C, _f64(priors["cam_priors_eta"], C, 6), _f64(messages["cam_eta"], E, 6)),
+             "cam_lambda": (cam_id, C, lower_mirrored(priors["cam_priors_lambda"], 6).reshape(C, 36), cl.reshape(E, 36)),
+             "lmk_eta": (lmk_id, L, _f64(priors["lmk_priors_eta"], L, 3), _f64(messages["lmk_eta"], E, 3)),
+             "lmk_lambda": (lmk_id, L, _f64(priors["lmk_priors_lambda"], L, 9), _f64(messages["lmk_lambda"], E, 9))}
+    out = {}
+    for k, (ids, n, prior, msg) in terms.items():
+        s, a = prior.copy(), np.abs(prior)
+        np.add.at(s, ids[act], msg[act])
+        np.add.at(a, ids[act], np.abs(msg[act]))
+        out[k] = (s, a)
+    return out
+
+
+def sum_error(got, want, scale):
+    """per variable: max |got - want| / max scale (0 where a variable has no term at all and got is 0 too)"""
+    want, scale = np.asarray(want, np.float64), np.asarray(scale, np.float64)
+    d = np.max(np.abs(_f64(got, *want.shape) - want), axis=1)
+    den = np.max(scale, axis=1)
+    return np.where(den > 0, d / np.where(den > 0, den, 1.0), np.where(d == 0, 0.0, np.inf))
+
+
+def ldl_pivots(lambda_f32, width):
+    """The un-pivoted LDL^T pivots of float32 matrices (N x width x width, any shape that holds them), computed in float64 from the
+    LOWER triangle alone, as inv6x6 reads it (D(j,j) = A(j,j) - sum_k L(j,k)^2 D(k,k); L(i,j) = (A(i,j) - sum_k L(i,k) L(j,k) D(k,k)) /
+    D(j,j), i > j).  Returns (pivots (N, width), scales (N, width)): a scale is |A(j,j)| + sum_k |L(j,k)^2 D(k,k)|, what a pivot's
+    distance from zero is relative to."""
+    A = _f64(lambda_f32, -1, width, width)
+    N = A.shape[0]
+    Lm, D, S = np.zeros((N, width, width)), np.zeros((N, width)), np.zeros((N, width))
+    with np.errstate(all="ignore"):
+        for j in range(width):
+            d, s = A[:, j, j].copy(), np.abs(A[:, j, j])
+            for k in range(j):
+                t = Lm[:, j, k] * Lm[:, j, k] * D[:, k]
+                d -= t
+                s += np.abs(t)
+            D[:, j], S[:, j] = d, s
+            for i in range(j + 1, width):
+                v = A[:, i, j].copy()
+                for k in range(j):
+                    v -= Lm[:, i, k] * Lm[:, j, k] * D[:, k]
+                Lm[:, i, j] = v / d
+    return D, S
+
+
+def positive_definite(lambda_f32, width):
+    """per matrix: every LDL^T pivot > 0 (a NaN pivot is not)"""
+    with np.errstate(invalid="ignore"):
+        return np.all(ldl_pivots(lambda_f32, width)[0] > 0.0, axis=1)
+
+
+def pivot_solve(A, b):
+    """x of A x = b by Gaussian elimination with partial pivoting in float64, written out (numpy's solve() refuses a singular matrix and
+    leaves open what it does with a non-finite one): the pivot of column k is the first row of the largest |entry| among rows k.. (a NaN
+    never compares larger), then plain elimination and back substitution.  Whatever is non-finite stays in the arithmetic."""
+    M = np.concatenate([np.array(A, np.float64), np.array(b, np.float64)[:, None]], axis=1)
+    n = M.shape[0]
+    with np.errstate(all="ignore"):
+        for k in range(n):
+            piv, best = k, abs(M[k, k])
+            for i in range(k + 1, n):
+                if abs(M[i, k]) > best:
+                    piv, best = i, abs(M[i, k])
+            if piv != k:
+                M[[k, piv]] = M[[piv, k]]
+            for i in range(k + 1, n):
+                f = M[i, k] / M[k, k]
+                M[i, k:] -= f * M[k, k:]
+        x = np.zeros(n)
+        for i in range(n - 1, -1, -1):
+            x[i] = (M[i, n] - M[i, i + 1:n] @ x[i + 1:]) / M[i, i]
+    return x
+
+
+def nonfinite_means(eta, lam, width):
+    """per variable: is the mean of the float32 belief, solved in float64 (pivot_solve) and rounded to float32, non-finite?"""
+    e, lm = _f64(eta, -1, width), _f64(lam, -1, width, width)
+    with np.errstate(all="ignore"):
+        return np.array([not np.all(np.isfinite(pivot_solve(lm[v], e[v]).astype(np.float32))) for v in range(e.shape[0])], bool)
