@@ -100,6 +100,7 @@ _DEBUG_SIGS = {
     "gbp_debug_sweep_variant": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "gbp_debug_persist_flow": (C.c_int, [C.c_void_p, C.c_int]),
     "gbp_debug_persist_verify": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
+    "gbp_debug_persist_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "gbp_debug_flow_torture": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.POINTER(C.c_uint64)]),
     "gbp_debug_persist_roles": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32]),
     "gbp_debug_layout_build": (C.c_int, [C.POINTER(cabi.GbpProblem), C.c_int, C.POINTER(cabi.GbpShard),

@@ -177,6 +177,25 @@ GBP_EXPORT(gbp_debug_persist_flow, c, (gbp_ctx* c, int on), (c, on)) {
   c->persist.use_flow = on != 0;
   return GBP_OK;
 }
+// The two host counters of the persistent kernel's protocol that keep counting for the life of a ctx: {persist.seq, persist.epoch_base}
+// (include/gbp_mi355x_debug.h).  set: the ctx is settled first (a launch in flight is validated or recovered), then set[0] becomes the
+// number of the last launch and set[1] the arrivals seen so far — on the host and in the device's arrival word psync[0], which are only
+// ever used as a pair.  The abort word and the status word are left alone.  get: the values after the call.
+GBP_EXPORT(gbp_debug_persist_counters, c, (gbp_ctx* c, const uint32_t* set, uint32_t* get), (c, set, get)) {
+  if (!c) return GBP_ERR_INVALID;
+  if (!c->persist.eligible) return fail(c, GBP_ERR_STATE, "gbp_debug_persist_counters: this ctx does not run in the persistent kernel");
+  if (stream_is_capturing(c)) return fail(c, GBP_ERR_INVALID, "gbp_debug_persist_counters: the stream is being captured");
+  if (set) {
+    if (int rc = settle(c)) return rc;
+    const unsigned arrivals = set[1];
+    HIPCHK(c, hipMemcpyAsync(c->persist.psync.p, &arrivals, sizeof(arrivals), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->persist.seq = set[0];
+    c->persist.epoch_base = arrivals;
+  }
+  if (get) { get[0] = c->persist.seq; get[1] = c->persist.epoch_base; }
+  return GBP_OK;
+}
 // Redundant records in the persistent kernel (k_persist_flow<EV, VER = true>): on != 0 — every tagged record of the following launches
 // is published twice (the second copy with its payload complemented) and a consumer accepts a record only when both copies carry the
 // same tag; a payload mismatch between the two is what a torn or stale 16-byte record would look like.  *mismatches (may be NULL)

@@ -24,7 +24,9 @@ int need_pos_edge(gbp_ctx* c) {
 // (settle: free when none is in flight).  A ctx that left the persistent path after a recovered time-out gets its fresh start.
 // Otherwise the reset gbp_upload makes (persist_reset: barrier words and persist.epoch_base back to zero, behind a stream
 // synchronisation) is not needed: the two are only ever used as a pair — the kernel waits for epoch_base + its own arrivals on a
-// counter that keeps counting across launches — the tags of the tagged records come from persist.seq, which no upload resets, and
+// counter that keeps counting across launches, wrap-safe — the tags of the tagged records come from persist.seq, which no upload
+// resets: it counts on for the life of the ctx, skipping the numbers that would make tag 0 or launch number 0, and the launch that
+// begins a new period of 2^19 - 1 tags clears the shadows first (gbp_persist_seq.hpp), so an upload has nothing to do for them — and
 // with the log empty and the status word zero there is nothing else persist_reset would change.  Leaving it out is what keeps
 // this call from blocking.
 int settle_for_upload(gbp_ctx* c) {

@@ -6,6 +6,7 @@
 // log of launches whose completion has not been validated yet, and the recovery (restore + replay on the two-kernel path) when a
 // wait inside a launch timed out.
 #include "gbp_ctx.hpp"
+#include "gbp_persist_seq.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -140,8 +141,10 @@ int persist_setup(gbp_ctx* c, const gbp_params* prm, bool sharded) {
   // gbp_debug_persist_verify: room for the redundant copy of every record + the mismatch counter (the product allocates neither)
   const int flow_rc = dev_alloc(c, c->persist.pflow, 2 * total * 16 + 64);
   c->persist.flow_total4 = (uint32_t)total;
+  c->persist.flow_bytes = 2 * total * 16;      // (not the mismatch counter behind them)
 #else
   const int flow_rc = dev_alloc(c, c->persist.pflow, total * 16);
+  c->persist.flow_bytes = total * 16;
 #endif
   if (flow_rc) return flow_rc;
   float4* q = static_cast<float4*>(c->persist.pflow.p);
@@ -176,7 +179,7 @@ static int persist_recover(gbp_ctx* c) {
   const unsigned first = persist_failed_seq(c);
   std::vector<gbp_ctx::Burst> redo;
   for (const gbp_ctx::Burst& b : c->persist.log)
-    if (b.seq >= first) redo.push_back(b);
+    if (!persist_seq_before(b.seq, first)) redo.push_back(b);      // (wrap-safe: the numbers of the log lie a handful apart)
   c->persist.log.clear();
   launch_copy_segments(c->persist.snap_restore, nullptr, c->stream);
   HIPCHK(c, hipGetLastError());
@@ -215,13 +218,14 @@ static int persist_recover(gbp_ctx* c) {
   return GBP_OK;
 }
 
-// The stream has been synchronised, or an event recorded behind launch `upto` has completed (0 = everything queued has).
+// The stream has been synchronised, or an event recorded behind launch `upto` has completed (0 = everything queued has: no launch
+// is numbered 0, gbp_persist_seq.hpp).
 int persist_check(gbp_ctx* c, unsigned upto) {
   if (!c->persist.status.host || c->persist.log.empty()) return GBP_OK;
   if (persist_failed_seq(c) != 0u) return persist_recover(c);
   if (upto == 0) c->persist.log.clear();
   else
-    while (!c->persist.log.empty() && c->persist.log.front().seq <= upto) c->persist.log.erase(c->persist.log.begin());
+    while (!c->persist.log.empty() && !persist_seq_before(upto, c->persist.log.front().seq)) c->persist.log.erase(c->persist.log.begin());
   return GBP_OK;
 }
 
@@ -262,13 +266,20 @@ int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, const Burst& b, const P
   A.sync = P<unsigned>(c->persist.psync);
   A.status = static_cast<unsigned*>(c->persist.status.dev);
   A.epoch_base = c->persist.epoch_base;
-  A.seq = c->persist.seq + 1;
+  // The number of this launch: never 0 — what *status holds while no launch has failed — and never one whose low 19 bits are 0, so
+  // tag0 is never the tag of a record that nobody has written (gbp_persist_seq.hpp).
+  A.seq = persist_next_seq(c->persist.seq);
   if (ev) A.ev = *ev;
   const bool flow = persist_tagged(c);      // hand-offs through tagged records (k_persist_flow)
   if (flow) {
     A.f = c->persist.flow;
-    A.f.tag0 = (A.seq & 0x7ffffu) << 13;      // + iteration (<= kPersistChunk) + 1: never the tag of a record an earlier launch left behind
+    // + iteration (<= kPersistChunk) + 1: never the tag of a record one of the 2^19 - 2 launches before this one left behind.  A
+    // launch further back can have had the same tags, and not every launch rewrites every shadow (the metric means: only launches that
+    // carry the metric; the second half of the landmark messages and row sums: only launches of two passes or more) — which is why the
+    // first launch of every tag period clears the shadows below: no record older than one period is ever read.
+    A.f.tag0 = persist_tag0(A.seq);
   }
+  static_assert(kPersistChunk + 1 < (1 << kPersistTagIterBits), "the tags of a launch stay inside its own 2^13");
   {
     // Two k_persist launches must never compete for CUs (each spins at its barriers until ALL its workgroups are resident).
     // Across processes that is the cooperative launch's guarantee; inside a process a launch from another ctx or stream than
@@ -280,6 +291,9 @@ int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, const Burst& b, const P
     if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     if (g_persist_last_ctx[dev & 15] && (g_persist_last_ctx[dev & 15] != c || g_persist_last_stream[dev & 15] != c->stream))
       HIPCHK(c, hipStreamWaitEvent(c->stream, e, 0));
+    // once per 2^19 - 1 launches (and in front of a ctx's first): every shadow back to "nobody's" (tag 0), the redundant copies of
+    // the test-hooks build included; the per-iteration health words among them are zero between launches anyway
+    if (persist_begins_period(A.seq)) HIPCHK(c, hipMemsetAsync(c->persist.pflow.p, 0, c->persist.flow_bytes, c->stream));
     launch_copy_segments(c->persist.snap_save, P<unsigned>(c->persist.psync) + 32, c->stream);       // skipped on the device once the abort word is set (5-7 us per launch)
     HIPCHK(c, hipGetLastError());
     const hipError_t le = launch_persist(A, c->persist.coop, c->stream);
@@ -301,7 +315,7 @@ int launch_persist_burst(gbp_ctx* c, const SweepArgs& a, const Burst& b, const P
   // arrivals of this launch (n <= kPersistChunk; the counter wraps, grid_sync compares wrap-safe): two hand-offs per iteration — with
   // tagged records none, and ONE barrier at the end of a launch that carries the metric
   c->persist.epoch_base += flow ? (ev ? nb : 0u) : nb * (unsigned)(2 * n - 1 + (ev ? 1 : 0));
-  c->persist.seq += 1;
+  c->persist.seq = A.seq;
   c->persist.log.push_back(b);
   c->persist.log.back().seq = c->persist.seq;
   *outcome = BurstOutcome::Ran;

@@ -154,10 +154,11 @@ struct gbp_ctx {
     // restores the snapshot and replays the logged launches from the first failed one on.
     DevBuf pflow;                        // tagged shadows of k_persist_flow (PersistFlow), one allocation
     gbp::PersistFlow flow{};                  // the tagged shadows of k_persist_flow
+    size_t flow_bytes = 0;               // the shadows (and their redundant copies): what the first launch of a tag period clears (gbp_persist_seq.hpp)
     uint32_t flow_total4 = 0;            // test-hooks builds: float4 of the shadows (the redundant copies of gbp_debug_persist_verify follow them)
     bool use_flow = true;                // test-hooks build: gbp_debug_persist_flow(ctx, 0) / GBP_PERSIST_FLOW=0 run the barrier kernel of rounds 3-4 instead
     std::vector<Burst> log;              // launched, completion not yet validated
-    unsigned seq = 0;
+    unsigned seq = 0;                    // the number of the last launch (0: none yet); the next one: persist_next_seq (gbp_persist_seq.hpp)
     DevBuf psnap;                        // snapshot arena
     gbp::CopySegs snap_save{}, snap_restore{};
     double probe_ms = 0;                 // gbp_create: what the co-residency probe took (the first kernel launch of the process: code-object load included)

@@ -404,6 +404,19 @@ class GbpEngine:
         self._chk(self.lib.gbp_debug_persist_verify(self.h, int(bool(on)), C.byref(n)), "gbp_debug_persist_verify")
         return int(n.value)
 
+    def persist_counters(self, seq=None, epoch_base=None):
+        """(number of the ctx's last launch of the persistent kernel, arrivals its barrier counter has seen) after the call (test hook).
+        seq / epoch_base: store these first (one of them alone: the other keeps its value); the ctx is settled before."""
+        self._need_hooks()
+        get = (C.c_uint32 * 2)()
+        if seq is not None or epoch_base is not None:
+            self._chk(self.lib.gbp_debug_persist_counters(self.h, None, get), "gbp_debug_persist_counters")
+            put = (C.c_uint32 * 2)(get[0] if seq is None else int(seq) & 0xffffffff, get[1] if epoch_base is None else int(epoch_base) & 0xffffffff)
+            self._chk(self.lib.gbp_debug_persist_counters(self.h, put, get), "gbp_debug_persist_counters")
+        else:
+            self._chk(self.lib.gbp_debug_persist_counters(self.h, None, get), "gbp_debug_persist_counters")
+        return int(get[0]), int(get[1])
+
     def factor_potentials(self):
         return self._debug(0, 9 * self.E, 81 * self.E)
 

@@ -97,6 +97,14 @@ GBP_API int gbp_debug_persist_flow(gbp_ctx* ctx, int on);
  * out[4] = {records seen torn, otherwise corrupt, waits that timed out, records checked}.  inject != 0: the control — one record in
  * 64 is stored tag first, payload a little later (what a tearing memory system would show): the detector must report torn records. */
 GBP_API int gbp_debug_persist_verify(gbp_ctx* ctx, int on, uint64_t* mismatches);
+/* The counters of the persistent kernel's protocol that keep counting for the life of a ctx, {number of the last launch (persist.seq: the
+ * tags of the tagged records and the word a time-out reports derive from it), arrivals the barrier counter has seen (persist.epoch_base
+ * and its twin on the device, the arrival word)}.  set (may be NULL): the ctx is settled first, then both are stored — the arrival count
+ * on the host and on the device, ordered on the ctx's stream and waited for; the abort word and the status word are left alone.  get (may
+ * be NULL): the values after the call.  What a test uses to put a ctx in front of a counter's wrap without the half a million launches
+ * (or 2^32 arrivals) that lead there; the shadows keep what the launches so far left.  GBP_ERR_STATE on a ctx without a persistent path,
+ * GBP_ERR_INVALID while the caller captures the stream. */
+GBP_API int gbp_debug_persist_counters(gbp_ctx* ctx, const uint32_t* set /* [2] or NULL */, uint32_t* get /* [2] or NULL */);
 GBP_API int gbp_debug_flow_torture(int blocks, int K, int rounds, unsigned mask, int inject, uint64_t* out /* [4] */);
 /* the grid and the belief-phase roles of a launch of the persistent kernel for a graph of n_tiles sweep tiles (a multiple of 4), n_cams
  * cameras, n_lmks landmarks, without / with the metric after every iteration (host evaluation of the function the kernel uses; no GPU):

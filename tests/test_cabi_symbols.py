@@ -104,7 +104,7 @@ def test_test_hooks_library_exports_the_debug_header():
     from gbp_poplar_amd import _lib
     lib = _lib.load(hooks=True)
     names = declared_functions("gbp_mi355x_debug.h")
-    assert names == sorted(_lib.debug_symbols()) and len(names) == 20       # 18 + gbp_debug_vertex + gbp_debug_sweep_variant
+    assert names == sorted(_lib.debug_symbols()) and len(names) == 21       # 18 + gbp_debug_vertex + gbp_debug_sweep_variant + gbp_debug_persist_counters
     for n in names + declared_functions():
         assert hasattr(lib, n), "libgbp_mi355x_test.so does not export %s" % n
 
