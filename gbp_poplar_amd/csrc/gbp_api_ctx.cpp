@@ -356,7 +356,8 @@ GBP_EXPORT(gbp_create, nullptr, (const gbp_problem* pr, const gbp_params* prm, c
   const Layout& y = c->lay;
   c->E_loc = y.E_loc; c->n_rows = y.n_rows; c->Ep = y.Ep; c->n_tiles = y.n_tiles;
   const uint32_t C = c->C;
-  c->sweep_policy = g_force_sweep_policy >= 0 ? (uint32_t)g_force_sweep_policy : sweep_policy_for(c->C, c->n_tiles);
+  c->sweep_policy = g_force_sweep_policy >= 0 ? (uint32_t)g_force_sweep_policy & ~kPolForceLateRelin : sweep_policy_for(c->C, c->n_tiles);
+  c->sweep_issue = g_force_sweep_policy >= 0 && ((uint32_t)g_force_sweep_policy & kPolForceLateRelin) ? kSweepIssue & ~kIssueEarlyRelin : kSweepIssue;
 
   HIPCHK(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
   c->stream = c->own_stream;

@@ -33,6 +33,7 @@ SweepArgs sweep_args(gbp_ctx* c, bool sweeps) {
   a.tile_perm = c->use_tile_perm ? P<uint32_t>(c->arr.tile_perm) : nullptr;
   a.seg_live = c->use_seg_live ? P<uint32_t>(c->arr.seg_live) : nullptr;
   a.policy = c->sweep_policy;
+  a.issue = c->sweep_issue;
   a.ev = EvalRide{};
   return a;
 }

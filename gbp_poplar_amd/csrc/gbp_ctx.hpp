@@ -71,6 +71,7 @@ struct gbp_ctx {
   bool use_tile_perm = false;
   bool use_seg_live = false;
   uint32_t sweep_policy = 0;           // kPol* bits of SweepArgs.policy for this graph's shape (sweep_policy_for)
+  uint32_t sweep_issue = gbp::kSweepIssue;  // kIssue* bits of SweepArgs.issue (gbp_debug_force_sweep_policy + kPolForceLateRelin: the other order)
   bool hoist = true;  // per-variable belief means (k_sweep<true>); false = literal per-factor mu/oldmu tensors
   hipStream_t own_stream = nullptr, stream = nullptr;
   bool uploaded = false, beliefs_valid = false;

@@ -123,6 +123,7 @@ struct SweepArgs {
                              // neither loads nor stores the all-pad segments (k_sweep<..., SEG>): graphs of many small cameras, where the unused
                              // tails of the cameras' last rows are a few per cent of all positions
   uint32_t policy;           // kPol* bits: cache policy of the two message streams, chosen per graph shape (gbp_api_ctx.cpp: sweep_policy_for)
+  uint32_t issue;            // kIssue* bits: read by the test-hooks build only (gbp_debug_force_sweep_policy + 8); the product runs kSweepIssue
   EvalRide ev;               // k_sweep<EV> only
 };
 // SweepArgs.policy.  The potentials (read once per sweep) and every tile STORE of the camera messages carry the non-temporal
@@ -131,6 +132,13 @@ struct SweepArgs {
 constexpr uint32_t kPolCmsgLoadCached = 1u;   // camera-message tiles LOADED with the default policy (few cameras, both streams within the Infinity Cache)
 constexpr uint32_t kPolLmsgLoadNt = 2u;       // landmark-message tiles loaded with the non-temporal hint (default: default policy — k_beliefs gathers them next)
 constexpr uint32_t kPolLmsgStoreNt = 4u;      // ... and stored with it
+// SweepArgs.issue: WHEN a wave of k_sweep requests the loads of its relinearising path — no byte moved and no floating-point operation
+// differs (profiles/sweep_issue_order.md has the measurements behind the choice, and the two knobs that were measured and not kept):
+constexpr uint32_t kIssueEarlyRelin = 1u;     // the relinearisation-only operands (FST_VAR, the camera's hoisted mean and CAM_LIN record) are
+                                              // requested ahead of factor_update, as LDS-DMA into a wave-private area, as soon as the
+                                              // packed word says that a lane of the wave MAY relinearise — not behind the dmu test
+constexpr uint32_t kSweepIssue = kIssueEarlyRelin;      // what the product compiles in
+constexpr uint32_t kPolForceLateRelin = 8u;   // gbp_debug_force_sweep_policy only, never in SweepArgs.policy: the ctx runs SweepArgs.issue without kIssueEarlyRelin
 
 // BeliefArgs.ev_split: a belief update made of two launches round an exchange (the sharded iteration, gbp_api_comm.cpp).  The burst's
 // iteration counter advances ONCE per iteration, in the last belief launch — the camera combine; every launch before it carries kEvNotLast.

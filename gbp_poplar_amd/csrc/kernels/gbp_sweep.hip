@@ -23,8 +23,12 @@ constexpr int kWpb = 4;      // wavefronts per workgroup of the sweep (the waves
 // EV: the metric of the PREVIOUS iteration rides in this sweep (EvalRide in gbp_kernels.h)
 // SEG: the tile's all-pad segments (four lanes) are neither loaded nor stored (SweepArgs.seg_live, load_tile_seg above); the state
 // planes — 4 or 8 bytes per position — are moved whole
-template <bool HOIST, uint32_t POL = 0, bool EV = false, bool SEG = false>
+// ISSUE: kIssue* bits (gbp_kernels.h) — WHEN the loads of the relinearising path are requested.  The same bytes and the same
+// arithmetic either way; the product runs kSweepIssue, the test-hooks build can be told to run the other (gbp_debug_force_sweep_policy).
+constexpr int kRelinSlots = 8;      // 1 KiB LDS-DMA slots of a wave's relinearisation operands: FST_VAR (256 B of it), CAM_MU 0..1, CAM_LIN 0..4
+template <bool HOIST, uint32_t POL = 0, bool EV = false, bool SEG = false, uint32_t ISSUE = kSweepIssue>
 GBP_DEV void sweep_tile(const SweepArgs& a, const uint32_t wslot) {
+  constexpr bool EARLY = HOIST && (ISSUE & kIssueEarlyRelin) != 0;      // (the literal-mu sweep keeps its path: it fetches the variance only)
   // (the slot is wave-uniform: as an SGPR it turns the permutation look-up into one scalar load)
   const uint32_t ws = (uint32_t)__builtin_amdgcn_readfirstlane((int)wslot);
   const uint32_t tile = a.tile_perm ? a.tile_perm[ws] : ws;
@@ -33,6 +37,10 @@ GBP_DEV void sweep_tile(const SweepArgs& a, const uint32_t wslot) {
 
   const uint32_t cam_i = a.row_cam[p >> 4];
   const uint32_t lmk_i = __builtin_nontemporal_load(a.lmk_idx + p);
+  // EARLY: the packed word goes out in FRONT of the streams — its count decides, behind cmsg_expand and while the gathers are still in
+  // flight, whether the wave requests its relinearisation operands (the vm counter retires in order: requested behind the gathers,
+  // as below, the word would be the last thing to land)
+  const int packed_first = EARLY ? a.fst_packed[p] : 0;
 
   // SEG: bit s of the tile's mask = the 64-byte segment of lanes 4s .. 4s + 3 holds at least one factor (one scalar load)
   const uint32_t segm = SEG ? a.seg_live[tile] : 0xffffu;
@@ -69,7 +77,7 @@ GBP_DEV void sweep_tile(const SweepArgs& a, const uint32_t wslot) {
   }, lm);
   load_rec<kCamRec4>(a.camb + (size_t)cam_i * kCamRec4, cb);
   load_rec<kLmkRec4>(a.lmkb + (size_t)lmk_i * kLmkRec4, lb);
-  const int packed = a.fst_packed[p];      // (behind the gathers: nothing needs them before the gathers have landed)
+  const int packed = EARLY ? packed_first : a.fst_packed[p];      // (behind the gathers: nothing needs them before the gathers have landed)
   float damping = a.fst_damp[p];
   // EV: the camera's metric record (one address per 16-lane row) and the landmark's metric mean (a 16-byte gather from a table
   // 1/4 the size of the beliefs') go out WITH the belief gathers — unconditionally: pads index 0 — and wait in a wave-private
@@ -108,17 +116,57 @@ GBP_DEV void sweep_tile(const SweepArgs& a, const uint32_t wslot) {
   float cm[28];
   cmsg_expand(fac, cmr, a.cmsg_lit, tile, lane, cm);
 
+  // EARLY: relin = dmu < threshold && count + 1 > min_linear_iters - num_undamped_iters (factor_update), and the second condition is
+  // known as soon as the packed word has landed.  Where it holds for a lane of the wave, the operands only a relinearising lane reads —
+  // its variance, its camera's hoisted mean and CAM_LIN record: L2-resident tables — are requested HERE, eight LDS-DMA transfers into
+  // a wave-private area (no register: the kernel stands at the limit of two waves per SIMD), so that they travel with the belief
+  // gathers factor_update is about to wait for — instead of inside factor_update behind the dmu test, where both waves of a SIMD sat
+  // out a round trip of their own in the middle of the arithmetic.  A lane whose dmu then fails the test leaves its 128 bytes
+  // unread.  On S1 no lane passes in 10 sweeps of 11, and the wave executes one compare and one branch more.
+  //  * HERE, not in the load prologue: a branch in the prologue ends the block in which the compiler interleaves cmsg_expand with the
+  //    loads, and the wave then waited for every gather before its first multiplication — in every sweep (profiles/sweep_issue_order.md).
+  //  * The test is ONE compare into a scalar pair, on the count alone (count + 1 > bound <=> packed >= 8 x bound: an arithmetic
+  //    shift rounds down): an inactive or pad lane beyond the bound makes its wave request operands nobody reads, which is correct.
+  //    The active bit would need a vector register, and so would address arithmetic: the free ones are dead slots of belief
+  //    records still in flight, and writing one waits for that gather.  So the wave's number is taken as a scalar and the camera
+  //    records are addressed by INDEX through descriptors that carry their stride.
+  __shared__ float4 rl_stage[EARLY ? kWpb : 1][EARLY ? 64 * kRelinSlots : 1];
+  static_assert(3 + kCamLin4 == kRelinSlots, "one slot per transfer");
+  if (EARLY) {
+    const int bound8 = (a.hp.min_linear_iters - a.hp.num_undamped_iters) * 8;
+    unsigned long long may_relin;      // the lanes with count + 1 > min_linear_iters - num_undamped_iters
+    asm volatile("v_cmp_le_i32 %0, %2, %1" : "=s"(may_relin) : "v"(packed_first), "s"(bound8));
+    if (may_relin != 0ull) {      // (every lane asks, pads too: row_cam and the planes cover all positions)
+      float4* rl = rl_stage[(uint32_t)__builtin_amdgcn_readfirstlane((int)threadIdx.x) >> 6];
+      const __amdgpu_buffer_rsrc_t mu_t = rec_rsrc(a.cam_mu, 4 * 16), lin_t = rec_rsrc(a.cam_lin, kCamLin4 * 16);
+      lds_dma<4>(a.fst_var + p, rl);
+      lds_dma_rec16(mu_t, cam_i, 0, rl + 64);
+      lds_dma_rec16(mu_t, cam_i, 16, rl + 128);
+      GBP_UNROLL
+      for (int g = 0; g < kCamLin4; ++g) lds_dma_rec16(lin_t, cam_i, g * 16, rl + (3 + g) * 64);
+    }
+  }
+
   float oc_eta[6], oc_lam[36], bi[9], ol[16];
   bool relin;
   factor_update<HOIST>(fac, cm, mu, lm, cb, lb, K, a.hp, damping, count, flags, var, active, oc_eta, oc_lam, bi, ol, relin,
                             [&](float (&x0c)[6], float (&x0l)[3], CamLin& cl, float& var_r) {   // rare path: loaded only by relinearising lanes
-                              var_r = a.fst_var[p];
-                              if (!HOIST) return;      // (the literal mu tensors: the means are the lane's own)
-                              // camera side: the hoisted mean and its CAM_LIN record — per-camera tables (C x 144 B) that live in L2
-                              const float4 m0 = a.cam_mu[(size_t)cam_i * 4], m1 = a.cam_mu[(size_t)cam_i * 4 + 1];
-                              float4 q[kCamLin4];
-                              GBP_UNROLL
-                              for (int g = 0; g < kCamLin4; ++g) q[g] = a.cam_lin[(size_t)cam_i * kCamLin4 + g];
+                              float4 m0, m1, q[kCamLin4];
+                              if (EARLY) {      // requested above (a lane that gets here passed the count test there)
+                                lds_dma_wait();
+                                const float4* rl = rl_stage[threadIdx.x >> 6];
+                                var_r = reinterpret_cast<const float*>(rl)[lane];
+                                m0 = rl[64 + lane]; m1 = rl[128 + lane];
+                                GBP_UNROLL
+                                for (int g = 0; g < kCamLin4; ++g) q[g] = rl[(3 + g) * 64 + lane];
+                              } else {
+                                var_r = a.fst_var[p];
+                                if (!HOIST) return;      // (the literal mu tensors: the means are the lane's own)
+                                // camera side: the hoisted mean and its CAM_LIN record — per-camera tables (C x 144 B) that live in L2
+                                m0 = a.cam_mu[(size_t)cam_i * 4]; m1 = a.cam_mu[(size_t)cam_i * 4 + 1];
+                                GBP_UNROLL
+                                for (int g = 0; g < kCamLin4; ++g) q[g] = a.cam_lin[(size_t)cam_i * kCamLin4 + g];
+                              }
                               x0c[0] = m0.x; x0c[1] = m0.y; x0c[2] = m0.z; x0c[3] = m0.w; x0c[4] = m1.x; x0c[5] = m1.y;
                               cam_lin_unpack(q, cl);
                               // landmark side: the mean is RECOMPUTED from the belief record the lane holds anyway — inf2mean3x3
@@ -177,9 +225,9 @@ GBP_DEV void sweep_tile(const SweepArgs& a, const uint32_t wslot) {
   }
 }
 
-template <bool HOIST, uint32_t POL = 0, bool EV = false, bool SEG = false>
+template <bool HOIST, uint32_t POL = 0, bool EV = false, bool SEG = false, uint32_t ISSUE = kSweepIssue>
 __global__ __launch_bounds__(64 * kWpb) void k_sweep(const SweepArgs a) {
-  sweep_tile<HOIST, POL, EV, SEG>(a, blockIdx.x * kWpb + (threadIdx.x >> 6));
+  sweep_tile<HOIST, POL, EV, SEG, ISSUE>(a, blockIdx.x * kWpb + (threadIdx.x >> 6));
 }
 
 // =================================================================================================
@@ -242,6 +290,15 @@ void launch_sweep(const SweepArgs& a, uint32_t n_tiles, bool hoist, hipStream_t 
   if (lab_launch_sweep(a, n_tiles, hoist, s)) return;     // a mapping experiment / an ablated sweep was asked for (SweepArgs.variant)
 #endif
   if (!hoist) { hipLaunchKernelGGL(k_sweep<false>, g, b, 0, s, a); return; }
+#ifdef GBP_BUILD_TEST_HOOKS      // the other issue order of the plain hoisted sweep (gbp_debug_force_sweep_policy + kPolForceLateRelin: A/B measurements, tests)
+  if (a.issue != kSweepIssue && (seg || a.policy <= kPolCmsgLoadCached)) {
+    constexpr uint32_t kOther = kSweepIssue ^ kIssueEarlyRelin;
+    if (seg) hipLaunchKernelGGL((k_sweep<true, 0, false, true, kOther>), g, b, 0, s, a);
+    else if (a.policy == kPolCmsgLoadCached) hipLaunchKernelGGL((k_sweep<true, kPolCmsgLoadCached, false, false, kOther>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_sweep<true, 0, false, false, kOther>), g, b, 0, s, a);
+    return;
+  }
+#endif
   if (seg) { hipLaunchKernelGGL((k_sweep<true, 0, false, true>), g, b, 0, s, a); return; }
   switch (a.policy) {      // the instantiations sweep_policy_for() (gbp_api_ctx.cpp) can choose
     case kPolCmsgLoadCached: hipLaunchKernelGGL((k_sweep<true, kPolCmsgLoadCached>), g, b, 0, s, a); break;

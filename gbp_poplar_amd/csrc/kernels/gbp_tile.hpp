@@ -73,6 +73,28 @@ GBP_DEV void load_rec(const float4* rec, float (&out)[G * 4]) {
   }
 }
 
+// LDS-DMA (global_load_lds_dword / _dwordx4, the gfx950 b128 form): every lane names its own SOURCE address, the data lands at
+// dst + lane * BYTES — dst is wave-uniform — without passing through a register, so a request costs the prologue no live VGPR
+// beyond its address.  Nothing orders a later ds_read behind the transfer but the issuing wave's own vmcnt: lds_dma_wait() goes
+// in front of the first read.
+template <int BYTES>
+GBP_DEV void lds_dma(const void* src, void* dst) {
+  static_assert(BYTES == 4 || BYTES == 16, "global_load_lds: dword or dwordx4");
+  const auto* g = (const __attribute__((address_space(1))) void*)src;
+  auto* l = (__attribute__((address_space(3))) void*)dst;
+  if (BYTES == 16) __builtin_amdgcn_global_load_lds(g, l, 16, 0, 0);      // (the size is a literal: the builtin takes no dependent value)
+  else __builtin_amdgcn_global_load_lds(g, l, 4, 0, 0);
+}
+// ... the same from a table of records: lane's source = record `index` of the table + `byte` (a multiple of 16 below the stride).  The
+// hardware scales the index by the stride of the descriptor, so the request needs no address arithmetic in vector registers.
+GBP_DEV __amdgpu_buffer_rsrc_t rec_rsrc(const float4* table, int stride_bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float4*>(table), (short)stride_bytes, 0x7fffffff, 0x00020000);
+}
+GBP_DEV void lds_dma_rec16(__amdgpu_buffer_rsrc_t table, uint32_t index, int byte, void* dst) {
+  __builtin_amdgcn_struct_ptr_buffer_load_lds(table, (__attribute__((address_space(3))) void*)dst, 16, (int)index, 0, byte, 0, 0);
+}
+GBP_DEV void lds_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
 // The 44-float ROWP record of every 16-lane row of a tile: the sums of the camera messages (6 eta + 36 Lambda entries, two
 // pad slots) over the row's 16 factors, each the balanced binary tree in lane order of row16_sum, handed to `st(g, float4)`
 // (float4 group g of the row's record) by the lanes that end up holding them.

@@ -75,7 +75,9 @@ GBP_API void gbp_debug_layout_default_options(gbp_layout_options* opt);
 /* the options LATER gbp_create calls of this process build their device order with (NULL = the defaults again); measurements */
 GBP_API int gbp_debug_layout_options(const gbp_layout_options* opt);
 /* the cache policy of the sweep's message streams (SweepArgs.policy bits: 1 = camera messages loaded cached, 2 / 4 = landmark
- * messages loaded / stored non-temporal) later gbp_create calls use instead of the choice by graph shape; -1 = by shape */
+ * messages loaded / stored non-temporal) later gbp_create calls use instead of the choice by graph shape; -1 = by shape.
+ * + 8: the plain hoisted sweep of those calls also requests its relinearisation operands behind the dmu test instead of ahead of it
+ * (SweepArgs.issue = 0, policies 0 and 1 only); identical results — A/B measurements and tests */
 GBP_API int gbp_debug_force_sweep_policy(int policy);
 /* the sweep of later gbp_create calls skips the all-pad 64-byte segments of its tiles (k_sweep<..., SEG>): -1 = by shape (the default:
  * graphs of >= 2 048 tiles where they are >= 1 % of the positions), 0 = never, 1 = always; identical results — A/B measurements and tests */
