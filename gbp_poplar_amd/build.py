@@ -5,6 +5,7 @@
                                                                                    include/gbp_mi355x_debug.h (tests/ only)
                                              gbp_poplar_amd/libgbp_mi355x_post.so  the solution readout (post/, include/gbp_mi355x_post.h)
                                              gbp_poplar_amd/libgbp_mi355x_seed.so  landmark / keyframe seeding (seed/, include/gbp_mi355x_seed.h)
+                                             gbp_poplar_amd/libgbp_mi355x_resect.so  camera resection (resect/, include/gbp_mi355x_resect.h)
     python -m gbp_poplar_amd.build --experiments
                                           -> gbp_poplar_amd/libgbp_mi355x_exp.so   + csrc/experiments/: timing ablations / mapping
                                                                                    experiments (profiles/*.py only)
@@ -32,12 +33,14 @@ TEST_LIB = os.path.join(HERE, "libgbp_mi355x_test.so")  # + gbp_debug_* (include
 EXP_LIB = os.path.join(HERE, "libgbp_mi355x_exp.so")    # + timing ablations and mapping experiments (profiles/*.py only)
 POST_LIB = os.path.join(HERE, "libgbp_mi355x_post.so")  # the solution readout
 SEED_LIB = os.path.join(HERE, "libgbp_mi355x_seed.so")  # landmark / keyframe seeding
+RESECT_LIB = os.path.join(HERE, "libgbp_mi355x_resect.so")  # camera resection against the map
 # The libraries without a ctx, each one HIP translation unit with the product's flags and an export map of its own:
 # name (= its directory under _obj/) -> (source directory, source, export map, library).  stateless/ is what they share.
 STATELESS = os.path.join(HERE, "stateless")
 SATELLITES = {
     "post": (os.path.join(HERE, "post"), "gbp_post.hip", "gbp_post_exports.map", POST_LIB),
     "seed": (os.path.join(HERE, "seed"), "gbp_seed.hip", "gbp_seed_exports.map", SEED_LIB),
+    "resect": (os.path.join(HERE, "resect"), "gbp_resect.hip", "gbp_resect_exports.map", RESECT_LIB),
 }
 BIN = os.path.join(HERE, "bin")
 ARCH = "gfx950"
@@ -161,15 +164,16 @@ def build(force=False, verbose=False, test_hooks=True, variants=None):
     _build_libs(list(variants), force, verbose, list(SATELLITES))
     os.makedirs(BIN, exist_ok=True)
     inc = os.path.join(HERE, "..", "include")
-    cli_deps = [os.path.join(CSRC, f) for f in ("cli_common.hpp", "gbp_transport.hpp", "gbp_metric_gather.hpp")] + [os.path.join(inc, f) for f in os.listdir(inc)] + [LIB, POST_LIB, SEED_LIB]
+    cli_deps = [os.path.join(CSRC, f) for f in ("cli_common.hpp", "gbp_transport.hpp", "gbp_metric_gather.hpp")] + [os.path.join(inc, f) for f in os.listdir(inc)] + [LIB, POST_LIB, SEED_LIB, RESECT_LIB]
     for name, src in CLI_SRCS.items():
         path = os.path.join(CSRC, src)
         exe = os.path.join(BIN, name)
         if os.path.exists(path) and (force or _stale(exe, cli_deps + [path])):
             # the CLIs are plain C++ on top of the C-ABI: host compiler, linked against the in-tree library
-            # (ba / slam: + the readout and seeding libraries, and the HIP runtime for the device arrays --cov_file / --lmk_init hand them)
+            # (ba / slam: + the readout, seeding and resection libraries, and the HIP runtime for the device arrays --cov_file / --lmk_init /
+            # --kf_init hand them)
             rocm = os.path.dirname(os.path.dirname(os.path.realpath(hipcc())))
-            post = [] if name == "bal_convert" else ["-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), "-lgbp_mi355x_post", "-lgbp_mi355x_seed",
+            post = [] if name == "bal_convert" else ["-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), "-lgbp_mi355x_post", "-lgbp_mi355x_seed", "-lgbp_mi355x_resect",
                                                      "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath," + os.path.join(rocm, "lib")]
             cmd = [shutil.which("g++") or "g++", "-o", exe, "-O2", "-std=c++17", "-ffp-contract=off", "-pthread", path,
                    "-L" + HERE, "-lgbp_mi355x"] + post + ["-Wl,-rpath,$ORIGIN/.."]

@@ -12,7 +12,9 @@
 //   * `--seed S` makes the initialisation-noise flags reproducible (the reference seeds from the clock,
 //     dataio.cpp:334,349,406); `--eval_every K` thins the per-iteration read-back + metric (default 1);
 //   * `--lmk_init triangulate` takes the landmarks' prior means and strengths from the observations and the camera prior means
-//     (libgbp_mi355x_seed.so) instead of the file's `points` section, which is then not used at all.
+//     (libgbp_mi355x_seed.so) instead of the file's `points` section, which is then not used at all;
+//   * slam's `--kf_init resect` refines every new keyframe's pose guess — the reference's copy of its predecessor — against the
+//     landmarks mapped so far (libgbp_mi355x_resect.so) before its prior is set; the default, `copy`, is the reference's.
 #pragma once
 #include "../../include/gbp_mi355x.h"
 #include "../../include/gbp_mi355x_multi.h"       // --ipus N: one forked rank per GPU
@@ -20,6 +22,7 @@
 #include "gbp_metric_gather.hpp"                  // --ipus N: the cross-rank sum of a burst's metric records
 #include "../../include/gbp_mi355x_post.h"        // --cov_file: means and marginal covariances of the beliefs (libgbp_mi355x_post.so)
 #include "../../include/gbp_mi355x_seed.h"        // --lmk_init triangulate: landmark priors from observations (libgbp_mi355x_seed.so)
+#include "../../include/gbp_mi355x_resect.h"      // slam --kf_init resect: the new keyframe's pose from the mapped landmarks (libgbp_mi355x_resect.so)
 #include "../../include/gbp_mi355x_compat.h"      // MetricPipe: the metric in two halves (gbp_iterate_eval / gbp_eval_end), so that printing overlaps the next iterations
 
 #include <hip/hip_runtime_api.h>                  // --cov_file: the device arrays the readout works on (nothing else here touches HIP)
@@ -109,6 +112,7 @@ struct Options {
   std::string out_file;         // --out_file: write the refined problem (belief means) in the input's format
   std::string cov_file;         // --cov_file: write every variable's mean and marginal covariance (gbp_post_moments)
   bool triangulate = false;     // --lmk_init triangulate (default: file)
+  bool kf_resect = false;       // slam --kf_init resect (default: copy)
   bool force_sharded = false;   // --force_sharded: run the multi-rank code path (fork, shard ctx, communicator) with one rank
 };
 
@@ -138,13 +142,15 @@ inline void usage(bool slam) {
                "                                 share a GPU; host is also spelled host-staged; measured: time every transport the ranks\n"
                "                                 can form, keep the fastest)\n"
                "  --lmk_init arg (=file)         landmark prior means and strengths: file (the file's points) | triangulate (from the\n"
-               "                                 observations and the camera prior means; the file's points are not used; one GPU)\n"
-               "  --out_file arg                 write the refined cameras / landmarks (belief means) in the input's format\n"
+               "                                 observations and the camera prior means; the file's points are not used; one GPU)\n";
+  if (slam) std::cout << "  --kf_init arg (=copy)          a new keyframe's pose guess: copy (its predecessor's pose) | resect (the copy, refined\n"
+                         "                                 against the landmarks mapped so far; one GPU)\n";
+  std::cout << "  --out_file arg                write the refined cameras / landmarks (belief means) in the input's format\n"
                "  --cov_file arg                 write every camera's / landmark's mean and marginal covariance: line 1 `C L`, then per camera\n"
                "                                 6 + 36 values, per landmark 3 + 9 values (covariances row-major)\n";
 }
 
-// returns 0 = run, 1 = exit with code 0 (help), 2 = exit with code 1 (error)
+// returns 0 = run, 1 = exit with code 0 (help), 2 = exit with code 1 (error), 3 = exit with code 2 (a --kf_init that cannot be run)
 inline int parse(int argc, char** argv, bool slam, Options& o) {
   std::map<std::string, std::string> kv;
   for (int i = 1; i < argc; ++i) {
@@ -187,6 +193,10 @@ inline int parse(int argc, char** argv, bool slam, Options& o) {
         if (v != "file" && v != "triangulate") { std::cerr << "--lmk_init: expected file or triangulate\n"; return 2; }
         o.triangulate = v == "triangulate";
       }
+      else if (k == "kf_init" && slam) {
+        if (v != "copy" && v != "resect") { std::cerr << "--kf_init: expected copy or resect\n"; return 3; }
+        o.kf_resect = v == "resect";
+      }
       else if (k == "out_file") o.out_file = v;
       else if (k == "cov_file") o.cov_file = v;
       else if (k == "transport") {
@@ -203,6 +213,7 @@ inline int parse(int argc, char** argv, bool slam, Options& o) {
   if (o.bal_file.empty()) { std::cerr << "the option '--bal_file' is required but missing\n"; return 2; }
   if (o.triangulate && o.av_depth_on) { std::cerr << "--lmk_init triangulate and --avdepth_on both place the landmarks: choose one\n"; return 2; }
   if (o.triangulate && (o.gpus > 1 || o.force_sharded)) { std::cerr << "--lmk_init triangulate runs on one GPU\n"; return 2; }
+  if (o.kf_resect && (o.gpus > 1 || o.force_sharded)) { std::cerr << "--kf_init resect runs on one GPU\n"; return 3; }
   return 0;
 }
 
@@ -405,7 +416,9 @@ struct Seeder {
   }
 
   // slam: P.cpe / P.cpl / P.lpe / P.lpl hold gbp_read_priors' arrays, rb the beliefs, P.active / P.lwf the flags gbp_slam_update_flags left
-  int keyframe(Problem& P, uint32_t data_counter, const float* cbe, const float* cbl, const float* lbe, const float* lbl) {
+  // refine (may be empty): called with the new camera's pose guess [6] once P.cpe holds its copied prior eta — --kf_init resect
+  int keyframe(Problem& P, uint32_t data_counter, const float* cbe, const float* cbl, const float* lbe, const float* lbl,
+               const std::function<int(float*)>& refine = {}) {
     if (!up(d_cbe, cbe, 6 * (size_t)C) || !up(d_cbl, cbl, 36 * (size_t)C) || !up(d_cpl, P.cpl.data(), 36 * (size_t)C) || !up(d_cpe, P.cpe.data(), 6 * (size_t)C))
       return 1;
     if (!seed_ok(gbp_seed_keyframe(nullptr, C, data_counter, data_counter + 1, d_cbe, d_cbl, d_cpl, d_cpe, d_guess))) return 1;
@@ -413,8 +426,93 @@ struct Seeder {
     gbp_belief_means(C, L, cbe, cbl, lbe, lbl, cams64.data(), pts64.data());
     for (size_t i = 0; i < cam_mean.size(); ++i) cam_mean[i] = (float)cams64[i];
     if (!down(P.cpe.data(), d_cpe, 6 * (size_t)C) || !down(cam_mean.data() + 6 * ((size_t)data_counter + 1), d_guess, 6)) return 1;
+    if (refine && refine(cam_mean.data() + 6 * ((size_t)data_counter + 1))) return 1;
     for (uint32_t l = 0; l < L; ++l) select[l] = P.lwf[l] != 0u;      // what this keyframe activated (gbp_slam_update_flags)
     return landmarks(P, cam_mean.data(), P.active.data(), select.data());
+  }
+};
+
+// ---- slam --kf_init resect: the new keyframe's pose from the landmarks mapped so far (include/gbp_mi355x_resect.h) -------
+// The device arrays of the resection call, allocated once; blocking copies on the default stream, as Seeder.  keyframe(): camera
+// data_counter + 1 alone, from its pose guess (`guess` [6], or the belief mean of camera data_counter where it is NULL), against the
+// belief means of the landmarks that were mapped before this keyframe (lmk_active != 0 and lmk_weaken_flag == 0 as
+// gbp_slam_update_flags left them), over the updated active flags.  P.cpe / P.cpl hold the priors with the COPIED eta of the new
+// camera: a resected pose replaces that eta (prior Lambda . pose) and the guess; otherwise both stand.  `line` says which happened.
+struct Resecter {
+  uint32_t C = 0, L = 0, E = 0;
+  std::vector<uint32_t> cam_start, cam_edges, lmk_use, select;
+  std::vector<float> cam_mean, lmk_mean;
+  std::vector<double> cams64, pts64;
+  gbp_resect_options opts{};
+  char* base = nullptr;
+  uint32_t *d_lmk_id = nullptr, *d_start = nullptr, *d_edges = nullptr, *d_active = nullptr, *d_use = nullptr, *d_select = nullptr, *d_status = nullptr,
+           *d_views = nullptr;
+  float *d_meas = nullptr, *d_cam_mean = nullptr, *d_lmk_mean = nullptr, *d_cpl = nullptr, *d_cpe = nullptr, *d_report = nullptr;
+  ~Resecter() { if (base) (void)hipFree(base); }
+  static bool ok(hipError_t e, const char* what) {
+    if (e != hipSuccess) std::cerr << "--kf_init resect: " << what << " failed: " << hipGetErrorString(e) << "\n";
+    return e == hipSuccess;
+  }
+  static bool resect_ok(int rc) {
+    if (rc != GBP_OK) std::cerr << "--kf_init resect: " << gbp_resect_last_error() << "\n";
+    return rc == GBP_OK;
+  }
+  template <class T> bool up(T* d, const T* h, size_t n) { return n == 0 || ok(hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy"); }
+  template <class T> bool down(T* h, const T* d, size_t n) { return n == 0 || ok(hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost), "hipMemcpy"); }
+
+  int start(const Options& o, const Problem& P) {
+    C = P.bal.n_cams; L = P.bal.n_lmks; E = P.bal.n_edges;
+    gbp_resect_default_options(&opts);
+    opts.reproj_meas_var = o.reproj_meas_var;
+    cam_start.resize((size_t)C + 1); cam_edges.resize(E); lmk_use.resize(L); select.assign(C, 0u);
+    if (!resect_ok(gbp_resect_index(C, E, P.cam_id.data(), cam_start.data(), cam_edges.data()))) return 1;
+    size_t at = 0;
+    const auto take = [&at](size_t bytes) { const size_t here = at; at += (bytes + 255) & ~(size_t)255; return here; };
+    const size_t o_lmk_id = take(4 * (size_t)E), o_start = take(4 * ((size_t)C + 1)), o_edges = take(4 * (size_t)E), o_active = take(4 * (size_t)E),
+                 o_use = take(4 * (size_t)L), o_select = take(4 * (size_t)C), o_status = take(4 * (size_t)C), o_views = take(4 * (size_t)C),
+                 o_meas = take(8 * (size_t)E), o_cam_mean = take(24 * (size_t)C), o_lmk_mean = take(12 * (size_t)L), o_cpl = take(144 * (size_t)C),
+                 o_cpe = take(24 * (size_t)C), o_report = take(16 * (size_t)C);
+    if (!ok(hipMalloc(reinterpret_cast<void**>(&base), at), "hipMalloc")) return 1;
+    const auto u32 = [this](size_t off) { return reinterpret_cast<uint32_t*>(base + off); };
+    const auto f32 = [this](size_t off) { return reinterpret_cast<float*>(base + off); };
+    d_lmk_id = u32(o_lmk_id); d_start = u32(o_start); d_edges = u32(o_edges); d_active = u32(o_active); d_use = u32(o_use); d_select = u32(o_select);
+    d_status = u32(o_status); d_views = u32(o_views); d_meas = f32(o_meas); d_cam_mean = f32(o_cam_mean); d_lmk_mean = f32(o_lmk_mean);
+    d_cpl = f32(o_cpl); d_cpe = f32(o_cpe); d_report = f32(o_report);
+    return up(d_lmk_id, P.lmk_id.data(), E) && up(d_start, cam_start.data(), (size_t)C + 1) && up(d_edges, cam_edges.data(), E) &&
+                   up(d_meas, P.meas.data(), 2 * (size_t)E) ? 0 : 1;
+  }
+
+  int keyframe(Problem& P, uint32_t data_counter, const float* cbe, const float* cbl, const float* lbe, const float* lbl, const uint32_t* lmk_active,
+               float* guess, std::string& line) {
+    const uint32_t kf = data_counter + 1;
+    cams64.resize(6 * (size_t)C); pts64.resize(3 * (size_t)L); cam_mean.resize(6 * (size_t)C); lmk_mean.resize(3 * (size_t)L);
+    gbp_belief_means(C, L, cbe, cbl, lbe, lbl, cams64.data(), pts64.data());
+    for (size_t i = 0; i < cam_mean.size(); ++i) cam_mean[i] = (float)cams64[i];
+    for (size_t i = 0; i < lmk_mean.size(); ++i) lmk_mean[i] = (float)pts64[i];
+    for (int i = 0; i < 6; ++i) cam_mean[6 * (size_t)kf + i] = guess ? guess[i] : cam_mean[6 * (size_t)data_counter + i];
+    for (uint32_t l = 0; l < L; ++l) lmk_use[l] = lmk_active[l] != 0u && P.lwf[l] == 0u;
+    std::fill(select.begin(), select.end(), 0u);
+    select[kf] = 1u;
+    if (!up(d_cam_mean, cam_mean.data(), 6 * (size_t)C) || !up(d_lmk_mean, lmk_mean.data(), 3 * (size_t)L) || !up(d_active, P.active.data(), E) ||
+        !up(d_use, lmk_use.data(), L) || !up(d_select, select.data(), C) || !up(d_cpl, P.cpl.data(), 36 * (size_t)C) || !up(d_cpe, P.cpe.data(), 6 * (size_t)C))
+      return 1;
+    if (!resect_ok(gbp_resect_cameras(nullptr, C, L, E, d_lmk_id, d_start, d_edges, P.K.data(), d_lmk_mean, d_meas, d_active, d_use, d_select, &opts,
+                                      d_cam_mean, d_cpl, d_cpe, nullptr, d_report, d_status, d_views)))
+      return 1;
+    uint32_t st = 0, n = 0;
+    float report[4] = {0.f, 0.f, 0.f, 0.f};
+    if (!down(&st, d_status + kf, 1) || !down(&n, d_views + kf, 1)) return 1;
+    char buf[200];
+    if (st & (GBP_RESECT_NO_VIEW | GBP_RESECT_FEW_VIEWS | GBP_RESECT_NONFINITE | GBP_RESECT_STALLED)) {
+      std::snprintf(buf, sizeof(buf), "Keyframe %u: pose copied from keyframe %u (resection status %u, %u views)\n", kf + 1, kf, st, n);
+    } else {
+      if (!down(report, d_report + 4 * (size_t)kf, 4) || !down(P.cpe.data() + 6 * (size_t)kf, d_cpe + 6 * (size_t)kf, 6) ||
+          (guess && !down(guess, d_cam_mean + 6 * (size_t)kf, 6)))
+        return 1;
+      std::snprintf(buf, sizeof(buf), "Keyframe %u: pose resected from %u views, cost %.6f -> %.6f (status %u)\n", kf + 1, n, report[0], report[1], st);
+    }
+    line = buf;
+    return 0;
   }
 };
 

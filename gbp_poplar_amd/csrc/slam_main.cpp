@@ -21,6 +21,8 @@ static int run(const cli::Options& o, cli::Problem& P, cli::RankCtx& rk) {
   if (const int rc = cli::create_rank_ctx(o, P, rk, &ctx)) return rc;
   cli::Seeder seeder;
   if (o.triangulate && seeder.start(o, P)) { gbp_destroy(ctx); return 1; }
+  cli::Resecter resecter;       // --kf_init resect
+  if (o.kf_resect && resecter.start(o, P)) { gbp_destroy(ctx); return 1; }
   const gbp_state_in in = cli::state_in(P);
   CLI_CHECK(ctx, gbp_upload(ctx, &in));
   cli::phases().mark("upload_s");
@@ -74,10 +76,20 @@ static int run(const cli::Options& o, cli::Problem& P, cli::RankCtx& rk) {
       else banner();
       CLI_CHECK(ctx, gbp_read_priors(ctx, &po));
       CLI_CHECK(ctx, gbp_read(ctx, &rb.out));
+      std::string kf_line;      // --kf_init resect: what became of the new keyframe's pose guess
+      const auto refine = [&](float* guess) {
+        return resecter.keyframe(P, data_counter, rb.cbe.data(), rb.cbl.data(), rb.lbe.data(), rb.lbl.data(), lmk_active.data(), guess, kf_line);
+      };
       if (o.triangulate) {
-        if (seeder.keyframe(P, data_counter, rb.cbe.data(), rb.cbl.data(), rb.lbe.data(), rb.lbl.data())) { gbp_destroy(ctx); return 1; }
+        if (seeder.keyframe(P, data_counter, rb.cbe.data(), rb.cbl.data(), rb.lbe.data(), rb.lbl.data(),
+                            o.kf_resect ? std::function<int(float*)>(refine) : std::function<int(float*)>())) { gbp_destroy(ctx); return 1; }
       } else {
         gbp_slam_initialise_new_kf(data_counter, rb.cbe.data(), rb.cbl.data(), P.cpl.data(), P.cpe.data());
+        if (o.kf_resect && refine(nullptr)) { gbp_destroy(ctx); return 1; }
+      }
+      if (o.kf_resect) {
+        if (bursts) lines.post([kf_line] { std::cout << kf_line; });
+        else std::cout << kf_line;
       }
       std::fill(P.count.begin(), P.count.end(), -15);           // literal, slam.cpp:1039-1041
       gbp_kf_update up{};
@@ -180,7 +192,7 @@ static int run(const cli::Options& o, cli::Problem& P, cli::RankCtx& rk) {
 int main(int argc, char** argv) {
   cli::Options o;
   const int pr = cli::parse(argc, argv, /*slam=*/true, o);
-  if (pr) return pr == 1 ? 0 : 1;
+  if (pr) return pr == 1 ? 0 : pr == 3 ? 2 : 1;
   cli::Problem P;
   const bool one_process = cli::round_up_pow2(std::max(1, o.gpus)) == 1 && !o.force_sharded;
   if (one_process) cli::prime_address_space();      // (an empirical 40 - 60 ms off the process's exit: see its comment)

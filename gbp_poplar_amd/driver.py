@@ -158,14 +158,56 @@ def run_ba(engine, state, opts, n_iters=None, eval_every=1, log=None):
     return traj
 
 
-def run_slam(engine, host, bal, state, extra, opts, iters_between_kfs=None, max_iters=None, eval_every=1, log=None, lmk_init="file"):
+def _resect_keyframe(host, bal, state, opts, extra, bel, pri, guess, active, laf, lwf, kf, log):
+    """kf_init = "resect": camera kf alone from the pose guess (the copy of its predecessor), against the belief means of the landmarks
+    that were mapped before this keyframe, over the updated active_flag.  A resected pose replaces the prior eta of camera kf (prior
+    Lambda . pose, the Lambda stays the file's) and is returned; otherwise the copy stands and the guess is returned."""
+    from . import resect
+    C, L = int(bal["n_cams"]), int(bal["n_lmks"])
+    if "cam_index" not in extra:
+        extra["cam_index"] = resect.index(bal["cam_id"], C)
+    with np.errstate(all="ignore"):      # (a landmark that was never active has a zero belief: its mean is not used)
+        cam_mean, lmk_mean = host.belief_means(C, L, bel["cam_beliefs_eta"], bel["cam_beliefs_lambda"], bel["lmk_beliefs_eta"],
+                                               bel["lmk_beliefs_lambda"])
+    cam_mean, lmk_mean = cam_mean.astype(np.float32), lmk_mean.astype(np.float32)
+    if guess is None:      # the copy: the belief mean of the camera before
+        guess = cam_mean[6 * (kf - 1):6 * kf].copy()
+    cam_mean[6 * kf:6 * kf + 6] = guess
+    select = np.zeros(C, np.uint32)
+    select[kf] = 1
+    r = resect.cameras(bal["lmk_id"], *extra["cam_index"], k_matrix(bal), cam_mean, lmk_mean, state["measurements"], active_flag=active,
+                       lmk_use=((laf != 0) & (lwf == 0)).astype(np.uint32), select=select,
+                       options=resect.default_options(reproj_meas_var=opts.reproj_meas_var), priors_lambda=pri["cam_priors_lambda"],
+                       out={"cam_priors_eta": pri["cam_priors_eta"]})
+    st, n = int(r["status"][kf]), int(r["n_views"][kf])
+    if st & resect.NOT_RESECTED:
+        if log:
+            log("Keyframe %d: pose copied from keyframe %d (resection status %d, %d views)" % (kf + 1, kf, st, n))
+        return guess
+    pri["cam_priors_eta"] = r["cam_priors_eta"]
+    if log:
+        log("Keyframe %d: pose resected from %d views, cost %.6f -> %.6f (status %d)" % (kf + 1, n, r["report"][4 * kf], r["report"][4 * kf + 1], st))
+    return r["cam_mean"][6 * kf:6 * kf + 6]
+
+
+KF_INIT = ("copy", "resect")
+
+
+def run_slam(engine, host, bal, state, extra, opts, iters_between_kfs=None, max_iters=None, eval_every=1, log=None, lmk_init="file",
+             kf_init="copy"):
     """slam.cpp:1013-1103.
 
     lmk_init = "triangulate", at every keyframe: the new camera's prior eta comes from seed.keyframe (the bits of
     slam_initialise_new_kf), and the landmarks this keyframe activated are seeded from every now-active observation, at the belief
-    means of the cameras so far and the new camera's pose guess; every other prior passes through."""
+    means of the cameras so far and the new camera's pose guess; every other prior passes through.
+
+    kf_init = "resect", at every keyframe: the new camera's pose guess — the copy of its predecessor — is refined against the landmarks
+    mapped so far (resect.cameras: _resect_keyframe); its prior eta, and with lmk_init = "triangulate" the pose the new landmarks are
+    seeded at, come from the resected pose.  Runs on the GPU, through host arrays."""
     if lmk_init not in LMK_INIT:
         raise ValueError("lmk_init: expected one of %s, got %r" % (LMK_INIT, lmk_init))
+    if kf_init not in KF_INIT:
+        raise ValueError("kf_init: expected one of %s, got %r" % (KF_INIT, kf_init))
     C, L, E = int(bal["n_cams"]), int(bal["n_lmks"]), int(bal["n_edges"])
     ibk = opts.iters_between_kfs if iters_between_kfs is None else iters_between_kfs
     steps = int(opts.steps)
@@ -199,6 +241,8 @@ def run_slam(engine, host, bal, state, extra, opts, iters_between_kfs=None, max_
                                                              pri["cam_priors_lambda"], pri["cam_priors_eta"])
                 cam_mean = host.belief_means(C, L, bel["cam_beliefs_eta"], bel["cam_beliefs_lambda"], bel["lmk_beliefs_eta"],
                                              bel["lmk_beliefs_lambda"])[0].astype(np.float32)
+                if kf_init == "resect":
+                    guess = _resect_keyframe(host, bal, state, opts, extra, bel, pri, guess, active, laf, lwf, data_counter + 1, log)
                 cam_mean[6 * (data_counter + 1):6 * (data_counter + 2)] = guess
                 start, edges = extra["lmk_index"] if "lmk_index" in extra else seed.index(bal["lmk_id"], L)
                 s = seed.landmarks(bal["cam_id"], start, edges, k_matrix(bal), cam_mean, state["measurements"], active_flag=active,
@@ -208,6 +252,8 @@ def run_slam(engine, host, bal, state, extra, opts, iters_between_kfs=None, max_
             else:
                 host.slam_initialise_new_kf(data_counter, bel["cam_beliefs_eta"], bel["cam_beliefs_lambda"],
                                             pri["cam_priors_lambda"], pri["cam_priors_eta"])
+                if kf_init == "resect":
+                    _resect_keyframe(host, bal, state, opts, extra, bel, pri, None, active, laf, lwf, data_counter + 1, log)
             engine.new_keyframe({"damping_count": np.full(E, -15, np.int32),   # literal -15, slam.cpp:1040
                                  "cam_priors_eta": pri["cam_priors_eta"], "cam_priors_lambda": pri["cam_priors_lambda"],
                                  "lmk_priors_eta": pri["lmk_priors_eta"], "lmk_priors_lambda": pri["lmk_priors_lambda"],
