@@ -1,6 +1,6 @@
 # Top-level build for C/C++ users (the Python entry point __graft_entry__.build() does the same).
 #   make            libgbp_mi355x.so (HIP kernels + C-ABI + host helpers, gfx950), libgbp_mi355x_post.so (the solution readout),
-#                   libgbp_mi355x_seed.so (landmark / keyframe seeding), libgbp_mi355x_resect.so (camera resection) and bin/ba,
+#                   libgbp_mi355x_seed.so (landmark / keyframe seeding), libgbp_mi355x_resect.so (camera resection), libgbp_mi355x_locate.so (camera location) and bin/ba,
 #                   bin/slam, bin/bal_convert
 #   make oracle     the CPU oracle (test infrastructure)
 #   make test       CPU test suite
@@ -10,8 +10,8 @@ ARCH    ?= gfx950
 PKG     := gbp_poplar_amd
 CSRC    := $(PKG)/csrc
 LIB     := $(PKG)/libgbp_mi355x.so
-# the libraries without a ctx (post: the solution readout, seed: landmark / keyframe seeding, resect: camera resection): directory $(PKG)/<name>, one rule below
-SATELLITES := post seed resect
+# the libraries without a ctx (post: the solution readout, seed: landmark / keyframe seeding, resect: camera resection, locate: camera location with no pose guess): directory $(PKG)/<name>, one rule below
+SATELLITES := post seed resect locate
 SAT_LIBS := $(SATELLITES:%=$(PKG)/libgbp_mi355x_%.so)
 HIPFLAGS := -O3 -std=c++17 -fPIC -ffp-contract=off -fvisibility=hidden -Wall -Wno-unused-function
 OBJDIR  := $(PKG)/_obj/make
@@ -49,10 +49,12 @@ $(PKG)/libgbp_mi355x_$(1).so: $(OBJDIR)/gbp_$(1).o $(PKG)/$(1)/gbp_$(1)_exports.
 	$$(HIPCC) -shared -o $$@ --offload-arch=$$(ARCH) $$< -Wl,--version-script=$(PKG)/$(1)/gbp_$(1)_exports.map
 endef
 $(foreach s,$(SATELLITES),$(eval $(call SATELLITE_RULES,$(s))))
+# locate_math.hpp includes the resection's Graph, filtering and camera_range
+$(OBJDIR)/gbp_locate.o: $(PKG)/resect/resect_math.hpp
 
-$(PKG)/bin/%: $(CSRC)/%_main.cpp $(CSRC)/cli_common.hpp $(CSRC)/gbp_transport.hpp $(CSRC)/gbp_metric_gather.hpp include/gbp_mi355x.h include/gbp_mi355x_multi.h include/gbp_mi355x_compat.h include/gbp_mi355x_post.h include/gbp_mi355x_seed.h include/gbp_mi355x_resect.h $(LIB) $(SAT_LIBS)
+$(PKG)/bin/%: $(CSRC)/%_main.cpp $(CSRC)/cli_common.hpp $(CSRC)/gbp_transport.hpp $(CSRC)/gbp_metric_gather.hpp include/gbp_mi355x.h include/gbp_mi355x_multi.h include/gbp_mi355x_compat.h include/gbp_mi355x_post.h include/gbp_mi355x_seed.h include/gbp_mi355x_resect.h include/gbp_mi355x_locate.h $(LIB) $(SAT_LIBS)
 	@mkdir -p $(PKG)/bin
-	$(CXX) -o $@ -O2 -std=c++17 -ffp-contract=off -pthread -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include $< -L$(PKG) -lgbp_mi355x -lgbp_mi355x_post -lgbp_mi355x_seed -lgbp_mi355x_resect \
+	$(CXX) -o $@ -O2 -std=c++17 -ffp-contract=off -pthread -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include $< -L$(PKG) -lgbp_mi355x -lgbp_mi355x_post -lgbp_mi355x_seed -lgbp_mi355x_resect -lgbp_mi355x_locate \
 		-L$(ROCM)/lib -lamdhip64 -Wl,-rpath,$(ROCM)/lib '-Wl,-rpath,$$ORIGIN/..'
 
 oracle:

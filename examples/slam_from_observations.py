@@ -1,7 +1,9 @@
 """SLAM from observations and rough camera poses alone: the file's `points` section is zeroed before use, every landmark prior comes
 from seed.landmarks (triangulated where the views allow, placed on the ray of the first observation otherwise), every new keyframe's
 prior from seed.keyframe — on device tensors, in place in what read_priors(device=True) returned, no host copy of the state.  The same
-loop with host arrays runs beside it; the printed metrics are equal.     python examples/slam_from_observations.py [sequence]"""
+loop with host arrays runs beside it; the printed metrics are equal.  Then the driver's loop from the same start with
+kf_init="locate": every new keyframe is first found with no pose guess among the landmarks mapped so far (locate.cameras), then resected
+over the observations that agree.     python examples/slam_from_observations.py [sequence]"""
 import os
 import sys
 
@@ -54,3 +56,11 @@ if __name__ == "__main__":
     print("device loop: mean reprojection error %.9f cost %.6f" % dev)
     print("host loop:   mean reprojection error %.9f cost %.6f" % host)
     assert dev == host, "the device loop and the host-array loop differ"
+
+    opts = driver.Options()
+    K, state, extra = driver.build_inputs(bal, opts, hostlib, slam=True, lmk_init="triangulate")
+    eng = GbpEngine(bal["cam_id"], bal["lmk_id"], int(bal["n_cams"]), int(bal["n_lmks"]), K)
+    traj = driver.run_slam(eng, hostlib, bal, state, extra, opts, iters_between_kfs=25, max_iters=5 * 25, lmk_init="triangulate", kf_init="locate",
+                           log=lambda line: print(line) if line.startswith("Keyframe ") else None)
+    eng.close()
+    print("driver, kf_init=locate: mean reprojection error %.9f cost %.6f" % (traj[-1][1], traj[-1][2]))

@@ -6,6 +6,7 @@
                                              gbp_poplar_amd/libgbp_mi355x_post.so  the solution readout (post/, include/gbp_mi355x_post.h)
                                              gbp_poplar_amd/libgbp_mi355x_seed.so  landmark / keyframe seeding (seed/, include/gbp_mi355x_seed.h)
                                              gbp_poplar_amd/libgbp_mi355x_resect.so  camera resection (resect/, include/gbp_mi355x_resect.h)
+                                             gbp_poplar_amd/libgbp_mi355x_locate.so  camera location with no pose guess (locate/, include/gbp_mi355x_locate.h)
     python -m gbp_poplar_amd.build --experiments
                                           -> gbp_poplar_amd/libgbp_mi355x_exp.so   + csrc/experiments/: timing ablations / mapping
                                                                                    experiments (profiles/*.py only)
@@ -34,6 +35,7 @@ EXP_LIB = os.path.join(HERE, "libgbp_mi355x_exp.so")    # + timing ablations and
 POST_LIB = os.path.join(HERE, "libgbp_mi355x_post.so")  # the solution readout
 SEED_LIB = os.path.join(HERE, "libgbp_mi355x_seed.so")  # landmark / keyframe seeding
 RESECT_LIB = os.path.join(HERE, "libgbp_mi355x_resect.so")  # camera resection against the map
+LOCATE_LIB = os.path.join(HERE, "libgbp_mi355x_locate.so")  # camera location with no pose guess
 # The libraries without a ctx, each one HIP translation unit with the product's flags and an export map of its own:
 # name (= its directory under _obj/) -> (source directory, source, export map, library).  stateless/ is what they share.
 STATELESS = os.path.join(HERE, "stateless")
@@ -41,7 +43,9 @@ SATELLITES = {
     "post": (os.path.join(HERE, "post"), "gbp_post.hip", "gbp_post_exports.map", POST_LIB),
     "seed": (os.path.join(HERE, "seed"), "gbp_seed.hip", "gbp_seed_exports.map", SEED_LIB),
     "resect": (os.path.join(HERE, "resect"), "gbp_resect.hip", "gbp_resect_exports.map", RESECT_LIB),
+    "locate": (os.path.join(HERE, "locate"), "gbp_locate.hip", "gbp_locate_exports.map", LOCATE_LIB),
 }
+SATELLITE_USES = {"locate": ["resect"]}      # the satellites whose headers a satellite includes
 BIN = os.path.join(HERE, "bin")
 ARCH = "gfx950"
 # -fvisibility=hidden: the library exports the gbp_* functions of include/*.h (GBP_API) and nothing else
@@ -132,7 +136,8 @@ def _recipes(variants, satellites):
         out[lib] = (v, [os.path.join(CSRC, s) for s in LIB_SRCS], hdr, defines, os.path.join(CSRC, "gbp_exports.map"), ["-ldl", "-pthread"])
     for n in satellites:    # stale against its own directory, stateless/ and the core's headers; the map only links
         src_dir, src, export_map, lib = SATELLITES[n]
-        own = [os.path.join(d, f) for d in (src_dir, STATELESS) for f in os.listdir(d) if f != export_map]
+        used = [SATELLITES[u][0] for u in SATELLITE_USES.get(n, [])]
+        own = [os.path.join(d, f) for d in [src_dir, STATELESS] + used for f in os.listdir(d) if f != export_map]
         out[lib] = (n, [os.path.join(src_dir, src)], hdr + own, [], os.path.join(src_dir, export_map), [])
     return out
 
@@ -164,16 +169,16 @@ def build(force=False, verbose=False, test_hooks=True, variants=None):
     _build_libs(list(variants), force, verbose, list(SATELLITES))
     os.makedirs(BIN, exist_ok=True)
     inc = os.path.join(HERE, "..", "include")
-    cli_deps = [os.path.join(CSRC, f) for f in ("cli_common.hpp", "gbp_transport.hpp", "gbp_metric_gather.hpp")] + [os.path.join(inc, f) for f in os.listdir(inc)] + [LIB, POST_LIB, SEED_LIB, RESECT_LIB]
+    cli_deps = [os.path.join(CSRC, f) for f in ("cli_common.hpp", "gbp_transport.hpp", "gbp_metric_gather.hpp")] + [os.path.join(inc, f) for f in os.listdir(inc)] + [LIB, POST_LIB, SEED_LIB, RESECT_LIB, LOCATE_LIB]
     for name, src in CLI_SRCS.items():
         path = os.path.join(CSRC, src)
         exe = os.path.join(BIN, name)
         if os.path.exists(path) and (force or _stale(exe, cli_deps + [path])):
             # the CLIs are plain C++ on top of the C-ABI: host compiler, linked against the in-tree library
-            # (ba / slam: + the readout, seeding and resection libraries, and the HIP runtime for the device arrays --cov_file / --lmk_init /
+            # (ba / slam: + the readout, seeding, resection and location libraries, and the HIP runtime for the device arrays --cov_file / --lmk_init /
             # --kf_init hand them)
             rocm = os.path.dirname(os.path.dirname(os.path.realpath(hipcc())))
-            post = [] if name == "bal_convert" else ["-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), "-lgbp_mi355x_post", "-lgbp_mi355x_seed", "-lgbp_mi355x_resect",
+            post = [] if name == "bal_convert" else ["-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"), "-lgbp_mi355x_post", "-lgbp_mi355x_seed", "-lgbp_mi355x_resect", "-lgbp_mi355x_locate",
                                                      "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath," + os.path.join(rocm, "lib")]
             cmd = [shutil.which("g++") or "g++", "-o", exe, "-O2", "-std=c++17", "-ffp-contract=off", "-pthread", path,
                    "-L" + HERE, "-lgbp_mi355x"] + post + ["-Wl,-rpath,$ORIGIN/.."]

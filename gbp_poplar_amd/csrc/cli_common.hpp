@@ -14,7 +14,9 @@
 //   * `--lmk_init triangulate` takes the landmarks' prior means and strengths from the observations and the camera prior means
 //     (libgbp_mi355x_seed.so) instead of the file's `points` section, which is then not used at all;
 //   * slam's `--kf_init resect` refines every new keyframe's pose guess — the reference's copy of its predecessor — against the
-//     landmarks mapped so far (libgbp_mi355x_resect.so) before its prior is set; the default, `copy`, is the reference's.
+//     landmarks mapped so far (libgbp_mi355x_resect.so) before its prior is set; `--kf_init locate` first finds the pose with no
+//     guess at all, and the observations that agree with it (libgbp_mi355x_locate.so), and resects from there over those
+//     observations — where that fails the keyframe takes the `resect` path; the default, `copy`, is the reference's.
 #pragma once
 #include "../../include/gbp_mi355x.h"
 #include "../../include/gbp_mi355x_multi.h"       // --ipus N: one forked rank per GPU
@@ -23,6 +25,7 @@
 #include "../../include/gbp_mi355x_post.h"        // --cov_file: means and marginal covariances of the beliefs (libgbp_mi355x_post.so)
 #include "../../include/gbp_mi355x_seed.h"        // --lmk_init triangulate: landmark priors from observations (libgbp_mi355x_seed.so)
 #include "../../include/gbp_mi355x_resect.h"      // slam --kf_init resect: the new keyframe's pose from the mapped landmarks (libgbp_mi355x_resect.so)
+#include "../../include/gbp_mi355x_locate.h"      // slam --kf_init locate: the new keyframe's pose with no guess (libgbp_mi355x_locate.so)
 #include "../../include/gbp_mi355x_compat.h"      // MetricPipe: the metric in two halves (gbp_iterate_eval / gbp_eval_end), so that printing overlaps the next iterations
 
 #include <hip/hip_runtime_api.h>                  // --cov_file: the device arrays the readout works on (nothing else here touches HIP)
@@ -112,7 +115,8 @@ struct Options {
   std::string out_file;         // --out_file: write the refined problem (belief means) in the input's format
   std::string cov_file;         // --cov_file: write every variable's mean and marginal covariance (gbp_post_moments)
   bool triangulate = false;     // --lmk_init triangulate (default: file)
-  bool kf_resect = false;       // slam --kf_init resect (default: copy)
+  bool kf_resect = false;       // slam --kf_init resect or locate (default: copy)
+  bool kf_locate = false;       // slam --kf_init locate: location in front of the resection
   bool force_sharded = false;   // --force_sharded: run the multi-rank code path (fork, shard ctx, communicator) with one rank
 };
 
@@ -144,7 +148,8 @@ inline void usage(bool slam) {
                "  --lmk_init arg (=file)         landmark prior means and strengths: file (the file's points) | triangulate (from the\n"
                "                                 observations and the camera prior means; the file's points are not used; one GPU)\n";
   if (slam) std::cout << "  --kf_init arg (=copy)          a new keyframe's pose guess: copy (its predecessor's pose) | resect (the copy, refined\n"
-                         "                                 against the landmarks mapped so far; one GPU)\n";
+                         "                                 against the landmarks mapped so far; one GPU) | locate (found with no guess\n"
+                         "                                 among wrong matches, then resected over the matches that agree; one GPU)\n";
   std::cout << "  --out_file arg                write the refined cameras / landmarks (belief means) in the input's format\n"
                "  --cov_file arg                 write every camera's / landmark's mean and marginal covariance: line 1 `C L`, then per camera\n"
                "                                 6 + 36 values, per landmark 3 + 9 values (covariances row-major)\n";
@@ -194,8 +199,9 @@ inline int parse(int argc, char** argv, bool slam, Options& o) {
         o.triangulate = v == "triangulate";
       }
       else if (k == "kf_init" && slam) {
-        if (v != "copy" && v != "resect") { std::cerr << "--kf_init: expected copy or resect\n"; return 3; }
-        o.kf_resect = v == "resect";
+        if (v != "copy" && v != "resect" && v != "locate") { std::cerr << "--kf_init: expected copy, resect or locate\n"; return 3; }
+        o.kf_resect = v == "resect" || v == "locate";
+        o.kf_locate = v == "locate";
       }
       else if (k == "out_file") o.out_file = v;
       else if (k == "cov_file") o.cov_file = v;
@@ -213,7 +219,7 @@ inline int parse(int argc, char** argv, bool slam, Options& o) {
   if (o.bal_file.empty()) { std::cerr << "the option '--bal_file' is required but missing\n"; return 2; }
   if (o.triangulate && o.av_depth_on) { std::cerr << "--lmk_init triangulate and --avdepth_on both place the landmarks: choose one\n"; return 2; }
   if (o.triangulate && (o.gpus > 1 || o.force_sharded)) { std::cerr << "--lmk_init triangulate runs on one GPU\n"; return 2; }
-  if (o.kf_resect && (o.gpus > 1 || o.force_sharded)) { std::cerr << "--kf_init resect runs on one GPU\n"; return 3; }
+  if (o.kf_resect && (o.gpus > 1 || o.force_sharded)) { std::cerr << "--kf_init " << (o.kf_locate ? "locate" : "resect") << " runs on one GPU\n"; return 3; }
   return 0;
 }
 
@@ -432,6 +438,21 @@ struct Seeder {
   }
 };
 
+struct Resecter;
+// ---- slam --kf_init locate: in front of the resection, the new keyframe's pose with no guess (include/gbp_mi355x_locate.h) ----
+// Works on the Resecter's device arrays, once keyframe() has filled them; its own: the mask, the count, the masked active flags.
+// located(): 1 the camera was located and resected from there over the observations that agree (eta, guess and `line` are set),
+// 0 it was not (the Resecter's arrays hold again what they held: the keyframe takes the resect path), -1 a call failed.
+struct Locator {
+  gbp_locate_options opts{};
+  char* base = nullptr;
+  uint32_t *d_inlier = nullptr, *d_ninl = nullptr, *d_masked = nullptr;
+  std::vector<uint32_t> inlier, masked;
+  ~Locator() { if (base) (void)hipFree(base); }
+  int start(const Resecter& R);
+  int located(Resecter& R, Problem& P, uint32_t kf, float* guess, std::string& line);
+};
+
 // ---- slam --kf_init resect: the new keyframe's pose from the landmarks mapped so far (include/gbp_mi355x_resect.h) -------
 // The device arrays of the resection call, allocated once; blocking copies on the default stream, as Seeder.  keyframe(): camera
 // data_counter + 1 alone, from its pose guess (`guess` [6], or the belief mean of camera data_counter where it is NULL), against the
@@ -439,6 +460,7 @@ struct Seeder {
 // gbp_slam_update_flags left them), over the updated active flags.  P.cpe / P.cpl hold the priors with the COPIED eta of the new
 // camera: a resected pose replaces that eta (prior Lambda . pose) and the guess; otherwise both stand.  `line` says which happened.
 struct Resecter {
+  Locator* locator = nullptr;   // --kf_init locate
   uint32_t C = 0, L = 0, E = 0;
   std::vector<uint32_t> cam_start, cam_edges, lmk_use, select;
   std::vector<float> cam_mean, lmk_mean;
@@ -496,6 +518,10 @@ struct Resecter {
     if (!up(d_cam_mean, cam_mean.data(), 6 * (size_t)C) || !up(d_lmk_mean, lmk_mean.data(), 3 * (size_t)L) || !up(d_active, P.active.data(), E) ||
         !up(d_use, lmk_use.data(), L) || !up(d_select, select.data(), C) || !up(d_cpl, P.cpl.data(), 36 * (size_t)C) || !up(d_cpe, P.cpe.data(), 6 * (size_t)C))
       return 1;
+    if (locator) {
+      const int done = locator->located(*this, P, kf, guess, line);
+      if (done) return done < 0 ? 1 : 0;
+    }
     if (!resect_ok(gbp_resect_cameras(nullptr, C, L, E, d_lmk_id, d_start, d_edges, P.K.data(), d_lmk_mean, d_meas, d_active, d_use, d_select, &opts,
                                       d_cam_mean, d_cpl, d_cpe, nullptr, d_report, d_status, d_views)))
       return 1;
@@ -515,6 +541,47 @@ struct Resecter {
     return 0;
   }
 };
+
+inline int Locator::start(const Resecter& R) {
+  gbp_locate_default_options(&opts);
+  const size_t e_bytes = (4 * (size_t)R.E + 255) & ~(size_t)255, c_bytes = (4 * (size_t)R.C + 255) & ~(size_t)255;
+  if (!Resecter::ok(hipMalloc(reinterpret_cast<void**>(&base), 2 * e_bytes + c_bytes), "hipMalloc")) return 1;
+  d_inlier = reinterpret_cast<uint32_t*>(base); d_masked = reinterpret_cast<uint32_t*>(base + e_bytes); d_ninl = reinterpret_cast<uint32_t*>(base + 2 * e_bytes);
+  inlier.resize(R.E); masked.resize(R.E);
+  return 0;
+}
+
+inline int Locator::located(Resecter& R, Problem& P, uint32_t kf, float* guess, std::string& line) {
+  const auto locate_ok = [](int rc) {
+    if (rc != GBP_OK) std::cerr << "--kf_init locate: " << gbp_locate_last_error() << "\n";
+    return rc == GBP_OK;
+  };
+  if (R.E && !Resecter::ok(hipMemset(d_inlier, 0, 4 * (size_t)R.E), "hipMemset")) return -1;
+  if (!locate_ok(gbp_locate_cameras(nullptr, R.C, R.L, R.E, R.d_lmk_id, R.d_start, R.d_edges, P.K.data(), R.d_lmk_mean, R.d_meas, R.d_active, R.d_use,
+                                    R.d_select, &opts, R.d_cam_mean, d_inlier, nullptr, R.d_status, R.d_views, d_ninl)))
+    return -1;
+  uint32_t st = 0, n = 0, n_in = 0;
+  if (!R.down(&st, R.d_status + kf, 1)) return -1;
+  if (st & (GBP_LOCATE_NO_VIEW | GBP_LOCATE_FEW_VIEWS | GBP_LOCATE_FEW_INLIERS | GBP_LOCATE_NO_HYPOTHESIS)) return 0;      // (nothing of the pose arrays was written)
+  if (!R.down(&n, R.d_views + kf, 1) || !R.down(&n_in, d_ninl + kf, 1) || !R.down(inlier.data(), d_inlier, R.E)) return -1;
+  for (uint32_t e = 0; e < R.E; ++e) masked[e] = P.active[e] == 1u && inlier[e] == 1u;
+  if (!R.up(d_masked, masked.data(), R.E)) return -1;
+  if (!Resecter::resect_ok(gbp_resect_cameras(nullptr, R.C, R.L, R.E, R.d_lmk_id, R.d_start, R.d_edges, P.K.data(), R.d_lmk_mean, R.d_meas, d_masked, R.d_use,
+                                              R.d_select, &R.opts, R.d_cam_mean, R.d_cpl, R.d_cpe, nullptr, R.d_report, R.d_status, R.d_views)))
+    return -1;
+  uint32_t rst = 0;
+  if (!R.down(&rst, R.d_status + kf, 1)) return -1;
+  if (rst & (GBP_RESECT_NO_VIEW | GBP_RESECT_FEW_VIEWS | GBP_RESECT_NONFINITE | GBP_RESECT_STALLED))      // back to what keyframe() uploaded
+    return R.up(R.d_cam_mean, R.cam_mean.data(), 6 * (size_t)R.C) && R.up(R.d_cpe, P.cpe.data(), 6 * (size_t)R.C) ? 0 : -1;
+  float report[4] = {0.f, 0.f, 0.f, 0.f};
+  if (!R.down(report, R.d_report + 4 * (size_t)kf, 4) || !R.down(P.cpe.data() + 6 * (size_t)kf, R.d_cpe + 6 * (size_t)kf, 6) ||
+      (guess && !R.down(guess, R.d_cam_mean + 6 * (size_t)kf, 6)))
+    return -1;
+  char buf[240];
+  std::snprintf(buf, sizeof(buf), "Keyframe %u: pose located from %u of %u views and resected, cost %.6f -> %.6f (status %u)\n", kf + 1, n_in, n, report[0], report[1], rst);
+  line = buf;
+  return 1;
+}
 
 // ---- one process per GPU (`--ipus N` / `--gpus N`) -------------------------------------------------------------------
 struct RankCtx {

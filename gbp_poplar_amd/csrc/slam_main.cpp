@@ -22,7 +22,12 @@ static int run(const cli::Options& o, cli::Problem& P, cli::RankCtx& rk) {
   cli::Seeder seeder;
   if (o.triangulate && seeder.start(o, P)) { gbp_destroy(ctx); return 1; }
   cli::Resecter resecter;       // --kf_init resect
+  cli::Locator locator;         // --kf_init locate: in front of it
   if (o.kf_resect && resecter.start(o, P)) { gbp_destroy(ctx); return 1; }
+  if (o.kf_locate) {
+    if (locator.start(resecter)) { gbp_destroy(ctx); return 1; }
+    resecter.locator = &locator;
+  }
   const gbp_state_in in = cli::state_in(P);
   CLI_CHECK(ctx, gbp_upload(ctx, &in));
   cli::phases().mark("upload_s");

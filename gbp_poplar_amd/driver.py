@@ -158,10 +158,14 @@ def run_ba(engine, state, opts, n_iters=None, eval_every=1, log=None):
     return traj
 
 
-def _resect_keyframe(host, bal, state, opts, extra, bel, pri, guess, active, laf, lwf, kf, log):
+def _resect_keyframe(host, bal, state, opts, extra, bel, pri, guess, active, laf, lwf, kf, log, locate_first=False):
     """kf_init = "resect": camera kf alone from the pose guess (the copy of its predecessor), against the belief means of the landmarks
     that were mapped before this keyframe, over the updated active_flag.  A resected pose replaces the prior eta of camera kf (prior
-    Lambda . pose, the Lambda stays the file's) and is returned; otherwise the copy stands and the guess is returned."""
+    Lambda . pose, the Lambda stays the file's) and is returned; otherwise the copy stands and the guess is returned.
+
+    locate_first (kf_init = "locate"): before that, locate.cameras finds the camera with no guess over the same observations; if it does,
+    the resection starts from the located pose over the active observations that agree with it, and its result is taken.  If the
+    camera is not located, or that resection is NOT_RESECTED, everything above happens as without it."""
     from . import resect
     C, L = int(bal["n_cams"]), int(bal["n_lmks"])
     if "cam_index" not in extra:
@@ -175,6 +179,25 @@ def _resect_keyframe(host, bal, state, opts, extra, bel, pri, guess, active, laf
     cam_mean[6 * kf:6 * kf + 6] = guess
     select = np.zeros(C, np.uint32)
     select[kf] = 1
+    if locate_first:
+        from . import locate
+        lmk_use = ((laf != 0) & (lwf == 0)).astype(np.uint32)
+        loc = locate.cameras(bal["lmk_id"], *extra["cam_index"], k_matrix(bal), lmk_mean, state["measurements"], active_flag=active, lmk_use=lmk_use,
+                             select=select)
+        if not int(loc["status"][kf]) & locate.NOT_LOCATED:
+            start = cam_mean.copy()
+            start[6 * kf:6 * kf + 6] = loc["cam_mean"][6 * kf:6 * kf + 6]
+            agreeing = ((np.asarray(active) == 1) & (loc["inlier"] == 1)).astype(np.uint32)
+            r = resect.cameras(bal["lmk_id"], *extra["cam_index"], k_matrix(bal), start, lmk_mean, state["measurements"], active_flag=agreeing,
+                               lmk_use=lmk_use, select=select, options=resect.default_options(reproj_meas_var=opts.reproj_meas_var),
+                               priors_lambda=pri["cam_priors_lambda"], out={"cam_priors_eta": pri["cam_priors_eta"]})
+            st = int(r["status"][kf])
+            if not st & resect.NOT_RESECTED:
+                pri["cam_priors_eta"] = r["cam_priors_eta"]
+                if log:
+                    log("Keyframe %d: pose located from %d of %d views and resected, cost %.6f -> %.6f (status %d)"
+                        % (kf + 1, loc["n_inliers"][kf], loc["n_views"][kf], r["report"][4 * kf], r["report"][4 * kf + 1], st))
+                return r["cam_mean"][6 * kf:6 * kf + 6]
     r = resect.cameras(bal["lmk_id"], *extra["cam_index"], k_matrix(bal), cam_mean, lmk_mean, state["measurements"], active_flag=active,
                        lmk_use=((laf != 0) & (lwf == 0)).astype(np.uint32), select=select,
                        options=resect.default_options(reproj_meas_var=opts.reproj_meas_var), priors_lambda=pri["cam_priors_lambda"],
@@ -190,7 +213,7 @@ def _resect_keyframe(host, bal, state, opts, extra, bel, pri, guess, active, laf
     return r["cam_mean"][6 * kf:6 * kf + 6]
 
 
-KF_INIT = ("copy", "resect")
+KF_INIT = ("copy", "resect", "locate")
 
 
 def run_slam(engine, host, bal, state, extra, opts, iters_between_kfs=None, max_iters=None, eval_every=1, log=None, lmk_init="file",
@@ -203,7 +226,11 @@ def run_slam(engine, host, bal, state, extra, opts, iters_between_kfs=None, max_
 
     kf_init = "resect", at every keyframe: the new camera's pose guess — the copy of its predecessor — is refined against the landmarks
     mapped so far (resect.cameras: _resect_keyframe); its prior eta, and with lmk_init = "triangulate" the pose the new landmarks are
-    seeded at, come from the resected pose.  Runs on the GPU, through host arrays."""
+    seeded at, come from the resected pose.  Runs on the GPU, through host arrays.
+
+    kf_init = "locate": the same, with locate.cameras in front — the new camera is first found with no guess at all among the landmarks
+    mapped so far, wrong matches tolerated, and resected from there over the observations that agree; a keyframe where that fails
+    takes the "resect" path unchanged."""
     if lmk_init not in LMK_INIT:
         raise ValueError("lmk_init: expected one of %s, got %r" % (LMK_INIT, lmk_init))
     if kf_init not in KF_INIT:
@@ -241,8 +268,9 @@ def run_slam(engine, host, bal, state, extra, opts, iters_between_kfs=None, max_
                                                              pri["cam_priors_lambda"], pri["cam_priors_eta"])
                 cam_mean = host.belief_means(C, L, bel["cam_beliefs_eta"], bel["cam_beliefs_lambda"], bel["lmk_beliefs_eta"],
                                              bel["lmk_beliefs_lambda"])[0].astype(np.float32)
-                if kf_init == "resect":
-                    guess = _resect_keyframe(host, bal, state, opts, extra, bel, pri, guess, active, laf, lwf, data_counter + 1, log)
+                if kf_init != "copy":
+                    guess = _resect_keyframe(host, bal, state, opts, extra, bel, pri, guess, active, laf, lwf, data_counter + 1, log,
+                                             kf_init == "locate")
                 cam_mean[6 * (data_counter + 1):6 * (data_counter + 2)] = guess
                 start, edges = extra["lmk_index"] if "lmk_index" in extra else seed.index(bal["lmk_id"], L)
                 s = seed.landmarks(bal["cam_id"], start, edges, k_matrix(bal), cam_mean, state["measurements"], active_flag=active,
@@ -252,8 +280,8 @@ def run_slam(engine, host, bal, state, extra, opts, iters_between_kfs=None, max_
             else:
                 host.slam_initialise_new_kf(data_counter, bel["cam_beliefs_eta"], bel["cam_beliefs_lambda"],
                                             pri["cam_priors_lambda"], pri["cam_priors_eta"])
-                if kf_init == "resect":
-                    _resect_keyframe(host, bal, state, opts, extra, bel, pri, None, active, laf, lwf, data_counter + 1, log)
+                if kf_init != "copy":
+                    _resect_keyframe(host, bal, state, opts, extra, bel, pri, None, active, laf, lwf, data_counter + 1, log, kf_init == "locate")
             engine.new_keyframe({"damping_count": np.full(E, -15, np.int32),   # literal -15, slam.cpp:1040
                                  "cam_priors_eta": pri["cam_priors_eta"], "cam_priors_lambda": pri["cam_priors_lambda"],
                                  "lmk_priors_eta": pri["lmk_priors_eta"], "lmk_priors_lambda": pri["lmk_priors_lambda"],
