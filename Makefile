@@ -49,8 +49,8 @@ $(PKG)/libgbp_mi355x_$(1).so: $(OBJDIR)/gbp_$(1).o $(PKG)/$(1)/gbp_$(1)_exports.
 	$$(HIPCC) -shared -o $$@ --offload-arch=$$(ARCH) $$< -Wl,--version-script=$(PKG)/$(1)/gbp_$(1)_exports.map
 endef
 $(foreach s,$(SATELLITES),$(eval $(call SATELLITE_RULES,$(s))))
-# locate_math.hpp includes the resection's Graph, filtering and camera_range
-$(OBJDIR)/gbp_locate.o: $(PKG)/resect/resect_math.hpp
+# locate includes the resection's headers: its Graph, filtering and camera_range, the argument checks of a camera-major call
+$(OBJDIR)/gbp_locate.o: $(wildcard $(PKG)/resect/*.hpp)
 
 $(PKG)/bin/%: $(CSRC)/%_main.cpp $(CSRC)/cli_common.hpp $(CSRC)/gbp_transport.hpp $(CSRC)/gbp_metric_gather.hpp include/gbp_mi355x.h include/gbp_mi355x_multi.h include/gbp_mi355x_compat.h include/gbp_mi355x_post.h include/gbp_mi355x_seed.h include/gbp_mi355x_resect.h include/gbp_mi355x_locate.h $(LIB) $(SAT_LIBS)
 	@mkdir -p $(PKG)/bin

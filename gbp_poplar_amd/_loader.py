@@ -1,4 +1,4 @@
-"""How every native library of the package is loaded (_lib.py, post.py, seed.py).  There is no CPU fallback: a library that is missing,
+"""How every native library of the package is loaded (_lib.py, post.py, seed.py, resect.py, locate.py).  There is no CPU fallback: a library that is missing,
 stale or lacks a declared symbol fails loudly."""
 import ctypes as C
 import os

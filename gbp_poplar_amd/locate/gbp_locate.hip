@@ -3,17 +3,15 @@
 // memory accesses and the argument checks.  Not on the iteration path: one call per keyframe, on the caller's stream, nothing
 // allocated, nothing waited for.
 #include "../../include/gbp_mi355x_locate.h"
-#include "../stateless/stateless_export.hpp"
+#include "../resect/resect_call.hpp"
+#include "../stateless/stateless_wave.hpp"
 #include "locate_math.hpp"
-
-#include <cmath>
 
 namespace gbp {
 namespace locate {
+using stateless::kWavesPerBlock;      // cameras per workgroup
+using stateless::lane0;
 
-constexpr int kWavesPerBlock = 4;      // cameras per workgroup
-
-GBP_DEV float lane0(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 GBP_DEV float from_lane(float v, uint32_t j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int)j)); }
 GBP_DEV uint32_t votes(bool b) { return (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(b)); }
 
@@ -107,7 +105,7 @@ struct DeviceWave {
 
 __global__ __launch_bounds__(64 * kWavesPerBlock) void k_locate_cameras(uint32_t n_cams, Graph g, const uint32_t* __restrict__ cam_start,
                                                                         const uint32_t* __restrict__ select, const Params p, Outputs o) {
-  const uint32_t c = blockIdx.x * kWavesPerBlock + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint32_t c = stateless::wave_item();
   if (c >= n_cams) return;                        // (the whole wave)
   if (select && select[c] == 0u) return;
   uint32_t k0, k1, st;
@@ -156,30 +154,21 @@ GBP_STATELESS_EXPORT(gbp_locate_cameras,
   if (o.rounds == 0u) return bad_arg(fn, "opts.rounds is 0");
   if (o.rounds > 4096u) return bad_arg(fn, "opts.rounds is above 4096");
   if (o.min_inliers < 4u) return bad_arg(fn, "opts.min_inliers is below 4");
-  if (!(o.inlier_px > 0.f) || !std::isfinite(o.inlier_px)) return bad_arg(fn, "opts.inlier_px is not a positive number");
+  if (const int rc = need_positive(fn, "opts.inlier_px", o.inlier_px)) return rc;
   if (n_cams) {
-    if (!K) return null_arg(fn, "K");
-    if (!cam_start) return null_arg(fn, "cam_start");
-    if (!cam_mean) return null_arg(fn, "cam_mean");
-    if (!status) return null_arg(fn, "status");
-    if (n_edges) {
-      if (!lmk_id) return null_arg(fn, "lmk_id");
-      if (!lmk_mean) return null_arg(fn, "lmk_mean");
-      if (!measurements) return null_arg(fn, "measurements");
-      if (n_lmks == 0) return bad_arg(fn, "n_lmks is 0 with n_edges > 0");
-    }
+    if (const int rc = gbp::resect::check_cameras(fn, K, cam_start, cam_mean, status)) return rc;
+    if (n_edges)
+      if (const int rc = gbp::resect::check_edges(fn, n_lmks, lmk_id, lmk_mean, measurements)) return rc;
   }
   last_error().clear();
   if (n_cams == 0) return GBP_OK;
   Params p;
   for (int i = 0; i < 9; ++i) p.K[i] = K[i];
   p.inlier_px = o.inlier_px; p.rounds = o.rounds; p.min_inliers = o.min_inliers; p.seed = o.seed;
-  Graph g;
-  g.n_lmks = n_lmks; g.n_edges = n_edges; g.lmk_id = lmk_id; g.cam_edges = cam_edges; g.lmk_mean = lmk_mean; g.meas = measurements;
-  g.active_flag = active_flag; g.lmk_use = lmk_use;
+  const Graph g = gbp::resect::graph_of(n_lmks, n_edges, lmk_id, cam_edges, lmk_mean, measurements, active_flag, lmk_use);
   Outputs out;
   out.cam_mean = cam_mean; out.inlier = inlier; out.report = report; out.status = status; out.n_views = n_views; out.n_inliers = n_inliers;
-  hipLaunchKernelGGL(k_locate_cameras, dim3(n_cams / kWavesPerBlock + (n_cams % kWavesPerBlock != 0u)), dim3(64 * kWavesPerBlock), 0,
-                     static_cast<hipStream_t>(hip_stream), n_cams, g, cam_start, select, p, out);
+  hipLaunchKernelGGL(k_locate_cameras, wave_grid(n_cams), dim3(64 * kWavesPerBlock), 0, static_cast<hipStream_t>(hip_stream), n_cams, g,
+                     cam_start, select, p, out);
   return launched(fn);
 }

@@ -3,18 +3,15 @@
 // memory accesses and the argument checks.  Not on the iteration path: one call per keyframe, on the caller's stream, nothing
 // allocated, nothing waited for.
 #include "../../include/gbp_mi355x_resect.h"
-#include "../stateless/stateless_export.hpp"
-#include "resect_math.hpp"
-
-#include <cmath>
-#include <vector>
+#include "../stateless/stateless_index.hpp"
+#include "../stateless/stateless_wave.hpp"
+#include "resect_call.hpp"
 
 namespace gbp {
 namespace resect {
+using stateless::kWavesPerBlock;      // cameras per workgroup
+using stateless::lane0;
 
-constexpr int kWavesPerBlock = 4;      // cameras per workgroup
-
-GBP_DEV float lane0(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 // lane i reads lane i + n of its own DPP row of 16 (n = 8, 4, 2, 1; a lane past the row's end keeps its value, which the tree never uses)
 template <int N> GBP_DEV int row_shl(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x100 + N, 0xF, 0xF, false); }
 template <int N> GBP_DEV float row_shl(float v) { return __int_as_float(row_shl<N>(__float_as_int(v))); }
@@ -72,7 +69,7 @@ struct DeviceWave {
 
 __global__ __launch_bounds__(64 * kWavesPerBlock) void k_resect_cameras(uint32_t n_cams, Graph g, const uint32_t* __restrict__ cam_start,
                                                                         const uint32_t* __restrict__ select, const Params p, Outputs o) {
-  const uint32_t c = blockIdx.x * kWavesPerBlock + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint32_t c = stateless::wave_item();
   if (c >= n_cams) return;                        // (the whole wave)
   if (select && select[c] == 0u) return;
   uint32_t k0, k1, st;
@@ -113,36 +110,12 @@ GBP_STATELESS_EXPORT(gbp_resect_default_options, (gbp_resect_options* opts), (op
 
 GBP_STATELESS_EXPORT(gbp_resect_index, (uint32_t n_cams, uint32_t n_edges, const uint32_t* cam_id, uint32_t* cam_start, uint32_t* cam_edges),
                 (n_cams, n_edges, cam_id, cam_start, cam_edges)) {
-  const char* fn = "gbp_resect_index";
-  if (!cam_start) return null_arg(fn, "cam_start");
-  if (n_edges && !cam_id) return null_arg(fn, "cam_id");
-  if (n_edges && !cam_edges) return null_arg(fn, "cam_edges");
-  for (uint32_t e = 0; e < n_edges; ++e)
-    if (cam_id[e] >= n_cams) return bad_arg(fn, "cam_id[" + std::to_string(e) + "] = " + std::to_string(cam_id[e]) + " is not below n_cams");
-  // counting sort: the degrees, their running sum, then every edge to the next free place of its camera (ascending e: stable)
-  for (uint64_t c = 0; c <= n_cams; ++c) cam_start[c] = 0u;
-  for (uint32_t e = 0; e < n_edges; ++e) ++cam_start[cam_id[e] + 1];
-  for (uint64_t c = 0; c < n_cams; ++c) cam_start[c + 1] += cam_start[c];
-  std::vector<uint32_t> next(cam_start, cam_start + n_cams);
-  for (uint32_t e = 0; e < n_edges; ++e) cam_edges[next[cam_id[e]]++] = e;
-  last_error().clear();
-  return GBP_OK;
+  return build_index("gbp_resect_index", kCamIndex, n_cams, n_edges, cam_id, cam_start, cam_edges);
 }
 
 GBP_STATELESS_EXPORT(gbp_resect_check_index, (uint32_t n_cams, uint32_t n_edges, const uint32_t* cam_start, const uint32_t* cam_edges),
                 (n_cams, n_edges, cam_start, cam_edges)) {
-  const char* fn = "gbp_resect_check_index";
-  if (!cam_start) return null_arg(fn, "cam_start");
-  if (cam_start[0] != 0u) return bad_arg(fn, "cam_start[0] is not 0");
-  for (uint64_t c = 0; c < n_cams; ++c)
-    if (cam_start[c + 1] < cam_start[c]) return bad_arg(fn, "cam_start is not ascending at " + std::to_string(c + 1));
-  if (cam_start[n_cams] != n_edges)
-    return bad_arg(fn, "cam_start[n_cams] = " + std::to_string(cam_start[n_cams]) + " is not n_edges = " + std::to_string(n_edges));
-  if (cam_edges)
-    for (uint32_t k = 0; k < n_edges; ++k)
-      if (cam_edges[k] >= n_edges) return bad_arg(fn, "cam_edges[" + std::to_string(k) + "] is not below n_edges");
-  last_error().clear();
-  return GBP_OK;
+  return check_index("gbp_resect_check_index", kCamIndex, n_cams, n_edges, cam_start, cam_edges, true);
 }
 
 GBP_STATELESS_EXPORT(gbp_resect_cameras,
@@ -158,34 +131,25 @@ GBP_STATELESS_EXPORT(gbp_resect_cameras,
   if (opts) o = *opts;
   if (o.max_passes == 0u) return bad_arg(fn, "opts.max_passes is 0");
   if (o.min_views < 3u) return bad_arg(fn, "opts.min_views is below 3");
-  if (std::isnan(o.huber_px)) return bad_arg(fn, "opts.huber_px is NaN");
-  if (!(o.lambda0 > 0.f) || !std::isfinite(o.lambda0)) return bad_arg(fn, "opts.lambda0 is not a positive number");
-  if (!(o.reproj_meas_var > 0.f) || !std::isfinite(o.reproj_meas_var)) return bad_arg(fn, "opts.reproj_meas_var is not a positive number");
+  if (const int rc = need_number(fn, "opts.huber_px", o.huber_px)) return rc;
+  if (const int rc = need_positive(fn, "opts.lambda0", o.lambda0)) return rc;
+  if (const int rc = need_positive(fn, "opts.reproj_meas_var", o.reproj_meas_var)) return rc;
   if (n_cams) {
-    if (!K) return null_arg(fn, "K");
-    if (!cam_start) return null_arg(fn, "cam_start");
-    if (!cam_mean) return null_arg(fn, "cam_mean");
-    if (!status) return null_arg(fn, "status");
+    if (const int rc = check_cameras(fn, K, cam_start, cam_mean, status)) return rc;
     if (cam_priors_eta && !cam_priors_lambda) return bad_arg(fn, "cam_priors_eta without cam_priors_lambda");
-    if (n_edges) {
-      if (!lmk_id) return null_arg(fn, "lmk_id");
-      if (!lmk_mean) return null_arg(fn, "lmk_mean");
-      if (!measurements) return null_arg(fn, "measurements");
-      if (n_lmks == 0) return bad_arg(fn, "n_lmks is 0 with n_edges > 0");
-    }
+    if (n_edges)
+      if (const int rc = check_edges(fn, n_lmks, lmk_id, lmk_mean, measurements)) return rc;
   }
   last_error().clear();
   if (n_cams == 0) return GBP_OK;
   Params p;
   for (int i = 0; i < 9; ++i) p.K[i] = K[i];
   p.huber_px = o.huber_px; p.lambda0 = o.lambda0; p.reproj_meas_var = o.reproj_meas_var; p.max_passes = o.max_passes; p.min_views = o.min_views;
-  Graph g;
-  g.n_lmks = n_lmks; g.n_edges = n_edges; g.lmk_id = lmk_id; g.cam_edges = cam_edges; g.lmk_mean = lmk_mean; g.meas = measurements;
-  g.active_flag = active_flag; g.lmk_use = lmk_use;
+  const Graph g = graph_of(n_lmks, n_edges, lmk_id, cam_edges, lmk_mean, measurements, active_flag, lmk_use);
   Outputs out;
   out.cam_mean = cam_mean; out.cam_priors_lambda = cam_priors_lambda; out.cam_priors_eta = cam_priors_eta; out.cam_info = cam_info;
   out.report = report; out.status = status; out.n_views = n_views;
-  hipLaunchKernelGGL(k_resect_cameras, dim3(n_cams / kWavesPerBlock + (n_cams % kWavesPerBlock != 0u)), dim3(64 * kWavesPerBlock), 0,
-                     static_cast<hipStream_t>(hip_stream), n_cams, g, cam_start, select, p, out);
+  hipLaunchKernelGGL(k_resect_cameras, wave_grid(n_cams), dim3(64 * kWavesPerBlock), 0, static_cast<hipStream_t>(hip_stream), n_cams, g,
+                     cam_start, select, p, out);
   return launched(fn);
 }

@@ -3,11 +3,8 @@
 // argument checks.  Not on the iteration path: one call per start / per keyframe, on the caller's stream, nothing allocated, nothing
 // waited for.
 #include "../../include/gbp_mi355x_seed.h"
-#include "../stateless/stateless_export.hpp"
+#include "../stateless/stateless_index.hpp"
 #include "seed_math.hpp"
-
-#include <cmath>
-#include <vector>
 
 namespace gbp {
 namespace seed {
@@ -97,36 +94,12 @@ GBP_STATELESS_EXPORT(gbp_seed_default_options, (gbp_seed_options* opts), (opts))
 
 GBP_STATELESS_EXPORT(gbp_seed_index, (uint32_t n_lmks, uint32_t n_edges, const uint32_t* lmk_id, uint32_t* lmk_start, uint32_t* lmk_edges),
                 (n_lmks, n_edges, lmk_id, lmk_start, lmk_edges)) {
-  const char* fn = "gbp_seed_index";
-  if (!lmk_start) return null_arg(fn, "lmk_start");
-  if (n_edges && !lmk_id) return null_arg(fn, "lmk_id");
-  if (n_edges && !lmk_edges) return null_arg(fn, "lmk_edges");
-  for (uint32_t e = 0; e < n_edges; ++e)
-    if (lmk_id[e] >= n_lmks) return bad_arg(fn, "lmk_id[" + std::to_string(e) + "] = " + std::to_string(lmk_id[e]) + " is not below n_lmks");
-  // counting sort: the degrees, their running sum, then every edge to the next free place of its landmark (ascending e: stable)
-  for (uint64_t l = 0; l <= n_lmks; ++l) lmk_start[l] = 0u;
-  for (uint32_t e = 0; e < n_edges; ++e) ++lmk_start[lmk_id[e] + 1];
-  for (uint64_t l = 0; l < n_lmks; ++l) lmk_start[l + 1] += lmk_start[l];
-  std::vector<uint32_t> next(lmk_start, lmk_start + n_lmks);
-  for (uint32_t e = 0; e < n_edges; ++e) lmk_edges[next[lmk_id[e]]++] = e;
-  last_error().clear();
-  return GBP_OK;
+  return build_index("gbp_seed_index", kLmkIndex, n_lmks, n_edges, lmk_id, lmk_start, lmk_edges);
 }
 
 GBP_STATELESS_EXPORT(gbp_seed_check_index, (uint32_t n_lmks, uint32_t n_edges, const uint32_t* lmk_start, const uint32_t* lmk_edges),
                 (n_lmks, n_edges, lmk_start, lmk_edges)) {
-  const char* fn = "gbp_seed_check_index";
-  if (!lmk_start) return null_arg(fn, "lmk_start");
-  if (n_edges && !lmk_edges) return null_arg(fn, "lmk_edges");
-  if (lmk_start[0] != 0u) return bad_arg(fn, "lmk_start[0] is not 0");
-  for (uint64_t l = 0; l < n_lmks; ++l)
-    if (lmk_start[l + 1] < lmk_start[l]) return bad_arg(fn, "lmk_start is not ascending at " + std::to_string(l + 1));
-  if (lmk_start[n_lmks] != n_edges)
-    return bad_arg(fn, "lmk_start[n_lmks] = " + std::to_string(lmk_start[n_lmks]) + " is not n_edges = " + std::to_string(n_edges));
-  for (uint32_t k = 0; k < n_edges; ++k)
-    if (lmk_edges[k] >= n_edges) return bad_arg(fn, "lmk_edges[" + std::to_string(k) + "] is not below n_edges");
-  last_error().clear();
-  return GBP_OK;
+  return check_index("gbp_seed_check_index", kLmkIndex, n_lmks, n_edges, lmk_start, lmk_edges, false);
 }
 
 GBP_STATELESS_EXPORT_T(size_t, 0, gbp_seed_workspace_bytes, (uint32_t n_cams), (n_cams)) { return sizeof(CamRec) * (size_t)n_cams; }
@@ -143,9 +116,9 @@ GBP_STATELESS_EXPORT(gbp_seed_landmarks,
   gbp_seed_options o;
   defaults(o);
   if (opts) o = *opts;
-  if (!(o.reproj_meas_var > 0.f) || !std::isfinite(o.reproj_meas_var)) return bad_arg(fn, "opts.reproj_meas_var is not a positive number");
-  if (!(o.fallback_depth > 0.f) || !std::isfinite(o.fallback_depth)) return bad_arg(fn, "opts.fallback_depth is not a positive number");
-  if (std::isnan(o.min_parallax)) return bad_arg(fn, "opts.min_parallax is NaN");
+  if (const int rc = need_positive(fn, "opts.reproj_meas_var", o.reproj_meas_var)) return rc;
+  if (const int rc = need_positive(fn, "opts.fallback_depth", o.fallback_depth)) return rc;
+  if (const int rc = need_number(fn, "opts.min_parallax", o.min_parallax)) return rc;
   if (n_lmks) {
     if (!lmk_start) return null_arg(fn, "lmk_start");
     if (!lmk_mean) return null_arg(fn, "lmk_mean");

@@ -1,10 +1,11 @@
-// stateless/stateless_export.hpp — how a function of a library WITHOUT a ctx (post/, seed/) is defined: the guard of
+// stateless/stateless_export.hpp — how a function of a library WITHOUT a ctx (post/, seed/, resect/, locate/) is defined: the guard of
 // csrc/gbp_export.hpp with the text of a failure kept per calling thread (gbp_<lib>_last_error), and what every such library's argument
 // checks and launches say the same way.  Include it behind the library's public header (GBP_API, the GBP_ERR_* codes) in a HIP
 // translation unit.  Not under csrc/: the core library does not depend on it.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <exception>
 #include <new>
@@ -58,6 +59,11 @@ inline int launched(const char* what) {
 }
 inline int null_arg(const char* fn, const char* arg) { return fail(GBP_ERR_INVALID, std::string(fn) + ": " + arg + " is NULL"); }
 inline int bad_arg(const char* fn, const std::string& what) { return fail(GBP_ERR_INVALID, std::string(fn) + ": " + what); }
+// an option (name: "opts.<field>") that has to be a positive number / must not be NaN: GBP_OK, or the failure
+inline int need_positive(const char* fn, const char* name, float x) {
+  return x > 0.f && std::isfinite(x) ? GBP_OK : bad_arg(fn, std::string(name) + " is not a positive number");
+}
+inline int need_number(const char* fn, const char* name, float x) { return std::isnan(x) ? bad_arg(fn, std::string(name) + " is NaN") : GBP_OK; }
 constexpr uint64_t kMaxLanes = 0xffffff00ull;      // one lane per item, 32-bit lane index
 
 }  // namespace stateless

@@ -1,5 +1,8 @@
-"""The C-ABI checks every ctx-less library passes (tests/test_post_cpu.py, tests/test_seed_cpu.py): the library exports its public header
-and nothing else, and every export is defined once, through the guard macros of gbp_poplar_amd/stateless/stateless_export.hpp."""
+"""The C-ABI checks every ctx-less library passes (tests/test_post_cpu.py, tests/test_seed_cpu.py, tests/test_resect_cpu.py,
+tests/test_locate_cpu.py, tests/test_stateless_cpu.py): the library exports its public header and nothing else, every export is defined
+once, through the guard macros of gbp_poplar_amd/stateless/stateless_export.hpp, and the Python bindings call every export with the
+header's parameter list."""
+import ctypes as C
 import os
 import re
 import subprocess
@@ -14,6 +17,47 @@ def declared(header):
     src = open(os.path.join(ROOT, "include", header)).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     return sorted(set(re.findall(r"^\s*(?:GBP_API\s+)?(?:const\s+char\s*\*|int|void|size_t)\s+(gbp_\w+)\s*\(", src, flags=re.M)))
+
+
+def signatures(header):
+    """name -> (kind of the return value, [kind per parameter]) of every gbp_* function include/<header> declares; a kind is "pointer"
+    (an array parameter such as `const float K[9]` too), "uint32_t", "size_t", "int" or, for a return value, "void" """
+    src = open(os.path.join(ROOT, "include", header)).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+
+    def kind(text):
+        if "*" in text or "[" in text:
+            return "pointer"
+        words = [w for w in text.split() if w != "const"]
+        assert words and words[0] in ("uint32_t", "size_t", "int", "void"), text
+        return words[0]
+
+    out = {}
+    for ret, name, params in re.findall(r"^\s*(?:GBP_API\s+)?((?:const\s+)?\w+\s*\*?)\s*(gbp_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
+        params = [p.strip() for p in params.split(",")]
+        out[name] = (kind(ret), [] if params == ["void"] else [kind(p) for p in params])
+    return out
+
+
+def _ctypes_kind(t):
+    if t is None:
+        return "void"
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "pointer"
+    return {C.c_uint32: "uint32_t", C.c_size_t: "size_t", C.c_int: "int"}[t]
+
+
+def check_signatures(module, header):
+    """what ctypes was told of every export (module.load().<name>: restype, argtypes) is the header's declaration, kind by kind"""
+    declared_sigs = signatures(header)
+    assert sorted(declared_sigs) == declared(header) == module.symbols()
+    lib = module.load()
+    for name, (ret, params) in declared_sigs.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(params), (name, len(fn.argtypes or ()), len(params))
+        assert [_ctypes_kind(t) for t in fn.argtypes] == params, (name, params)
+        assert _ctypes_kind(fn.restype) == ret, (name, fn.restype, ret)
 
 
 def check_exports(module, header, exports, abi_version):

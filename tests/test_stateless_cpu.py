@@ -1,8 +1,16 @@
 """What the ctx-less libraries get from gbp_poplar_amd/stateless/stateless_export.hpp, without a GPU: ONE header defines the error text,
 yet libgbp_mi355x_post.so and libgbp_mi355x_seed.so, loaded into one process as every Python user and bin/ba, bin/slam load them, each
-keep a text of their own, per thread.  The failing calls fail their argument checks, which precede every HIP call."""
+keep a text of their own, per thread.  The failing calls fail their argument checks, which precede every HIP call.  What all four
+libraries (post, seed, resect, locate) get from stateless/ and gbp_poplar_amd/_stateless.py: the ctypes signatures of the bindings are
+the public headers' (tests/stateless_cabi.py), and the shared host index is right under the sanitizers, as a program of its own."""
 import ctypes as C
+import os
+import subprocess
 import threading
+
+import pytest
+
+from tests import host_twin, stateless_cabi
 
 P = C.c_void_p(64)      # any non-NULL address: a call that fails its argument checks touches neither the array nor HIP
 
@@ -75,3 +83,22 @@ def test_a_second_thread_has_texts_of_its_own():
     assert "error" not in seen, seen["error"]
     assert seen["start"] == (b"", b"") and seen["end"] == mine
     assert (post.gbp_post_last_error(), seed.gbp_seed_last_error()) == mine
+
+
+LIBRARIES = ["post", "seed", "resect", "locate"]
+
+
+@pytest.mark.parametrize("name", LIBRARIES)
+def test_the_bindings_call_every_export_with_the_headers_parameter_list(name):
+    """per export: as many ctypes argtypes as the public header declares parameters, each of the header's kind (pointer — an array
+    parameter and the options pointer too —, uint32_t, size_t, int), and the restype of the declared return value"""
+    import importlib
+    stateless_cabi.check_signatures(importlib.import_module("gbp_poplar_amd." + name), "gbp_mi355x_%s.h" % name)
+
+
+def test_index_and_its_check_under_the_sanitizers(tmp_path):
+    """gbp_poplar_amd/stateless/stateless_index.hpp compiled for the host under ASan + UBSan into a program of its own
+    (tests/sanitize/stateless_index_main.cpp: the cases and the expected texts are there), run as a process"""
+    exe = host_twin.compile_host(os.path.join("tests", "sanitize", "stateless_index_main.cpp"), str(tmp_path / "stateless_index"), sanitize=True)
+    p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert p.returncode == 0 and "stateless_index: ok" in p.stdout, (p.returncode, p.stdout[-2000:], p.stderr[-3000:])
