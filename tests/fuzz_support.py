@@ -50,7 +50,8 @@ class Mismatch(AssertionError):
 def random_problem(rng, slam=False, big=False, max_edges=300000, size=None):
     """size None: as the soak has always drawn (log-uniform, up to max_edges).  "tiny" / "small" / "mid" / "tiles": the size classes of the
     suite's slice — at most 1 000 factors; the persistent kernel's range; between the persistent kernel's range and 2 048 tiles; just past
-    2 048 tiles with enough cameras for row placement.  (The classes aim; plan() measures what came out with the library's own layout.)"""
+    2 048 tiles with enough cameras for row placement; "half": 600 - 680 tiles, a persistent grid of 150 - 170 workgroups.  (The classes aim;
+    plan() measures what came out with the library's own layout.)"""
     if slam:      # a keyframe sequence: sorted by camera (slam.cpp relies on it), every keyframe sees a window of the landmarks that moves on
         C_ = int(rng.integers(3, 31))
         L = int(np.exp(rng.uniform(np.log(20), np.log(3000))))
@@ -83,6 +84,9 @@ def random_problem(rng, slam=False, big=False, max_edges=300000, size=None):
         elif size == "tiles":
             C_, L = int(rng.integers(300, 421)), int(rng.integers(15000, 30000))      # (rows are placed where a camera has few factors)
             E = int(rng.integers(133000, 150000))
+        elif size == "half":      # 600 - 680 tiles: a persistent grid of more than half an MI355X's CUs (tests/multi_ctx_support.py)
+            C_, L = int(rng.integers(8, 33)), int(rng.integers(2000, 3500))
+            E = int(rng.integers(38500, 42000))
         cam_id = rng.integers(0, C_, E)
         if rng.random() < 0.5:                                   # half of the graphs: a few cameras see almost everything
             m = rng.random(E) < 0.5
